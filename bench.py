@@ -2,6 +2,11 @@
 """Benchmark of the MI355X prover hot path ("Measurement").
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: under torch.distributed.run, or plain -- it then starts its N ranks itself)
+        [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...); `--full`
+adds everything else: the VALU roofline and its probes, the single-unit latency, the CPU baseline and the secondary figures.
+`--dump-outputs DIR` writes what the timed path returned in its last step (the gathered leaves and the aggregation root) as DIR/*.npy.
 
 Default workload `recursive` (BASELINE.json metric "recursive plonky2 proofs/sec (Semaphore d=20)", configs[3]; sharded
 over ranks it is configs[4]): one UNIT = one depth-20 Semaphore signal (make_signal, access_set.rs:61-104: witness, proof at
@@ -12,7 +17,7 @@ GPU, proven by K concurrent prover contexts (one HIP stream + one host thread ea
 value = units (= recursive proofs) per second of the whole job.  The roofline object is the kernel group with the largest
 HIP-event time inside the timed region: algorithmic bytes of its launches over their summed duration.
 
-`--workload lde` (configs[1]): 2^20-point Goldilocks LDE, blowup 8, 135 columns, value in algorithmic GB/s; also run for a
+`--workload lde` (configs[1]): 2^20-point Goldilocks LDE, blowup 8, 135 columns, value in algorithmic GB/s; with `--full` also run for a
 few steps after the default workload and reported as `ntt_lde` (the metric's "NTT HBM GB/s" half).
 `--workload semaphore`: the signals alone, no recursive proof.
 """
@@ -261,17 +266,17 @@ def main_recursive(args):
         if comm is not None:
             comm.barrier()
         torch.cuda.synchronize()
-    # the VALU roofline's peak: class issue rates measured on this device now (idle apart from the probe), the clock during the timed
-    # region sampled by a one-wave probe on a context of its own (rank 0)
+    # --full: the VALU roofline's peak: class issue rates measured on this device now (idle apart from the probe), the clock during the timed
+    # region sampled by a one-wave probe on a context of its own (rank 0), HIP-event scopes on one context during the timed region
     model = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             import bench_common
             model = bench_common.VALU_MODEL = ValuModel(pr.sets[0])
         except Exception as exc:
             sys.stderr.write("[bench] valu probes failed: %r\n" % (exc,))
-    sampler = ClockSampler(gl, local_rank) if rank == 0 and os.environ.get("GL355_BENCH_NO_CLOCK_SAMPLER") != "1" else None
-    pr.profile(True)
+    sampler = ClockSampler(gl, local_rank) if rank == 0 and args.full and os.environ.get("GL355_BENCH_NO_CLOCK_SAMPLER") != "1" else None
+    pr.profile(args.full)
     barrier()
     import resource
     ru0 = resource.getrusage(resource.RUSAGE_SELF)
@@ -301,8 +306,11 @@ def main_recursive(args):
     pr.profile(False)
     if comm is not None:
         elapsed = comm.max(elapsed)                                         # gl355_comm_max_f64
-    if rank == 0:
-        units = total * args.steps
+    units = total * args.steps
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives from its last step: the gathered (nullifier | topic) leaves and the aggregation root
+        dump_outputs(args.dump_outputs, {"leaves": allv, "aggregation_root": root})
+    if rank == 0 and args.full:
         # ---- roofline pass: the same units on ONE prover context right after the timed region.  With 12 streams sharing the
         # GPU a HIP-event pair around a launch also measures the time the launch waits behind other streams' kernels
         # (3-4x the kernel's own duration, and rocprofv3's per-kernel durations do not see that wait), so per-kernel
@@ -430,6 +438,7 @@ def main_recursive(args):
         roofline["timed_region_events"] = {"what": "the same scopes on 1 of the %d concurrent streams during the timed region "
                                                    "(includes queueing behind the other streams)" % n_threads,
                                            "units": local_units, "kernel_groups": groups(prof, local_units, 6)}
+    if rank == 0:
         line = {
             "metric": "recursive plonky2 proofs/sec (Semaphore d=%d)" % args.log_members,
             "value": round(units / elapsed, 2), "unit": "recursive proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -452,13 +461,15 @@ def main_recursive(args):
                                      "tape_replay_threads": replay_threads, "pinned_cpus": pinned},
                        "expected_units_per_s_per_gpu": expected_rate(cores_per_rank),
                        "host_cpu_ms_per_unit": round(1e3 * host_cpu_s / max(1, (hi - lo) * args.steps), 2),
-                       "units_proven_in_process": int(sum(pr.units_done)),
-                       "host_split": host_split},
-            "roofline": roofline,
-            "aggregation_root": ["%016x" % int(x) for x in root[0]],
-            "latency_single_unit_ms": latency,
+                       "units_proven_in_process": int(sum(pr.units_done))},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            line["config"]["host_split"] = host_split
+            line["roofline"] = roofline
+        line["aggregation_root"] = ["%016x" % int(x) for x in root[0]]
+        if args.full:
+            line["latency_single_unit_ms"] = latency
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline_recursive(pr)
             except Exception as exc:
@@ -590,7 +601,16 @@ def main():
                          "GL355_OPT_BATCH_UNITS = 8 units in lock-step.  Default: 10 with >= 12 usable host cores per rank, else 8 "
                          "(round 3, final kernels: 8 -> 289.6, 9 -> 291.7, 10 -> 291.4, 11 -> 290.5, 16 -> 249 units/s; profiles/r03b_contexts_sweep.txt)")
     ap.add_argument("--log-members", type=int, default=20, help="log2 of the access-set size (tree depth)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the VALU roofline (issue-rate probes, clock sampler, HIP-event scopes in the timed region, the "
+                         "one-context pass), the single-unit latency, the CPU baseline and the secondary figures (wrap, LDE, Merkle, BN254, "
+                         "aggregation, Halo2); --workload lde: the cfg-2 sweep and the CPU baseline.  Off: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64; u64 field "
+                         "elements as exact (low 32 bits, high 32 bits) pairs on a trailing axis); the inputs are seeded, so runs compare output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)        # no external launcher: this process becomes the launcher of its N ranks
     if args.threads <= 0:

@@ -13,6 +13,8 @@
   unit_depth20.json   SHA-256 of the two proofs of one depth-20 unit (tests/cpu_unit.py UNIT_CASE), same rule.
   semaphore_depth25.json  the 2^25-member group of the reference's sweep (tests/cpu_semaphore.py GROUP25_CASE): root, public inputs, proof
                       SHA-256; `python tests/golden/make_golden.py depth25` (minutes: 67 M CPU permutations), not part of the default run.
+  poseidon_fast_partial_tables.json  the reference's literal Poseidon fast-partial-round tables (poseidon.rs), transcribed;
+                      `python tests/golden/make_golden.py poseidon-fast-tables <the reference's poseidon.rs>`, not part of the default run.
 Run: python tests/golden/make_golden.py
 """
 import json
@@ -120,9 +122,25 @@ def mint_bn254_kat():
     json.dump(kat, open(os.path.join(HERE, "poseidon_bn254_kat.json"), "w"), indent=1)
 
 
+def mint_poseidon_fast_tables(src_path):
+    """poseidon_fast_partial_tables.json: the reference's literal fast-partial-round tables (its
+    src/plonky2_verifier/chip/plonk/gates/poseidon.rs, given as `src_path`), transcribed as they stand, so that
+    tests/test_tables.py can hold tools/gen_poseidon_tables.py's derivation against them without the reference tree."""
+    import re
+    src = open(src_path).read()
+    out = {"_source": "the reference's src/plonky2_verifier/chip/plonk/gates/poseidon.rs, literal tables as written"}
+    for name in ("FAST_PARTIAL_FIRST_ROUND_CONSTANT", "FAST_PARTIAL_ROUND_CONSTANTS", "FAST_PARTIAL_ROUND_VS",
+                 "FAST_PARTIAL_ROUND_W_HATS", "FAST_PARTIAL_ROUND_INITIAL_MATRIX"):
+        m = re.search(r"const %s.*?=\s*\[(.*?)\];" % name, src, re.S)
+        out[name] = ["%016x" % int(x, 16) for x in re.findall(r"0x[0-9a-f]+", m.group(1))]
+    json.dump(out, open(os.path.join(HERE, "poseidon_fast_partial_tables.json"), "w"), indent=0)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "depth25":
         return mint_group_depth25()
+    if len(sys.argv) > 2 and sys.argv[1] == "poseidon-fast-tables":
+        return mint_poseidon_fast_tables(sys.argv[2])
     mint_semaphore_proof()
     mint_unit_depth20()
     mint_bn254_kat()

@@ -14,6 +14,6 @@ L=stark-verifier_amd/lib
 cp $L/libgl355.so /tmp/main.so
 for v in main lanesform0 main lanesform0; do
   if [ $v = main ]; then cp /tmp/main.so $L/libgl355.so; else cp $L/variants/libgl355_$v.so $L/libgl355.so; fi
-  python bench.py --steps 6 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', 'units/s', d['value'], 'latency', d['latency_single_unit_ms']['median_ms'], d['latency_single_unit_ms']['min_ms'])"
+  python bench.py --full --steps 6 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', 'units/s', d['value'], 'latency', d['latency_single_unit_ms']['median_ms'], d['latency_single_unit_ms']['min_ms'])"
 done
 cp /tmp/main.so $L/libgl355.so

@@ -573,6 +573,8 @@ def main_exchange(args):
     if comm is not None:
         comm.barrier()
         elapsed = comm.max(elapsed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"leaves": allv})
     if rank == 0:
         print(json.dumps({"metric": "exchange plumbing (no prover)", "value": round(total * (args.warmup + args.steps) / elapsed, 1), "unit": "leaves/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "leaves_in_rank_order": bool(ok),
@@ -647,6 +649,10 @@ def main_lde(args):
     t1 = time.perf_counter()
     prof = {k: v for k, v in ctx.profile_read().items() if not k.startswith("host:")}
     ctx.profile_enable(False)
+    if rank == 0 and args.dump_outputs:
+        # the last step's LDE output (a fixed, seeded sample of it: flat index, value) and the digest hashed from it
+        sample_idx, sample_vals = lde_output_sample(out)
+        dump_outputs(args.dump_outputs, {"lde_sample_index": sample_idx, "lde_sample": sample_vals, "digest": digest.cpu().numpy()})
 
     elapsed = t1 - t0
     if comm is not None:
@@ -703,14 +709,14 @@ def main_lde(args):
                                                   "element (162 + 99 on the radix-8 kernels of round 2, ~490 in round 1)"}
         if root is not None:
             line["aggregation_root"] = ["%016x" % x for x in root]
-        if world == 1:
+        if args.full and world == 1:
             try:
                 del coeffs, out
                 torch.cuda.empty_cache()
                 line["cfg2_sweep"] = cfg2_sweep(ctx, dev)
             except Exception as exc:
                 line["cfg2_sweep"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if comm is not None:
@@ -755,6 +761,8 @@ def main_semaphore(args):
     elapsed = time.perf_counter() - t0
     if comm is not None:
         elapsed = comm.max(elapsed)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"leaves": allv, "aggregation_root": root})
     if rank == 0:
         line = {"metric": "plonky2 proofs/sec (Semaphore d=20, no recursive wrap)", "value": round(total * args.steps / elapsed, 2),
                 "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

@@ -477,6 +477,35 @@ def thread_cpu_snapshot():
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one out_dir/<name>.npy per array, float64.  A field element (u64)
+    does not fit a float64, so u64 / i64 arrays get a trailing axis of 2: (low 32 bits, high 32 bits), both exact; compare them exactly."""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype in (np.uint64, np.int64):
+            u = a.view(np.uint64)
+            a = np.stack([(u & np.uint64(0xFFFFFFFF)).astype(np.float64), (u >> np.uint64(32)).astype(np.float64)], axis=-1)
+        conv[name] = a.astype(np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def lde_output_sample(out, n_sample=1 << 19, seed=0x355D):
+    """a fixed, seeded sample of an LDE output tensor [columns][N] (int64 on the device) for --dump-outputs: (flat indices, values)"""
+    import torch
+    idx = np.sort(np.random.default_rng(seed).choice(out.numel(), size=min(n_sample, out.numel()), replace=False))
+    vals = out.reshape(-1)[torch.from_numpy(idx.astype(np.int64)).to(out.device)].cpu().numpy()
+    return idx.astype(np.float64), vals
+
+
 _STORE_KEEPALIVE = []
 
 

@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -q > $O/gpu_tests.txt 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
-python bench.py > $O/bench_recursive.json 2> $O/bench_recursive.err
+python bench.py --full > $O/bench_recursive.json 2> $O/bench_recursive.err
 python tools/halo2_bench.py 17 20 23 > $O/halo2_bench.json 2> $O/halo2_bench.err
 python tools/aggregate_native.py 8 > $O/aggregate_native.json 2> $O/aggregate_native.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/h2stats -- python tools/halo2_bench.py 23 > /dev/null 2> $O/h2stats.err

@@ -3,7 +3,7 @@
 # usage (GPU box): bash tools/hostside_one_rank.sh > gpurun_out/r06/hostside_one_rank.txt
 cd $GRAFT_REPO_ROOT
 for K in 1 2 3 4 6 8 12 16; do
-  line=$(taskset -c 0-$((K-1)) python bench.py --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1)
+  line=$(taskset -c 0-$((K-1)) python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1)
   python - "$K" "$line" <<'PY'
 import json, sys
 k, line = int(sys.argv[1]), sys.argv[2]

@@ -63,7 +63,7 @@ if steady:
                 e[key] = t3 - t1
         if "SQ_INSTS_VALU" in v3:
             e["steady_launches"] = v3["SQ_INSTS_VALU"][1] - (v1["SQ_INSTS_VALU"][1] if "SQ_INSTS_VALU" in v1 else 0)
-doc = {"_source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes over `python bench.py --steps 1 --warmup 0 --proofs-per-step 16 "
+doc = {"_source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes over `python bench.py --full --steps 1 --warmup 0 --proofs-per-step 16 "
                   "--threads 1 --no-cpu-baseline` (one context, lock-step batches of 8 units; tools/prof_round5.sh, tools/make_pmc_traffic.py), per-dispatch averages in KB; FETCH_SIZE doubled "
                   "per the gfx950 note of MI355X_MICROARCH.md (HBM section); WRITE_SIZE taken as reported",
        "_valu_note": "SQ_INSTS_VALU (wave instructions, whole chip) / 1024 SIMDs vs SQ_BUSY_CYCLES / 32 shader engines, same rocprofv3 --pmc run: "

@@ -8,14 +8,14 @@ O=$R/gpurun_out/prof_r04
 mkdir -p $O
 cd $R
 python tools/valu_probe_run.py > $O/valu_probe.json 2> $O/valu_probe.err
-python bench.py > $O/bench_recursive.json 2> $O/bench_recursive.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python bench.py --steps 1 --warmup 1 --proofs-per-step 16 --threads 1 --no-cpu-baseline > $O/bench_under_rocprof_1stream.json 2> $O/stats1.err
+python bench.py --full > $O/bench_recursive.json 2> $O/bench_recursive.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python bench.py --full --steps 1 --warmup 1 --proofs-per-step 16 --threads 1 --no-cpu-baseline > $O/bench_under_rocprof_1stream.json 2> $O/stats1.err
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python bench.py --steps 1 --warmup 0 --proofs-per-step 16 --threads 1 --no-cpu-baseline > /dev/null 2> $O/pmc_$c.err
+  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python bench.py --full --steps 1 --warmup 0 --proofs-per-step 16 --threads 1 --no-cpu-baseline > /dev/null 2> $O/pmc_$c.err
 done
 SQC="SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU"
-rocprofv3 --pmc $SQC --output-format csv -d $O/pmc_sq -- python bench.py --steps 1 --warmup 0 --proofs-per-step 16 --threads 1 --no-cpu-baseline > $O/bench_under_pmc_sq.json 2> $O/pmc_sq.err
+rocprofv3 --pmc $SQC --output-format csv -d $O/pmc_sq -- python bench.py --full --steps 1 --warmup 0 --proofs-per-step 16 --threads 1 --no-cpu-baseline > $O/bench_under_pmc_sq.json 2> $O/pmc_sq.err
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 --output-format csv -d $O/pmc_probe -- python tools/valu_probe_run.py > $O/valu_probe_under_pmc.json 2> $O/pmc_probe.err
 python - <<'PY'
 import csv, glob, os, collections, shutil

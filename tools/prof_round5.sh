@@ -6,11 +6,11 @@ O=$R/gpurun_out/prof_r05
 WHAT=${1:-all}
 mkdir -p $O
 cd $R
-ONE="python bench.py --steps 1 --warmup 0 --proofs-per-step 16 --threads 1 --no-cpu-baseline"
+ONE="python bench.py --full --steps 1 --warmup 0 --proofs-per-step 16 --threads 1 --no-cpu-baseline"
 if [ $WHAT != lde ]; then
   python tools/valu_probe_run.py > $O/valu_probe.json 2> $O/valu_probe.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python bench.py --steps 1 --warmup 1 --proofs-per-step 16 --threads 1 --no-cpu-baseline > $O/bench_under_rocprof_1stream.json 2> $O/stats1.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python bench.py --full --steps 1 --warmup 1 --proofs-per-step 16 --threads 1 --no-cpu-baseline > $O/bench_under_rocprof_1stream.json 2> $O/stats1.err
   for c in FETCH_SIZE WRITE_SIZE; do
     GL355_BENCH_NO_AGGREGATE=1 rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- $ONE > /dev/null 2> $O/pmc_$c.err
   done

@@ -8,14 +8,14 @@ mkdir -p $O
 cd $R
 # steady state of the PMC pass: the same one-context job with 1 step and with 3 steps; (3 steps) - (1 step) = two steps' kernels without the set-up
 # (key hashes, group tree, the two circuits' preprocessed commitments), VERDICT r5 #1 (c)
-ONE="python bench.py --warmup 0 --proofs-per-step 16 --threads 1 --no-cpu-baseline"
+ONE="python bench.py --full --warmup 0 --proofs-per-step 16 --threads 1 --no-cpu-baseline"
 if [ $WHAT = probe ] || [ $WHAT = all ]; then
   python tools/valu_probe_run.py > $O/valu_probe.json 2> $O/valu_probe.err
   rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_WAVES --output-format csv -d $O/pmc_probe -- python tools/valu_probe_run.py > $O/valu_probe_under_pmc.json 2> $O/pmc_probe.err
 fi
 if [ $WHAT = recursive ] || [ $WHAT = all ]; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python bench.py --steps 1 --warmup 1 --proofs-per-step 16 --threads 1 --no-cpu-baseline > $O/bench_under_rocprof_1stream.json 2> $O/stats1.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python bench.py --full --steps 1 --warmup 1 --proofs-per-step 16 --threads 1 --no-cpu-baseline > $O/bench_under_rocprof_1stream.json 2> $O/stats1.err
   for c in FETCH_SIZE WRITE_SIZE; do
     GL355_BENCH_NO_AGGREGATE=1 rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- $ONE --steps 1 > /dev/null 2> $O/pmc_$c.err
   done
