@@ -587,7 +587,11 @@ int32_t gl355_aggregation_root(gl355_ctx* ctx, const uint64_t* leaves, uint64_t 
  *                        2^(c w) P_i of every base for every window w (64 B x n x windows, 6.4 GB at n = 2^23); with them the digits of ALL windows of a
  *                        scalar set fall into one set of buckets, so the bucket reduction and the per-bucket bookkeeping are paid once per set instead of
  *                        once per window, and no window sums are combined on the host.  _msm_prepared: results as gl355_bn254_g1_msm_batch over the
- *                        prepared points (scalars n_sets x n x 4).  The handle belongs to the context it was made on; free it before the context. */
+ *                        prepared points (scalars n_sets x n x 4).  The handle belongs to the context it was made on; free it before the context.
+ *   gl355_bn254_g1_fft   the same transform as gl355_bn254_fr_ntt with G1 points as the elements: in place, natural order in and out,
+ *                        p[k] <- sum_i [w^(ik)] p[i], same w and 1/n convention; log_n <= 26.  What halo2's g_to_lagrange runs on the monomial
+ *                        bases of ParamsKZG (verifier_api.rs:77 makes them with ParamsKZG::setup, which a deployment replaces by downsize / read).
+ *                        Every point is checked (coordinates < q, on the curve): GL355_E_INVALID_ARG otherwise, with the points untouched. */
 int32_t gl355_bn254_fr_ntt(gl355_ctx* ctx, uint64_t* data /* n x 4 */, uint32_t log_n, int32_t inverse);
 int32_t gl355_bn254_fr_coset_ntt(gl355_ctx* ctx, const uint64_t* in, uint32_t log_small, uint32_t log_n, const uint64_t shift[4], int32_t inverse,
                                  uint64_t* out);
@@ -595,6 +599,7 @@ int32_t gl355_bn254_g1_msm(gl355_ctx* ctx, const uint64_t* points /* n x 8 */, c
 int32_t gl355_bn254_g1_msm_batch(gl355_ctx* ctx, const uint64_t* points /* n x 8 */, const uint64_t* scalars /* n_sets x n x 4 */, uint64_t n,
                                  uint32_t n_sets, uint64_t* results /* n_sets x 8 */);
 int32_t gl355_bn254_g1_fixed_base_mul(gl355_ctx* ctx, const uint64_t base[8], const uint64_t* scalars /* n x 4 */, uint64_t n, uint64_t* out /* n x 8 */);
+int32_t gl355_bn254_g1_fft(gl355_ctx* ctx, uint64_t* points /* 2^log_n x 8 */, uint32_t log_n, int32_t inverse);
 typedef struct gl355_msm_bases gl355_msm_bases;
 int32_t gl355_bn254_g1_msm_prepare(gl355_ctx* ctx, const uint64_t* points /* n x 8 */, uint64_t n, gl355_msm_bases** out);
 int32_t gl355_bn254_g1_msm_prepared(gl355_ctx* ctx, const gl355_msm_bases* bases, const uint64_t* scalars /* n_sets x n x 4 */, uint32_t n_sets,
@@ -607,12 +612,19 @@ int32_t gl355_bn254_g1_msm_bases_free(gl355_ctx* ctx, gl355_msm_bases* bases);
  * array may be host or device memory.
  *   gl355_kzg_setup    ParamsKZG::setup with the secret handed in: g[i] = [tau^i] G1, g_lagrange[i] = [L_i(tau)] G1 (NULL to skip), G1 = (1, 2),
  *                      L_i the Lagrange basis of the 2^log_n domain.  GL355_E_INVALID_ARG if tau lies in the domain.
+ *   gl355_kzg_lagrange_from_powers   ParamsKZG::downsize / g_to_lagrange: g_lagrange = the inverse G1 FFT of g[0 .. 2^log_n), the Lagrange
+ *                      bases of a parameter set whose secret nobody knows (ceremony powers of tau in place of ParamsKZG::setup, verifier_api.rs:77).
+ *                      n_points >= 2^log_n (only that prefix is read: a larger set downsizes).  Equal to gl355_kzg_setup's g_lagrange for the same tau.
+ *                      GL355_E_INVALID_ARG for n_points < 2^log_n or a point that is non-canonical or off the curve (g_lagrange untouched),
+ *                      GL355_E_UNSUPPORTED for log_n > 26.
  *   gl355_kzg_commit   ParamsKZG::commit / commit_lagrange: sum_i poly[i] g[i].  values_form 0: poly goes with the bases as given (coefficients
  *                      with g, evaluations with g_lagrange); 1: poly are evaluations over the domain and g the MONOMIAL bases (inverse FFT, then MSM)
  *   gl355_kzg_open     eval = p(z) and witness = commit((p - p(z)) / (X - z)) for the coefficients of p: the single-point opening halo2's
  *                      multi-open provers reduce to.  quotient (optional, 2^log_n x 4) receives the quotient's coefficients.
  * A verifier with the pairing checks e(C - [eval] G1, G2) = e(witness, [tau - z] G2); with a known tau: C - [eval] G1 = [tau - z] witness. */
 int32_t gl355_kzg_setup(gl355_ctx* ctx, const uint64_t tau[4], uint32_t log_n, uint64_t* g /* 2^log_n x 8 */, uint64_t* g_lagrange /* or NULL */);
+int32_t gl355_kzg_lagrange_from_powers(gl355_ctx* ctx, const uint64_t* g /* n_points x 8 */, uint64_t n_points, uint32_t log_n,
+                                       uint64_t* g_lagrange /* 2^log_n x 8 */);
 int32_t gl355_kzg_commit(gl355_ctx* ctx, const uint64_t* g /* 2^log_n x 8 */, const uint64_t* poly /* 2^log_n x 4 */, uint32_t log_n, int32_t values_form,
                          uint64_t result[8]);
 int32_t gl355_kzg_open(gl355_ctx* ctx, const uint64_t* g, const uint64_t* coeffs, uint32_t log_n, const uint64_t z[4], uint64_t eval[4],

@@ -460,6 +460,57 @@ def kzg_setup(ctx, k, tau, lagrange=True):
     return g, gl
 
 
+def _points_ptr(a):
+    """(void* value, number of points) of a [n][8] uint64 numpy array or torch tensor; (a, None) for a raw device pointer (int)"""
+    if isinstance(a, int):
+        return a, None
+    if isinstance(a, np.ndarray):
+        assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"] and a.ndim == 2 and a.shape[1] == 8, "need a C-contiguous [n][8] uint64 array"
+        return a.ctypes.data, a.shape[0]
+    assert a.is_contiguous() and a.dim() == 2 and a.shape[1] == 8 and a.element_size() == 8, "need a contiguous [n][8] 64-bit tensor"
+    return a.data_ptr(), a.shape[0]
+
+
+def g1_fft(ctx, points, inverse=False, log_n=None):
+    """The Fr FFT of gl355_bn254_fr_ntt with G1 points as the elements: out[k] = sum_i [w^(ik)] points[i] (inverse: w^-1 and 1/n).
+    A numpy array is transformed into a new array; a torch tensor or a device pointer (int, log_n required) in place, and returned."""
+    ptr, n = _points_ptr(points)
+    if n is None:
+        assert log_n is not None, "a raw pointer needs log_n"
+    else:
+        log_n = n.bit_length() - 1 if log_n is None else log_n
+        assert n == 1 << log_n, "g1_fft takes 2^log_n points"
+    if isinstance(points, np.ndarray):
+        points = points.copy()
+        ptr = points.ctypes.data
+    ctx.check(ctx.lib.gl355_bn254_g1_fft(ctx.h, ptr, log_n, 1 if inverse else 0))
+    if not isinstance(points, np.ndarray):
+        ctx.sync()                      # device results: done before the caller's own streams read them
+    return points
+
+
+def kzg_lagrange_from_powers(ctx, g, k, out=None, n_points=None):
+    """ParamsKZG::downsize(k) / g_to_lagrange: the Lagrange bases of the 2^k domain from public monomial bases g[i] = [tau^i] G1
+    (n_points >= 2^k of them, e.g. a larger ceremony's; only the prefix is read), with no knowledge of tau.  g: numpy [n][8] uint64,
+    a torch tensor, or a device pointer (int, with n_points).  Returns `out`, or a new array / tensor of g's kind (2^k x 8): it goes
+    straight into PlonkProver(ctx, cs, k, g[:2**k], g_lagrange, ...)."""
+    ptr, n = _points_ptr(g)
+    n = n_points if n is None else n
+    assert n is not None, "a raw pointer needs n_points"
+    if out is None:
+        if isinstance(g, np.ndarray) or isinstance(g, int):
+            out = np.zeros((1 << k, 8), dtype=np.uint64)
+        else:
+            import torch
+            out = torch.empty((1 << k, 8), dtype=g.dtype, device=g.device)
+    optr, on = _points_ptr(out)
+    assert on is None or on == 1 << k, "out holds 2^k points"
+    ctx.check(ctx.lib.gl355_kzg_lagrange_from_powers(ctx.h, ptr, n, k, optr))
+    if not isinstance(out, np.ndarray):
+        ctx.sync()
+    return out
+
+
 class PlonkProver:
     """keygen_pk + create_proof of one circuit on one GPU context (chip/native_chip/test_utils.rs:57-95 through gl355_plonk_*).
     g / g_lagrange: numpy arrays (copied to the device) or device pointers (ints; must outlive the prover)."""
