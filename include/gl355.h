@@ -692,6 +692,43 @@ int32_t gl355_zs_partial_products(gl355_ctx* ctx, const uint64_t* wires, const u
                                   uint32_t max_degree, uint64_t beta, uint64_t gamma,
                                   uint64_t* z_out, uint64_t* pp_out);
 
+/* ---- test hooks: the BN254 device arithmetic on raw limbs (tests/test_gpu_bn254_arith.py).  Not a product path: nothing is reduced,
+ * canonicalised or validated on the way in or out, so a test can feed the lazy representations the kernels themselves produce.
+ * Every operand / result is 9 x u32: the 8 x 32-bit Montgomery form (R = 2^256, bn254_field.cuh) uses words 0..7 and gets 0 in word 8;
+ * the 29-bit form (R' = 2^261, bn254_f29.cuh) uses all nine.  Buffers may be host or device memory.
+ *   gl355_bn254_arith_batch   out[i] = op(a[i], b[i]) for n records.  op: GL355_BN_M_* (m_mul ... m_eq over Fr; | GL355_BN_FQ for Fq;
+ *                             IS_ZERO / EQ write 0 / 1 to word 0), GL355_BN_F29_* (FQ29 = Fq, the MSM's form; MUL_FR = Fr, the hasher's; ADD_NORM =
+ *                             f29_norm(f29_add); SUB_Ck = f29_sub(a, b, C_k) and NEG_C2 = f29_neg(a, C2), both NOT normalised; LIFT / LIFT_INL /
+ *                             LOWER / TABLE_FORM between the two forms as the MSM converts), GL355_BN_HASH_FR_ENTER / _LEAVE (the BN254-Poseidon
+ *                             hasher's fr_enter: 4 x u64 integer in words 0..7 -> its 29-bit Montgomery form; fr_leave: back).  b is read by the
+ *                             two-operand ops only (may be NULL otherwise).  GL355_E_INVALID_ARG for an unknown op.
+ *   gl355_bn254_g1_chain      n_chains chains of n_steps point operations, one lane per chain; after every step the lane writes one trace record
+ *                             of 40 u32: four 9-word coordinate slots (x, y, z or zz, zzz), [36] identity flag, [37] the accumulator written
+ *                             (0 = A, 1 = B), [38..39] 0; [37] = 0xffffffff for a step that names a missing operand or kind (nothing done).
+ *                             operands: n_operands records of 28 u32 (three 9-word slots x, y, z, then [27] an identity flag).  Forms:
+ *                               GL355_BN_CHAIN_XYZZ / _JAC29 / _JAC   the MSM bucket accumulators msm_add_point_xyzz, msm_add_point29, msm_add_point
+ *                                 (8 x 32 Jacobian): operands are affine canonical integers (x, y in words 0..7 of slots 0 and 1), turned into the
+ *                                 point table as msm_digits_kernel does; a step is what the bucket kernel passes: operand index | 1 << 31 to subtract.
+ *                               GL355_BN_CHAIN_RED29_LIFT / _RED29_RAW   jac29_add / jac29_double of the reduction levels, operands given as 8 x 32
+ *                                 Jacobian R-form points (lifted by jac29_lift as msm_level_kernel does) or as raw 29-bit coordinates with the flag.
+ *                               GL355_BN_CHAIN_J   j_add / j_madd / j_double (bn254_g1.cuh) on 8 x 32 Jacobian R-form operands.
+ *                             The last three run two accumulators A and B, both starting at the identity; a step is kind << 28 | operand index:
+ *                             GL355_BN_STEP_ADD A += operand, _DOUBLE A = 2 A, _ACC B += A (msm_level_kernel's acc += run), _SELF A += A (the
+ *                             addition formula with equal operands), _MADD A += (x, y) of the operand (GL355_BN_CHAIN_J only, j_madd). */
+enum { GL355_BN_M_MUL = 0, GL355_BN_M_ADD = 1, GL355_BN_M_SUB = 2, GL355_BN_M_CANON = 3, GL355_BN_M_FROM_INT = 4, GL355_BN_M_TO_INT = 5,
+       GL355_BN_M_INV = 6, GL355_BN_M_IS_ZERO = 7, GL355_BN_M_EQ = 8, GL355_BN_FQ = 16,
+       GL355_BN_F29_MUL = 32, GL355_BN_F29_MUL_FR = 33, GL355_BN_F29_ADD_NORM = 34, GL355_BN_F29_SUB_C2 = 35, GL355_BN_F29_SUB_C4 = 36,
+       GL355_BN_F29_SUB_C8 = 37, GL355_BN_F29_SUB_C16 = 38, GL355_BN_F29_NEG_C2 = 39, GL355_BN_F29_FROM_U256 = 40, GL355_BN_F29_TO_U256 = 41,
+       GL355_BN_F29_LIFT = 42, GL355_BN_F29_LIFT_INL = 43, GL355_BN_F29_LOWER = 44, GL355_BN_F29_IS_ZERO_MOD = 45, GL355_BN_F29_TABLE_FORM = 46,
+       GL355_BN_F29_NORM = 47, GL355_BN_HASH_FR_ENTER = 48, GL355_BN_HASH_FR_LEAVE = 49 };
+enum { GL355_BN_CHAIN_XYZZ = 0, GL355_BN_CHAIN_JAC29 = 1, GL355_BN_CHAIN_JAC = 2, GL355_BN_CHAIN_RED29_LIFT = 3, GL355_BN_CHAIN_RED29_RAW = 4,
+       GL355_BN_CHAIN_J = 5 };
+enum { GL355_BN_STEP_ADD = 0, GL355_BN_STEP_DOUBLE = 1, GL355_BN_STEP_ACC = 2, GL355_BN_STEP_SELF = 3, GL355_BN_STEP_MADD = 4 };
+int32_t gl355_bn254_arith_batch(gl355_ctx* ctx, int32_t op, const uint32_t* a /* n x 9 */, const uint32_t* b /* n x 9 or NULL */, uint32_t* out /* n x 9 */,
+                                uint64_t n);
+int32_t gl355_bn254_g1_chain(gl355_ctx* ctx, int32_t form, const uint32_t* operands /* n_operands x 28 */, uint32_t n_operands,
+                             const uint32_t* steps /* n_chains x n_steps */, uint32_t n_chains, uint32_t n_steps, uint32_t* trace /* n_chains x n_steps x 40 */);
+
 #ifdef __cplusplus
 }
 #endif

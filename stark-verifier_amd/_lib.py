@@ -198,6 +198,9 @@ SIGNATURES = {
     "gl355_kzg_open": (C.c_int32, [vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
     "gl355_zs_partial_products": (C.c_int32, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                               C.c_uint64, vp, vp]),
+    # test hooks (include/gl355.h): the BN254 device arithmetic on raw limbs
+    "gl355_bn254_arith_batch": (C.c_int32, [vp, C.c_int32, vp, vp, vp, C.c_uint64]),
+    "gl355_bn254_g1_chain": (C.c_int32, [vp, C.c_int32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp]),
 }
 
 _lib = None

@@ -77,7 +77,9 @@ GL_DEV f29 f29_add(const f29& a, const f29& b) {
     for (int j = 0; j < 9; j++) r.l[j] = a.l[j] + b.l[j];
     return r;
 }
-// a + (K q - b): C = the lent representation of K q; b's limbs below what C lends, b < K q
+// a + (K q - b): C = the lent representation of K q; b's limbs below what C lends, b < K q.  C lends from its top limb too, so the top limb of
+// the result is a's + C's - b's and goes below zero (wraps) when that is negative: for b in the last 2^232 below K q with a's top limb 0.  The
+// wrapped word is still right modulo 2^32, so a following f29_norm gives the true value; the bounds of every caller keep b far below that.
 GL_DEV f29 f29_sub(const f29& a, const f29& b, const uint32_t* C) {
     f29 r;
 #pragma unroll

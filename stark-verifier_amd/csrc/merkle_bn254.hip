@@ -284,4 +284,33 @@ int32_t pow_grind_any(Ctx* ctx, int32_t hasher, const uint64_t state[12], uint32
     return pow_grind_dev(ctx, state, pos, bits, start, witness_host);
 }
 
+// ---- test hook: the hasher's fr_enter / fr_leave on raw 9-word records (gl355_bn254_arith_batch, GL355_BN_HASH_FR_*; device buffers)
+__global__ void bn254_hash_fr_hook_kernel(int32_t leave, const uint32_t* a, uint32_t* out, uint64_t n) {
+    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* pa = a + 9 * i;
+    uint32_t* po = out + 9 * i;
+    uint64_t w[4];
+    if (!leave) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = (uint64_t)pa[2 * k] | ((uint64_t)pa[2 * k + 1] << 32);
+        const fr8 r = fr_enter(w);
+#pragma unroll
+        for (int j = 0; j < 9; j++) po[j] = j < FR_W ? r.l[j] : 0u;
+    } else {
+        fr8 x;
+#pragma unroll
+        for (int j = 0; j < FR_W; j++) x.l[j] = pa[j];
+        fr_leave(x, w);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { po[2 * k] = (uint32_t)w[k]; po[2 * k + 1] = (uint32_t)(w[k] >> 32); }
+        po[8] = 0;
+    }
+}
+int32_t bn254_hash_fr_hook(Ctx* ctx, int32_t leave, const uint32_t* a, uint32_t* out, uint64_t n) {
+    hipLaunchKernelGGL(bn254_hash_fr_hook_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, leave, a, out, n);
+    GL355_HIP(ctx, hipGetLastError());
+    return GL355_OK;
+}
+
 }  // namespace gl355
