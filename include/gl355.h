@@ -686,6 +686,69 @@ int32_t gl355_plonk_prove(gl355_ctx* ctx, gl355_plonk_pk* pk, const uint64_t* ad
                           uint8_t* proof, uint64_t capacity, uint64_t* proof_len, uint64_t* trace, double* stage_ms);
 int32_t gl355_plonk_pk_destroy(gl355_plonk_pk* pk);
 
+/* ---- SURVEY 8(f) N4, the other half: the BN254 pairing and halo2_proofs' verify_proof::<_, VerifierSHPLONK<_>, _, _, SingleStrategy<_>> as
+ * chip/native_chip/test_utils.rs:82-93 runs it on every proof create_proof_checked makes (verifier_api.rs:77-92).  Nothing here takes the
+ * SRS secret: the verifier sees the public [s] G2 of the parameter set only, so proofs under ceremony powers
+ * (gl355_kzg_lagrange_from_powers) can be checked.  The pairing, the transcript and the scalar work are host code; the only device work is
+ * the combined G1 MSM of a batch and the MSMs / FFT of the parameter check (existing kernels).
+ * G2 points are 16 x u64: a point of the twist y^2 = x^3 + 3 / (9 + u) over Fq2 = Fq[u] / (u^2 + 1), stored x.c0 | x.c1 | y.c0 | y.c1 as
+ * canonical integers (4 little-endian u64 each); all zeros = the identity.  The generator is Ethereum's (EIP-197) and halo2curves':
+ *   x.c0 = 0x1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed   x.c1 = 0x198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2
+ *   y.c0 = 0x12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa   y.c1 = 0x090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b
+ * [RECALLED] (no second source for the four numbers in the tree); tests/test_pairing_host.py shows the point is on the twist and has order r.
+ *   gl355_bn254_g2_mul          out = scalar * point (NULL: the generator).  The point must be on the twist; any 256-bit scalar.
+ *   gl355_bn254_pairing_check   *ok = 1 iff prod_i e(g1[i], g2[i]) = 1: the optimal ate pairing (Miller loop over 6x + 2, x = 4965661367192848881,
+ *                               two Frobenius line steps; the n loops share their squarings and one final exponentiation).  An identity on
+ *                               either side contributes 1.  GL355_E_INVALID_ARG, with the pair named by gl355_plonk_verify_last_error, for a
+ *                               non-canonical coordinate, a G1 point off the curve, a G2 point off the twist or outside the order-r subgroup.
+ *   gl355_plonk_vk_create       the verifying key: the descriptor blob gl355_plonk_keygen takes, the key's fixed and permutation commitments
+ *                               (gl355_plonk_pk_commitments), the transcript's initial scalar and the parameter set's [s] G2 (checked as above).
+ *                               digest NULL: header words 16..19, or keygen's pinned-key Keccak rule when those are zero.
+ *   gl355_plonk_vk_from_pk      the same from a proving key (descriptor, commitments and digest as the key holds them now)
+ *   gl355_plonk_verify          one proof.  Returns GL355_OK with *ok = 1 (accepted) or *ok = 0 (rejected; gl355_plonk_verify_last_error names
+ *                               the step); error codes are for malformed calls only.  Stages: transcript (commitments and challenges in the
+ *                               prover's order; every point 64 big-endian bytes, canonical and on the curve; every scalar 32 bytes below r),
+ *                               evaluations, the quotient's evaluation at x from the gate / permutation / lookup expressions (the descriptor's
+ *                               register programs, interpreted once), SHPLONK's rotation sets, L and h2 as one host MSM over the proof's
+ *                               commitments, trailing bytes refused, then e(L + u h2, G2) e(-h2, [s] G2) = 1.  ctx is not used (may be NULL).
+ *                               Instance values are canonical like every scalar here: one that is not below r is GL355_E_INVALID_ARG
+ *                               (in a batch as well), not a verdict.
+ *   gl355_plonk_verify_batch    n_proofs proofs under one key, one verdict: per proof the host work above on up to 16 threads, the MSM terms
+ *                               of L_b + u_b h2_b kept apart; 128-bit rho_b from ChaCha20 under `seed` (block b of stream 0x21, nonce
+ *                               (0x21, 0, 0), the first 16 bytes little-endian; rho_0 = 1; seed NULL: getrandom); sum_b rho_b (L_b + u_b h2_b) as
+ *                               ONE MSM and sum_b rho_b h2_b as a second, each on the device (gl355_bn254_g1_msm) when ctx is given and it has
+ *                               at least 83 terms (the count from which the device call measured faster), else on the host; one two-pair pairing check.
+ *                               GL355_PLONK_VERIFY_DEVICE_MSM_MIN=<terms> in the environment replaces that count (0: every MSM of a batch on
+ *                               the device; read at each call; the verdict does not depend on it).  A batch with an invalid proof
+ *                               is accepted with probability <= 2^-128.  first_bad (optional): -1, or after a failed batch the first proof that
+ *                               fails on its own.
+ *   gl355_kzg_params_check      *ok = 1 iff g[0 .. n_points) are consecutive powers [s^i] g[0] of the s of s_g2, and (g_lagrange given) g_lagrange is
+ *                               the Lagrange form of g[0 .. 2^log_n).  Powers: 128-bit r_i from ChaCha20 (stream 0x22, as above), A = sum_{i<n-1} r_i g[i]
+ *                               and B = sum_{i<n-1} r_i g[i+1] as one gl355_bn254_g1_msm_batch call over the same bases, e(B, G2) e(-A, [s] G2) = 1;
+ *                               g[0] or s_g2 = identity is refused.  Lagrange: a polynomial p with 128-bit coefficients (stream 0x23), its evaluations
+ *                               by gl355_bn254_fr_ntt, sum_j p_j g[j] = sum_i p(w^i) g_lagrange[i].  Each check accepts a wrong set with probability
+ *                               <= 2^-128 over the seed (NULL: getrandom).  Malformed points (non-canonical, off the curve) are a verdict 0 as well.
+ *                               g and g_lagrange are host arrays.  gl355_kzg_lagrange_from_powers itself checks no more than before.
+ *   gl355_plonk_verify_stage_ms the calling thread's last gl355_plonk_verify / _verify_batch in wall milliseconds: [0] transcript, evaluations and
+ *                               expressions, [1] the multi-scalar multiplication(s), [2] the pairing check (what tools/halo2_bench.py reports);
+ *                               zeros for the stages a call did not reach */
+typedef struct gl355_plonk_vk gl355_plonk_vk;
+int32_t gl355_bn254_g2_mul(const uint64_t scalar[4], const uint64_t* point /* 16 words, NULL = the generator */, uint64_t out[16]);
+int32_t gl355_bn254_pairing_check(const uint64_t* g1 /* n x 8 */, const uint64_t* g2 /* n x 16 */, uint32_t n, int32_t* ok);
+int32_t gl355_plonk_vk_create(const uint64_t* desc, uint64_t desc_words, const uint64_t* fixed_commitments, const uint64_t* sigma_commitments,
+                              const uint64_t digest[4] /* or NULL */, const uint64_t s_g2[16], gl355_plonk_vk** out);
+int32_t gl355_plonk_vk_from_pk(const gl355_plonk_pk* pk, const uint64_t s_g2[16], gl355_plonk_vk** out);
+int32_t gl355_plonk_vk_destroy(gl355_plonk_vk* vk);
+int32_t gl355_plonk_verify(gl355_ctx* ctx /* may be NULL */, const gl355_plonk_vk* vk, const uint64_t* instances, const uint32_t* instance_lens,
+                           const uint8_t* proof, uint64_t proof_len, int32_t* ok);
+int32_t gl355_plonk_verify_batch(gl355_ctx* ctx /* may be NULL */, const gl355_plonk_vk* vk, uint32_t n_proofs, const uint64_t* instances /* back to back */,
+                                 const uint32_t* instance_lens /* n_proofs x instance columns */, const uint8_t* const* proofs, const uint64_t* proof_lens,
+                                 const uint8_t seed[32], int32_t* ok, int32_t* first_bad /* or NULL */);
+const char* gl355_plonk_verify_last_error(void);
+int32_t gl355_plonk_verify_stage_ms(double ms[3]);
+int32_t gl355_kzg_params_check(gl355_ctx* ctx, const uint64_t* g /* n_points x 8 */, uint64_t n_points, const uint64_t* g_lagrange /* 2^log_n x 8 or NULL */,
+                               uint32_t log_n, const uint64_t s_g2[16], const uint8_t seed[32], int32_t* ok);
+
 /* ---- a9: wires_permutation_partial_products_and_zs (vanishing_poly.rs:54-108,183-218) --------- */
 int32_t gl355_zs_partial_products(gl355_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas,
                                   const uint64_t* k_is, uint32_t log_n, uint32_t n_routed,

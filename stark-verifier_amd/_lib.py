@@ -77,6 +77,16 @@ SIGNATURES = {
     "gl355_plonk_pk_export_quotient": (C.c_int32, [vp, vp]),
     "gl355_plonk_prove": (C.c_int32, [vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, vp]),
     "gl355_plonk_pk_destroy": (C.c_int32, [vp]),
+    "gl355_bn254_g2_mul": (C.c_int32, [vp, vp, vp]),
+    "gl355_bn254_pairing_check": (C.c_int32, [vp, vp, C.c_uint32, C.POINTER(C.c_int32)]),
+    "gl355_plonk_vk_create": (C.c_int32, [vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(vp)]),
+    "gl355_plonk_vk_from_pk": (C.c_int32, [vp, vp, C.POINTER(vp)]),
+    "gl355_plonk_vk_destroy": (C.c_int32, [vp]),
+    "gl355_plonk_verify": (C.c_int32, [vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(C.c_int32)]),
+    "gl355_plonk_verify_batch": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gl355_plonk_verify_last_error": (C.c_char_p, []),
+    "gl355_plonk_verify_stage_ms": (C.c_int32, [vp]),
+    "gl355_kzg_params_check": (C.c_int32, [vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp, C.POINTER(C.c_int32)]),
     "gl355_valu_probe": (C.c_int32, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gl355_clock_probe": (C.c_int32, [vp, C.c_uint32, C.POINTER(C.c_double)]),
     "gl355_valu_probe_op_name": (C.c_char_p, [C.c_uint32]),

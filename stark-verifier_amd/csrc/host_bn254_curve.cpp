@@ -7,97 +7,15 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "bn254_curve_tables.h"
+#include <algorithm>
+#include <vector>
+
+#include "host_fq.h"
+#include "host_pairing.h"
 
 namespace gl355 {
+using namespace hostfq;
 namespace {
-typedef unsigned __int128 u128;
-struct Fq { uint64_t l[4]; };
-const uint64_t* Q = BN254C_FQ_MOD_64;
-
-bool geq_q(const Fq& a) {
-    for (int i = 3; i >= 0; i--) { if (a.l[i] > Q[i]) return true; if (a.l[i] < Q[i]) return false; }
-    return true;
-}
-void sub_q(Fq& a) {
-    u128 br = 0;
-    for (int i = 0; i < 4; i++) { const u128 d = (u128)a.l[i] - Q[i] - (uint64_t)br; a.l[i] = (uint64_t)d; br = (d >> 64) & 1; }
-}
-Fq fq_canon(Fq a) { while (geq_q(a)) sub_q(a); return a; }      // the kernels keep values lazily below 2q
-Fq fq_add(const Fq& a, const Fq& b) {
-    Fq r; u128 c = 0;
-    for (int i = 0; i < 4; i++) { c += (u128)a.l[i] + b.l[i]; r.l[i] = (uint64_t)c; c >>= 64; }
-    if (c || geq_q(r)) sub_q(r);          // q < 2^254: the sum of two canonical values never carries out of 256 bits
-    return r;
-}
-Fq fq_sub(const Fq& a, const Fq& b) {
-    Fq r; u128 br = 0;
-    for (int i = 0; i < 4; i++) { const u128 d = (u128)a.l[i] - b.l[i] - (uint64_t)br; r.l[i] = (uint64_t)d; br = (d >> 64) & 1; }
-    if (br) { u128 c = 0; for (int i = 0; i < 4; i++) { c += (u128)r.l[i] + Q[i]; r.l[i] = (uint64_t)c; c >>= 64; } }
-    return r;
-}
-Fq fq_mul(const Fq& a, const Fq& b) {       // a b R^-1 mod q, canonical operands and result
-    uint64_t t[6] = {0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < 4; i++) {
-        u128 c = 0;
-        for (int j = 0; j < 4; j++) { c += (u128)a.l[j] * b.l[i] + t[j]; t[j] = (uint64_t)c; c >>= 64; }
-        c += t[4]; t[4] = (uint64_t)c; t[5] = (uint64_t)(c >> 64);
-        const uint64_t m = t[0] * BN254C_FQ_N0INV_64;
-        c = ((u128)m * Q[0] + t[0]) >> 64;
-        for (int j = 1; j < 4; j++) { c += (u128)m * Q[j] + t[j]; t[j - 1] = (uint64_t)c; c >>= 64; }
-        c += t[4]; t[3] = (uint64_t)c; t[4] = t[5] + (uint64_t)(c >> 64);
-    }
-    Fq r = {{t[0], t[1], t[2], t[3]}};
-    if (t[4] || geq_q(r)) sub_q(r);
-    return r;
-}
-bool fq_is_zero(const Fq& a) { return (a.l[0] | a.l[1] | a.l[2] | a.l[3]) == 0; }
-Fq fq_one() { Fq r; memcpy(r.l, BN254C_FQ_ONE_64, 32); return r; }
-Fq fq_inv(const Fq& a) {                    // a^(q-2)
-    uint64_t e[4] = {Q[0] - 2, Q[1], Q[2], Q[3]};
-    Fq r = fq_one();
-    for (int i = 255; i >= 0; i--) {
-        r = fq_mul(r, r);
-        if ((e[i >> 6] >> (i & 63)) & 1) r = fq_mul(r, a);
-    }
-    return r;
-}
-struct Jac { Fq x, y, z; };
-bool j_is_identity(const Jac& p) { return fq_is_zero(p.z); }
-Jac j_double(const Jac& p) {                // y^2 = x^3 + 3 (a = 0)
-    if (j_is_identity(p)) return p;
-    const Fq a = fq_mul(p.x, p.x), b = fq_mul(p.y, p.y), c = fq_mul(b, b);
-    const Fq xb = fq_add(p.x, b);
-    Fq d = fq_sub(fq_sub(fq_mul(xb, xb), a), c);
-    d = fq_add(d, d);
-    const Fq e = fq_add(fq_add(a, a), a), f = fq_mul(e, e);
-    Jac r;
-    r.x = fq_sub(f, fq_add(d, d));
-    Fq c8 = fq_add(c, c); c8 = fq_add(c8, c8); c8 = fq_add(c8, c8);
-    r.y = fq_sub(fq_mul(e, fq_sub(d, r.x)), c8);
-    const Fq yz = fq_mul(p.y, p.z);
-    r.z = fq_add(yz, yz);
-    return r;
-}
-Jac j_add(const Jac& p, const Jac& q) {
-    if (j_is_identity(p)) return q;
-    if (j_is_identity(q)) return p;
-    const Fq z1z1 = fq_mul(p.z, p.z), z2z2 = fq_mul(q.z, q.z);
-    const Fq u1 = fq_mul(p.x, z2z2), u2 = fq_mul(q.x, z1z1);
-    const Fq s1 = fq_mul(fq_mul(p.y, q.z), z2z2), s2 = fq_mul(fq_mul(q.y, p.z), z1z1);
-    const Fq h = fq_sub(u2, u1), r = fq_sub(s2, s1);
-    if (fq_is_zero(h)) {
-        if (fq_is_zero(r)) return j_double(p);
-        Jac id; id.x = fq_one(); id.y = id.x; memset(id.z.l, 0, 32);
-        return id;
-    }
-    const Fq h2 = fq_mul(h, h), h3 = fq_mul(h2, h), v = fq_mul(u1, h2);
-    Jac o;
-    o.x = fq_sub(fq_sub(fq_mul(r, r), h3), fq_add(v, v));
-    o.y = fq_sub(fq_mul(r, fq_sub(v, o.x)), fq_mul(s1, h3));
-    o.z = fq_mul(fq_mul(p.z, q.z), h);
-    return o;
-}
 Fq load_fq(const uint32_t* p) {
     Fq r;
     for (int i = 0; i < 4; i++) r.l[i] = (uint64_t)p[2 * i] | ((uint64_t)p[2 * i + 1] << 32);
@@ -147,5 +65,48 @@ void bn254_g1_add_host(const uint64_t a[8], const uint64_t b[8], uint64_t out[8]
     memcpy(out, x.l, 32);
     memcpy(out + 4, y.l, 32);
 }
+
+// sum_i scalars[i] points[i] on one core: the verifier's MSM over a proof's ~150 commitments, and the batch verifier's below the size
+// where a device launch pays.  Pippenger buckets over unsigned c-bit digits; windows above the longest scalar are never built (the batch
+// verifier's 128-bit weights).
+void bn254_g1_msm_host(const uint64_t* points, const uint64_t* scalars, uint64_t n, uint64_t out[8]) {
+    uint32_t bits = 0;
+    for (uint64_t i = 0; i < n; i++)
+        for (int l = 3; l >= 0; l--) if (scalars[4 * i + l]) { bits = std::max<uint32_t>(bits, 64 * l + 64 - (uint32_t)__builtin_clzll(scalars[4 * i + l])); break; }
+    uint32_t lg = 0;
+    while ((2ull << lg) <= n) lg++;
+    const uint32_t c = std::min(14u, std::max(2u, lg > 1 ? lg - 1 : 2u));
+    const uint32_t n_windows = (bits + c - 1) / c;
+    std::vector<Jac> pts(n);
+    for (uint64_t i = 0; i < n; i++) pts[i] = g1_load(points + 8 * i);
+    std::vector<Jac> buckets((size_t)1 << c);
+    Jac acc = j_identity();
+    for (uint32_t w = n_windows; w-- > 0;) {
+        for (uint32_t k = 0; k < c; k++) acc = j_double(acc);
+        for (auto& b : buckets) b = j_identity();
+        const uint32_t lo = w * c;
+        for (uint64_t i = 0; i < n; i++) {
+            const uint64_t* sc = scalars + 4 * i;
+            uint64_t d = sc[lo >> 6] >> (lo & 63);
+            if ((lo & 63) + c > 64 && (lo >> 6) + 1 < 4) d |= sc[(lo >> 6) + 1] << (64 - (lo & 63));
+            d &= (1ull << c) - 1;
+            if (d) buckets[d] = j_add(buckets[d], pts[i]);
+        }
+        Jac run = j_identity(), sum = j_identity();
+        for (size_t j = buckets.size(); j-- > 1;) { run = j_add(run, buckets[j]); sum = j_add(sum, run); }
+        acc = j_add(acc, sum);
+    }
+    g1_store(acc, out);
+}
+
+void bn254_g1_neg_host(const uint64_t p[8], uint64_t out[8]) {
+    bool ident = true;
+    for (int i = 0; i < 8; i++) ident = ident && p[i] == 0;
+    if (ident) { memset(out, 0, 64); return; }
+    memcpy(out, p, 32);
+    fq_to_int(fq_neg(fq_from_int(p + 4)), out + 4);
+}
+
+bool bn254_g1_valid_host(const uint64_t p[8]) { return g1_valid(p); }
 
 }  // namespace gl355

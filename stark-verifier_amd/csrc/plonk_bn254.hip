@@ -54,6 +54,7 @@ struct gl355_plonk_pk {
     uint32_t ext_k = 0, n_pieces = 0, n_sets = 0, chunk_len = 0;
     uint64_t n = 0, usable = 0;
     Fr digest;
+    std::vector<uint64_t> desc;                                           // the descriptor as given (gl355_plonk_vk_from_pk hands it to the verifier)
     std::vector<std::pair<uint32_t, uint32_t>> perm_cols;                 // (kind, index)
     std::vector<std::pair<int32_t, int32_t>> queries[3];                  // (column, rotation)
     std::vector<Fr> consts;
@@ -486,6 +487,7 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
     pk->chunk_len = pk->degree - 2;
     pk->n_sets = pk->n_perm ? (pk->n_perm + pk->chunk_len - 1) / pk->chunk_len : 0;
     pk->digest = Fr::from_words(desc + 16);
+    pk->desc.assign(desc, desc + words);
     if ((pk->n_fixed && !fixed_values) || (pk->n_perm && !mapping)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: fixed values / permutation mapping missing");
     // ---- the rest of the descriptor
     const uint64_t* p = desc + PLK_HDR;
@@ -717,6 +719,14 @@ int32_t gl355_plonk_pk_set_digest(gl355_plonk_pk* pk, const uint64_t digest[4]) 
     if (!pk || !digest) return GL355_E_INVALID_ARG;
     pk->digest = Fr::from_words(digest);
     return GL355_OK;
+}
+
+// the verifying key of a proving key (plonk_verifier.cpp): its descriptor, commitments and the digest it holds NOW (after any _set_digest)
+int32_t gl355_plonk_vk_from_pk(const gl355_plonk_pk* pk, const uint64_t s_g2[16], gl355_plonk_vk** out) {
+    if (!pk || !s_g2 || !out) return GL355_E_INVALID_ARG;
+    uint64_t digest[4];
+    pk->digest.to_words(digest);
+    return gl355_plonk_vk_create(pk->desc.data(), pk->desc.size(), pk->fixed_commitments.data(), pk->sigma_commitments.data(), digest, s_g2, out);
 }
 
 int32_t gl355_plonk_prove(gl355_ctx* h, gl355_plonk_pk* pk, const uint64_t* advice, const uint64_t* instances, const uint32_t* instance_lens, const uint8_t seed[32],

@@ -5,12 +5,10 @@
 #pragma once
 #include "bn254_field.cuh"
 #include "blinding.cuh"
+#include "plonk_program.h"
 
 namespace gl355 {
 
-constexpr uint32_t PLK_MAX_REGS = 12;        // halo2.py MAX_REGS
-enum { PLK_OP_ADD = 0, PLK_OP_SUB = 1, PLK_OP_MUL = 2, PLK_OP_EMIT = 3, PLK_OP_NEG = 4, PLK_OP_MOV = 5 };
-enum { PLK_K_REG = 0, PLK_K_CONST = 1, PLK_K_ADVICE = 2, PLK_K_FIXED = 3, PLK_K_INSTANCE = 4 };
 // random-scalar streams (include/gl355.h, oracle/halo2_model.py)
 enum { PLK_STREAM_ADVICE = 0x11, PLK_STREAM_LOOKUP_PERMUTED = 0x12, PLK_STREAM_PERM_Z = 0x13, PLK_STREAM_LOOKUP_Z = 0x14, PLK_STREAM_RANDOM_POLY = 0x15 };
 

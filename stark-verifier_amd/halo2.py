@@ -511,6 +511,165 @@ def kzg_lagrange_from_powers(ctx, g, k, out=None, n_points=None):
     return out
 
 
+# ---- the pairing side (include/gl355.h: gl355_bn254_g2_mul / _pairing_check, gl355_plonk_vk_* / _verify*, gl355_kzg_params_check) ---------
+Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583     # bn256::Fq
+# Ethereum's (EIP-197) / halo2curves' generator of G2: ((x.c0, x.c1), (y.c0, y.c1)) on y^2 = x^3 + 3 / (9 + u) over Fq[u] / (u^2 + 1)
+G2_GENERATOR = ((0x1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed, 0x198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2),
+                (0x12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa, 0x090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b))
+
+
+def _raw_limbs(values):
+    """Python integers below 2^256 -> flat uint64 words, NOT reduced (coordinates, and values whose range the library is to check)"""
+    out = np.zeros(4 * len(values), dtype=np.uint64)
+    for i, v in enumerate(values):
+        for j in range(4):
+            out[4 * i + j] = (int(v) >> (64 * j)) & 0xFFFFFFFFFFFFFFFF
+    return out
+
+
+def g1_words(p):
+    """(x, y) | None -> [8] uint64"""
+    return np.zeros(8, dtype=np.uint64) if p is None else _raw_limbs([p[0], p[1]])
+
+
+def g2_words(p):
+    """((x.c0, x.c1), (y.c0, y.c1)) | None | a [16] uint64 array -> [16] uint64"""
+    if isinstance(p, np.ndarray):
+        assert p.dtype == np.uint64 and p.size == 16
+        return np.ascontiguousarray(p).reshape(16)
+    return np.zeros(16, dtype=np.uint64) if p is None else _raw_limbs([p[0][0], p[0][1], p[1][0], p[1][1]])
+
+
+def g2_from_words(w):
+    v = from_limbs(w)
+    return None if not any(v) else ((v[0], v[1]), (v[2], v[3]))
+
+
+def _host_check(rc):
+    if rc != 0:
+        from . import _lib
+        raise _lib.Gl355Error(rc, (_lib.load().gl355_plonk_verify_last_error() or b"").decode())
+
+
+def g2_mul(scalar, point=None):
+    """scalar * point on the G2 twist (point None: the generator) -> ((x.c0, x.c1), (y.c0, y.c1)) or None for the identity.  No GPU."""
+    from . import _lib
+    out = np.zeros(16, dtype=np.uint64)
+    s = _raw_limbs([int(scalar) % (1 << 256)])
+    pw = None if point is None else g2_words(point)
+    _host_check(_lib.load().gl355_bn254_g2_mul(s.ctypes.data, None if pw is None else pw.ctypes.data, out.ctypes.data))
+    return g2_from_words(out)
+
+
+def pairing_check(g1s, g2s):
+    """prod_i e(g1s[i], g2s[i]) == 1.  g1s: (x, y) | None; g2s: as g2_mul returns.  Raises Gl355Error (INVALID_ARG) for a point that is
+    non-canonical, off its curve or (G2) outside the order-r subgroup.  No GPU."""
+    import ctypes as C
+    from . import _lib
+    assert len(g1s) == len(g2s)
+    a = np.concatenate([g1_words(p) for p in g1s]) if len(g1s) else np.zeros(8, dtype=np.uint64)
+    b = np.concatenate([g2_words(p) for p in g2s]) if len(g2s) else np.zeros(16, dtype=np.uint64)
+    ok = C.c_int32(0)
+    _host_check(_lib.load().gl355_bn254_pairing_check(a.ctypes.data, b.ctypes.data, len(g1s), C.byref(ok)))
+    return bool(ok.value)
+
+
+def kzg_setup_g2(tau):
+    """[tau] G2: the G2 half of ParamsKZG::setup (verifier_api.rs:77) for a known secret -- tests, and users of kzg_setup"""
+    return g2_mul(int(tau) % R)
+
+
+def kzg_params_check(ctx, g, s_g2, k, g_lagrange=None, seed=None):
+    """Is g (numpy [n][8] uint64) a run of consecutive powers of the secret behind s_g2, and g_lagrange (optional, [2^k][8]) the Lagrange form of
+    g[:2^k]?  Randomised (error <= 2^-128 per check); seed: 32 bytes, None = the OS's generator.  -> bool"""
+    import ctypes as C
+    g = np.ascontiguousarray(g, dtype=np.uint64)
+    assert g.ndim == 2 and g.shape[1] == 8
+    if g_lagrange is not None:
+        g_lagrange = np.ascontiguousarray(g_lagrange, dtype=np.uint64)
+        assert g_lagrange.shape == (1 << k, 8)
+    s = g2_words(s_g2)
+    ok = C.c_int32(0)
+    rc = ctx.lib.gl355_kzg_params_check(ctx.h, g.ctypes.data, g.shape[0], None if g_lagrange is None else g_lagrange.ctypes.data, k, s.ctypes.data,
+                                        None if seed is None else bytes(seed), C.byref(ok))
+    _host_check(rc)
+    return bool(ok.value)
+
+
+class PlonkVerifier:
+    """verify_proof::<_, VerifierSHPLONK<_>, _, _, SingleStrategy<_>> (chip/native_chip/test_utils.rs:82-93) through gl355_plonk_vk_* /
+    gl355_plonk_verify*: the circuit description, the key's commitments ([cols][8] uint64) and the parameter set's [s] G2 -- never the secret.
+    digest None: the pinned-key rule of keygen (vk_digest)."""
+
+    def __init__(self, cs, k, fixed_commitments, sigma_commitments, s_g2, digest=None, _handle=None):
+        import ctypes as C
+        from . import _lib
+        self.lib, self.cs, self.k = _lib.load(), cs, k
+        self.h = C.c_void_p()
+        if _handle is not None:
+            self.h = _handle
+            return
+        desc = export_desc(cs, k, 0)
+        fc = np.ascontiguousarray(fixed_commitments, dtype=np.uint64).reshape(-1)
+        sc = np.ascontiguousarray(sigma_commitments, dtype=np.uint64).reshape(-1)
+        assert fc.size == 8 * cs.num_fixed and sc.size == 8 * len(cs.permutation)
+        d = None if digest is None else to_limbs([digest])[0]
+        s = g2_words(s_g2)
+        _host_check(self.lib.gl355_plonk_vk_create(desc.ctypes.data, desc.size, fc.ctypes.data if fc.size else None, sc.ctypes.data if sc.size else None,
+                                                   None if d is None else d.ctypes.data, s.ctypes.data, C.byref(self.h)))
+
+    @property
+    def last_error(self):
+        return (self.lib.gl355_plonk_verify_last_error() or b"").decode()
+
+    def _instances(self, instances):
+        assert len(instances) == self.cs.num_instance
+        flat = _raw_limbs([int(v) % R for col in instances for v in col] or [0])
+        return flat, [len(c) for c in instances]
+
+    def verify(self, instances, proof, ctx=None):
+        """instances: per instance column a list of integers; proof: bytes.  -> bool (last_error names the failed step)"""
+        import ctypes as C
+        flat, lens = self._instances(instances)
+        lens = np.array(lens + [0], dtype=np.uint32)
+        proof = bytes(proof)
+        ok = C.c_int32(0)
+        _host_check(self.lib.gl355_plonk_verify(None if ctx is None else ctx.h, self.h, flat.ctypes.data, lens.ctypes.data, proof, len(proof), C.byref(ok)))
+        return bool(ok.value)
+
+    def verify_batch(self, ctx, instances_list, proofs, seed=None, want_first_bad=False):
+        """many proofs under this key, one pairing-product check; ctx (or None): where the combined MSM may run.  -> bool (, first bad index or -1)"""
+        import ctypes as C
+        assert len(instances_list) == len(proofs)
+        parts = [self._instances(i) for i in instances_list]
+        flat = np.concatenate([np.zeros(0, dtype=np.uint64)] + [f for f, l in parts if sum(l)] + [np.zeros(4, dtype=np.uint64)])
+        lens = np.array([x for _, l in parts for x in l] + [0], dtype=np.uint32)
+        proofs = [bytes(p) for p in proofs]
+        ptrs = (C.c_char_p * max(1, len(proofs)))(*proofs)
+        plens = np.array([len(p) for p in proofs] + [0], dtype=np.uint64)
+        ok, first = C.c_int32(0), C.c_int32(-1)
+        _host_check(self.lib.gl355_plonk_verify_batch(None if ctx is None else ctx.h, self.h, len(proofs), flat.ctypes.data, lens.ctypes.data, ptrs, plens.ctypes.data,
+                                                      None if seed is None else bytes(seed), C.byref(ok), C.byref(first) if want_first_bad else None))
+        return (bool(ok.value), first.value) if want_first_bad else bool(ok.value)
+
+    def stage_ms(self):
+        """the last verify / verify_batch of this thread: dict(host=transcript + expressions, msm, pairing) in milliseconds"""
+        ms = np.zeros(3, dtype=np.float64)
+        _host_check(self.lib.gl355_plonk_verify_stage_ms(ms.ctypes.data))
+        return dict(host=float(ms[0]), msm=float(ms[1]), pairing=float(ms[2]))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gl355_plonk_vk_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PlonkProver:
     """keygen_pk + create_proof of one circuit on one GPU context (chip/native_chip/test_utils.rs:57-95 through gl355_plonk_*).
     g / g_lagrange: numpy arrays (copied to the device) or device pointers (ints; must outlive the prover)."""
@@ -569,6 +728,14 @@ class PlonkProver:
         if timed:
             out.append(dict(zip(STAGES, (float(v) for v in ms))))
         return out[0] if len(out) == 1 else tuple(out)
+
+    def verifying_key(self, s_g2):
+        """the PlonkVerifier of this key (its descriptor, commitments and current digest) under the parameter set's [s] G2"""
+        import ctypes as C
+        h = C.c_void_p()
+        s = g2_words(s_g2)
+        _host_check(self.ctx.lib.gl355_plonk_vk_from_pk(self.h, s.ctypes.data, C.byref(h)))
+        return PlonkVerifier(self.cs, self.k, None, None, None, _handle=h)
 
     def close(self):
         if getattr(self, "h", None):

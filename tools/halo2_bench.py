@@ -1,7 +1,10 @@
 """SURVEY 8(f) N4 at size: a synthetic circuit with the reference's column / gate / lookup shape (halo2_chips.AllChipConfig: 19 advice and 13 fixed
 columns, 12 permutation columns, nine 16-bit range lookups, degree 6) at k = argv[1:] (default 17 20 23; the reference finalises at k = 23:
 README.md:171-177, 505-511 s on 16 vCPUs) through gl355_plonk_keygen / gl355_plonk_prove on cuda:0, every proof checked by the restated
-halo2 verifier (tests/halo2_verifier.py; pairing check in the exponent under the known tau).  One JSON line per k."""
+halo2 verifier (tests/halo2_verifier.py; pairing check in the exponent under the known tau) and by the native one (gl355_plonk_verify under
+[tau] G2, host only: native_verified, native_verify_ms and its split into transcript + expressions / MSM / pairing).  One JSON line per k.
+`--batch` instead of k values: the batch verifier's numbers at k = 12 (batches of 32 and 256, device against host MSM, the MSM alone over a
+range of term counts) and gl355_kzg_params_check at k = 20 and 23, one JSON line."""
 import importlib
 import json
 import os
@@ -55,6 +58,19 @@ def run(gl, ctx, k, verify=True, reps=2):
     used = (torch.cuda.mem_get_info()[1] - torch.cuda.mem_get_info()[0]) / 1e9
     out["gpu_mem_GB"] = round(used - used_before, 1)             # SRS + proving key + witness + everything the proofs allocated (allocator cache included)
     out["gpu_mem_device_total_used_GB"] = round(used, 1)
+    # the native verifier (verify_proof with VerifierSHPLONK, chip/native_chip/test_utils.rs:82-93): host only, best of three
+    nv = prover.verifying_key(h2.kzg_setup_g2(TAU % h2.R))
+    nbest = None
+    for _ in range(3):
+        t0 = time.perf_counter()
+        ok = nv.verify(w.instance, best[2])
+        dt = (time.perf_counter() - t0) * 1e3
+        if nbest is None or dt < nbest[0]:
+            nbest = (dt, nv.stage_ms())
+    out["native_verified"] = bool(ok)
+    out["native_verify_ms"] = round(nbest[0], 3)
+    out["native_verify_stage_ms"] = {k_: round(v, 3) for k_, v in nbest[1].items()}
+    nv.close()
     if verify:
         import halo2_verifier as hv
         pt = lambda a: (lambda x, y: None if (x, y) == (0, 0) else (x, y))(h2.from_limbs(a[:4])[0], h2.from_limbs(a[4:])[0])      # noqa: E731
@@ -68,11 +84,70 @@ def run(gl, ctx, k, verify=True, reps=2):
     return out
 
 
+def timed(f, reps=3):
+    best = None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        r = f()
+        dt = (time.perf_counter() - t0) * 1e3
+        best = dt if best is None or dt < best else best
+    return r, round(best, 3)
+
+
+def run_batch(gl, ctx, k=12):
+    """verify_batch of 32 and 256 proofs of the reference's chip shape against n x one proof, with the device and the host MSM; the MSM alone
+    (host sum against gl355_bn254_g1_msm from host arrays) over term counts -- the figure behind PLONK_VERIFY_DEVICE_MSM_MIN; the parameter check"""
+    h2 = importlib.import_module("stark-verifier_amd.halo2")
+    ch = importlib.import_module("stark-verifier_amd.halo2_chips")
+    out = {"k": k}
+    cs, cfg, w = ch.synthetic_circuit(k, table_bits=k - 1, n_permutations=4)
+    g, gl_ = h2.kzg_setup(ctx, k, TAU % h2.R)
+    prover = h2.PlonkProver(ctx, cs, k, g, gl_, w.fixed, w.assembly.mapping_array())
+    nv = prover.verifying_key(h2.kzg_setup_g2(TAU % h2.R))
+    proofs = [prover.prove(w.advice, w.instance, bytes([b & 0xFF, b >> 8] * 16)) for b in range(256)]
+    ok, one = timed(lambda: nv.verify(w.instance, proofs[0]), 5)
+    out["single"] = {"ok": ok, "ms": one, "stage_ms": nv.stage_ms(), "proof_bytes": len(proofs[0])}
+    for nb in (32, 256):
+        insts = [w.instance] * nb
+        ok_d, ms_d = timed(lambda: nv.verify_batch(ctx, insts, proofs[:nb], seed=bytes(32)))
+        st_d = nv.stage_ms()
+        ok_h, ms_h = timed(lambda: nv.verify_batch(None, insts, proofs[:nb], seed=bytes(32)))
+        st_h = nv.stage_ms()
+        out["batch_%d" % nb] = {"ok": ok_d and ok_h, "device_msm_ms": ms_d, "device_stage_ms": st_d, "host_msm_ms": ms_h, "host_stage_ms": st_h,
+                                "n_times_single_ms": round(nb * one, 1)}
+    # the combined MSM alone (stage time of verify_batch), forced to the device against the host sum, over batch sizes: the figure behind
+    # PLONK_VERIFY_DEVICE_MSM_MIN (plonk_verifier.cpp)
+    cl = cs.chunk_len()
+    per_proof = cs.num_advice + 3 * len(cs.lookups) + (len(cs.permutation) + cl - 1) // cl + 1 + (cs.degree() - 1) + 2
+    sweep = {}
+    for nb in (1, 2, 4, 8, 16, 32, 64, 128):
+        insts = [w.instance] * nb
+        os.environ["GL355_PLONK_VERIFY_DEVICE_MSM_MIN"] = "0"
+        msd = min(nv.stage_ms()["msm"] for _ in range(3) if nv.verify_batch(ctx, insts, proofs[:nb], seed=bytes(32)))
+        del os.environ["GL355_PLONK_VERIFY_DEVICE_MSM_MIN"]
+        msh = min(nv.stage_ms()["msm"] for _ in range(3) if nv.verify_batch(None, insts, proofs[:nb], seed=bytes(32)))
+        sweep[nb] = {"terms": nb * per_proof + cs.num_fixed + len(cs.permutation) + 1, "device_msm_ms": round(msd, 3), "host_msm_ms": round(msh, 3)}
+    out["msm_sweep"] = sweep
+    prover.close()
+    for kk in (20, 23):
+        gg, ll = h2.kzg_setup(ctx, kk, TAU % h2.R)
+        s2 = h2.kzg_setup_g2(TAU % h2.R)
+        okp, msp = timed(lambda: h2.kzg_params_check(ctx, gg, s2, kk, seed=bytes(32)), 1)
+        okl, msl = timed(lambda: h2.kzg_params_check(ctx, gg, s2, kk, g_lagrange=ll, seed=bytes(32)), 1)
+        out["params_check_k%d" % kk] = {"ok": okp and okl, "powers_ms": msp, "powers_and_lagrange_ms": msl}
+        del gg, ll
+    return out
+
+
 if __name__ == "__main__":
     import torch
     torch.cuda.init()            # torch's bundled ROCm runtime first, then libgl355.so (tests/conftest.py has the reason)
     gl = importlib.import_module("stark-verifier_amd")
     ctx = gl.Context(0)
+    if sys.argv[1:] == ["--batch"]:
+        print(json.dumps(run_batch(gl, ctx)), flush=True)
+        ctx.close()
+        sys.exit(0)
     for k in [int(a) for a in sys.argv[1:]] or [17, 20, 23]:
         print(json.dumps(run(gl, ctx, k)), flush=True)
     ctx.close()
