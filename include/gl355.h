@@ -686,6 +686,34 @@ int32_t gl355_plonk_prove(gl355_ctx* ctx, gl355_plonk_pk* pk, const uint64_t* ad
                           uint8_t* proof, uint64_t capacity, uint64_t* proof_len, uint64_t* trace, double* stage_ms);
 int32_t gl355_plonk_pk_destroy(gl355_plonk_pk* pk);
 
+/* ---- SURVEY 8(f) N4, before any proof: halo2's MockProver::run(k, &circuit, instances).assert_satisfied() -- the whole of
+ * verify_inside_snark_mock (src/plonky2_verifier/verifier_api.rs:34-52), the first step of verify_inside_snark (verifier_api.rs:72-73) and what every
+ * chip test of the reference runs (goldilocks_chip.rs, arithmetic_chip.rs, poseidon_bn254_chip.rs, all_chip.rs, the gate tests through
+ * gate_test.rs).  "Does this witness satisfy this circuit, and if not, where?" from the descriptor alone: no SRS, no key.
+ *   gl355_plonk_check_witness  desc / fixed_values / mapping / advice / instances / instance_lens exactly as gl355_plonk_keygen and
+ *                            gl355_plonk_prove take them (host or device memory; advice is not modified; mapping NULL: copy constraints are
+ *                            not checked).  With n = 2^k and usable = n - (blinding_factors + 1), following MockProver::verify:
+ *                            GATE          every polynomial of the gate program (EMIT ordinal = cs.all_gate_polys() order) evaluated exactly at
+ *                                          every row < usable, rotations mod n, instance columns padded with zeros; non-zero -> (GATE, ordinal, row, 0)
+ *                            GATE_POISONED an advice query that lands in a row >= usable (which the prover overwrites with blinding values) is
+ *                                          poisoned; poison goes through ADD SUB NEG MOV, and through MUL unless the other operand is an unpoisoned
+ *                                          zero, when the product is an unpoisoned zero (a switched-off selector silences its gate); a poisoned
+ *                                          polynomial -> (GATE_POISONED, ordinal, row, 0)
+ *                            LOOKUP        for every lookup and row < usable the input tuple must equal the table tuple of some row < usable --
+ *                                          exactly, tuple against tuple, no theta and no randomness; poisoned table tuples are no part of the
+ *                                          table, a poisoned input fails; -> (LOOKUP, lookup, row, 1 if the input was poisoned else 0)
+ *                            PERMUTATION   every cell (j, i) of the permutation's columns must hold the value of the cell mapping[j][i] names;
+ *                                          -> (PERMUTATION, column position j, row i, column position of the partner)
+ *                            A failure record is four u32 (kind, index, row, aux).  *n_failures = the exact total; failures (host or device,
+ *                            capacity x 4 u32; NULL with capacity 0: a pure yes / no) gets the first min(capacity, total) records in ascending
+ *                            (kind, index, row) order -- the same on every run.  stage_ms (optional, 3 doubles): wall milliseconds of the
+ *                            gates, lookups and permutation stages.  An unsatisfied witness is NOT an error (GL355_OK, *n_failures > 0);
+ *                            GL355_E_INVALID_ARG for a malformed descriptor or a mapping entry out of range. */
+enum { GL355_PLONK_FAIL_GATE = 0, GL355_PLONK_FAIL_GATE_POISONED = 1, GL355_PLONK_FAIL_LOOKUP = 2, GL355_PLONK_FAIL_PERMUTATION = 3 };
+int32_t gl355_plonk_check_witness(gl355_ctx* ctx, const uint64_t* desc, uint64_t desc_words, const uint64_t* fixed_values, const uint32_t* mapping /* or NULL */,
+                                  const uint64_t* advice, const uint64_t* instances, const uint32_t* instance_lens, uint32_t* failures /* capacity x 4 */,
+                                  uint64_t capacity, uint64_t* n_failures, double* stage_ms /* 3 doubles or NULL */);
+
 /* ---- SURVEY 8(f) N4, the other half: the BN254 pairing and halo2_proofs' verify_proof::<_, VerifierSHPLONK<_>, _, _, SingleStrategy<_>> as
  * chip/native_chip/test_utils.rs:82-93 runs it on every proof create_proof_checked makes (verifier_api.rs:77-92).  Nothing here takes the
  * SRS secret: the verifier sees the public [s] G2 of the parameter set only, so proofs under ceremony powers

@@ -29,6 +29,7 @@
 #include <memory>
 
 #include "host_fr.h"
+#include "plonk_desc.h"
 #include "plonk_kernels.cuh"
 
 using namespace gl355;
@@ -37,10 +38,7 @@ namespace gl355 { void bn254_g1_add_host(const uint64_t a[8], const uint64_t b[8
 
 namespace {
 
-constexpr uint64_t PLK_MAGIC = 0x4B4C503535334C47ull;       // "GL355PLK"
-constexpr uint32_t PLK_HDR = 24;
-
-struct Lookup { std::vector<uint32_t> in_code, tab_code; };
+using Lookup = PlkLookup;
 
 inline uint32_t blocks(uint64_t n, uint32_t per = 256) { return (uint32_t)((n + per - 1) / per); }
 inline u256 to_dev(const Fr& a) { u256 r; for (int i = 0; i < 4; i++) { r.l[2 * i] = (uint32_t)a.l[i]; r.l[2 * i + 1] = (uint32_t)(a.l[i] >> 32); } return r; }
@@ -199,18 +197,7 @@ int32_t run_program(gl355_plonk_pk* pk, const uint32_t* d_code, uint32_t n_instr
     return GL355_OK;
 }
 
-// a lookup expression list that is one column at the current rotation (the reference's nine range checks, arithmetic_chip.rs:140-151):
-// the "compressed" column is the column itself, no program run, no copy.  -> (kind, column) or kind = 3
-std::pair<uint32_t, uint32_t> single_query(const gl355_plonk_pk* pk, const std::vector<uint32_t>& code) {
-    if (code.size() == 4 && code[0] == PLK_OP_EMIT) {
-        const uint32_t kind = code[2] >> 24, idx = code[2] & 0xFFFFFFu;
-        if (kind >= PLK_K_ADVICE && kind <= PLK_K_INSTANCE) {
-            const auto& q = pk->queries[kind - PLK_K_ADVICE][idx];
-            if (q.second == 0) return {kind - PLK_K_ADVICE, (uint32_t)q.first};
-        }
-    }
-    return {3u, 0u};
-}
+std::pair<uint32_t, uint32_t> single_query(const gl355_plonk_pk* pk, const std::vector<uint32_t>& code) { return plk_single_query(pk->queries, code); }
 
 // z[0] = *start, z[i] = z[i - 1] r[i - 1]
 int32_t running_product(Ctx* ctx, const uint64_t* r, uint64_t n, const uint64_t* d_start, uint64_t* z) {
@@ -463,7 +450,8 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
     if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail(GL355_E_HIP, "hipSetDevice failed");
     if (!desc || !g || !g_lagrange || !out || words < PLK_HDR) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: null or truncated argument");
     *out = nullptr;
-    if (desc[0] != PLK_MAGIC || desc[1] != 1) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: not a version-1 gl355 PLONK descriptor");
+    PlkDesc d;
+    if (const char* what = plk_parse_desc(desc, words, d)) return ctx->fail(GL355_E_INVALID_ARG, (std::string("plonk_keygen: ") + what).c_str());
     // keygen's temporaries (staged fixed values and mapping, the MSM scratch of 25 commitments, transform scratch: 66 GB at k = 23) are of no use to a
     // proof: back to the device, not into the context's cache -- on every return path (declared first, so it runs after the key's own destructor on
     // a failure), and only the blocks this call created: a context that already serves proofs keeps its warmed cache
@@ -471,69 +459,19 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
     std::unique_ptr<gl355_plonk_pk, int32_t (*)(gl355_plonk_pk*)> pk(new (std::nothrow) gl355_plonk_pk(), gl355_plonk_pk_destroy);
     if (!pk) return GL355_E_OOM;
     pk->ctx = ctx; pk->handle = h;
-    pk->k = (uint32_t)desc[2]; pk->n_advice = (uint32_t)desc[3]; pk->n_fixed = (uint32_t)desc[4]; pk->n_instance = (uint32_t)desc[5];
-    pk->n_perm = (uint32_t)desc[6]; pk->n_lookups = (uint32_t)desc[7]; pk->degree = (uint32_t)desc[8]; pk->bf = (uint32_t)desc[9];
-    const uint64_t nq[3] = {desc[10], desc[11], desc[12]}, n_consts = desc[13], gate_len = desc[14];
-    pk->n_gate_polys = (uint32_t)desc[15];
-    if (pk->k < 3 || pk->k > 24 || pk->n_advice > 256 || pk->n_fixed > 256 || pk->n_instance > 16 || pk->n_perm > 256 || pk->n_lookups > 64 || pk->degree < 3 ||
-        pk->degree > 10 || pk->bf < 3 || pk->bf > 64 || nq[0] > 1024 || nq[1] > 1024 || nq[2] > 64 || n_consts > 4096 || gate_len > (1u << 20))
-        return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: implausible circuit shape");
-    pk->n = 1ull << pk->k;
-    if (pk->n < pk->bf + 3ull) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: fewer rows than the blinding needs");
-    pk->usable = pk->n - (pk->bf + 1);
+    pk->k = d.k; pk->n_advice = d.n_advice; pk->n_fixed = d.n_fixed; pk->n_instance = d.n_instance; pk->n_perm = d.n_perm; pk->n_lookups = d.n_lookups;
+    pk->degree = d.degree; pk->bf = d.bf; pk->n_gate_polys = d.n_gate_polys; pk->n = d.n; pk->usable = d.usable; pk->digest = d.digest;
+    pk->perm_cols = std::move(d.perm_cols);
+    for (int kd = 0; kd < 3; kd++) pk->queries[kd] = std::move(d.queries[kd]);
+    pk->consts = std::move(d.consts); pk->gate_code = std::move(d.gate_code); pk->lookups = std::move(d.lookups);
     pk->n_pieces = pk->degree - 1;
     pk->ext_k = pk->k;
     while ((1ull << pk->ext_k) < pk->n * pk->n_pieces) pk->ext_k++;
     pk->chunk_len = pk->degree - 2;
     pk->n_sets = pk->n_perm ? (pk->n_perm + pk->chunk_len - 1) / pk->chunk_len : 0;
-    pk->digest = Fr::from_words(desc + 16);
     pk->desc.assign(desc, desc + words);
     if ((pk->n_fixed && !fixed_values) || (pk->n_perm && !mapping)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: fixed values / permutation mapping missing");
-    // ---- the rest of the descriptor
-    const uint64_t* p = desc + PLK_HDR;
-    const uint64_t* end = desc + words;
-    auto need = [&](uint64_t w) { return (uint64_t)(end - p) >= w; };
-    if (!need(pk->n_perm)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: truncated descriptor");
     const uint32_t kind_cols[3] = {pk->n_advice, pk->n_fixed, pk->n_instance};
-    for (uint32_t j = 0; j < pk->n_perm; j++, p++) {
-        const uint32_t kind = (uint32_t)(*p >> 32), idx = (uint32_t)*p;
-        if (kind > 2 || idx >= kind_cols[kind]) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: bad permutation column");
-        pk->perm_cols.push_back({kind, idx});
-    }
-    for (int kd = 0; kd < 3; kd++) {
-        if (!need(nq[kd])) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: truncated descriptor");
-        for (uint64_t q = 0; q < nq[kd]; q++, p++) {
-            const int32_t col = (int32_t)(*p >> 32), rot = (int32_t)(uint32_t)*p;
-            if (col < 0 || (uint32_t)col >= kind_cols[kd] || rot < -(int32_t)pk->bf - 1 || rot > (int32_t)pk->bf + 1) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: bad query");
-            pk->queries[kd].push_back({col, rot});
-        }
-    }
-    if (!need(4 * n_consts)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: truncated descriptor");
-    for (uint64_t c = 0; c < n_consts; c++, p += 4) pk->consts.push_back(Fr::from_words(p));
-    auto read_code = [&](uint64_t len, std::vector<uint32_t>& code) -> bool {
-        if (!need(2 * len)) return false;
-        code.assign(reinterpret_cast<const uint32_t*>(p), reinterpret_cast<const uint32_t*>(p) + 4 * len);
-        p += 2 * len;
-        for (uint64_t i = 0; i < len; i++) {                  // every operand in range: the evaluator trusts its program
-            const uint32_t op = code[4 * i], dst = code[4 * i + 1];
-            if (op > PLK_OP_MOV || dst >= PLK_MAX_REGS) return false;
-            for (int o = 0; o < (op == PLK_OP_ADD || op == PLK_OP_SUB || op == PLK_OP_MUL ? 2 : 1); o++) {
-                const uint32_t v = code[4 * i + 2 + o], kind = v >> 24, idx = v & 0xFFFFFFu;
-                if (kind == PLK_K_REG ? idx >= PLK_MAX_REGS : (kind == PLK_K_CONST ? idx >= n_consts : (kind > PLK_K_INSTANCE || idx >= nq[kind - PLK_K_ADVICE]))) return false;
-            }
-        }
-        return true;
-    };
-    if (!read_code(gate_len, pk->gate_code)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: bad gate program");
-    for (uint32_t l = 0; l < pk->n_lookups; l++) {
-        if (!need(2)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: truncated descriptor");
-        const uint64_t li = p[0], lt = p[1];
-        p += 2;
-        Lookup lk;
-        if (li > (1u << 16) || lt > (1u << 16) || !read_code(li, lk.in_code) || !read_code(lt, lk.tab_code)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: bad lookup program");
-        pk->lookups.push_back(std::move(lk));
-    }
-    if (p != end) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: descriptor length does not match its header");
     // every permutation column must be queried at rotation 0 (halo2's enable_equality does that): the verifier reads it at x
     for (auto& pc : pk->perm_cols) {
         bool ok = false;

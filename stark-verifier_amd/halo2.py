@@ -10,6 +10,8 @@ halo2_proofs itself is an un-vendored dependency of the reference (Cargo.lock); 
 `cs.blinding_factors()`).  Deviations, all on the host side of the boundary: selectors are plain fixed columns (halo2 compresses
 simple selectors into fewer fixed columns at keygen), one phase, no challenges-as-expressions.
 """
+import collections
+
 import numpy as np
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617     # bn256::Fr
@@ -670,11 +672,97 @@ class PlonkVerifier:
             pass
 
 
+# ---- MockProver (include/gl355.h: gl355_plonk_check_witness) ------------------------------------------------------------------------------
+FAIL_GATE, FAIL_GATE_POISONED, FAIL_LOOKUP, FAIL_PERMUTATION = range(4)
+FAIL_KIND_NAMES = ("gate", "gate (poisoned)", "lookup", "permutation")
+Failure = collections.namedtuple("Failure", "kind index row aux name position")
+Failure.__doc__ = """one record of gl355_plonk_check_witness (kind, index, row, aux) with, resolved on the host from the constraint system, `name`: the
+gate's or the lookup's name / the permutation column, and `position`: the polynomial's place within its gate (None for the other kinds)"""
+
+
+class NotSatisfied(AssertionError):
+    def __init__(self, failures, total, shown=8):
+        self.failures, self.total = failures, total
+        lines = [describe_failure(f) for f in failures[:shown]]
+        if total > len(lines):
+            lines.append("... and %d more" % (total - len(lines)))
+        super().__init__("the witness does not satisfy the circuit (%d failure%s):\n  %s" % (total, "" if total == 1 else "s", "\n  ".join(lines)))
+
+
+def describe_failure(f):
+    if f.kind in (FAIL_GATE, FAIL_GATE_POISONED):
+        what = "reads a blinding row (poisoned)" if f.kind == FAIL_GATE_POISONED else "is not zero"
+        return "gate '%s', polynomial %d (ordinal %d) %s at row %d" % (f.name, f.position, f.index, what, f.row)
+    if f.kind == FAIL_LOOKUP:
+        return "lookup '%s' (index %d): the input at row %d %s" % (f.name, f.index, f.row, "reads a blinding row (poisoned)" if f.aux else "is not in the table")
+    return "copy constraint: %s (permutation column %d) row %d differs from its partner in permutation column %d" % (f.name, f.index, f.row, f.aux)
+
+
+class MockProver:
+    """halo2's MockProver::run(k, &circuit, instances) + verify / assert_satisfied (verifier_api.rs:34-52, :72-73) on one GPU context through
+    gl355_plonk_check_witness: no SRS, no key.  fixed: [num_fixed][n][4] uint64, mapping: Assembly.mapping_array() or None (copy constraints
+    are then not checked); both numpy arrays or device pointers (ints)."""
+
+    def __init__(self, ctx, cs, k, fixed, mapping=None):
+        self.ctx, self.cs, self.k, self.n = ctx, cs, k, 1 << k
+        self.desc = export_desc(cs, k, 0)
+        if not isinstance(fixed, int):
+            fixed = np.ascontiguousarray(fixed, dtype=np.uint64)
+            assert fixed.shape == (cs.num_fixed, self.n, 4)
+        if mapping is not None and not isinstance(mapping, int):
+            mapping = np.ascontiguousarray(mapping, dtype=np.uint32)
+            assert mapping.shape == (len(cs.permutation), self.n, 2)
+        self.fixed, self.mapping = fixed, mapping
+        self.usable = self.n - (cs.blinding_factors() + 1)
+        self._polys = [(name, j) for name, polys in cs.gates for j in range(len(polys))]
+        self.stage_ms = None
+
+    def _resolve(self, rec):
+        kind, index, row, aux = (int(v) for v in rec)
+        if kind in (FAIL_GATE, FAIL_GATE_POISONED):
+            name, pos = self._polys[index]
+        elif kind == FAIL_LOOKUP:
+            name, pos = self.cs.lookups[index][0], None
+        else:
+            name, pos = repr(self.cs.permutation[index]), None
+        return Failure(kind, index, row, aux, name, pos)
+
+    def check(self, advice, instances, capacity=1 << 16):
+        """-> (the first min(capacity, total) records as a [.][4] uint32 array in (kind, index, row) order, the exact total)"""
+        import ctypes as C
+        ctx = self.ctx
+        if not isinstance(advice, int):
+            advice = np.ascontiguousarray(advice, dtype=np.uint64)
+            assert advice.shape == (self.cs.num_advice, self.n, 4)
+        assert len(instances) == self.cs.num_instance
+        flat = to_limbs([v for col in instances for v in col]) if any(len(c) for c in instances) else np.zeros((1, 4), dtype=np.uint64)
+        lens = np.array([len(c) for c in instances] + [0], dtype=np.uint32)
+        out = np.zeros((max(1, capacity), 4), dtype=np.uint32)
+        total = C.c_uint64(0)
+        ms = np.zeros(3, dtype=np.float64)
+        ptr = lambda a: None if a is None else (a if isinstance(a, int) else a.ctypes.data)       # noqa: E731
+        ctx.check(ctx.lib.gl355_plonk_check_witness(ctx.h, self.desc.ctypes.data, self.desc.size, ptr(self.fixed), ptr(self.mapping), ptr(advice), flat.ctypes.data,
+                                                    lens.ctypes.data, out.ctypes.data if capacity else None, capacity, C.byref(total), ms.ctypes.data))
+        self.stage_ms = dict(gates=float(ms[0]), lookups=float(ms[1]), permutation=float(ms[2]))
+        return out[:min(capacity, total.value)], total.value
+
+    def verify(self, advice, instances, capacity=1 << 16):
+        """MockProver::verify: the failures (at most `capacity` of them), [] for a satisfied witness"""
+        recs, _ = self.check(advice, instances, capacity)
+        return [self._resolve(r) for r in recs]
+
+    def assert_satisfied(self, advice, instances):
+        recs, total = self.check(advice, instances, 8)
+        if total:
+            raise NotSatisfied([self._resolve(r) for r in recs], total)
+
+
 class PlonkProver:
     """keygen_pk + create_proof of one circuit on one GPU context (chip/native_chip/test_utils.rs:57-95 through gl355_plonk_*).
     g / g_lagrange: numpy arrays (copied to the device) or device pointers (ints; must outlive the prover)."""
 
-    def __init__(self, ctx, cs, k, g, g_lagrange, fixed, mapping, digest=None):
+    def __init__(self, ctx, cs, k, g, g_lagrange, fixed, mapping, digest=None, checkable=False):
+        """checkable: keep `fixed` and `mapping` (host arrays or device pointers) so that prove(check=True) can run the MockProver"""
         import ctypes as C
         self.ctx, self.cs, self.k, self.n = ctx, cs, k, 1 << k
         self.desc = export_desc(cs, k, 0 if digest is None else digest)
@@ -682,6 +770,9 @@ class PlonkProver:
         mapping = np.ascontiguousarray(mapping, dtype=np.uint32)
         assert fixed.shape == (cs.num_fixed, self.n, 4) and mapping.shape == (len(cs.permutation), self.n, 2)
         self._keep = (g, g_lagrange)
+        # prove(check=True) needs the circuit's side again: kept only on request (at k = 23 the host arrays are several GB a caller may want to free)
+        self._check_args = (fixed, mapping) if checkable else None
+        self._mock = None
         ptr = lambda a: a if isinstance(a, int) else a.ctypes.data       # noqa: E731
         self.h = C.c_void_p()
         ctx.check(ctx.lib.gl355_plonk_keygen(ctx.h, self.desc.ctypes.data, self.desc.size, ptr(g), ptr(g_lagrange), fixed.ctypes.data, mapping.ctypes.data, C.byref(self.h)))
@@ -703,11 +794,19 @@ class PlonkProver:
         self.ctx.check(self.ctx.lib.gl355_plonk_pk_set_digest(self.h, d.ctypes.data))
         self.digest = digest
 
-    def prove(self, advice, instances, seed, want_trace=False, timed=False):
+    def prove(self, advice, instances, seed, want_trace=False, timed=False, check=False):
         """advice: [num_advice][n][4] uint64 (numpy, or a device pointer as int); instances: per instance column a list of integers;
-        seed: 32 bytes.  -> proof bytes (, trace dict)(, {stage: ms})"""
+        seed: 32 bytes.  check (a prover built with checkable=True): run MockProver.assert_satisfied on the witness first and raise
+        NotSatisfied instead of proving.
+        -> proof bytes (, trace dict)(, {stage: ms})"""
         import ctypes as C
         ctx = self.ctx
+        if check:
+            if self._mock is None:
+                if self._check_args is None:
+                    raise ValueError("prove(check=True) needs a PlonkProver built with checkable=True (it keeps the fixed columns and the mapping)")
+                self._mock = MockProver(ctx, self.cs, self.k, *self._check_args)
+            self._mock.assert_satisfied(advice, instances)
         if not isinstance(advice, int):
             advice = np.ascontiguousarray(advice, dtype=np.uint64)
             assert advice.shape == (self.cs.num_advice, self.n, 4)

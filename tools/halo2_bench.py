@@ -3,6 +3,10 @@ columns, 12 permutation columns, nine 16-bit range lookups, degree 6) at k = arg
 README.md:171-177, 505-511 s on 16 vCPUs) through gl355_plonk_keygen / gl355_plonk_prove on cuda:0, every proof checked by the restated
 halo2 verifier (tests/halo2_verifier.py; pairing check in the exponent under the known tau) and by the native one (gl355_plonk_verify under
 [tau] G2, host only: native_verified, native_verify_ms and its split into transcript + expressions / MSM / pairing).  One JSON line per k.
+`--check` with the k values: the same run also puts the same witness through gl355_plonk_check_witness (MockProver), inputs resident on the
+device, warm, best of five, once clean and once with one advice cell broken: check_witness_ms, its three stage times, the host-to-device time
+of its inputs on its own, and the ratio to create_proof + native verify -- the only way to tell a bad witness without it (the restated Python
+verifier is skipped in this mode).
 `--batch` instead of k values: the batch verifier's numbers at k = 12 (batches of 32 and 256, device against host MSM, the MSM alone over a
 range of term counts) and gl355_kzg_params_check at k = 20 and 23, one JSON line."""
 import importlib
@@ -19,7 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 TAU = 0x1234567890ABCDEF1234567890ABCDEF0123456789ABCDEF
 
 
-def run(gl, ctx, k, verify=True, reps=2):
+def run(gl, ctx, k, verify=True, reps=2, check=False):
     import torch
     h2 = importlib.import_module("stark-verifier_amd.halo2")
     ch = importlib.import_module("stark-verifier_amd.halo2_chips")
@@ -78,9 +82,47 @@ def run(gl, ctx, k, verify=True, reps=2):
         t0 = time.perf_counter()
         out["verified"] = bool(hv.verify(k, cs, vk, w.instance, best[2], TAU % h2.R))
         out["verify_host_s"] = round(time.perf_counter() - t0, 2)
+    if check:
+        out["check"] = run_check(ctx, h2, cs, cfg, w, k, adv, (out["create_proof_s"] * 1e3 + out["native_verify_ms"]))
     prover.close()
     del adv, g, gl_
     torch.cuda.empty_cache()
+    return out
+
+
+def run_check(ctx, h2, cs, cfg, w, k, adv, prove_verify_ms, reps=5):
+    """gl355_plonk_check_witness on the witness `adv` (device) that was just proved: device-resident inputs, one warm-up call, best of `reps`"""
+    import torch
+    out = {}
+    mapping = np.ascontiguousarray(w.assembly.mapping_array())
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fixed_d = torch.from_numpy(w.fixed.view(np.int64)).cuda()
+    map_d = torch.from_numpy(mapping.view(np.int32)).cuda()
+    adv_again = torch.from_numpy(w.advice.view(np.int64)).cuda()
+    torch.cuda.synchronize()
+    out["h2d_ms"] = round((time.perf_counter() - t0) * 1e3, 1)          # fixed + mapping + advice from pageable host memory: not part of check_witness_ms
+    del adv_again
+    mp = h2.MockProver(ctx, cs, k, fixed_d.data_ptr(), map_d.data_ptr())
+    broken = adv.clone()
+    row = 5
+    broken[cfg.arithmetic_config.c.index, row, 0] += 1                 # one cell of an active "base field constraint" row
+    torch.cuda.synchronize()
+    for name, a in (("clean", adv), ("broken", broken)):
+        mp.check(a.data_ptr(), w.instance, 64)                          # warm: the context's allocator holds the buffers afterwards
+        best = None
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            recs, total = mp.check(a.data_ptr(), w.instance, 64)
+            dt = (time.perf_counter() - t0) * 1e3
+            if best is None or dt < best[0]:
+                best = (dt, dict(mp.stage_ms))
+        out[name] = {"check_witness_ms": round(best[0], 2), "stage_ms": {k_: round(v, 2) for k_, v in best[1].items()}, "failures": int(total),
+                     "first": [h2.describe_failure(mp._resolve(r)) for r in recs[:2]]}
+    out["check_witness_ms"] = out["clean"]["check_witness_ms"]
+    out["prove_plus_native_verify_ms"] = round(prove_verify_ms, 1)
+    out["ratio_to_prove_plus_verify"] = round(out["check_witness_ms"] / prove_verify_ms, 4)
+    del fixed_d, map_d, broken
     return out
 
 
@@ -148,6 +190,7 @@ if __name__ == "__main__":
         print(json.dumps(run_batch(gl, ctx)), flush=True)
         ctx.close()
         sys.exit(0)
-    for k in [int(a) for a in sys.argv[1:]] or [17, 20, 23]:
-        print(json.dumps(run(gl, ctx, k)), flush=True)
+    check = "--check" in sys.argv[1:]
+    for k in [int(a) for a in sys.argv[1:] if a != "--check"] or [17, 20, 23]:
+        print(json.dumps(run(gl, ctx, k, verify=not check, check=check)), flush=True)
     ctx.close()
