@@ -1,4 +1,4 @@
-// BN254 base field (Fq) on nine 29-bit limbs for the MSM's bucket accumulation (bn254_curve.hip): the mixed Jacobian addition with
+// BN254 base field (Fq) on nine 29-bit limbs for the MSM's bucket accumulation (bn254_msm_acc.cuh, bn254_msm.hip): the mixed Jacobian addition with
 //   * products as carry-free column sums: every limb product lands in a 64-bit accumulator, 162 v_mad_u64_u32 + 58 shifts / adds / masks per
 //     product and no moves (plain C: the compiler's accumulate-in-place form), Montgomery radix R' = 2^261 -- 1.26x the 8 x 32-bit asm product
 //     as a bare product (tools/ubench/ubench_mont29.hip, profiles/r04_ubench_mont29.txt), and it is INLINED (its 9-word operands would

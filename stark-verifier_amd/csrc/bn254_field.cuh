@@ -1,6 +1,6 @@
 // BN254 (halo2curves bn256) field arithmetic for the device: Fr and Fq elements as 8 x 32-bit limbs in Montgomery form (R = 2^256), CIOS on
 // v_mad_u64_u32 (4 m < R for both primes, so products of operands < 2m stay < 2m without a final subtraction; sums and differences take one
-// conditional subtraction of 2m).  Shared by the curve / FFT kernels (bn254_curve.hip) and the PLONK prover kernels (plonk_bn254.hip).
+// conditional subtraction of 2m).  Shared by the curve units (bn254_fr_fft.hip, bn254_msm.hip, bn254_kzg.hip) and the PLONK prover kernels (plonk_bn254.hip).
 #pragma once
 #include "gl355_internal.h"
 
@@ -10,6 +10,13 @@
 #include "bn254_curve_tables.h"
 #include "bn254_addsub_asm.cuh"
 
+// gl355_bn254_g1_msm_prepare's handle (built in bn254_kzg.hip, read by bn254_msm.hip): the window multiples of a base set (device), see msm_table_build_kernel
+struct gl355_msm_bases {
+    gl355::Ctx* ctx;
+    uint32_t* tab;              // [wps][n][16]
+    uint64_t n;
+    uint32_t c, wps;
+};
 namespace gl355 {
 
 struct u256 { uint32_t l[8]; };
@@ -276,13 +283,16 @@ inline H256 h_root_of_unity(uint32_t log_n) {
 
 
 
-// ---- bn254_curve.hip: resident building blocks for the PLONK prover (plonk_bn254.hip) -------------------------------------------
+// ---- bn254_fr_fft.hip / bn254_msm.hip / bn254_kzg.hip: what the curve units call of each other, and the resident building blocks of the PLONK
+// prover (plonk_bn254.hip)
 int32_t bn254_fr_twiddles(Ctx* ctx, uint32_t log_n, bool inverse, uint64_t* tw /* n / 2 + 1 elements */);
 int32_t bn254_fr_power_table(Ctx* ctx, const uint64_t base[4], const uint64_t f[4], uint64_t count, uint64_t* tab);
 int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint64_t n_out, uint32_t log_n, const uint64_t* tw,
                           const uint64_t* pre, const uint64_t* post, const uint64_t scale_plain[4], uint64_t* work);
 // `bases` (gl355_bn254_g1_msm_prepare over the same points, or null): the table of the points' window multiples -- every window's digits then fall into ONE
-// set of buckets per scalar set (bn254_curve.hip, "shared buckets")
+// set of buckets per scalar set (bn254_msm.hip, "shared buckets").
+// max_bits: every scalar of the call is below 2^max_bits (256: no promise).  Windows above that hold only zero digits: they are not built,
+// sorted or reduced (range-check columns are 16-bit values, the arithmetic chip's operands 64-bit: 2 and 5 windows of 20 bits instead of 13)
 int32_t bn254_msm_bits(gl355_ctx* h, const uint64_t* points, const uint64_t* scalars, uint64_t n, uint32_t m, uint32_t max_bits, uint64_t* result,
                        const gl355_msm_bases* bases = nullptr);
 int32_t bn254_fr_ntt_mont_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t* pre);
@@ -290,6 +300,8 @@ int32_t bn254_fr_ntt_mont_coset_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in,
                                     uint64_t* btw /* n elements */, bool fill);
 int32_t bn254_fr_ntt_mont_from_bitrev(Ctx* ctx, const uint64_t* in, uint64_t* out, uint64_t n_out, uint32_t log_n, const uint64_t* tw, const uint64_t* post,
                                       const uint64_t scale_plain[4]);
-// Q[i] = sum_{j > i} A[j] z^(j - i - 1), E = sum_j A[j] z^j on device arrays (see the division kernels)
+// in: 2^log_in values, out: n_out values of the 2^log_n-point transform, device arrays of plain integers; shift == nullptr: the plain transform
+int32_t fr_ntt_run(Ctx* ctx, const uint64_t* in, uint32_t log_in, uint64_t* out, uint64_t n_out, uint32_t log_n, int32_t inverse, const uint64_t* shift);
+// Q[i] = sum_{j > i} A[j] z^(j - i - 1), E = sum_j A[j] z^j on device arrays (see the division kernels of bn254_kzg.hip)
 int32_t kzg_divide(Ctx* ctx, const uint64_t* A, uint64_t m, const H256& z, int a_is_mont, uint64_t* Q, int q_plain, uint64_t* E_mont);
 }  // namespace gl355

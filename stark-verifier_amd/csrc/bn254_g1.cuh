@@ -1,5 +1,5 @@
 // BN254 G1 point arithmetic for the device: Jacobian coordinates over Fq in Montgomery form (bn254_field.cuh).  Shared by the MSM /
-// fixed-base kernels (bn254_curve.hip) and the group FFT (bn254_g1_fft.hip).
+// fixed-base kernels (bn254_msm.hip, bn254_kzg.hip) and the group FFT (bn254_g1_fft.hip).
 #pragma once
 #include "bn254_field.cuh"
 

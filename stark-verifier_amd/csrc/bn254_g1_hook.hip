@@ -1,6 +1,6 @@
 // The j_* chains of gl355_bn254_g1_chain (GL355_BN_CHAIN_J, a test hook): j_add / j_madd / j_double of bn254_g1.cuh in a translation unit of
-// their own -- called from bn254_curve.hip these __noinline__ functions would be compiled for one more caller there, and the MSM / fixed-base
-// kernels that call them came out with other register counts.
+// their own -- a __noinline__ function is compiled once per unit, for all of its callers there, and the MSM / fixed-base kernels that call these
+// came out with other register counts when this hook was one more caller in their unit.
 #include "gl355_internal.h"
 #include "bn254_hook.cuh"
 

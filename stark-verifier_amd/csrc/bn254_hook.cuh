@@ -1,5 +1,5 @@
 // Record layouts and limb helpers of the BN254 test hooks (include/gl355.h "test hooks"): gl355_bn254_arith_batch / gl355_bn254_g1_chain in
-// bn254_curve.hip, their j_* chains in bn254_g1_hook.hip, the hasher's fr_enter / fr_leave in merkle_bn254.hip.  Test entry points only.
+// bn254_curve_hook.hip, their j_* chains in bn254_g1_hook.hip, the hasher's fr_enter / fr_leave in merkle_bn254.hip.  Test entry points only.
 #pragma once
 #include "bn254_f29.cuh"
 #include "bn254_g1.cuh"

@@ -138,7 +138,7 @@ int32_t commit_columns(gl355_plonk_pk* pk, const uint64_t* bases, const uint64_t
     tail = std::min(tail, n);
     const uint64_t nt = n - tail;
     const gl355_msm_bases* tab = bases == pk->g ? pk->tab_g : (bases == pk->g_lagrange ? pk->tab_gl : nullptr);
-    // <= 2^27 scalars and <= 64 sets per batched MSM (bn254_curve.hip)
+    // <= 2^27 scalars and <= 64 sets per batched MSM (bn254_msm.hip)
     const uint32_t per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(16, (1ull << 27) / n));
     Scratch plain(ctx);
     GL355_TRY(plain.get((size_t)sets * n * 32 + (size_t)sets * nt * 32 + (size_t)sets * 32));

@@ -254,7 +254,7 @@ __global__ void __launch_bounds__(64) plk_batch_div_kernel(const uint64_t* num, 
         store256(out + 4 * i, m_mul<F_R>(load256(num + 4 * i), dinv));
     }
 }
-// Running product: z[0] = start, z[i] = start * prod_{j < i} r[j] (i < n).  Levels like the division of bn254_curve.hip: (1) a lane's chunk
+// Running product: z[0] = start, z[i] = start * prod_{j < i} r[j] (i < n).  Levels like the division of bn254_kzg.hip: (1) a lane's chunk
 // product, (2) the same problem on the chunk products, (3) a lane walks its chunk from its start value.
 constexpr uint32_t PLK_SCAN_CHUNK = 64;
 __global__ void plk_scan_chunk_kernel(const uint64_t* r, uint64_t n, uint64_t* P) {

@@ -10,7 +10,7 @@
 //                 -- the quotient's pieces, the key's commitments and [1] G1 included -- so the group work is a single MSM
 //   pairing       e(L + u h2, G2) e(-h2, [s] G2) = 1 (host_bn254_pairing.cpp).  Nothing here takes the SRS secret.
 // A batch keeps the terms of its proofs apart, weighs proof b with a 128-bit rho_b and sums everything in one MSM -- on the device
-// (gl355_bn254_g1_msm, bn254_curve.hip) from PLONK_VERIFY_DEVICE_MSM_MIN terms on -- and one two-pair pairing check.
+// (gl355_bn254_g1_msm, bn254_msm.hip) from PLONK_VERIFY_DEVICE_MSM_MIN terms on -- and one two-pair pairing check.
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>

@@ -1,5 +1,5 @@
 """Plain-integer restatement of the BN254 limb arithmetic the device runs (stark-verifier_amd/csrc/bn254_field.cuh, bn254_f29.cuh, the point
-formulas of bn254_g1.cuh and bn254_curve.hip) and the operands that sit at the edges of its lazy bounds.  Used by tests/test_bn254_limbs.py
+formulas of bn254_g1.cuh and bn254_msm_acc.cuh) and the operands that sit at the edges of its lazy bounds.  Used by tests/test_bn254_limbs.py
 (the restatement itself, on the CPU) and tests/test_gpu_bn254_arith.py (the device functions against it, through the test hooks of
 include/gl355.h).  Nothing here is shared with the kernels: moduli and constants are derived from the two primes."""
 import ctypes as C
@@ -172,7 +172,7 @@ BOUNDS = {
     # f29_lower: "any value below 2^261 -> < 1.3 q"
     "f29_lower_in": R261,
 }
-# bn254_curve.hip, per coordinate, "n" = limbs normalised:
+# bn254_msm_acc.cuh, per coordinate, "n" = limbs normalised:
 #   struct jac29: "x < 5.2 n, y < 3.3 n, z < 1.3 n" (the bucket accumulators, Jacobian and XYZZ: "ZZ, ZZZ are products: < 1.3")
 #   jac29_same_x: x3 "< 5.1", y = y3 * one and z = (2 y) * one are products
 #   reduction: "inputs (X, Y, Z) < 12 q give X3 < 5.2, Y3 < 3.3, Z3 < 1.1 (addition) and X3 < 9.3, Y3 < 1.2, Z3 < 3.8 (doubling: ... < 2.1 for
