@@ -820,6 +820,24 @@ int32_t gl355_bn254_arith_batch(gl355_ctx* ctx, int32_t op, const uint32_t* a /*
 int32_t gl355_bn254_g1_chain(gl355_ctx* ctx, int32_t form, const uint32_t* operands /* n_operands x 28 */, uint32_t n_operands,
                              const uint32_t* steps /* n_chains x n_steps */, uint32_t n_chains, uint32_t n_steps, uint32_t* trace /* n_chains x n_steps x 40 */);
 
+
+/* ---- test hooks: the MSM under a caller's bit length, and the prover's column commitments (tests/test_gpu_msm_bits.py).  They wrap shipped code
+ * only, and no product path calls them.
+ *   gl355_bn254_g1_msm_bits         n_sets MSMs over n points as gl355_bn254_g1_msm_batch, planned for scalars below 2^max_bits (256: no promise) the way
+ *                                   the prover's commitments are: fewer windows, or one window of max_bits + 1 bits.  With `bases` (gl355_bn254_g1_msm_prepare
+ *                                   over n points) `points` is ignored, as in gl355_bn254_g1_msm_prepared.  plan_out (or NULL) gets the plan that ran:
+ *                                   window bits c, windows per scalar set, 1 for the one-window form, 1 for the sort in two levels.
+ *                                   GL355_E_INVALID_ARG when a scalar on a non-identity base does not fit the plan's signed digits (a carry out of
+ *                                   the last window, or bits at and above windows x c): never a wrong sum.
+ *   gl355_plonk_pk_commit_columns   the commitments of `sets` columns of 2^k plain integers below r over the key's g (which = 0) or g_lagrange (1), by the
+ *                                   prover's own path: bit lengths measured, runs of neighbouring columns of one 20-bit class batched under that length,
+ *                                   the key's prepared tables where it has them, rows >= tail (~0: none) committed apart and added.  results: host memory.
+ *                                   GL355_E_INVALID_ARG for a null pk / columns / results, which > 1, or tail > 2^k other than ~0. */
+int32_t gl355_bn254_g1_msm_bits(gl355_ctx* ctx, const uint64_t* points, const gl355_msm_bases* bases /* prepared, or NULL */, const uint64_t* scalars, uint64_t n,
+                                uint32_t n_sets, uint32_t max_bits, uint64_t* results /* n_sets x 8 */, uint32_t plan_out[4] /* or NULL */);
+int32_t gl355_plonk_pk_commit_columns(gl355_plonk_pk* pk, uint32_t which, const uint64_t* columns /* [sets][2^k][4] */, uint32_t sets, uint64_t tail,
+                                      uint64_t* results /* sets x 8 */);
+
 #ifdef __cplusplus
 }
 #endif

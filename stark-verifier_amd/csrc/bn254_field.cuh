@@ -291,10 +291,11 @@ int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t*
                           const uint64_t* pre, const uint64_t* post, const uint64_t scale_plain[4], uint64_t* work);
 // `bases` (gl355_bn254_g1_msm_prepare over the same points, or null): the table of the points' window multiples -- every window's digits then fall into ONE
 // set of buckets per scalar set (bn254_msm.hip, "shared buckets").
-// max_bits: every scalar of the call is below 2^max_bits (256: no promise).  Windows above that hold only zero digits: they are not built,
+// max_bits: every scalar of the call is below 2^max_bits (256: no promise; a scalar on a non-identity base that breaks the promise further than the
+// plan's digits can hold is GL355_E_INVALID_ARG, never a wrong sum).  Windows above that hold only zero digits: they are not built,
 // sorted or reduced (range-check columns are 16-bit values, the arithmetic chip's operands 64-bit: 2 and 5 windows of 20 bits instead of 13)
 int32_t bn254_msm_bits(gl355_ctx* h, const uint64_t* points, const uint64_t* scalars, uint64_t n, uint32_t m, uint32_t max_bits, uint64_t* result,
-                       const gl355_msm_bases* bases = nullptr);
+                       const gl355_msm_bases* bases = nullptr, uint32_t* plan_out /* c, wps, one window, two-level sort */ = nullptr);
 int32_t bn254_fr_ntt_mont_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t* pre);
 int32_t bn254_fr_ntt_mont_coset_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t shift_plain[4],
                                     uint64_t* btw /* n elements */, bool fill);

@@ -34,7 +34,8 @@ struct MsmArgs {
     uint64_t* result;           // [8]
     // buckets of more than MSM_BIG points (skewed scalars: selector columns of 0 / 1, constants, the sparse top window) are summed by
     // whole workgroups instead of one lane
-    uint32_t* big_counters;     // [4]           work items, big buckets; of those, the items / buckets of more than MSM_MID points (workgroup path)
+    uint32_t* big_counters;     // [5]           work items, big buckets; of those, the items / buckets of more than MSM_MID points (workgroup path);
+                                //               [4] != 0: some scalar does not fit the plan's wps signed digits of c bits (msm_digits_overflow)
     uint32_t* big_items;        // [max_items][2] bucket id, first point of the item (relative to the bucket)
     uint32_t* big_buckets;      // [max_big][3]  bucket id, first item, items
     uint32_t* big_partial;      // [max_items][24]
@@ -104,6 +105,15 @@ GL_DEV uint32_t msm_wave_inc(uint32_t* counter, uint32_t key, bool active) {
     if (!done) slot = atomicAdd(counter + key, 1u);
     return slot;
 }
+// what wps signed digits of c bits cannot hold: the carry out of the last window, or scalar bits at and above wps * c.  A plan cut to the caller's
+// max_bits (msm_plan) silently dropped both; with max_bits = 256 neither exists (wps * c > 256, and the top window's 256 mod c < c - 1 bits never carry)
+GL_DEV bool msm_digits_overflow(const uint64_t* k, uint32_t bit, uint32_t carry) {
+    if (bit >= 256) return carry != 0;
+    const uint32_t limb = bit >> 6;
+    uint64_t v = k[limb] >> (bit & 63);
+    for (uint32_t l = limb + 1; l < 4; l++) v |= k[l];
+    return (v | carry) != 0;
+}
 __global__ void msm_prepare_kernel(MsmArgs a) {          // points to Montgomery form + digit histograms
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     bool live = i < a.n;                                  // every lane stays for the wave-level combining below
@@ -125,6 +135,7 @@ __global__ void msm_prepare_kernel(MsmArgs a) {          // points to Montgomery
             const uint32_t mag = msm_signed_digit(k, w, a.c, carry, neg);
             (void)msm_wave_inc(a.hist + ((uint64_t)(set * a.wps + w) << a.cb), mag ? mag - 1 : 0, live && mag != 0);
         }
+        if (live && msm_digits_overflow(k, a.wps * a.c, carry)) atomicOr(a.big_counters + 4, 1u);      // (the identity's scalar does not count)
     }
 }
 // per window: exclusive scan of the 2^cb counts (one workgroup), offsets copied to the cursors
@@ -205,6 +216,7 @@ __global__ void msm_digits_kernel(MsmArgs a) {            // points to Montgomer
             const uint32_t mag = msm_signed_digit(k, w, a.c, carry, neg);
             a.dig[(uint64_t)(set * a.wps + w) * a.n + i] = ident ? 0u : (mag | (neg && mag ? 0x80000000u : 0u));
         }
+        if (!ident && msm_digits_overflow(k, a.wps * a.c, carry)) atomicOr(a.big_counters + 4, 1u);
     }
 }
 __global__ void __launch_bounds__(256) msm_coarse_count_kernel(MsmArgs a) {
@@ -667,7 +679,7 @@ struct MsmPlan {
     uint64_t rn;                // the real number of points
     uint64_t n, W;              // points per window and windows as those kernels see them
     uint64_t nb, nbin;          // buckets per window, coarse bins of the two-level sort
-    bool two_level;
+    bool two_level, one_window;
     std::vector<MsmLv> levels;  // reduction levels: groups of 8 items, the last level takes what is left
     uint64_t lvl_words;
     uint64_t fb_max_reg, fb_max_items;
@@ -691,6 +703,7 @@ static int32_t msm_plan(Ctx* ctx, uint64_t n, uint32_t m, uint32_t max_bits, con
     // scalars shorter than a window (range-check limbs): ONE window just wide enough that no digit reaches 2^(c-1), so nothing is negative, nothing carries
     // and the carry window does not exist -- 2^16 buckets for a 16-bit column instead of two windows of 2^19 (two-level sort from 12 bits on)
     const bool one_window = !bases && max_bits + 1 < a.c && max_bits + 1 >= 12;
+    pl.one_window = one_window;
     if (one_window) a.c = max_bits + 1;
     a.cb = a.c - 1;
     a.wps = 256 / a.c + 1;                                       // signed digits: the carry out of bit 255 needs a window of its own
@@ -734,7 +747,7 @@ static int32_t msm_plan(Ctx* ctx, uint64_t n, uint32_t m, uint32_t max_bits, con
     a.max_items = (uint32_t)(W * n / MSM_MID_SLICE + a.max_big + 1);      // (mid-size buckets: items of MSM_MID_SLICE points)
     pl.fb_max_reg = W * n / MSM_FINE_BIG + 1; pl.fb_max_items = W * n / MSM_FINE_SLICE + pl.fb_max_reg + 1;      // (sums over all pairs)
     const uint64_t sort_words = pl.two_level ? 3 * W * n + 3 * W * nbin + 2 + 2 + 2 * pl.fb_max_reg + 2 * pl.fb_max_items : 0;
-    pl.words32 = (bases ? 0 : n * 16) + 3 * W * nb + W * n + W * nb * 24 + (MSM_SIZE_BINS + 4) + pl.lvl_words + 64 +
+    pl.words32 = (bases ? 0 : n * 16) + 3 * W * nb + W * n + W * nb * 24 + (MSM_SIZE_BINS + 5) + pl.lvl_words + 64 +
                  2ull * a.max_items + 3ull * a.max_big + 24ull * a.max_items + sort_words;
     return GL355_OK;
 }
@@ -744,7 +757,7 @@ static int32_t msm_carve(Ctx* ctx, MsmPlan& pl, uint32_t* p, uint32_t* tab) {
     const uint64_t n = pl.n, W = pl.W, nb = pl.nb, nbin = pl.nbin;
     if (tab) a.pm = tab; else { a.pm = p; p += n * 16; }
     a.hist = p; p += W * nb;
-    a.size_hist = p; a.big_counters = p + MSM_SIZE_BINS; p += MSM_SIZE_BINS + 4;      // behind the histograms: cleared with them
+    a.size_hist = p; a.big_counters = p + MSM_SIZE_BINS; p += MSM_SIZE_BINS + 5;      // behind the histograms: cleared with them
     a.cursor = p; p += W * nb;
     a.order = p; p += W * nb;
     a.idx = p; p += W * n;
@@ -767,7 +780,7 @@ static int32_t msm_carve(Ctx* ctx, MsmPlan& pl, uint32_t* p, uint32_t* tab) {
         GL355_HIP(ctx, hipMemsetAsync(a.coarse_cnt, 0, 2 * W * nbin * 4, ctx->stream));
         GL355_HIP(ctx, hipMemsetAsync(a.fb_counters, 0, 8, ctx->stream));
     }
-    GL355_HIP(ctx, hipMemsetAsync(a.hist, 0, (W * nb + (MSM_SIZE_BINS + 4)) * 4, ctx->stream));
+    GL355_HIP(ctx, hipMemsetAsync(a.hist, 0, (W * nb + (MSM_SIZE_BINS + 5)) * 4, ctx->stream));
     return GL355_OK;
 }
 // hist / cursor (start and end of every bucket's range) and idx (the point indices by bucket)
@@ -832,7 +845,7 @@ static void msm_launch_reduce(Ctx* ctx, MsmPlan& pl) {
 }
 
 int32_t gl355::bn254_msm_bits(gl355_ctx* h, const uint64_t* points, const uint64_t* scalars, uint64_t n, uint32_t m, uint32_t max_bits, uint64_t* result,
-                              const gl355_msm_bases* bases) {
+                              const gl355_msm_bases* bases, uint32_t* plan_out) {
     Ctx* ctx = ctx_of(h);
     if (!ctx) return GL355_E_INVALID_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail(GL355_E_HIP, "hipSetDevice failed");
@@ -849,6 +862,7 @@ int32_t gl355::bn254_msm_bits(gl355_ctx* h, const uint64_t* points, const uint64
     }
     MsmPlan pl;
     GL355_TRY(msm_plan(ctx, n, m, max_bits, bases, pl));
+    if (plan_out) { plan_out[0] = pl.a.c; plan_out[1] = pl.a.wps; plan_out[2] = pl.one_window; plan_out[3] = pl.two_level; }
     Staged sp(ctx), ss(ctx);
     if (!bases) GL355_TRY(sp.open(points, n * 64, 1));
     GL355_TRY(ss.open(scalars, (uint64_t)m * n * 32, 1));
@@ -867,12 +881,13 @@ int32_t gl355::bn254_msm_bits(gl355_ctx* h, const uint64_t* points, const uint64
     const MsmArgs& a = pl.a;
     const uint64_t W = pl.W;
     std::vector<uint32_t> hs(W * 24), hw(W * 24, 0);
-    uint32_t big_used[2] = {0, 0};
-    GL355_HIP(ctx, ctx->d2h(big_used, a.big_counters, 8));
+    uint32_t big_used[5] = {0, 0, 0, 0, 0};
+    GL355_HIP(ctx, ctx->d2h(big_used, a.big_counters, sizeof big_used));
     GL355_HIP(ctx, ctx->d2h(hs.data(), pl.fin_s, W * 96));
     if (pl.fin_w) GL355_HIP(ctx, ctx->d2h(hw.data(), pl.fin_w, W * 96));
     GL355_HIP(ctx, ctx->wait());
     if (big_used[0] > a.max_items || big_used[1] > a.max_big) return ctx->fail(GL355_E_HIP, "bn254_g1_msm: big-bucket work list overflow (internal bound)");
+    if (big_used[4]) return ctx->fail(GL355_E_INVALID_ARG, "bn254_g1_msm: a scalar has more bits than max_bits promised (the plan's signed digits cannot hold it)");
     const bool have_w = !pl.levels.empty();
     std::vector<uint64_t> res(8ull * m);
     for (uint32_t set = 0; set < m; set++)
@@ -895,6 +910,11 @@ int32_t gl355_bn254_g1_msm_prepared(gl355_ctx* h, const gl355_msm_bases* bases, 
     if (!ctx) return GL355_E_INVALID_ARG;
     if (!bases) return ctx->fail(GL355_E_INVALID_ARG, "bn254_g1_msm_prepared: null bases");
     return bn254_msm_bits(h, nullptr, scalars, bases->n, n_sets, 256, results, bases);
+}
+// test hook (tests/test_gpu_msm_bits.py): bn254_msm_bits under a caller's max_bits, and the plan it ran
+int32_t gl355_bn254_g1_msm_bits(gl355_ctx* h, const uint64_t* points, const gl355_msm_bases* bases, const uint64_t* scalars, uint64_t n, uint32_t n_sets,
+                                uint32_t max_bits, uint64_t* results, uint32_t plan_out[4]) {
+    return bn254_msm_bits(h, bases ? nullptr : points, scalars, n, n_sets, max_bits, results, bases, plan_out);
 }
 int32_t gl355_bn254_g1_msm_bases_free(gl355_ctx* h, gl355_msm_bases* bases) {
     Ctx* ctx = ctx_of(h);

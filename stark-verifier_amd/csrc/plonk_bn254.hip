@@ -653,6 +653,25 @@ int32_t gl355_plonk_pk_export_quotient(gl355_plonk_pk* pk, uint64_t* host_out) {
     return GL355_OK;
 }
 
+// test hook (tests/test_gpu_msm_bits.py): the prover's own commit_columns over the key's bases and tables, on columns of the caller's choosing
+int32_t gl355_plonk_pk_commit_columns(gl355_plonk_pk* pk, uint32_t which, const uint64_t* columns, uint32_t sets, uint64_t tail, uint64_t* results) {
+    if (!pk) return GL355_E_INVALID_ARG;
+    Ctx* ctx = pk->ctx;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail(GL355_E_HIP, "hipSetDevice failed");
+    if (!columns || !results) return ctx->fail(GL355_E_INVALID_ARG, "plonk_pk_commit_columns: null argument");
+    if (which > 1) return ctx->fail(GL355_E_INVALID_ARG, "plonk_pk_commit_columns: which is 0 (g) or 1 (g_lagrange)");
+    if (tail > pk->n && tail != ~0ull) return ctx->fail(GL355_E_INVALID_ARG, "plonk_pk_commit_columns: tail beyond the rows");
+    if (!sets) return GL355_OK;
+    const uint64_t total = (uint64_t)sets * pk->n;
+    Staged sc(ctx);
+    GL355_TRY(sc.open(columns, total * 32, 1));
+    Scratch mont(ctx);
+    GL355_TRY(mont.get(total * 32));
+    hipLaunchKernelGGL(plk_to_mont_kernel, dim3(blocks(total)), dim3(256), 0, ctx->stream, sc.as<uint64_t>(), mont.as<uint64_t>(), total);
+    GL355_HIP(ctx, hipGetLastError());
+    return commit_columns(pk, which ? pk->g_lagrange : pk->g, mont.as<uint64_t>(), sets, results, tail);
+}
+
 int32_t gl355_plonk_pk_set_digest(gl355_plonk_pk* pk, const uint64_t digest[4]) {
     if (!pk || !digest) return GL355_E_INVALID_ARG;
     pk->digest = Fr::from_words(digest);
