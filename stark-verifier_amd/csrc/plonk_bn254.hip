@@ -17,6 +17,7 @@
 //                y, division by X^n - 1; one inverse FFT over the extended domain; split into `degree - 1` pieces, commit
 //   evaluations  every queried polynomial at x omega^rot (block Horner + reduction)
 //   SHPLONK      rotation sets, sum_j y^j (p_ij - r_ij) / Z_i combined with v, commit; linearisation at u, division by (X - u), commit
+// One member function of `Proving` per stage; the opening plan (query order, rotation sets) is plonk_openings.h, shared with plonk_verifier.cpp.
 // The transcript (Keccak-256, host_keccak.cpp) and a few dozen field operations per stage run on the host.  Byte-for-byte the same proof as
 // oracle/halo2_model.py on the same (witness, seed) -- tests/test_gpu_halo2.py -- and accepted by the restated verifier.
 #include <cstring>
@@ -31,6 +32,7 @@
 #include "host_fr.h"
 #include "plonk_desc.h"
 #include "plonk_kernels.cuh"
+#include "plonk_openings.h"
 
 using namespace gl355;
 
@@ -38,26 +40,18 @@ namespace gl355 { void bn254_g1_add_host(const uint64_t a[8], const uint64_t b[8
 
 namespace {
 
-using Lookup = PlkLookup;
-
 inline uint32_t blocks(uint64_t n, uint32_t per = 256) { return (uint32_t)((n + per - 1) / per); }
 inline u256 to_dev(const Fr& a) { u256 r; for (int i = 0; i < 4; i++) { r.l[2 * i] = (uint32_t)a.l[i]; r.l[2 * i + 1] = (uint32_t)(a.l[i] >> 32); } return r; }
 
 }  // namespace
 
-struct gl355_plonk_pk {
+struct gl355_plonk_pk : PlkDesc {                                         // the parsed descriptor, and what keygen derives from it
     Ctx* ctx = nullptr;
     gl355_ctx* handle = nullptr;
-    uint32_t k = 0, n_advice = 0, n_fixed = 0, n_instance = 0, n_perm = 0, n_lookups = 0, degree = 0, bf = 0, n_gate_polys = 0;
-    uint32_t ext_k = 0, n_pieces = 0, n_sets = 0, chunk_len = 0;
-    uint64_t n = 0, usable = 0;
-    Fr digest;
+    uint32_t ext_k = 0, n_pieces = 0, n_sets = 0, chunk_len = 0, kind_cols[3] = {0, 0, 0} /* advice, fixed, instance */;
+    std::vector<Fr> coset_base;                                           // zeta ext_omega^c: the cosets of the extended domain that evaluate_h visits
     std::vector<uint64_t> desc;                                           // the descriptor as given (gl355_plonk_vk_from_pk hands it to the verifier)
-    std::vector<std::pair<uint32_t, uint32_t>> perm_cols;                 // (kind, index)
-    std::vector<std::pair<int32_t, int32_t>> queries[3];                  // (column, rotation)
-    std::vector<Fr> consts;
-    std::vector<uint32_t> gate_code;
-    std::vector<Lookup> lookups;
+    std::vector<std::pair<uint32_t, uint32_t>> lk_single;                 // plk_single_query of every lookup's input (2 l) and table (2 l + 1) expressions
     std::vector<void*> owned;                                             // device allocations of the key
     // device, Montgomery: values and coefficient forms
     uint64_t *fixed_vals = nullptr, *fixed_polys = nullptr, *sigma_vals = nullptr, *sigma_polys = nullptr, *l_polys = nullptr /* l0 | l_last | l_active */;
@@ -77,7 +71,7 @@ struct gl355_plonk_pk {
     std::vector<uint32_t*> d_lk_code;                                     // per lookup: input program, table program
     int32_t* d_q[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
     std::vector<uint64_t> fixed_commitments, sigma_commitments;           // host, affine
-    int32_t dalloc(size_t bytes, void** out) { GL355_TRY(ctx->alloc(bytes, out)); owned.push_back(*out); return GL355_OK; }
+    template <typename T> int32_t dalloc(size_t bytes, T** out) { void* p = nullptr; GL355_TRY(ctx->alloc(bytes, &p)); owned.push_back(p); *out = static_cast<T*>(p); return GL355_OK; }
 };
 
 namespace {
@@ -106,25 +100,31 @@ int32_t upload(Ctx* ctx, void* dst, const void* src, size_t bytes) {
     if (!ptr_is_device(src)) GL355_HIP(ctx, ctx->wait());          // pageable source: the buffer may go away
     return GL355_OK;
 }
-int32_t fr_to_device(Ctx* ctx, const std::vector<Fr>& v, uint64_t* d) {
-    if (v.empty()) return GL355_OK;
-    GL355_HIP(ctx, hipMemcpyAsync(d, v.data(), v.size() * 32, hipMemcpyHostToDevice, ctx->stream));
+// a caller's columns (host or device, canonical integers) in Montgomery form at `dst`
+int32_t columns_to_mont(Ctx* ctx, const uint64_t* src, uint64_t count, uint64_t* dst) {
+    Staged st(ctx);
+    GL355_TRY(st.open(src, count * 32, 1));
+    hipLaunchKernelGGL(plk_to_mont_kernel, dim3(blocks(count)), dim3(256), 0, ctx->stream, st.as<uint64_t>(), dst, count);
+    GL355_HIP(ctx, hipGetLastError());
     GL355_HIP(ctx, ctx->wait());
     return GL355_OK;
 }
-int32_t ptrs_to_device(Ctx* ctx, const std::vector<const uint64_t*>& v, const uint64_t** d) {
+// a small host array (field elements, pointers, program words) to the device
+template <typename T> int32_t to_device(Ctx* ctx, const std::vector<T>& v, void* d) {
     if (v.empty()) return GL355_OK;
-    GL355_HIP(ctx, hipMemcpyAsync((void*)d, v.data(), v.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    GL355_HIP(ctx, hipMemcpyAsync(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     GL355_HIP(ctx, ctx->wait());
     return GL355_OK;
 }
-void words_of(const Fr& a, uint64_t w[4]) { a.to_words(w); }
 
-// values (n) -> coefficients: inverse transform with the 1 / n
-int32_t lagrange_to_coeff(gl355_plonk_pk* pk, const uint64_t* vals, uint64_t* coeffs, uint64_t* work) {
+// values (n) -> coefficients of `count` neighbouring columns: inverse transform with the 1 / n; the coefficient forms `dst_stride` words apart (0: neighbouring too)
+int32_t to_coeffs(gl355_plonk_pk* pk, const uint64_t* vals, uint64_t* coeffs, uint32_t count, uint64_t* work, uint64_t dst_stride = 0) {
+    const uint64_t n = pk->n;
     uint64_t ninv[4];
-    Fr::from_u64(pk->n).inv().to_words(ninv);
-    return bn254_fr_ntt_mont(pk->ctx, vals, pk->n, coeffs, pk->n, pk->k, pk->tw_inv, nullptr, nullptr, ninv, work);
+    Fr::from_u64(n).inv().to_words(ninv);
+    for (uint32_t c = 0; c < count; c++)
+        GL355_TRY(bn254_fr_ntt_mont(pk->ctx, vals + 4ull * c * n, n, coeffs + (dst_stride ? dst_stride : 4 * n) * c, n, pk->k, pk->tw_inv, nullptr, nullptr, ninv, work));
+    return GL355_OK;
 }
 
 // commitments of `sets` columns (Montgomery scalars, [sets][n]) over n bases: plain copies of the scalars, their bit lengths (one OR
@@ -196,8 +196,6 @@ int32_t run_program(gl355_plonk_pk* pk, const uint32_t* d_code, uint32_t n_instr
     GL355_HIP(pk->ctx, hipGetLastError());
     return GL355_OK;
 }
-
-std::pair<uint32_t, uint32_t> single_query(const gl355_plonk_pk* pk, const std::vector<uint32_t>& code) { return plk_single_query(pk->queries, code); }
 
 // z[0] = *start, z[i] = z[i - 1] r[i - 1]
 int32_t running_product(Ctx* ctx, const uint64_t* r, uint64_t n, const uint64_t* d_start, uint64_t* z) {
@@ -321,9 +319,9 @@ int32_t eval_polys(gl355_plonk_pk* pk, const std::vector<const uint64_t*>& polys
     uint64_t* d_partial = (uint64_t*)p;
     std::vector<Fr> p256(nq);
     for (uint32_t q = 0; q < nq; q++) p256[q] = points[q].pow_u64(256);
-    GL355_TRY(ptrs_to_device(ctx, polys, d_polys));
-    GL355_TRY(fr_to_device(ctx, points, d_pts));
-    GL355_TRY(fr_to_device(ctx, p256, d_pts256));
+    GL355_TRY(to_device(ctx, polys, d_polys));
+    GL355_TRY(to_device(ctx, points, d_pts));
+    GL355_TRY(to_device(ctx, p256, d_pts256));
     PlkEvalPolyArgs a;
     a.polys = d_polys; a.points = d_pts; a.points256 = d_pts256; a.n = pk->n; a.blocks_per_q = bpq; a.partial = d_partial;
     hipLaunchKernelGGL(plk_eval_poly_kernel, dim3(bpq, nq), dim3(256), 0, ctx->stream, a);
@@ -343,8 +341,8 @@ int32_t lincomb(gl355_plonk_pk* pk, const std::vector<const uint64_t*>& polys, c
     GL355_TRY(sc.get((size_t)cnt * 40 + 256));
     const uint64_t** d_polys = sc.as<const uint64_t*>();
     uint64_t* d_co = (uint64_t*)(sc.as<uint8_t>() + (((size_t)cnt * 8 + 31) & ~size_t(31)));
-    GL355_TRY(ptrs_to_device(ctx, polys, d_polys));
-    GL355_TRY(fr_to_device(ctx, coeffs, d_co));
+    GL355_TRY(to_device(ctx, polys, d_polys));
+    GL355_TRY(to_device(ctx, coeffs, d_co));
     PlkLincombArgs a;
     memset(&a, 0, sizeof a);
     a.polys = d_polys; a.coeffs = d_co; a.count = cnt; a.n = pk->n; a.acc_in = acc_in; a.out = out;
@@ -357,28 +355,54 @@ int32_t lincomb(gl355_plonk_pk* pk, const std::vector<const uint64_t*>& polys, c
     return GL355_OK;
 }
 
-Fr plonk_zeta() {
-    const uint64_t zw[4] = {0xb8ca0b2d36636f23ull, 0xcc37a73fec2bc5e9ull, 0x048b6e193fd84104ull, 0x30644e72e131a029ull};      // Fr::ZETA
-    return Fr::from_words(zw);
-}
 // the key's polynomials (fixed | sigma | l0 l_last l_active) on cosets [c0, c1) of the extended domain: out[(c - c0)][poly][n]
 int32_t plonk_fixed_cosets(gl355_plonk_pk* pk, uint32_t c0, uint32_t c1, uint64_t* out, uint64_t* pre, uint64_t* work) {
     const uint64_t n = pk->n;
-    const Fr ext_omega = Fr::root_of_unity(pk->ext_k);
-
-    Fr base = plonk_zeta() * ext_omega.pow_u64(c0);
     for (uint32_t c = c0; c < c1; c++) {
         uint64_t bw[4];
-        base.to_words(bw);
+        pk->coset_base[c].to_words(bw);
         uint64_t* dst = out + 4ull * (uint64_t)(c - c0) * pk->n_fix_cos * n;
         for (uint32_t i = 0; i < pk->n_fix_cos; i++) {
             const uint64_t* src = i < pk->n_fixed ? pk->fixed_polys + 4ull * i * n
                                   : (i < pk->n_fixed + pk->n_perm ? pk->sigma_polys + 4ull * (i - pk->n_fixed) * n : pk->l_polys + 4ull * (i - pk->n_fixed - pk->n_perm) * n);
             GL355_TRY(bn254_fr_ntt_mont_coset_dif(pk->ctx, src, n, dst + 4ull * i * n, pk->k, pk->tw_fwd, bw, pre, i == 0));     // `pre`: the coset's block constants
         }
-        base = base * ext_omega;
     }
     return GL355_OK;
+}
+
+// a small host array into an allocation of its own that the key keeps
+template <typename T> int32_t key_upload(gl355_plonk_pk* pk, const std::vector<T>& v, T** d) {
+    GL355_TRY(pk->dalloc(std::max<size_t>(16, v.size() * sizeof(T)), d));
+    return to_device(pk->ctx, v, *d);
+}
+// `count` of the key's columns: commitments (Lagrange form), then coefficients
+int32_t key_columns(gl355_plonk_pk* pk, const uint64_t* vals, uint64_t* polys, uint32_t count, std::vector<uint64_t>& commitments, uint64_t* work) {
+    commitments.assign(8ull * count, 0);
+    GL355_TRY(commit_columns(pk, pk->g_lagrange, vals, count, commitments.data()));
+    return to_coeffs(pk, vals, polys, count, work);
+}
+
+// A^-1 by Gauss-Jordan over Fr; false: A is singular
+bool invert(std::vector<std::vector<Fr>> M, std::vector<std::vector<Fr>>& inv) {
+    const size_t P = M.size();
+    for (size_t r = 0; r < P; r++) { M[r].resize(2 * P, Fr::zero()); M[r][P + r] = Fr::one(); }
+    for (size_t col = 0; col < P; col++) {
+        size_t piv = col;
+        while (piv < P && M[piv][col].is_zero()) piv++;
+        if (piv == P) return false;
+        std::swap(M[piv], M[col]);
+        const Fr pinv = M[col][col].inv();
+        for (size_t j = 0; j < 2 * P; j++) M[col][j] = M[col][j] * pinv;
+        for (size_t r = 0; r < P; r++) {
+            if (r == col || M[r][col].is_zero()) continue;
+            const Fr f = M[r][col];
+            for (size_t j = 0; j < 2 * P; j++) M[r][j] = M[r][j] - f * M[col][j];
+        }
+    }
+    inv.resize(P);
+    for (size_t r = 0; r < P; r++) inv[r].assign(M[r].begin() + P, M[r].end());
+    return true;
 }
 
 // coefficients (ascending) of the polynomial of degree < m through (pts[i], evs[i])
@@ -405,6 +429,444 @@ Fr horner(const std::vector<Fr>& c, const Fr& x) {
     for (size_t i = c.size(); i-- > 0;) acc = acc * x + c[i];
     return acc;
 }
+
+// ---- one proof ----------------------------------------------------------------------------------------------------------------------------
+// A device buffer of a proof: Scratch, as 64-bit words, never asked for less than 32 bytes
+struct Buf : Scratch {
+    using Scratch::Scratch;
+    int32_t get(size_t bytes) { return Scratch::get(std::max<size_t>(bytes, 32)); }
+    operator uint64_t*() const { return as<uint64_t>(); }
+};
+// ... that only one stage uses: reset() where the stage is done with it; a return that still holds it (an error) waits for the stream first
+struct Local : Buf { using Buf::Buf; ~Local() { if (p) (void)ctx->wait(); } };
+
+// create_proof, one member function per stage (names as in halo2), called in the order they are declared.  The members are what lives past one
+// stage; every block goes back to the context's allocator only after the stream was waited for, on every return path (the destructor's body
+// runs before the members'), or earlier where no later stage reads it -- everything runs on the context's stream, so a later owner of the
+// block is ordered behind its last reader.  At k = 23 the allocator's cache decides the peak memory: keep the order of get() and reset().
+struct Proving {
+    Ctx* const ctx;
+    gl355_plonk_pk* const pk;
+    const BlindKey key;
+    const uint64_t n, u;
+    const uint32_t L;
+    const int32_t last_rot;
+    const PlkSlots sl;
+    const PlkRotate rotate;
+    const bool timed;
+    double ms[GL355_PLONK_STAGES] = {};
+    KeccakTranscript tr;
+    Fr theta, beta, gamma, y, x, sy, sv, su;
+    Buf work{ctx} /* FFT scratch of the natural-order transforms */, inst_vals{ctx}, inst_polys{ctx}, adv_vals{ctx}, adv_polys{ctx};
+    // pointer tables: [values: adv | fix | inst][coset: adv | fix | inst][perm vals][perm sigma vals][coset perm cols][coset sigma][coset z]
+    Buf d_ptrs{ctx};
+    Buf lkA{ctx}, lkS{ctx}, lkAp{ctx} /* A'_0 S'_0 A'_1 S'_1 ... : one batched commitment */, lkZ{ctx}, lk_polys{ctx} /* [L][3]: A', S', z */;
+    Buf perm_z{ctx}, perm_polys{ctx}, num{ctx}, den{ctx}, ratio{ctx}, d_small{ctx} /* [0..3] the constant one, [4] a flag word */;
+    Buf random_poly{ctx}, h_ext{ctx} /* [n_pieces] the quotient restricted to each coset */, pre{ctx}, h_coeffs{ctx} /* [n_pieces] the quotient's pieces */, h_poly{ctx};
+    uint32_t n_all_cols = 0;
+    const uint64_t** dp = nullptr;
+    const uint64_t* const* d_val_cols[3] = {nullptr, nullptr, nullptr};
+    const uint64_t **d_perm_vals = nullptr, **d_perm_sig = nullptr;
+    std::vector<const uint64_t*> lk_a_ptr, lk_s_ptr;          // the compressed input / table columns (values)
+    std::vector<const uint64_t*> opened;                      // per slot of the opening plan: its polynomial
+    std::vector<std::vector<std::pair<Fr, Fr>>> evals_at;     // per slot of the opening plan: (point, evaluation)
+
+    Proving(Ctx* c, gl355_plonk_pk* k, const uint8_t seed[32], bool timed_)
+        : ctx(c), pk(k), key(blind_key_from_bytes(seed)), n(k->n), u(k->usable), L(k->n_lookups), last_rot(-(int32_t)(k->bf + 1)),
+          sl(k->n_advice, k->n_sets, k->n_lookups, k->n_fixed, k->n_perm), rotate(k->k), timed(timed_) {}
+    ~Proving() { (void)ctx->wait(); }
+
+    double* ms_of(int i) { return timed ? &ms[i] : nullptr; }
+    uint32_t* d_bad() const { return reinterpret_cast<uint32_t*>(d_small + 4); }
+    const uint64_t* col_vals(uint32_t kind, uint32_t idx) const { return (kind == 0 ? adv_vals : (kind == 1 ? pk->fixed_vals : inst_vals)) + 4ull * idx * n; }
+    // commitments of `sets` columns into the transcript
+    int32_t commit(const uint64_t* bases, const uint64_t* cols, uint32_t sets, uint64_t tail = ~0ull) {
+        std::vector<uint64_t> pts(8ull * sets);
+        GL355_TRY(commit_columns(pk, bases, cols, sets, pts.data(), tail));
+        for (uint32_t s = 0; s < sets; s++) tr.write_point(pts.data() + 8 * s);
+        return GL355_OK;
+    }
+    // what both grand products do with the row kernel's num / den: ratio, running product from *start, blinding of rows u + 1 ...
+    int32_t grand_product(uint32_t stream, uint32_t index, const uint64_t* start, uint64_t* z) {
+        hipLaunchKernelGGL(plk_batch_div_kernel, dim3(blocks((n + PLK_INV_CHUNK - 1) / PLK_INV_CHUNK, 64)), dim3(64), 0, ctx->stream, (const uint64_t*)num, (uint64_t*)den, (uint64_t*)ratio, n, d_bad());
+        GL355_HIP(ctx, hipGetLastError());
+        GL355_TRY(running_product(ctx, ratio, n, start, z));
+        return random_rows(ctx, key, stream, index, u + 1, n - u - 1, z + 4 * (u + 1));
+    }
+    // a table of `count` column pointers on the device: entry i = of(i)
+    template <typename F> int32_t ptr_table(const uint64_t** d, uint32_t count, F of) {
+        std::vector<const uint64_t*> v(count);
+        for (uint32_t i = 0; i < count; i++) v[i] = of(i);
+        return to_device(ctx, v, d);
+    }
+    int32_t lookup_program(uint32_t l, bool table, const uint64_t* const* const cols[3], uint64_t* out, bool bitrev) {
+        const std::vector<uint32_t>& code = table ? pk->lookups[l].tab_code : pk->lookups[l].in_code;
+        return run_program(pk, pk->d_lk_code[2 * l + table], (uint32_t)(code.size() / 4), cols, theta, nullptr, out, bitrev);
+    }
+
+    int32_t instances(const uint64_t* instances, const uint32_t* instance_lens) {
+        GL355_TRY(work.get(n * 32));
+        tr.common_scalar(pk->digest);
+        GL355_TRY(inst_vals.get(std::max<uint32_t>(1, pk->n_instance) * n * 32));
+        GL355_TRY(inst_polys.get(std::max<uint32_t>(1, pk->n_instance) * n * 32));
+        GL355_HIP(ctx, hipMemsetAsync(inst_vals, 0, std::max<uint32_t>(1, pk->n_instance) * n * 32, ctx->stream));
+        uint64_t off = 0;
+        for (uint32_t c = 0; c < pk->n_instance; c++) {
+            const uint32_t len = instance_lens[c];
+            if (len > u) return ctx->fail(GL355_E_INVALID_ARG, "plonk_prove: more instance values than usable rows");
+            if (len && !instances) return ctx->fail(GL355_E_INVALID_ARG, "plonk_prove: instance values missing");
+            if (len) {
+                std::vector<uint64_t> hv(4ull * len);
+                GL355_HIP(ctx, hipMemcpy(hv.data(), instances + 4 * off, 32ull * len, ptr_is_device(instances) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+                std::vector<Fr> fv(len);
+                for (uint32_t i = 0; i < len; i++) { fv[i] = Fr::from_words(hv.data() + 4 * i); tr.common_scalar(fv[i]); }
+                GL355_TRY(to_device(ctx, fv, inst_vals + 4ull * c * n));
+            }
+            off += len;
+        }
+        return to_coeffs(pk, inst_vals, inst_polys, pk->n_instance, work);
+    }
+
+    int32_t advice(const uint64_t* advice) {
+        GL355_TRY(adv_vals.get(std::max<uint32_t>(1, pk->n_advice) * n * 32));
+        GL355_TRY(adv_polys.get(std::max<uint32_t>(1, pk->n_advice) * n * 32));
+        {
+            Timer t(ctx, ms_of(GL355_PLONK_STAGE_ADVICE), "advice");
+            if (pk->n_advice) GL355_TRY(columns_to_mont(ctx, advice, (uint64_t)pk->n_advice * n, adv_vals));
+            for (uint32_t c = 0; c < pk->n_advice; c++) GL355_TRY(random_rows(ctx, key, PLK_STREAM_ADVICE, c, u, n - u, adv_vals + 4 * ((uint64_t)c * n + u)));
+            GL355_TRY(commit(pk->g_lagrange, adv_vals, pk->n_advice, u));
+            GL355_TRY(to_coeffs(pk, adv_vals, adv_polys, pk->n_advice, work));
+        }
+        // column pointer tables (values / coefficient forms) on the device
+        n_all_cols = pk->n_advice + pk->n_fixed + pk->n_instance;
+        GL355_TRY(d_ptrs.get((size_t)(2 * n_all_cols + 5 * pk->n_perm + pk->n_sets + 16) * 8));
+        dp = (const uint64_t**)d_ptrs.as<uint64_t>();
+        std::vector<const uint64_t*> v;
+        for (uint32_t kd = 0; kd < 3; kd++) for (uint32_t c = 0; c < pk->kind_cols[kd]; c++) v.push_back(col_vals(kd, c));
+        GL355_TRY(to_device(ctx, v, dp));
+        d_val_cols[0] = dp; d_val_cols[1] = dp + pk->n_advice; d_val_cols[2] = dp + pk->n_advice + pk->n_fixed;
+        return GL355_OK;
+    }
+
+    // lookups: compress, permute, commit
+    int32_t lookup_permute() {
+        theta = tr.squeeze_challenge();
+        // compressed input / table columns only for the lookups whose expressions are not a single column query (none of the reference's nine)
+        uint32_t n_lk_a = 0, n_lk_s = 0;
+        for (uint32_t l = 0; l < L; l++) { n_lk_a += pk->lk_single[2 * l].first >= 3; n_lk_s += pk->lk_single[2 * l + 1].first >= 3; }
+        GL355_TRY(lkA.get((size_t)std::max(1u, n_lk_a) * n * 32));
+        GL355_TRY(lkS.get((size_t)std::max(1u, n_lk_s) * n * 32));
+        GL355_TRY(lkAp.get((size_t)std::max(1u, 2 * L) * n * 32));
+        GL355_TRY(lkZ.get((size_t)std::max(1u, L) * n * 32));
+        GL355_TRY(lk_polys.get((size_t)std::max(1u, 3 * L) * n * 32));
+        lk_a_ptr.resize(L); lk_s_ptr.resize(L);
+        Timer t(ctx, ms_of(GL355_PLONK_STAGE_LOOKUP_PERMUTE), "lookup_permute");
+        for (uint32_t l = 0, ia = 0, is = 0; l < L; l++) {
+            const auto qa = pk->lk_single[2 * l], qs = pk->lk_single[2 * l + 1];
+            if (qa.first < 3) lk_a_ptr[l] = col_vals(qa.first, qa.second);
+            else { uint64_t* a = lkA + 4ull * (ia++) * n; lk_a_ptr[l] = a; GL355_TRY(lookup_program(l, false, d_val_cols, a, false)); }
+            if (qs.first < 3) lk_s_ptr[l] = col_vals(qs.first, qs.second);
+            else { uint64_t* s = lkS + 4ull * (is++) * n; lk_s_ptr[l] = s; GL355_TRY(lookup_program(l, true, d_val_cols, s, false)); }
+            uint64_t* Ap = lkAp + 8ull * l * n;
+            uint64_t* Sp = Ap + 4 * n;
+            GL355_TRY(permute_pair(ctx, lk_a_ptr[l], lk_s_ptr[l], u, Ap, Sp));
+            GL355_TRY(random_rows(ctx, key, PLK_STREAM_LOOKUP_PERMUTED, 2 * l, u, n - u, Ap + 4 * u));
+            GL355_TRY(random_rows(ctx, key, PLK_STREAM_LOOKUP_PERMUTED, 2 * l + 1, u, n - u, Sp + 4 * u));
+        }
+        GL355_TRY(commit(pk->g_lagrange, lkAp, 2 * L, u));
+        for (uint32_t l = 0; l < L; l++) GL355_TRY(to_coeffs(pk, lkAp + 8ull * l * n, lk_polys + 12ull * l * n, 2, work));
+        return GL355_OK;
+    }
+
+    int32_t permutation_product() {
+        beta = tr.squeeze_challenge();
+        gamma = tr.squeeze_challenge();
+        GL355_TRY(perm_z.get((size_t)std::max(1u, pk->n_sets) * n * 32));
+        GL355_TRY(perm_polys.get((size_t)std::max(1u, pk->n_sets) * n * 32));
+        GL355_TRY(num.get(n * 32));
+        GL355_TRY(den.get(n * 32));
+        GL355_TRY(ratio.get(n * 32));
+        GL355_TRY(d_small.get(256));
+        GL355_TRY(to_device(ctx, std::vector<Fr>(1, Fr::one()), d_small));
+        GL355_HIP(ctx, hipMemsetAsync(d_bad(), 0, 4, ctx->stream));
+        d_perm_vals = dp + 2 * n_all_cols;
+        d_perm_sig = d_perm_vals + pk->n_perm;
+        Timer t(ctx, ms_of(GL355_PLONK_STAGE_PERMUTATION), "permutation");
+        GL355_TRY(ptr_table(d_perm_vals, pk->n_perm, [&](uint32_t j) { return col_vals(pk->perm_cols[j].first, pk->perm_cols[j].second); }));
+        GL355_TRY(ptr_table(d_perm_sig, pk->n_perm, [&](uint32_t j) { return pk->sigma_vals + 4ull * j * n; }));
+        for (uint32_t s = 0; s < pk->n_sets; s++) {
+            PlkPermRowArgs a;
+            a.n = n; a.j0 = s * pk->chunk_len; a.j1 = std::min(pk->n_perm, (s + 1) * pk->chunk_len);
+            a.vals = d_perm_vals; a.sigma = d_perm_sig; a.omega_pows = pk->omega_pows; a.delta_pows = pk->delta_pows;
+            a.beta = to_dev(beta); a.gamma = to_dev(gamma); a.num = num; a.den = den;
+            hipLaunchKernelGGL(plk_perm_rows_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, a);
+            // z_s[0] = z_{s-1}[usable]: read before the blinding of set s overwrites nothing of set s - 1 (its rows > usable only)
+            GL355_TRY(grand_product(PLK_STREAM_PERM_Z, s, s ? perm_z + 4 * ((uint64_t)(s - 1) * n + u) : d_small, perm_z + 4ull * s * n));
+        }
+        GL355_TRY(commit(pk->g_lagrange, perm_z, pk->n_sets));
+        return to_coeffs(pk, perm_z, perm_polys, pk->n_sets, work);
+    }
+
+    int32_t lookup_product() {
+        {
+            Timer t(ctx, ms_of(GL355_PLONK_STAGE_LOOKUP_PRODUCT), "lookup_product");
+            for (uint32_t l = 0; l < L; l++) {
+                const uint64_t* Ap = lkAp + 8ull * l * n;
+                hipLaunchKernelGGL(plk_lookup_rows_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, lk_a_ptr[l], lk_s_ptr[l], Ap, Ap + 4 * n, n, to_dev(beta), to_dev(gamma), (uint64_t*)num, (uint64_t*)den);
+                GL355_TRY(grand_product(PLK_STREAM_LOOKUP_Z, l, d_small, lkZ + 4ull * l * n));
+            }
+            GL355_TRY(commit(pk->g_lagrange, lkZ, L));
+            GL355_TRY(to_coeffs(pk, lkZ, lk_polys + 8 * n, L, work, 12 * n));
+            uint32_t bad = 0;
+            GL355_HIP(ctx, ctx->d2h(&bad, d_bad(), 4));
+            GL355_HIP(ctx, ctx->wait());
+            if (bad) return ctx->fail(GL355_E_INVALID_ARG, "plonk_prove: a grand-product denominator is zero under these challenges (retry with another transcript input)");
+        }
+        // the value forms have done their work (commitments, grand products): from here on only coefficient forms are read
+        adv_vals.reset(); lkA.reset(); lkS.reset(); lkAp.reset(); lkZ.reset(); perm_z.reset(); num.reset(); den.reset(); ratio.reset();
+        return GL355_OK;
+    }
+
+    // vanishing argument: the random polynomial
+    int32_t random_polynomial() {
+        GL355_TRY(random_poly.get(n * 32));
+        Timer t(ctx, ms_of(GL355_PLONK_STAGE_VANISHING_RANDOM), "vanishing_random");
+        GL355_TRY(random_rows(ctx, key, PLK_STREAM_RANDOM_POLY, 0, 0, n, random_poly));
+        return commit(pk->g, random_poly, 1);
+    }
+
+    int32_t evaluate_h() {
+        y = tr.squeeze_challenge();
+        const uint32_t n_dyn = pk->n_advice + pk->n_instance + pk->n_sets + 3 * L;           // per-proof polynomials: advice | instance | perm z | lookups (A' S' z)
+        Local acc(ctx), cos(ctx), a_in(ctx), s_in(ctx), fix_tmp(ctx);
+        GL355_TRY(h_ext.get((size_t)pk->n_pieces * n * 32));
+        GL355_TRY(acc.get(n * 32));
+        GL355_TRY(cos.get((size_t)std::max(1u, n_dyn) * n * 32));
+        GL355_TRY(a_in.get(n * 32));
+        GL355_TRY(s_in.get(n * 32));
+        GL355_TRY(pre.get(n * 32));
+        if (!pk->fixed_cos) GL355_TRY(fix_tmp.get((size_t)pk->n_fix_cos * n * 32));
+        {
+            Timer t(ctx, ms_of(GL355_PLONK_STAGE_EVALUATE_H), "evaluate_h");
+            std::vector<const uint64_t*> src;
+            for (uint32_t c = 0; c < pk->n_advice; c++) src.push_back(adv_polys + 4ull * c * n);
+            for (uint32_t c = 0; c < pk->n_instance; c++) src.push_back(inst_polys + 4ull * c * n);
+            for (uint32_t s = 0; s < pk->n_sets; s++) src.push_back(perm_polys + 4ull * s * n);
+            for (uint32_t l = 0; l < 3 * L; l++) src.push_back(lk_polys + 4ull * l * n);
+            auto dyn = [&](uint32_t i) -> const uint64_t* { return cos + 4ull * i * n; };
+            const uint32_t o_inst = pk->n_advice, o_z = o_inst + pk->n_instance, o_lk = o_z + pk->n_sets;
+            const uint64_t** d_cos_cols = dp + n_all_cols;
+            const uint64_t* const* d_cos_kind[3] = {d_cos_cols, d_cos_cols + pk->n_advice, d_cos_cols + pk->n_advice + pk->n_fixed};
+            const uint64_t **d_cperm = d_perm_sig + pk->n_perm, **d_csig = d_cperm + pk->n_perm, **d_cz = d_csig + pk->n_perm;
+            for (uint32_t c = 0; c < pk->n_pieces; c++) {
+                // the key's polynomials on this coset: precomputed, or recomputed into fix_tmp
+                const uint64_t* fix = pk->fixed_cos ? pk->fixed_cos + 4ull * (uint64_t)c * pk->n_fix_cos * n : fix_tmp;
+                if (!pk->fixed_cos) GL355_TRY(plonk_fixed_cosets(pk, c, c + 1, fix_tmp, pre, work));
+                auto fixc = [&](uint32_t i) -> const uint64_t* { return fix + 4ull * i * n; };
+                auto col_cos = [&](uint32_t kind, uint32_t idx) -> const uint64_t* { return kind == 0 ? dyn(idx) : (kind == 1 ? fixc(idx) : dyn(o_inst + idx)); };
+                std::vector<const uint64_t*> v;
+                for (uint32_t kd = 0; kd < 3; kd++) for (uint32_t i = 0; i < pk->kind_cols[kd]; i++) v.push_back(col_cos(kd, i));
+                GL355_TRY(to_device(ctx, v, d_cos_cols));
+                GL355_TRY(ptr_table(d_cperm, pk->n_perm, [&](uint32_t j) { return col_cos(pk->perm_cols[j].first, pk->perm_cols[j].second); }));
+                GL355_TRY(ptr_table(d_csig, pk->n_perm, [&](uint32_t j) { return fixc(pk->n_fixed + j); }));
+                GL355_TRY(ptr_table(d_cz, pk->n_sets, [&](uint32_t s) { return dyn(o_z + s); }));
+                const uint64_t *c_l0 = fixc(pk->n_fixed + pk->n_perm), *c_ll = c_l0 + 4 * n, *c_la = c_l0 + 8 * n;
+                const Fr& base = pk->coset_base[c];
+                uint64_t bw[4];
+                base.to_words(bw);
+                // (round 6: the coset transform in block form -- no power table, no product per coefficient, broadcast twiddles in the high stages)
+                for (uint32_t i = 0; i < n_dyn; i++) GL355_TRY(bn254_fr_ntt_mont_coset_dif(ctx, src[i], n, cos + 4ull * i * n, pk->k, pk->tw_fwd, bw, pre, i == 0));
+                // custom gates
+                GL355_TRY(run_program(pk, pk->d_gate_code, (uint32_t)(pk->gate_code.size() / 4), d_cos_kind, y, nullptr, acc, true));
+                if (pk->n_sets) {
+                    PlkPermHArgs a;
+                    a.n = n; a.log_n = pk->k; a.n_sets = pk->n_sets; a.chunk_len = pk->chunk_len; a.n_perm = pk->n_perm; a.last_rot = last_rot; a.acc = acc;
+                    a.l0 = c_l0; a.l_last = c_ll; a.l_active = c_la;
+                    a.z = d_cz; a.sigma = d_csig; a.col = d_cperm; a.omega_pows = pk->omega_pows; a.delta_pows = pk->delta_pows;
+                    a.y = to_dev(y); a.beta = to_dev(beta); a.gamma = to_dev(gamma); a.coset_base = to_dev(base);
+                    hipLaunchKernelGGL(plk_perm_h_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, a);
+                    GL355_HIP(ctx, hipGetLastError());
+                }
+                for (uint32_t l = 0; l < L; l++) {
+                    const auto qa = pk->lk_single[2 * l], qs = pk->lk_single[2 * l + 1];
+                    if (qa.first == 3) GL355_TRY(lookup_program(l, false, d_cos_kind, a_in, true));
+                    if (qs.first == 3) GL355_TRY(lookup_program(l, true, d_cos_kind, s_in, true));
+                    PlkLookupHArgs a;
+                    a.n = n; a.log_n = pk->k; a.acc = acc; a.l0 = c_l0; a.l_last = c_ll; a.l_active = c_la;
+                    a.ap = dyn(o_lk + 3 * l); a.sp = dyn(o_lk + 3 * l + 1); a.z = dyn(o_lk + 3 * l + 2);
+                    a.a_in = qa.first < 3 ? col_cos(qa.first, qa.second) : a_in; a.s_in = qs.first < 3 ? col_cos(qs.first, qs.second) : s_in;
+                    a.y = to_dev(y); a.beta = to_dev(beta); a.gamma = to_dev(gamma);
+                    hipLaunchKernelGGL(plk_lookup_h_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, a);
+                    GL355_HIP(ctx, hipGetLastError());
+                }
+                const Fr t_inv = (base.pow_u64(n) - Fr::one()).inv();                 // 1 / ((zeta omega_ext^c)^n - 1)
+                hipLaunchKernelGGL(plk_finish_h_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, (const uint64_t*)acc, n, (uint64_t)c, to_dev(t_inv), (uint64_t*)h_ext);
+                GL355_HIP(ctx, hipGetLastError());
+            }
+        }
+        cos.reset(); acc.reset(); a_in.reset(); s_in.reset(); fix_tmp.reset();
+        return GL355_OK;
+    }
+
+    // vanishing argument: h's coefficients, pieces, commitments.
+    // halo2 evaluates h on the whole extended domain (2^(extended_k - k) cosets of the 2^k domain) and inverts one transform of that size.  The
+    // same polynomial follows from `degree - 1` cosets: h = sum_p X^(p n) h_p with deg h_p < n, and on the coset g_c H, X^n is the constant
+    // t_c = g_c^n, so h restricted to the coset IS the polynomial R_c = sum_p t_c^p h_p (degree < n): one inverse coset transform of size n
+    // per coset gives R_c, and the pieces are h_p = sum_c (V^-1)[p][c] R_c with the Vandermonde matrix V[c][p] = t_c^p -- a host-side inversion
+    // of a (degree - 1)^2 matrix and one linear combination per piece.  5 of 8 cosets at the reference's degree 6: 3/8 of evaluate_h's
+    // transforms and kernels gone, no transform over the extended domain at all, same bytes (the quotient is unique).
+    // `export_quotient` (gl355_plonk_pk_export_quotient): the pieces as canonical integers, for a comparison with the extended-domain quotient
+    int32_t quotient(uint64_t* export_quotient) {
+        const uint32_t P = pk->n_pieces;
+        Local plain(ctx);
+        GL355_TRY(h_coeffs.get((size_t)P * n * 32));
+        {
+            Timer t(ctx, ms_of(GL355_PLONK_STAGE_QUOTIENT_COMMIT), "quotient_commit");
+            const Fr n_inv = Fr::from_u64(n).inv();
+            std::vector<std::vector<Fr>> V(P, std::vector<Fr>(P)), Vinv;
+            for (uint32_t c = 0; c < P; c++) {
+                // R_c: values on g_c H in bit-reversed order -> coefficients: inverse transform (no gather), coefficient i times g_c^-i / n
+                uint64_t bw[4], fw[4];
+                pk->coset_base[c].inv().to_words(bw);
+                n_inv.to_words(fw);
+                GL355_TRY(bn254_fr_power_table(ctx, bw, fw, n, pre));
+                GL355_TRY(bn254_fr_ntt_mont_from_bitrev(ctx, h_ext + 4ull * c * n, h_ext + 4ull * c * n, n, pk->k, pk->tw_inv, pre, nullptr));
+                const Fr tc = pk->coset_base[c].pow_u64(n);
+                Fr pw = Fr::one();
+                for (uint32_t q = 0; q < P; q++) { V[c][q] = pw; pw = pw * tc; }
+            }
+            if (!invert(V, Vinv)) return ctx->fail(GL355_E_HIP, "plonk_prove: singular coset matrix (internal)");       // (P <= 9)
+            std::vector<const uint64_t*> rs;
+            for (uint32_t c = 0; c < P; c++) rs.push_back(h_ext + 4ull * c * n);
+            for (uint32_t q = 0; q < P; q++) GL355_TRY(lincomb(pk, rs, Vinv[q], {}, nullptr, h_coeffs + 4ull * q * n));
+            if (export_quotient) {
+                GL355_TRY(plain.get((size_t)P * n * 32));
+                hipLaunchKernelGGL(plk_from_mont_kernel, dim3(blocks((uint64_t)P * n)), dim3(256), 0, ctx->stream, (const uint64_t*)h_coeffs, (uint64_t*)plain, (uint64_t)P * n);
+                GL355_HIP(ctx, hipGetLastError());
+                GL355_HIP(ctx, ctx->d2h(export_quotient, plain, (size_t)P * n * 32));
+                GL355_HIP(ctx, ctx->wait());
+            }
+            GL355_TRY(commit(pk->g, h_coeffs, P));
+        }
+        plain.reset();
+        return GL355_OK;
+    }
+
+    // every evaluation the proof carries, in transcript order, then h; all of them into evals_at, where SHPLONK finds them by (slot, point)
+    int32_t evaluations() {
+        x = tr.squeeze_challenge();
+        const Fr xn = x.pow_u64(n);
+        GL355_TRY(h_poly.get(n * 32));
+        Timer t(ctx, ms_of(GL355_PLONK_STAGE_EVALUATIONS), "evaluations");
+        // h(X) = sum_i x^(n i) h_i(X)
+        {
+            std::vector<const uint64_t*> ps;
+            std::vector<Fr> cs;
+            Fr p = Fr::one();
+            for (uint32_t i = 0; i < pk->n_pieces; i++) { ps.push_back(h_coeffs + 4ull * i * n); cs.push_back(p); p = p * xn; }
+            GL355_TRY(lincomb(pk, ps, cs, {}, nullptr, h_poly));
+        }
+        // the polynomial behind every slot of the opening plan
+        opened.resize(sl.count);
+        auto cols = [&](uint32_t slot0, uint32_t count, const uint64_t* first, uint64_t stride) { for (uint32_t i = 0; i < count; i++) opened[slot0 + i] = first + stride * i; };
+        cols(sl.advice, pk->n_advice, adv_polys, 4 * n); cols(sl.perm_z, pk->n_sets, perm_polys, 4 * n);
+        cols(sl.lookup_a, L, lk_polys, 12 * n); cols(sl.lookup_s, L, lk_polys + 4 * n, 12 * n); cols(sl.lookup_z, L, lk_polys + 8 * n, 12 * n);
+        cols(sl.fixed, pk->n_fixed, pk->fixed_polys, 4 * n); cols(sl.sigma, pk->n_perm, pk->sigma_polys, 4 * n);
+        cols(sl.h, 1, h_poly, 0); cols(sl.random, 1, random_poly, 0);
+        std::vector<uint32_t> slots;
+        std::vector<const uint64_t*> ps;
+        std::vector<Fr> pts, evals;
+        auto eval = [&](uint32_t slot, int32_t rot) { slots.push_back(slot); ps.push_back(opened[slot]); pts.push_back(rotate(x, rot)); };
+        for (auto& q : pk->queries[0]) eval(sl.advice + q.first, q.second);
+        for (auto& q : pk->queries[1]) eval(sl.fixed + q.first, q.second);
+        eval(sl.random, 0);
+        for (uint32_t j = 0; j < pk->n_perm; j++) eval(sl.sigma + j, 0);
+        for (uint32_t s = 0; s < pk->n_sets; s++) { eval(sl.perm_z + s, 0); eval(sl.perm_z + s, 1); if (s + 1 < pk->n_sets) eval(sl.perm_z + s, last_rot); }
+        for (uint32_t l = 0; l < L; l++) { eval(sl.lookup_z + l, 0); eval(sl.lookup_z + l, 1); eval(sl.lookup_a + l, 0); eval(sl.lookup_a + l, -1); eval(sl.lookup_s + l, 0); }
+        const size_t n_written = slots.size();
+        eval(sl.h, 0);
+        GL355_TRY(eval_polys(pk, ps, pts, evals));
+        for (size_t i = 0; i < n_written; i++) tr.write_scalar(evals[i]);
+        evals_at.assign(sl.count, {});
+        for (size_t i = 0; i < slots.size(); i++) evals_at[slots[i]].push_back({pts[i], evals[i]});
+        return GL355_OK;
+    }
+
+    int32_t shplonk() {
+        Local sh_h(ctx), bufa(ctx), bufb(ctx);
+        Timer t(ctx, ms_of(GL355_PLONK_STAGE_SHPLONK), "shplonk");
+        const PlkRotationSets plan(plk_opening_queries(sl, pk->queries[0], pk->queries[1], pk->bf, rotate, x), sl.count);
+        sy = tr.squeeze_challenge();
+        sv = tr.squeeze_challenge();
+        // h(X) = sum_i v^i (sum_j y^j (p_ij(X) - r_ij(X))) / prod_{t in S_i} (X - t)
+        GL355_TRY(sh_h.get(n * 32));
+        GL355_TRY(bufa.get(n * 32));
+        GL355_TRY(bufb.get(n * 32));
+        GL355_HIP(ctx, hipMemsetAsync(sh_h, 0, n * 32, ctx->stream));
+        std::vector<std::vector<std::vector<Fr>>> r_coeffs(plan.sets.size());      // [set][member] low-degree remainders
+        Fr vi = Fr::one();
+        for (size_t s = 0; s < plan.sets.size(); s++) {
+            const std::vector<Fr>& set_pts = plan.sets[s].pts;
+            std::vector<const uint64_t*> ps;
+            std::vector<Fr> cs, low(set_pts.size(), Fr::zero());
+            Fr yj = Fr::one();
+            for (size_t m : plan.sets[s].coms) {
+                const uint32_t slot = plan.coms[m].slot;
+                std::vector<Fr> ev;
+                for (auto& p : set_pts)
+                    for (auto& e : evals_at[slot]) if (e.first == p) { ev.push_back(e.second); break; }
+                // a (polynomial, point) pair that the evaluation stage never computed: an internal error, not a zero
+                if (ev.size() != set_pts.size()) return ctx->fail(GL355_E_UNSUPPORTED, "plonk_prove: an opening asks for an evaluation that was not computed");
+                r_coeffs[s].push_back(interpolate(set_pts, ev));
+                for (size_t t_ = 0; t_ < low.size(); t_++) low[t_] = low[t_] + yj * r_coeffs[s].back()[t_];
+                ps.push_back(opened[slot]);
+                cs.push_back(yj);
+                yj = yj * sy;
+            }
+            GL355_TRY(lincomb(pk, ps, cs, low, nullptr, bufa));
+            uint64_t *src_ = bufa, *dst_ = bufb;
+            for (auto& p : set_pts) {
+                uint64_t pw[4];
+                p.to_words(pw);
+                GL355_TRY(kzg_divide(ctx, src_, n, h_from_words(pw), 1, dst_, 0, nullptr));
+                std::swap(src_, dst_);
+            }
+            GL355_TRY(lincomb(pk, {src_}, {vi}, {}, sh_h, sh_h));
+            vi = vi * sv;
+        }
+        GL355_TRY(commit(pk->g, sh_h, 1));
+        su = tr.squeeze_challenge();
+        // L(X) = (sum_i v^i Z_{T \ S_i}(u) sum_j y^j (p_ij(X) - r_ij(u)) - Z_T(u) h(X)) / Z_{T \ S_0}(u)
+        Fr zt = Fr::one();
+        for (auto& p : plan.all_points) zt = zt * (su - p);
+        std::vector<Fr> zdiff(plan.sets.size(), Fr::one());
+        for (size_t s = 0; s < plan.sets.size(); s++)
+            for (auto& p : plan.all_points) if (!plan.has(plan.sets[s].pts, p)) zdiff[s] = zdiff[s] * (su - p);
+        const Fr z0inv = zdiff[0].inv();
+        std::vector<const uint64_t*> ps;
+        std::vector<Fr> cs;
+        Fr cterm = Fr::zero();
+        vi = Fr::one();
+        for (size_t s = 0; s < plan.sets.size(); s++) {
+            const Fr scale = vi * zdiff[s] * z0inv;
+            Fr yj = Fr::one();
+            for (size_t mi = 0; mi < plan.sets[s].coms.size(); mi++) {
+                ps.push_back(opened[plan.coms[plan.sets[s].coms[mi]].slot]);
+                cs.push_back(scale * yj);
+                cterm = cterm + scale * yj * horner(r_coeffs[s][mi], su);
+                yj = yj * sy;
+            }
+            vi = vi * sv;
+        }
+        ps.push_back(sh_h);
+        cs.push_back((zt * z0inv).neg());
+        GL355_TRY(lincomb(pk, ps, cs, {cterm}, nullptr, bufa));
+        uint64_t uw[4];
+        su.to_words(uw);
+        GL355_TRY(kzg_divide(ctx, bufa, n, h_from_words(uw), 1, bufb, 0, nullptr));
+        return commit(pk->g, bufb, 1);
+    }
+};
 
 }  // namespace
 
@@ -458,12 +920,8 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
     struct TrimGuard { Ctx* c; uint64_t mark; ~TrimGuard() { c->trim_since(mark); } } trim_guard{ctx, ctx->block_serial};
     std::unique_ptr<gl355_plonk_pk, int32_t (*)(gl355_plonk_pk*)> pk(new (std::nothrow) gl355_plonk_pk(), gl355_plonk_pk_destroy);
     if (!pk) return GL355_E_OOM;
+    static_cast<PlkDesc&>(*pk) = std::move(d);
     pk->ctx = ctx; pk->handle = h;
-    pk->k = d.k; pk->n_advice = d.n_advice; pk->n_fixed = d.n_fixed; pk->n_instance = d.n_instance; pk->n_perm = d.n_perm; pk->n_lookups = d.n_lookups;
-    pk->degree = d.degree; pk->bf = d.bf; pk->n_gate_polys = d.n_gate_polys; pk->n = d.n; pk->usable = d.usable; pk->digest = d.digest;
-    pk->perm_cols = std::move(d.perm_cols);
-    for (int kd = 0; kd < 3; kd++) pk->queries[kd] = std::move(d.queries[kd]);
-    pk->consts = std::move(d.consts); pk->gate_code = std::move(d.gate_code); pk->lookups = std::move(d.lookups);
     pk->n_pieces = pk->degree - 1;
     pk->ext_k = pk->k;
     while ((1ull << pk->ext_k) < pk->n * pk->n_pieces) pk->ext_k++;
@@ -471,7 +929,14 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
     pk->n_sets = pk->n_perm ? (pk->n_perm + pk->chunk_len - 1) / pk->chunk_len : 0;
     pk->desc.assign(desc, desc + words);
     if ((pk->n_fixed && !fixed_values) || (pk->n_perm && !mapping)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: fixed values / permutation mapping missing");
-    const uint32_t kind_cols[3] = {pk->n_advice, pk->n_fixed, pk->n_instance};
+    pk->kind_cols[0] = pk->n_advice; pk->kind_cols[1] = pk->n_fixed; pk->kind_cols[2] = pk->n_instance;
+    for (auto& lk : pk->lookups) { pk->lk_single.push_back(plk_single_query(pk->queries, lk.in_code)); pk->lk_single.push_back(plk_single_query(pk->queries, lk.tab_code)); }
+    {
+        const uint64_t zeta[4] = {0xb8ca0b2d36636f23ull, 0xcc37a73fec2bc5e9ull, 0x048b6e193fd84104ull, 0x30644e72e131a029ull};      // Fr::ZETA
+        const Fr ext_omega = Fr::root_of_unity(pk->ext_k);
+        Fr base = Fr::from_words(zeta);
+        for (uint32_t c = 0; c < pk->n_pieces; c++) { pk->coset_base.push_back(base); base = base * ext_omega; }
+    }
     // every permutation column must be queried at rotation 0 (halo2's enable_equality does that): the verifier reads it at x
     for (auto& pc : pk->perm_cols) {
         bool ok = false;
@@ -482,7 +947,7 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
     // five or more distinct rotations is refused HERE, not at the end of every proof.  The arguments' own polynomials are opened
     // at <= 3 points (z: x, wx, w^last x; permuted input: x, w^-1 x).
     for (int kd = 0; kd < 2; kd++) {
-        std::vector<std::vector<int32_t>> rots(kind_cols[kd]);
+        std::vector<std::vector<int32_t>> rots(pk->kind_cols[kd]);
         for (auto& q : pk->queries[kd]) {
             auto& r = rots[q.first];
             if (std::find(r.begin(), r.end(), q.second) == r.end()) r.push_back(q.second);
@@ -491,10 +956,8 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
     }
     // ---- device side
     const uint64_t n = pk->n;
-    gl355_plonk_pk* k_ = pk.get();
-    auto D = [&](size_t bytes, auto** ptr) { return k_->dalloc(bytes, reinterpret_cast<void**>(ptr)); };
-    if (ptr_is_device(g)) pk->g = g; else { uint64_t* d; GL355_TRY(D(n * 64, &d)); GL355_TRY(upload(ctx, d, g, n * 64)); pk->g = d; }
-    if (ptr_is_device(g_lagrange)) pk->g_lagrange = g_lagrange; else { uint64_t* d; GL355_TRY(D(n * 64, &d)); GL355_TRY(upload(ctx, d, g_lagrange, n * 64)); pk->g_lagrange = d; }
+    if (ptr_is_device(g)) pk->g = g; else { uint64_t* d; GL355_TRY(pk->dalloc(n * 64, &d)); GL355_TRY(upload(ctx, d, g, n * 64)); pk->g = d; }
+    if (ptr_is_device(g_lagrange)) pk->g_lagrange = g_lagrange; else { uint64_t* d; GL355_TRY(pk->dalloc(n * 64, &d)); GL355_TRY(upload(ctx, d, g_lagrange, n * 64)); pk->g_lagrange = d; }
     {
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
@@ -507,60 +970,43 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
             GL355_TRY(gl355_bn254_g1_msm_prepare(h, pk->g_lagrange, n, &pk->tab_gl));
         }
     }
-    GL355_TRY(D((n / 2 + 1) * 32, &pk->tw_fwd));
-    GL355_TRY(D((n / 2 + 1) * 32, &pk->tw_inv));
+    GL355_TRY(pk->dalloc((n / 2 + 1) * 32, &pk->tw_fwd));
+    GL355_TRY(pk->dalloc((n / 2 + 1) * 32, &pk->tw_inv));
     GL355_TRY(bn254_fr_twiddles(ctx, pk->k, false, pk->tw_fwd));
     GL355_TRY(bn254_fr_twiddles(ctx, pk->k, true, pk->tw_inv));
     const uint64_t one_w[4] = {1, 0, 0, 0};
     uint64_t w_w[4], d_w[4];
     Fr::root_of_unity(pk->k).to_words(w_w);
-    GL355_TRY(D(n * 32, &pk->omega_pows));
+    GL355_TRY(pk->dalloc(n * 32, &pk->omega_pows));
     GL355_TRY(bn254_fr_power_table(ctx, w_w, one_w, n, pk->omega_pows));
     const Fr delta = Fr::from_u64(7).pow_u64(1ull << 28);            // Fr::DELTA = GENERATOR^(2^S)
     delta.to_words(d_w);
-    GL355_TRY(D(std::max<uint32_t>(1, pk->n_perm) * 32, &pk->delta_pows));
+    GL355_TRY(pk->dalloc(std::max<uint32_t>(1, pk->n_perm) * 32, &pk->delta_pows));
     if (pk->n_perm) GL355_TRY(bn254_fr_power_table(ctx, d_w, one_w, pk->n_perm, pk->delta_pows));
-    GL355_TRY(D(std::max<size_t>(1, pk->consts.size()) * 32, &pk->d_consts));
-    GL355_TRY(fr_to_device(ctx, pk->consts, pk->d_consts));
-    auto code_to_dev = [&](const std::vector<uint32_t>& code, uint32_t** d) -> int32_t {
-        GL355_TRY(D(std::max<size_t>(16, code.size() * 4), d));
-        if (!code.empty()) { GL355_HIP(ctx, hipMemcpyAsync(*d, code.data(), code.size() * 4, hipMemcpyHostToDevice, ctx->stream)); GL355_HIP(ctx, ctx->wait()); }
-        return GL355_OK;
-    };
-    GL355_TRY(code_to_dev(pk->gate_code, &pk->d_gate_code));
-    for (auto& lk : pk->lookups) {
-        uint32_t *a = nullptr, *b = nullptr;
-        GL355_TRY(code_to_dev(lk.in_code, &a));
-        GL355_TRY(code_to_dev(lk.tab_code, &b));
-        pk->d_lk_code.push_back(a);
-        pk->d_lk_code.push_back(b);
+    GL355_TRY(pk->dalloc(std::max<size_t>(1, pk->consts.size()) * 32, &pk->d_consts));
+    GL355_TRY(to_device(ctx, pk->consts, pk->d_consts));
+    GL355_TRY(key_upload(pk.get(), pk->gate_code, &pk->d_gate_code));
+    pk->d_lk_code.assign(2 * pk->lookups.size(), nullptr);
+    for (size_t l = 0; l < pk->lookups.size(); l++) {
+        GL355_TRY(key_upload(pk.get(), pk->lookups[l].in_code, &pk->d_lk_code[2 * l]));
+        GL355_TRY(key_upload(pk.get(), pk->lookups[l].tab_code, &pk->d_lk_code[2 * l + 1]));
     }
     for (int kd = 0; kd < 3; kd++) {
         std::vector<int32_t> cols, rots;
         for (auto& q : pk->queries[kd]) { cols.push_back(q.first); rots.push_back(q.second); }
-        for (int w = 0; w < 2; w++) {
-            GL355_TRY(D(std::max<size_t>(16, cols.size() * 4), &pk->d_q[kd][w]));
-            if (!cols.empty()) { GL355_HIP(ctx, hipMemcpyAsync(pk->d_q[kd][w], (w ? rots : cols).data(), cols.size() * 4, hipMemcpyHostToDevice, ctx->stream)); GL355_HIP(ctx, ctx->wait()); }
-        }
+        GL355_TRY(key_upload(pk.get(), cols, &pk->d_q[kd][0]));
+        GL355_TRY(key_upload(pk.get(), rots, &pk->d_q[kd][1]));
     }
     Scratch work(ctx);
     GL355_TRY(work.get(n * 32));
     // fixed columns: values, coefficients, commitments (Lagrange form)
-    GL355_TRY(D(std::max<uint32_t>(1, pk->n_fixed) * n * 32, &pk->fixed_vals));
-    GL355_TRY(D(std::max<uint32_t>(1, pk->n_fixed) * n * 32, &pk->fixed_polys));
-    if (pk->n_fixed) {
-        Staged sf(ctx);
-        GL355_TRY(sf.open(fixed_values, (size_t)pk->n_fixed * n * 32, 1));
-        hipLaunchKernelGGL(plk_to_mont_kernel, dim3(blocks((uint64_t)pk->n_fixed * n)), dim3(256), 0, ctx->stream, sf.as<uint64_t>(), pk->fixed_vals, (uint64_t)pk->n_fixed * n);
-        GL355_HIP(ctx, hipGetLastError());
-        GL355_HIP(ctx, ctx->wait());
-    }
-    pk->fixed_commitments.assign(8ull * pk->n_fixed, 0);
-    GL355_TRY(commit_columns(k_, pk->g_lagrange, pk->fixed_vals, pk->n_fixed, pk->fixed_commitments.data()));
-    for (uint32_t c = 0; c < pk->n_fixed; c++) GL355_TRY(lagrange_to_coeff(k_, pk->fixed_vals + 4ull * c * n, pk->fixed_polys + 4ull * c * n, work.as<uint64_t>()));
+    GL355_TRY(pk->dalloc(std::max<uint32_t>(1, pk->n_fixed) * n * 32, &pk->fixed_vals));
+    GL355_TRY(pk->dalloc(std::max<uint32_t>(1, pk->n_fixed) * n * 32, &pk->fixed_polys));
+    if (pk->n_fixed) GL355_TRY(columns_to_mont(ctx, fixed_values, (uint64_t)pk->n_fixed * n, pk->fixed_vals));
+    GL355_TRY(key_columns(pk.get(), pk->fixed_vals, pk->fixed_polys, pk->n_fixed, pk->fixed_commitments, work.as<uint64_t>()));
     // permutation: sigma values from the mapping, coefficients, commitments
-    GL355_TRY(D(std::max<uint32_t>(1, pk->n_perm) * n * 32, &pk->sigma_vals));
-    GL355_TRY(D(std::max<uint32_t>(1, pk->n_perm) * n * 32, &pk->sigma_polys));
+    GL355_TRY(pk->dalloc(std::max<uint32_t>(1, pk->n_perm) * n * 32, &pk->sigma_vals));
+    GL355_TRY(pk->dalloc(std::max<uint32_t>(1, pk->n_perm) * n * 32, &pk->sigma_polys));
     if (pk->n_perm) {
         Staged sm(ctx);
         GL355_TRY(sm.open(mapping, (size_t)pk->n_perm * n * 8, 1));
@@ -577,43 +1023,40 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
         GL355_HIP(ctx, ctx->wait());
         if (bad) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: permutation mapping out of range");
     }
-    pk->sigma_commitments.assign(8ull * pk->n_perm, 0);
-    GL355_TRY(commit_columns(k_, pk->g_lagrange, pk->sigma_vals, pk->n_perm, pk->sigma_commitments.data()));
-    for (uint32_t c = 0; c < pk->n_perm; c++) GL355_TRY(lagrange_to_coeff(k_, pk->sigma_vals + 4ull * c * n, pk->sigma_polys + 4ull * c * n, work.as<uint64_t>()));
+    GL355_TRY(key_columns(pk.get(), pk->sigma_vals, pk->sigma_polys, pk->n_perm, pk->sigma_commitments, work.as<uint64_t>()));
     // the transcript's initial scalar (halo2: vk.transcript_repr, a hash of the PINNED verifying key -- shape, fixed commitments, permutation
     // commitments): a descriptor whose digest field is zero gets Keccak-256 over (the whole descriptor | fixed commitments | sigma
     // commitments), as a big-endian integer mod r, so two circuits that differ only in fixed values or copy constraints never share a
     // Fiat-Shamir prefix and a C caller cannot forget the step.  A non-zero field is taken as given (a host that computed
     // halo2's own transcript_repr); gl355_plonk_pk_set_digest still overrides.
     if (!(desc[16] | desc[17] | desc[18] | desc[19])) {
-        std::vector<uint8_t> pre((size_t)words * 8 + (pk->fixed_commitments.size() + pk->sigma_commitments.size()) * 8);
-        memcpy(pre.data(), desc, (size_t)words * 8);
-        if (!pk->fixed_commitments.empty()) memcpy(pre.data() + (size_t)words * 8, pk->fixed_commitments.data(), pk->fixed_commitments.size() * 8);
-        if (!pk->sigma_commitments.empty()) memcpy(pre.data() + (size_t)words * 8 + pk->fixed_commitments.size() * 8, pk->sigma_commitments.data(), pk->sigma_commitments.size() * 8);
+        std::vector<uint64_t> pre(desc, desc + words);
+        pre.insert(pre.end(), pk->fixed_commitments.begin(), pk->fixed_commitments.end());
+        pre.insert(pre.end(), pk->sigma_commitments.begin(), pk->sigma_commitments.end());
         uint8_t hsh[32];
-        keccak256_host(pre.data(), pre.size(), hsh);
+        keccak256_host(reinterpret_cast<const uint8_t*>(pre.data()), pre.size() * 8, hsh);
         uint64_t w[4];
         for (int i = 0; i < 4; i++) { w[i] = 0; for (int b = 0; b < 8; b++) w[i] |= (uint64_t)hsh[31 - (8 * i + b)] << (8 * b); }
         pk->digest = Fr::from_words(w);
     }
     // l_0, l_last, l_active_row
-    GL355_TRY(D(3 * n * 32, &pk->l_polys));
+    GL355_TRY(pk->dalloc(3 * n * 32, &pk->l_polys));
     hipLaunchKernelGGL(plk_indicator_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, pk->l_polys, pk->l_polys + 4 * n, pk->l_polys + 8 * n, n, pk->usable);
     GL355_HIP(ctx, hipGetLastError());
-    for (int c = 0; c < 3; c++) GL355_TRY(lagrange_to_coeff(k_, pk->l_polys + 4ull * c * n, pk->l_polys + 4ull * c * n, work.as<uint64_t>()));
+    GL355_TRY(to_coeffs(pk.get(), pk->l_polys, pk->l_polys, 3, work.as<uint64_t>()));
     GL355_HIP(ctx, ctx->wait());
     pk->n_fix_cos = pk->n_fixed + pk->n_perm + 3;
     {
-        const uint32_t n_cosets = pk->n_pieces;              // evaluate_h visits as many cosets as the quotient has pieces (see gl355_plonk_prove)
+        const uint32_t n_cosets = pk->n_pieces;              // evaluate_h visits as many cosets as the quotient has pieces (see Proving::quotient)
         const size_t bytes = (size_t)n_cosets * pk->n_fix_cos * n * 32;
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
         static const bool off = getenv("GL355_PLONK_NO_FIXED_COSETS") != nullptr;            // A/B and small-memory runs
         if (!off && bytes < free_b / 3) {
-            GL355_TRY(D(bytes, &pk->fixed_cos));
+            GL355_TRY(pk->dalloc(bytes, &pk->fixed_cos));
             Scratch pre(ctx);
             GL355_TRY(pre.get(n * 32));
-            GL355_TRY(plonk_fixed_cosets(k_, 0, n_cosets, pk->fixed_cos, pre.as<uint64_t>(), work.as<uint64_t>()));
+            GL355_TRY(plonk_fixed_cosets(pk.get(), 0, n_cosets, pk->fixed_cos, pre.as<uint64_t>(), work.as<uint64_t>()));
             GL355_HIP(ctx, ctx->wait());
         }
     }
@@ -697,540 +1140,26 @@ int32_t gl355_plonk_prove(gl355_ctx* h, gl355_plonk_pk* pk, const uint64_t* advi
     // stage disarms it too and no later proof writes through a pointer its caller may have freed
     uint64_t* const export_quotient = pk->export_quotient;
     pk->export_quotient = nullptr;
-    const uint64_t n = pk->n, u = pk->usable;
-    const uint32_t n_cosets = pk->n_pieces;
-    const int32_t last_rot = -(int32_t)(pk->bf + 1);
-    const BlindKey key = blind_key_from_bytes(seed);
-    double ms[GL355_PLONK_STAGES];
-    for (int i = 0; i < GL355_PLONK_STAGES; i++) ms[i] = 0;
-    const bool timed = stage_ms != nullptr;
-    auto slot = [&](int i) { return timed ? &ms[i] : nullptr; };
-    KeccakTranscript tr;
-    std::vector<void*> mine;                                  // this proof's device buffers
-    struct Freer { Ctx* c; std::vector<void*>* v; ~Freer() { (void)c->wait(); for (void* p : *v) c->release(p); } } freer{ctx, &mine};
-    auto D = [&](size_t bytes, uint64_t** ptr) -> int32_t { void* p = nullptr; GL355_TRY(ctx->alloc(std::max<size_t>(bytes, 32), &p)); mine.push_back(p); *ptr = (uint64_t*)p; return GL355_OK; };
-    // a proof buffer that no later stage reads goes back to the context's allocator at once (everything runs on the context's stream, so a later
-    // owner of the block is ordered behind its last reader); what is still held at the end is released by `freer`
-    auto Free = [&](uint64_t*& ptr) {
-        if (!ptr) return;
-        for (auto it = mine.begin(); it != mine.end(); ++it) if (*it == (void*)ptr) { mine.erase(it); break; }
-        ctx->release(ptr);
-        ptr = nullptr;
-    };
-    uint64_t* work = nullptr;
-    GL355_TRY(D(n * 32, &work));                              // FFT scratch of the natural-order transforms
-    const Fr omega = Fr::root_of_unity(pk->k), omega_inv = omega.inv();
-    auto rotate = [&](const Fr& x, int32_t r) { return x * (r >= 0 ? omega : omega_inv).pow_u64((uint64_t)(r >= 0 ? r : -r)); };
-
-    // ---- vk, instances ------------------------------------------------------------------------------------------------------------
-    tr.common_scalar(pk->digest);
-    uint64_t *inst_vals = nullptr, *inst_polys = nullptr;
-    GL355_TRY(D(std::max<uint32_t>(1, pk->n_instance) * n * 32, &inst_vals));
-    GL355_TRY(D(std::max<uint32_t>(1, pk->n_instance) * n * 32, &inst_polys));
-    {
-        GL355_HIP(ctx, hipMemsetAsync(inst_vals, 0, std::max<uint32_t>(1, pk->n_instance) * n * 32, ctx->stream));
-        uint64_t off = 0;
-        for (uint32_t c = 0; c < pk->n_instance; c++) {
-            const uint32_t len = instance_lens[c];
-            if (len > u) return ctx->fail(GL355_E_INVALID_ARG, "plonk_prove: more instance values than usable rows");
-            if (len && !instances) return ctx->fail(GL355_E_INVALID_ARG, "plonk_prove: instance values missing");
-            if (len) {
-                std::vector<uint64_t> hv(4ull * len);
-                GL355_HIP(ctx, hipMemcpy(hv.data(), instances + 4 * off, 32ull * len, ptr_is_device(instances) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-                std::vector<Fr> fv(len);
-                for (uint32_t i = 0; i < len; i++) { fv[i] = Fr::from_words(hv.data() + 4 * i); tr.common_scalar(fv[i]); }
-                GL355_TRY(fr_to_device(ctx, fv, inst_vals + 4ull * c * n));
-            }
-            off += len;
-        }
-        for (uint32_t c = 0; c < pk->n_instance; c++) GL355_TRY(lagrange_to_coeff(pk, inst_vals + 4ull * c * n, inst_polys + 4ull * c * n, work));
+    Proving p(ctx, pk, seed, stage_ms != nullptr);
+    GL355_TRY(p.instances(instances, instance_lens));
+    GL355_TRY(p.advice(advice));
+    GL355_TRY(p.lookup_permute());
+    GL355_TRY(p.permutation_product());
+    GL355_TRY(p.lookup_product());
+    GL355_TRY(p.random_polynomial());
+    GL355_TRY(p.evaluate_h());
+    GL355_TRY(p.quotient(export_quotient));
+    GL355_TRY(p.evaluations());
+    GL355_TRY(p.shplonk());
+    if (trace) {
+        const Fr* challenges[8] = {&p.theta, &p.beta, &p.gamma, &p.y, &p.x, &p.sy, &p.sv, &p.su};
+        for (int i = 0; i < 8; i++) challenges[i]->to_words(trace + 4 * i);
     }
-
-    // ---- advice ---------------------------------------------------------------------------------------------------------------------
-    uint64_t *adv_vals = nullptr, *adv_polys = nullptr;
-    GL355_TRY(D(std::max<uint32_t>(1, pk->n_advice) * n * 32, &adv_vals));
-    GL355_TRY(D(std::max<uint32_t>(1, pk->n_advice) * n * 32, &adv_polys));
-    {
-        Timer t(ctx, slot(GL355_PLONK_STAGE_ADVICE), "advice");
-        if (pk->n_advice) {
-            Staged sa(ctx);
-            GL355_TRY(sa.open(advice, (size_t)pk->n_advice * n * 32, 1));
-            hipLaunchKernelGGL(plk_to_mont_kernel, dim3(blocks((uint64_t)pk->n_advice * n)), dim3(256), 0, ctx->stream, sa.as<uint64_t>(), adv_vals, (uint64_t)pk->n_advice * n);
-            GL355_HIP(ctx, hipGetLastError());
-            GL355_HIP(ctx, ctx->wait());
-        }
-        for (uint32_t c = 0; c < pk->n_advice; c++) GL355_TRY(random_rows(ctx, key, PLK_STREAM_ADVICE, c, u, n - u, adv_vals + 4 * ((uint64_t)c * n + u)));
-        std::vector<uint64_t> pts(8ull * pk->n_advice);
-        GL355_TRY(commit_columns(pk, pk->g_lagrange, adv_vals, pk->n_advice, pts.data(), u));
-        for (uint32_t c = 0; c < pk->n_advice; c++) tr.write_point(pts.data() + 8 * c);
-        for (uint32_t c = 0; c < pk->n_advice; c++) GL355_TRY(lagrange_to_coeff(pk, adv_vals + 4ull * c * n, adv_polys + 4ull * c * n, work));
-    }
-    // column pointer tables (values / coefficient forms) on the device
-    auto col_vals = [&](uint32_t kind, uint32_t idx) -> const uint64_t* { return (kind == 0 ? adv_vals : (kind == 1 ? pk->fixed_vals : inst_vals)) + 4ull * idx * n; };
-    const uint32_t kind_cols[3] = {pk->n_advice, pk->n_fixed, pk->n_instance};
-    const uint32_t n_all_cols = pk->n_advice + pk->n_fixed + pk->n_instance;
-    uint64_t* d_ptrs = nullptr;          // pointer tables: [values: adv | fix | inst][coset: adv | fix | inst][perm vals][perm sigma vals][coset perm cols][coset sigma][coset z]
-    GL355_TRY(D((size_t)(2 * n_all_cols + 5 * pk->n_perm + pk->n_sets + 16) * 8, &d_ptrs));
-    const uint64_t** dp = (const uint64_t**)d_ptrs;
-    const uint64_t* const* d_val_cols[3];
-    {
-        std::vector<const uint64_t*> v;
-        for (uint32_t kd = 0; kd < 3; kd++) for (uint32_t c = 0; c < kind_cols[kd]; c++) v.push_back(col_vals(kd, c));
-        GL355_TRY(ptrs_to_device(ctx, v, dp));
-        d_val_cols[0] = dp; d_val_cols[1] = dp + pk->n_advice; d_val_cols[2] = dp + pk->n_advice + pk->n_fixed;
-    }
-
-    // ---- lookups: compress, permute, commit ----------------------------------------------------------------------------------------
-    const Fr theta = tr.squeeze_challenge();
-    const uint32_t L = pk->n_lookups;
-    uint64_t *lkA = nullptr, *lkS = nullptr, *lkAp = nullptr, *lkZ = nullptr, *lk_polys = nullptr /* [L][3]: A', S', z */;
-    // compressed input / table columns only for the lookups whose expressions are not a single column query (none of the reference's nine)
-    uint32_t n_lk_a = 0, n_lk_s = 0;
-    for (uint32_t l = 0; l < L; l++) {
-        if (single_query(pk, pk->lookups[l].in_code).first >= 3) n_lk_a++;
-        if (single_query(pk, pk->lookups[l].tab_code).first >= 3) n_lk_s++;
-    }
-    GL355_TRY(D((size_t)std::max(1u, n_lk_a) * n * 32, &lkA));
-    GL355_TRY(D((size_t)std::max(1u, n_lk_s) * n * 32, &lkS));
-    GL355_TRY(D((size_t)std::max(1u, 2 * L) * n * 32, &lkAp));          // A'_0 S'_0 A'_1 S'_1 ... : one batched commitment
-    GL355_TRY(D((size_t)std::max(1u, L) * n * 32, &lkZ));
-    GL355_TRY(D((size_t)std::max(1u, 3 * L) * n * 32, &lk_polys));
-    std::vector<const uint64_t*> lk_a_ptr(L), lk_s_ptr(L);         // the compressed input / table columns (values)
-    {
-        uint32_t ia = 0, is = 0;
-        for (uint32_t l = 0; l < L; l++) {
-            lk_a_ptr[l] = single_query(pk, pk->lookups[l].in_code).first >= 3 ? lkA + 4ull * (ia++) * n : nullptr;
-            lk_s_ptr[l] = single_query(pk, pk->lookups[l].tab_code).first >= 3 ? lkS + 4ull * (is++) * n : nullptr;
-        }
-    }
-    {
-        Timer t(ctx, slot(GL355_PLONK_STAGE_LOOKUP_PERMUTE), "lookup_permute");
-        for (uint32_t l = 0; l < L; l++) {
-            const auto qa = single_query(pk, pk->lookups[l].in_code), qs = single_query(pk, pk->lookups[l].tab_code);
-            if (qa.first < 3) lk_a_ptr[l] = col_vals(qa.first, qa.second);
-            else GL355_TRY(run_program(pk, pk->d_lk_code[2 * l], (uint32_t)(pk->lookups[l].in_code.size() / 4), d_val_cols, theta, nullptr, const_cast<uint64_t*>(lk_a_ptr[l]), false));
-            if (qs.first < 3) lk_s_ptr[l] = col_vals(qs.first, qs.second);
-            else GL355_TRY(run_program(pk, pk->d_lk_code[2 * l + 1], (uint32_t)(pk->lookups[l].tab_code.size() / 4), d_val_cols, theta, nullptr, const_cast<uint64_t*>(lk_s_ptr[l]), false));
-            uint64_t* Ap = lkAp + 8ull * l * n;
-            uint64_t* Sp = Ap + 4 * n;
-            GL355_TRY(permute_pair(ctx, lk_a_ptr[l], lk_s_ptr[l], u, Ap, Sp));
-            GL355_TRY(random_rows(ctx, key, PLK_STREAM_LOOKUP_PERMUTED, 2 * l, u, n - u, Ap + 4 * u));
-            GL355_TRY(random_rows(ctx, key, PLK_STREAM_LOOKUP_PERMUTED, 2 * l + 1, u, n - u, Sp + 4 * u));
-        }
-        std::vector<uint64_t> pts(16ull * L);
-        GL355_TRY(commit_columns(pk, pk->g_lagrange, lkAp, 2 * L, pts.data(), u));
-        for (uint32_t l = 0; l < 2 * L; l++) tr.write_point(pts.data() + 8 * l);
-        for (uint32_t l = 0; l < L; l++) {
-            GL355_TRY(lagrange_to_coeff(pk, lkAp + 8ull * l * n, lk_polys + 12ull * l * n, work));
-            GL355_TRY(lagrange_to_coeff(pk, lkAp + 8ull * l * n + 4 * n, lk_polys + 12ull * l * n + 4 * n, work));
-        }
-    }
-
-    // ---- permutation grand products ----------------------------------------------------------------------------------------------------
-    const Fr beta = tr.squeeze_challenge();
-    const Fr gamma = tr.squeeze_challenge();
-    uint64_t *perm_z = nullptr, *perm_polys = nullptr, *num = nullptr, *den = nullptr, *ratio = nullptr, *d_small = nullptr;
-    GL355_TRY(D((size_t)std::max(1u, pk->n_sets) * n * 32, &perm_z));
-    GL355_TRY(D((size_t)std::max(1u, pk->n_sets) * n * 32, &perm_polys));
-    GL355_TRY(D(n * 32, &num));
-    GL355_TRY(D(n * 32, &den));
-    GL355_TRY(D(n * 32, &ratio));
-    GL355_TRY(D(256, &d_small));                     // [0..3] the constant one, [4] a flag word
-    uint32_t* d_bad = reinterpret_cast<uint32_t*>(d_small + 4);
-    {
-        std::vector<Fr> one(1, Fr::one());
-        GL355_TRY(fr_to_device(ctx, one, d_small));
-        GL355_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
-    }
-    const uint64_t** d_perm_vals = dp + 2 * n_all_cols;
-    const uint64_t** d_perm_sig = d_perm_vals + pk->n_perm;
-    {
-        Timer t(ctx, slot(GL355_PLONK_STAGE_PERMUTATION), "permutation");
-        std::vector<const uint64_t*> pv, psg;
-        for (uint32_t j = 0; j < pk->n_perm; j++) { pv.push_back(col_vals(pk->perm_cols[j].first, pk->perm_cols[j].second)); psg.push_back(pk->sigma_vals + 4ull * j * n); }
-        GL355_TRY(ptrs_to_device(ctx, pv, d_perm_vals));
-        GL355_TRY(ptrs_to_device(ctx, psg, d_perm_sig));
-        for (uint32_t s = 0; s < pk->n_sets; s++) {
-            PlkPermRowArgs a;
-            a.n = n; a.j0 = s * pk->chunk_len; a.j1 = std::min(pk->n_perm, (s + 1) * pk->chunk_len);
-            a.vals = d_perm_vals; a.sigma = d_perm_sig; a.omega_pows = pk->omega_pows; a.delta_pows = pk->delta_pows;
-            a.beta = to_dev(beta); a.gamma = to_dev(gamma); a.num = num; a.den = den;
-            hipLaunchKernelGGL(plk_perm_rows_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, a);
-            hipLaunchKernelGGL(plk_batch_div_kernel, dim3(blocks((n + PLK_INV_CHUNK - 1) / PLK_INV_CHUNK, 64)), dim3(64), 0, ctx->stream, (const uint64_t*)num, den, ratio, n, d_bad);
-            GL355_HIP(ctx, hipGetLastError());
-            uint64_t* z = perm_z + 4ull * s * n;
-            // z_s[0] = z_{s-1}[usable]: read before the blinding of set s overwrites nothing of set s - 1 (its rows > usable only)
-            GL355_TRY(running_product(ctx, ratio, n, s ? perm_z + 4 * ((uint64_t)(s - 1) * n + u) : d_small, z));
-            GL355_TRY(random_rows(ctx, key, PLK_STREAM_PERM_Z, s, u + 1, n - u - 1, z + 4 * (u + 1)));
-        }
-        std::vector<uint64_t> pts(8ull * pk->n_sets);
-        GL355_TRY(commit_columns(pk, pk->g_lagrange, perm_z, pk->n_sets, pts.data()));
-        for (uint32_t s = 0; s < pk->n_sets; s++) tr.write_point(pts.data() + 8 * s);
-        for (uint32_t s = 0; s < pk->n_sets; s++) GL355_TRY(lagrange_to_coeff(pk, perm_z + 4ull * s * n, perm_polys + 4ull * s * n, work));
-    }
-    // ---- lookup grand products --------------------------------------------------------------------------------------------------------
-    {
-        Timer t(ctx, slot(GL355_PLONK_STAGE_LOOKUP_PRODUCT), "lookup_product");
-        for (uint32_t l = 0; l < L; l++) {
-            const uint64_t* Ap = lkAp + 8ull * l * n;
-            hipLaunchKernelGGL(plk_lookup_rows_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, lk_a_ptr[l], lk_s_ptr[l], Ap, Ap + 4 * n, n,
-                               to_dev(beta), to_dev(gamma), num, den);
-            hipLaunchKernelGGL(plk_batch_div_kernel, dim3(blocks((n + PLK_INV_CHUNK - 1) / PLK_INV_CHUNK, 64)), dim3(64), 0, ctx->stream, (const uint64_t*)num, den, ratio, n, d_bad);
-            GL355_HIP(ctx, hipGetLastError());
-            uint64_t* z = lkZ + 4ull * l * n;
-            GL355_TRY(running_product(ctx, ratio, n, d_small, z));
-            GL355_TRY(random_rows(ctx, key, PLK_STREAM_LOOKUP_Z, l, u + 1, n - u - 1, z + 4 * (u + 1)));
-        }
-        std::vector<uint64_t> pts(8ull * L);
-        GL355_TRY(commit_columns(pk, pk->g_lagrange, lkZ, L, pts.data()));
-        for (uint32_t l = 0; l < L; l++) tr.write_point(pts.data() + 8 * l);
-        for (uint32_t l = 0; l < L; l++) GL355_TRY(lagrange_to_coeff(pk, lkZ + 4ull * l * n, lk_polys + 12ull * l * n + 8 * n, work));
-        uint32_t bad = 0;
-        GL355_HIP(ctx, ctx->d2h(&bad, d_bad, 4));
-        GL355_HIP(ctx, ctx->wait());
-        if (bad) return ctx->fail(GL355_E_INVALID_ARG, "plonk_prove: a grand-product denominator is zero under these challenges (retry with another transcript input)");
-    }
-    // the value forms have done their work (commitments, grand products): from here on only coefficient forms are read
-    Free(adv_vals); Free(lkA); Free(lkS); Free(lkAp); Free(lkZ); Free(perm_z); Free(num); Free(den); Free(ratio);
-    // ---- vanishing argument: the random polynomial -----------------------------------------------------------------------------------------
-    uint64_t* random_poly = nullptr;
-    GL355_TRY(D(n * 32, &random_poly));
-    {
-        Timer t(ctx, slot(GL355_PLONK_STAGE_VANISHING_RANDOM), "vanishing_random");
-        GL355_TRY(random_rows(ctx, key, PLK_STREAM_RANDOM_POLY, 0, 0, n, random_poly));
-        uint64_t pt[8];
-        GL355_TRY(commit_columns(pk, pk->g, random_poly, 1, pt));
-        tr.write_point(pt);
-    }
-
-    // ---- evaluate_h -----------------------------------------------------------------------------------------------------------------------
-    const Fr y = tr.squeeze_challenge();
-    uint64_t *h_ext = nullptr, *acc = nullptr, *cos = nullptr, *a_in = nullptr, *s_in = nullptr, *pre = nullptr, *fix_tmp = nullptr;
-    const uint32_t n_dyn = pk->n_advice + pk->n_instance + pk->n_sets + 3 * L;           // per-proof polynomials: advice | instance | perm z | lookups (A' S' z)
-    GL355_TRY(D((size_t)pk->n_pieces * n * 32, &h_ext));              // [n_pieces] the quotient restricted to each coset
-    GL355_TRY(D(n * 32, &acc));
-    GL355_TRY(D((size_t)std::max(1u, n_dyn) * n * 32, &cos));
-    GL355_TRY(D(n * 32, &a_in));
-    GL355_TRY(D(n * 32, &s_in));
-    GL355_TRY(D(n * 32, &pre));
-    if (!pk->fixed_cos) GL355_TRY(D((size_t)pk->n_fix_cos * n * 32, &fix_tmp));
-    {
-        Timer t(ctx, slot(GL355_PLONK_STAGE_EVALUATE_H), "evaluate_h");
-        std::vector<const uint64_t*> src;
-        for (uint32_t c = 0; c < pk->n_advice; c++) src.push_back(adv_polys + 4ull * c * n);
-        for (uint32_t c = 0; c < pk->n_instance; c++) src.push_back(inst_polys + 4ull * c * n);
-        for (uint32_t s = 0; s < pk->n_sets; s++) src.push_back(perm_polys + 4ull * s * n);
-        for (uint32_t l = 0; l < 3 * L; l++) src.push_back(lk_polys + 4ull * l * n);
-        auto dyn = [&](uint32_t i) -> const uint64_t* { return cos + 4ull * i * n; };
-        const uint32_t o_inst = pk->n_advice, o_z = o_inst + pk->n_instance, o_lk = o_z + pk->n_sets;
-        const uint64_t** d_cos_cols = dp + n_all_cols;
-        const uint64_t* const* d_cos_kind[3] = {d_cos_cols, d_cos_cols + pk->n_advice, d_cos_cols + pk->n_advice + pk->n_fixed};
-        const uint64_t** d_cperm = d_perm_sig + pk->n_perm;
-        const uint64_t** d_csig = d_cperm + pk->n_perm;
-        const uint64_t** d_cz = d_csig + pk->n_perm;
-        const Fr ext_omega = Fr::root_of_unity(pk->ext_k);
-
-        Fr base = plonk_zeta();                                    // zeta * ext_omega^c
-        for (uint32_t c = 0; c < n_cosets; c++) {
-            // the key's polynomials on this coset: precomputed, or recomputed into fix_tmp
-            const uint64_t* fix = pk->fixed_cos ? pk->fixed_cos + 4ull * (uint64_t)c * pk->n_fix_cos * n : fix_tmp;
-            if (!pk->fixed_cos) GL355_TRY(plonk_fixed_cosets(pk, c, c + 1, fix_tmp, pre, work));
-            auto fixc = [&](uint32_t i) -> const uint64_t* { return fix + 4ull * i * n; };
-            auto col_cos = [&](uint32_t kind, uint32_t idx) -> const uint64_t* { return kind == 0 ? dyn(idx) : (kind == 1 ? fixc(idx) : dyn(o_inst + idx)); };
-            {
-                std::vector<const uint64_t*> v;
-                for (uint32_t kd = 0; kd < 3; kd++) for (uint32_t i = 0; i < kind_cols[kd]; i++) v.push_back(col_cos(kd, i));
-                GL355_TRY(ptrs_to_device(ctx, v, d_cos_cols));
-                v.clear();
-                for (uint32_t j = 0; j < pk->n_perm; j++) v.push_back(col_cos(pk->perm_cols[j].first, pk->perm_cols[j].second));
-                GL355_TRY(ptrs_to_device(ctx, v, d_cperm));
-                v.clear();
-                for (uint32_t j = 0; j < pk->n_perm; j++) v.push_back(fixc(pk->n_fixed + j));
-                GL355_TRY(ptrs_to_device(ctx, v, d_csig));
-                v.clear();
-                for (uint32_t s = 0; s < pk->n_sets; s++) v.push_back(dyn(o_z + s));
-                GL355_TRY(ptrs_to_device(ctx, v, d_cz));
-            }
-            const uint64_t *c_l0 = fixc(pk->n_fixed + pk->n_perm), *c_ll = c_l0 + 4 * n, *c_la = c_l0 + 8 * n;
-            uint64_t bw[4];
-            base.to_words(bw);
-            // (round 6: the coset transform in block form -- no power table, no product per coefficient, broadcast twiddles in the high stages)
-            for (uint32_t i = 0; i < n_dyn; i++) GL355_TRY(bn254_fr_ntt_mont_coset_dif(ctx, src[i], n, cos + 4ull * i * n, pk->k, pk->tw_fwd, bw, pre, i == 0));
-            // custom gates
-            GL355_TRY(run_program(pk, pk->d_gate_code, (uint32_t)(pk->gate_code.size() / 4), d_cos_kind, y, nullptr, acc, true));
-            if (pk->n_sets) {
-                PlkPermHArgs a;
-                a.n = n; a.log_n = pk->k; a.n_sets = pk->n_sets; a.chunk_len = pk->chunk_len; a.n_perm = pk->n_perm; a.last_rot = last_rot; a.acc = acc;
-                a.l0 = c_l0; a.l_last = c_ll; a.l_active = c_la;
-                a.z = d_cz; a.sigma = d_csig; a.col = d_cperm; a.omega_pows = pk->omega_pows; a.delta_pows = pk->delta_pows;
-                a.y = to_dev(y); a.beta = to_dev(beta); a.gamma = to_dev(gamma); a.coset_base = to_dev(base);
-                hipLaunchKernelGGL(plk_perm_h_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, a);
-                GL355_HIP(ctx, hipGetLastError());
-            }
-            for (uint32_t l = 0; l < L; l++) {
-                const auto qa = single_query(pk, pk->lookups[l].in_code), qs = single_query(pk, pk->lookups[l].tab_code);
-                if (qa.first == 3) GL355_TRY(run_program(pk, pk->d_lk_code[2 * l], (uint32_t)(pk->lookups[l].in_code.size() / 4), d_cos_kind, theta, nullptr, a_in, true));
-                if (qs.first == 3) GL355_TRY(run_program(pk, pk->d_lk_code[2 * l + 1], (uint32_t)(pk->lookups[l].tab_code.size() / 4), d_cos_kind, theta, nullptr, s_in, true));
-                PlkLookupHArgs a;
-                a.n = n; a.log_n = pk->k; a.acc = acc; a.l0 = c_l0; a.l_last = c_ll; a.l_active = c_la;
-                a.ap = dyn(o_lk + 3 * l); a.sp = dyn(o_lk + 3 * l + 1); a.z = dyn(o_lk + 3 * l + 2);
-                a.a_in = qa.first < 3 ? col_cos(qa.first, qa.second) : a_in; a.s_in = qs.first < 3 ? col_cos(qs.first, qs.second) : s_in;
-                a.y = to_dev(y); a.beta = to_dev(beta); a.gamma = to_dev(gamma);
-                hipLaunchKernelGGL(plk_lookup_h_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, a);
-                GL355_HIP(ctx, hipGetLastError());
-            }
-            const Fr t_inv = (base.pow_u64(n) - Fr::one()).inv();                 // 1 / ((zeta omega_ext^c)^n - 1)
-            hipLaunchKernelGGL(plk_finish_h_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, (const uint64_t*)acc, n, (uint64_t)c, to_dev(t_inv), h_ext);
-            GL355_HIP(ctx, hipGetLastError());
-            base = base * ext_omega;
-        }
-    }
-    // ---- vanishing argument: h's coefficients, pieces, commitments ---------------------------------------------------------------------------
-    // halo2 evaluates h on the whole extended domain (2^(extended_k - k) cosets of the 2^k domain) and inverts one transform of that size.  The
-    // same polynomial follows from `degree - 1` cosets: h = sum_p X^(p n) h_p with deg h_p < n, and on the coset g_c H, X^n is the constant
-    // t_c = g_c^n, so h restricted to the coset IS the polynomial R_c = sum_p t_c^p h_p (degree < n): one inverse coset transform of size n
-    // per coset gives R_c, and the pieces are h_p = sum_c (V^-1)[p][c] R_c with the Vandermonde matrix V[c][p] = t_c^p -- a host-side inversion
-    // of a (degree - 1)^2 matrix and one linear combination per piece.  5 of 8 cosets at the reference's degree 6: 3/8 of evaluate_h's
-    // transforms and kernels gone, no transform over the extended domain at all, same bytes (the quotient is unique).
-    Free(cos); Free(acc); Free(a_in); Free(s_in); Free(fix_tmp);
-    uint64_t* h_coeffs = nullptr;                                      // [n_pieces] the quotient's pieces
-    GL355_TRY(D((size_t)pk->n_pieces * n * 32, &h_coeffs));
-    {
-        Timer t(ctx, slot(GL355_PLONK_STAGE_QUOTIENT_COMMIT), "quotient_commit");
-        const uint32_t P = pk->n_pieces;
-        const Fr ext_omega = Fr::root_of_unity(pk->ext_k), n_inv = Fr::from_u64(n).inv();
-        std::vector<Fr> tc(P);
-        Fr base = plonk_zeta();
-        for (uint32_t c = 0; c < P; c++) {
-            // R_c: values on g_c H in bit-reversed order -> coefficients: inverse transform (no gather), coefficient i times g_c^-i / n
-            uint64_t bw[4], fw[4];
-            base.inv().to_words(bw);
-            n_inv.to_words(fw);
-            GL355_TRY(bn254_fr_power_table(ctx, bw, fw, n, pre));
-            GL355_TRY(bn254_fr_ntt_mont_from_bitrev(ctx, h_ext + 4ull * c * n, h_ext + 4ull * c * n, n, pk->k, pk->tw_inv, pre, nullptr));
-            tc[c] = base.pow_u64(n);
-            base = base * ext_omega;
-        }
-        // V^-1 by Gauss-Jordan over Fr (P <= 9)
-        std::vector<std::vector<Fr>> M(P, std::vector<Fr>(2 * P, Fr::zero()));
-        for (uint32_t c = 0; c < P; c++) {
-            Fr pw = Fr::one();
-            for (uint32_t q = 0; q < P; q++) { M[c][q] = pw; pw = pw * tc[c]; }
-            M[c][P + c] = Fr::one();
-        }
-        for (uint32_t col = 0; col < P; col++) {
-            uint32_t piv = col;
-            while (piv < P && M[piv][col].is_zero()) piv++;
-            if (piv == P) return ctx->fail(GL355_E_HIP, "plonk_prove: singular coset matrix (internal)");
-            std::swap(M[piv], M[col]);
-            const Fr inv = M[col][col].inv();
-            for (uint32_t j = 0; j < 2 * P; j++) M[col][j] = M[col][j] * inv;
-            for (uint32_t r = 0; r < P; r++) {
-                if (r == col || M[r][col].is_zero()) continue;
-                const Fr f = M[r][col];
-                for (uint32_t j = 0; j < 2 * P; j++) M[r][j] = M[r][j] - f * M[col][j];
-            }
-        }
-        std::vector<const uint64_t*> rs;
-        for (uint32_t c = 0; c < P; c++) rs.push_back(h_ext + 4ull * c * n);
-        for (uint32_t q = 0; q < P; q++) {
-            std::vector<Fr> cs(P);
-            for (uint32_t c = 0; c < P; c++) cs[c] = M[q][P + c];          // (V^-1)[q][c]
-            GL355_TRY(lincomb(pk, rs, cs, {}, nullptr, h_coeffs + 4ull * q * n));
-        }
-        if (export_quotient) {             // gl355_plonk_pk_export_quotient: the pieces as canonical integers, for a comparison with the extended-domain quotient
-            uint64_t* plain = nullptr;
-            GL355_TRY(D((size_t)P * n * 32, &plain));
-            hipLaunchKernelGGL(plk_from_mont_kernel, dim3(blocks((uint64_t)P * n)), dim3(256), 0, ctx->stream, (const uint64_t*)h_coeffs, plain, (uint64_t)P * n);
-            GL355_HIP(ctx, hipGetLastError());
-            GL355_HIP(ctx, ctx->d2h(export_quotient, plain, (size_t)P * n * 32));
-            GL355_HIP(ctx, ctx->wait());
-        }
-        std::vector<uint64_t> pts(8ull * pk->n_pieces);
-        GL355_TRY(commit_columns(pk, pk->g, h_coeffs, pk->n_pieces, pts.data()));
-        for (uint32_t i = 0; i < pk->n_pieces; i++) tr.write_point(pts.data() + 8 * i);
-    }
-
-    // ---- evaluations at x ----------------------------------------------------------------------------------------------------------------------
-    const Fr x = tr.squeeze_challenge();
-    const Fr xn = x.pow_u64(n);
-    const Fr x_next = rotate(x, 1), x_last = rotate(x, last_rot), x_inv = rotate(x, -1);
-    // (label, polynomial, point): every evaluation the proof carries, in transcript order, then h and the random polynomial
-    struct Q { uint32_t poly_id; const uint64_t* poly; Fr point; };
-    std::vector<Q> qs;
-    // polynomial ids: one per committed polynomial (the SHPLONK grouping is by polynomial)
-    auto id_adv = [&](uint32_t c) { return c; };
-    auto id_fix = [&](uint32_t c) { return 1000 + c; };
-    auto id_sig = [&](uint32_t j) { return 2000 + j; };
-    auto id_pz = [&](uint32_t s) { return 3000 + s; };
-    auto id_lk = [&](uint32_t l, uint32_t w) { return 4000 + 3 * l + w; };          // w: 0 A', 1 S', 2 z
-    const uint32_t ID_H = 9000, ID_RANDOM = 9001;
-    uint64_t* h_poly = nullptr;
-    GL355_TRY(D(n * 32, &h_poly));
-    std::vector<Fr> evals;
-    {
-        Timer t(ctx, slot(GL355_PLONK_STAGE_EVALUATIONS), "evaluations");
-        // h(X) = sum_i x^(n i) h_i(X)
-        {
-            std::vector<const uint64_t*> ps;
-            std::vector<Fr> cs;
-            Fr p = Fr::one();
-            for (uint32_t i = 0; i < pk->n_pieces; i++) { ps.push_back(h_coeffs + 4ull * i * n); cs.push_back(p); p = p * xn; }
-            GL355_TRY(lincomb(pk, ps, cs, {}, nullptr, h_poly));
-        }
-        for (auto& q : pk->queries[0]) qs.push_back({id_adv(q.first), adv_polys + 4ull * q.first * n, rotate(x, q.second)});
-        for (auto& q : pk->queries[1]) qs.push_back({id_fix(q.first), pk->fixed_polys + 4ull * q.first * n, rotate(x, q.second)});
-        qs.push_back({ID_RANDOM, random_poly, x});
-        for (uint32_t j = 0; j < pk->n_perm; j++) qs.push_back({id_sig(j), pk->sigma_polys + 4ull * j * n, x});
-        for (uint32_t s = 0; s < pk->n_sets; s++) {
-            qs.push_back({id_pz(s), perm_polys + 4ull * s * n, x});
-            qs.push_back({id_pz(s), perm_polys + 4ull * s * n, x_next});
-            if (s + 1 < pk->n_sets) qs.push_back({id_pz(s), perm_polys + 4ull * s * n, x_last});
-        }
-        for (uint32_t l = 0; l < L; l++) {
-            const uint64_t *Ap = lk_polys + 12ull * l * n, *Sp = Ap + 4 * n, *Z = Ap + 8 * n;
-            qs.push_back({id_lk(l, 2), Z, x});
-            qs.push_back({id_lk(l, 2), Z, x_next});
-            qs.push_back({id_lk(l, 0), Ap, x});
-            qs.push_back({id_lk(l, 0), Ap, x_inv});
-            qs.push_back({id_lk(l, 1), Sp, x});
-        }
-        const size_t n_written = qs.size();
-        qs.push_back({ID_H, h_poly, x});
-        std::vector<const uint64_t*> ps;
-        std::vector<Fr> pts;
-        for (auto& q : qs) { ps.push_back(q.poly); pts.push_back(q.point); }
-        GL355_TRY(eval_polys(pk, ps, pts, evals));
-        for (size_t i = 0; i < n_written; i++) tr.write_scalar(evals[i]);
-    }
-    // evaluation of (poly id, point) from the table above
-    bool eval_missing = false;              // a (polynomial, point) pair SHPLONK asks for that the evaluation stage never computed: an internal error, not a zero
-    auto eval_of = [&](uint32_t id, const Fr& pt) -> Fr {
-        for (size_t i = 0; i < qs.size(); i++) if (qs[i].poly_id == id && qs[i].point == pt) return evals[i];
-        eval_missing = true;
-        return Fr::zero();
-    };
-
-    // ---- SHPLONK -------------------------------------------------------------------------------------------------------------------------------
-    {
-        Timer t(ctx, slot(GL355_PLONK_STAGE_SHPLONK), "shplonk");
-        // the opening queries in create_proof's order
-        struct OQ { uint32_t id; const uint64_t* poly; Fr point; };
-        std::vector<OQ> oq;
-        for (auto& q : pk->queries[0]) oq.push_back({id_adv(q.first), adv_polys + 4ull * q.first * n, rotate(x, q.second)});
-        for (uint32_t s = 0; s < pk->n_sets; s++) { oq.push_back({id_pz(s), perm_polys + 4ull * s * n, x}); oq.push_back({id_pz(s), perm_polys + 4ull * s * n, x_next}); }
-        for (uint32_t s = pk->n_sets; s-- > 0;) if (s + 1 < pk->n_sets) oq.push_back({id_pz(s), perm_polys + 4ull * s * n, x_last});
-        for (uint32_t l = 0; l < L; l++) {
-            const uint64_t *Ap = lk_polys + 12ull * l * n, *Sp = Ap + 4 * n, *Z = Ap + 8 * n;
-            oq.push_back({id_lk(l, 2), Z, x}); oq.push_back({id_lk(l, 0), Ap, x}); oq.push_back({id_lk(l, 1), Sp, x});
-            oq.push_back({id_lk(l, 0), Ap, x_inv}); oq.push_back({id_lk(l, 2), Z, x_next});
-        }
-        for (auto& q : pk->queries[1]) oq.push_back({id_fix(q.first), pk->fixed_polys + 4ull * q.first * n, rotate(x, q.second)});
-        for (uint32_t j = 0; j < pk->n_perm; j++) oq.push_back({id_sig(j), pk->sigma_polys + 4ull * j * n, x});
-        oq.push_back({ID_H, h_poly, x});
-        oq.push_back({ID_RANDOM, random_poly, x});
-        const Fr sy = tr.squeeze_challenge();
-        const Fr sv = tr.squeeze_challenge();
-        // construct_intermediate_sets: polynomials in first-appearance order with their sorted point sets; rotation sets = the distinct
-        // point sets in first-appearance order
-        auto less = [](const Fr& a, const Fr& b) { return a.less_than(b); };
-        struct PolyPts { uint32_t id; const uint64_t* poly; std::vector<Fr> pts; };
-        std::vector<PolyPts> polys;
-        for (auto& q : oq) {
-            size_t i = 0;
-            for (; i < polys.size(); i++) if (polys[i].id == q.id) break;
-            if (i == polys.size()) polys.push_back({q.id, q.poly, {}});
-            bool have = false;
-            for (auto& p : polys[i].pts) have = have || p == q.point;
-            if (!have) polys[i].pts.push_back(q.point);
-        }
-        struct RSet { std::vector<Fr> pts; std::vector<size_t> members; };
-        std::vector<RSet> sets;
-        std::vector<Fr> super;
-        for (size_t i = 0; i < polys.size(); i++) {
-            std::sort(polys[i].pts.begin(), polys[i].pts.end(), less);
-            size_t s = 0;
-            for (; s < sets.size(); s++) if (sets[s].pts == polys[i].pts) break;
-            if (s == sets.size()) sets.push_back({polys[i].pts, {}});
-            sets[s].members.push_back(i);
-            for (auto& p : polys[i].pts) { bool have = false; for (auto& q : super) have = have || q == p; if (!have) super.push_back(p); }
-        }
-        std::sort(super.begin(), super.end(), less);
-        // h(X) = sum_i v^i (sum_j y^j (p_ij(X) - r_ij(X))) / prod_{t in S_i} (X - t)
-        uint64_t *sh_h = nullptr, *bufa = nullptr, *bufb = nullptr;
-        GL355_TRY(D(n * 32, &sh_h));
-        GL355_TRY(D(n * 32, &bufa));
-        GL355_TRY(D(n * 32, &bufb));
-        GL355_HIP(ctx, hipMemsetAsync(sh_h, 0, n * 32, ctx->stream));
-        std::vector<std::vector<std::vector<Fr>>> r_coeffs(sets.size());      // [set][member] low-degree remainders
-        Fr vi = Fr::one();
-        for (size_t s = 0; s < sets.size(); s++) {
-            std::vector<const uint64_t*> ps;
-            std::vector<Fr> cs, low(sets[s].pts.size(), Fr::zero());
-            Fr yj = Fr::one();
-            for (size_t m : sets[s].members) {
-                std::vector<Fr> ev;
-                for (auto& p : sets[s].pts) ev.push_back(eval_of(polys[m].id, p));
-                if (eval_missing) return ctx->fail(GL355_E_UNSUPPORTED, "plonk_prove: an opening asks for an evaluation that was not computed");
-                r_coeffs[s].push_back(interpolate(sets[s].pts, ev));
-                for (size_t t = 0; t < low.size(); t++) low[t] = low[t] + yj * r_coeffs[s].back()[t];
-                ps.push_back(polys[m].poly);
-                cs.push_back(yj);
-                yj = yj * sy;
-            }
-            GL355_TRY(lincomb(pk, ps, cs, low, nullptr, bufa));
-            uint64_t *src_ = bufa, *dst_ = bufb;
-            for (auto& p : sets[s].pts) {
-                uint64_t pw[4];
-                p.to_words(pw);
-                GL355_TRY(kzg_divide(ctx, src_, n, h_from_words(pw), 1, dst_, 0, nullptr));
-                std::swap(src_, dst_);
-            }
-            GL355_TRY(lincomb(pk, {src_}, {vi}, {}, sh_h, sh_h));
-            vi = vi * sv;
-        }
-        uint64_t pt[8];
-        GL355_TRY(commit_columns(pk, pk->g, sh_h, 1, pt));
-        tr.write_point(pt);
-        const Fr su = tr.squeeze_challenge();
-        // L(X) = (sum_i v^i Z_{T \ S_i}(u) sum_j y^j (p_ij(X) - r_ij(u)) - Z_T(u) h(X)) / Z_{T \ S_0}(u)
-        Fr zt = Fr::one();
-        for (auto& p : super) zt = zt * (su - p);
-        std::vector<Fr> zdiff(sets.size(), Fr::one());
-        for (size_t s = 0; s < sets.size(); s++)
-            for (auto& p : super) { bool in = false; for (auto& q : sets[s].pts) in = in || q == p; if (!in) zdiff[s] = zdiff[s] * (su - p); }
-        const Fr z0inv = zdiff[0].inv();
-        std::vector<const uint64_t*> ps;
-        std::vector<Fr> cs;
-        Fr cterm = Fr::zero();
-        vi = Fr::one();
-        for (size_t s = 0; s < sets.size(); s++) {
-            const Fr scale = vi * zdiff[s] * z0inv;
-            Fr yj = Fr::one();
-            for (size_t mi = 0; mi < sets[s].members.size(); mi++) {
-                ps.push_back(polys[sets[s].members[mi]].poly);
-                cs.push_back(scale * yj);
-                cterm = cterm + scale * yj * horner(r_coeffs[s][mi], su);
-                yj = yj * sy;
-            }
-            vi = vi * sv;
-        }
-        ps.push_back(sh_h);
-        cs.push_back((zt * z0inv).neg());
-        GL355_TRY(lincomb(pk, ps, cs, {cterm}, nullptr, bufa));
-        uint64_t uw[4];
-        su.to_words(uw);
-        GL355_TRY(kzg_divide(ctx, bufa, n, h_from_words(uw), 1, bufb, 0, nullptr));
-        GL355_TRY(commit_columns(pk, pk->g, bufb, 1, pt));
-        tr.write_point(pt);
-        if (trace) { sy.to_words(trace + 20); sv.to_words(trace + 24); su.to_words(trace + 28); }
-    }
-    if (trace) { theta.to_words(trace); beta.to_words(trace + 4); gamma.to_words(trace + 8); y.to_words(trace + 12); x.to_words(trace + 16); }
     GL355_HIP(ctx, ctx->wait());
-    *proof_len = tr.proof.size();
-    if (tr.proof.size() > capacity) return ctx->fail(GL355_E_INVALID_ARG, "plonk_prove: proof buffer too small (gl355_plonk_pk_info gives the size)");
-    memcpy(proof, tr.proof.data(), tr.proof.size());
-    if (stage_ms) for (int i = 0; i < GL355_PLONK_STAGES; i++) stage_ms[i] = ms[i];
+    *proof_len = p.tr.proof.size();
+    if (p.tr.proof.size() > capacity) return ctx->fail(GL355_E_INVALID_ARG, "plonk_prove: proof buffer too small (gl355_plonk_pk_info gives the size)");
+    memcpy(proof, p.tr.proof.data(), p.tr.proof.size());
+    if (stage_ms) for (int i = 0; i < GL355_PLONK_STAGES; i++) stage_ms[i] = p.ms[i];
     return GL355_OK;
 }
 

@@ -30,6 +30,7 @@
 #include "blinding.cuh"
 #include "host_fr.h"
 #include "host_pairing.h"
+#include "plonk_openings.h"
 #include "plonk_program.h"
 
 using namespace gl355;
@@ -158,8 +159,8 @@ struct Prepared {
 // everything of verify_proof up to the pairing.  false: rejected, *why says at which step
 bool prepare(const gl355_plonk_vk* vk, const uint64_t* instances, const uint32_t* lens, const uint8_t* proof, uint64_t proof_len, Prepared& out, const char** why) {
     const uint64_t n = vk->n, u_rows = vk->usable;
-    const Fr omega = Fr::root_of_unity(vk->k), omega_inv = omega.inv();
-    auto rotate = [&](const Fr& x, int32_t r) { return x * (r >= 0 ? omega : omega_inv).pow_u64((uint64_t)(r >= 0 ? r : -(int64_t)r)); };
+    const PlkRotate rotate(vk->k);
+    const Fr &omega = rotate.omega, &omega_inv = rotate.omega_inv;
     Reader rd{proof, proof_len};
     auto fail = [&](const char* w) { *why = w; return false; };
     rd.tr.common_scalar(vk->digest);
@@ -270,47 +271,36 @@ bool prepare(const gl355_plonk_vk* vk, const uint64_t* instances, const uint32_t
     }
     const Fr h_eval = acc * (xn - one).inv();
 
-    // ---- (commitment, point, evaluation) in the prover's query order.  A commitment is a list of (coefficient, point) parts: one part for a
-    // point of the proof or the key, the quotient's pieces with the powers of x^n
+    // ---- the opened commitments (plonk_openings.h: slots, query order, rotation sets).  A commitment is a list of (coefficient, point) parts: one
+    // part for a point of the proof or the key, the quotient's pieces with the powers of x^n
     struct Part { int where; Fr coef; };                                   // where >= 0: proof point; < 0: key point -1 - where
-    struct Com { std::vector<Part> parts; std::vector<Fr> pts, evs; bool seen = false; };
-    const int A0 = 0, P0 = A0 + (int)vk->n_advice, LZ0 = P0 + (int)vk->n_sets, LA0 = LZ0 + (int)vk->n_lookups, LS0 = LA0 + (int)vk->n_lookups,
-              F0 = LS0 + (int)vk->n_lookups, S0 = F0 + (int)vk->n_fixed, H = S0 + (int)vk->n_perm, RND = H + 1;
-    std::vector<Com> coms(RND + 1);
-    for (uint32_t c = 0; c < vk->n_advice; c++) coms[A0 + c].parts = {{advice_c[c], one}};
-    for (uint32_t s = 0; s < vk->n_sets; s++) coms[P0 + s].parts = {{perm_c[s], one}};
+    const PlkSlots sl(vk->n_advice, vk->n_sets, vk->n_lookups, vk->n_fixed, vk->n_perm);
+    std::vector<std::vector<Part>> parts(sl.count);
+    for (uint32_t c = 0; c < vk->n_advice; c++) parts[sl.advice + c] = {{advice_c[c], one}};
+    for (uint32_t s = 0; s < vk->n_sets; s++) parts[sl.perm_z + s] = {{perm_c[s], one}};
     for (uint32_t l = 0; l < vk->n_lookups; l++) {
-        coms[LZ0 + l].parts = {{lookups_c[l][2], one}};
-        coms[LA0 + l].parts = {{lookups_c[l][0], one}};
-        coms[LS0 + l].parts = {{lookups_c[l][1], one}};
+        parts[sl.lookup_z + l] = {{lookups_c[l][2], one}};
+        parts[sl.lookup_a + l] = {{lookups_c[l][0], one}};
+        parts[sl.lookup_s + l] = {{lookups_c[l][1], one}};
     }
-    for (uint32_t c = 0; c < vk->n_fixed; c++) coms[F0 + c].parts = {{-1 - (int)c, one}};
-    for (uint32_t j = 0; j < vk->n_perm; j++) coms[S0 + j].parts = {{-1 - (int)(vk->n_fixed + j), one}};
-    { Fr pw = one; for (uint32_t i = 0; i < vk->n_pieces; i++) { coms[H].parts.push_back({h_c[i], pw}); pw = pw * xn; } }
-    coms[RND].parts = {{random_c, one}};
-    std::vector<int> order;
-    std::vector<Fr> all_points;
-    bool clash = false;
-    auto query = [&](int com, const Fr& pt, const Fr& e) {
-        Com& c = coms[com];
-        if (!c.seen) { c.seen = true; order.push_back(com); }
-        for (size_t i = 0; i < c.pts.size(); i++) if (c.pts[i] == pt) { if (c.evs[i] != e) clash = true; return; }
-        c.pts.push_back(pt); c.evs.push_back(e);
-        if (std::find(all_points.begin(), all_points.end(), pt) == all_points.end()) all_points.push_back(pt);
+    for (uint32_t c = 0; c < vk->n_fixed + vk->n_perm; c++) parts[sl.fixed + c] = {{-1 - (int)c, one}};
+    { Fr pw = one; for (uint32_t i = 0; i < vk->n_pieces; i++) { parts[sl.h].push_back({h_c[i], pw}); pw = pw * xn; } }
+    parts[sl.random] = {{random_c, one}};
+    // the evaluation the proof claims for an opening
+    auto claimed = [&](const PlkOpening& o) -> const Fr& {
+        if (o.slot < sl.perm_z) return ev[0][o.query];
+        if (o.slot < sl.lookup_z) { const PermEv& e = perm_ev[o.slot - sl.perm_z]; return o.rot == 0 ? e.z : (o.rot == 1 ? e.z_next : e.z_last); }
+        if (o.slot < sl.lookup_a) { const LookupEv& e = lk_ev[o.slot - sl.lookup_z]; return o.rot == 0 ? e.z : e.z_next; }
+        if (o.slot < sl.lookup_s) { const LookupEv& e = lk_ev[o.slot - sl.lookup_a]; return o.rot == 0 ? e.a : e.a_inv; }
+        if (o.slot < sl.fixed) return lk_ev[o.slot - sl.lookup_s].s;
+        if (o.slot < sl.sigma) return ev[1][o.query];
+        if (o.slot < sl.h) return sigma_ev[o.slot - sl.sigma];
+        return o.slot == sl.h ? h_eval : random_ev;
     };
-    const Fr x_next = rotate(x, 1), x_last = rotate(x, -(int32_t)(vk->bf + 1)), x_inv = rotate(x, -1);
-    for (size_t q = 0; q < vk->queries[0].size(); q++) query(A0 + vk->queries[0][q].first, rotate(x, vk->queries[0][q].second), ev[0][q]);
-    for (uint32_t s = 0; s < vk->n_sets; s++) { query(P0 + s, x, perm_ev[s].z); query(P0 + s, x_next, perm_ev[s].z_next); }
-    for (int s = (int)vk->n_sets - 2; s >= 0; s--) query(P0 + s, x_last, perm_ev[s].z_last);
-    for (uint32_t l = 0; l < vk->n_lookups; l++) {
-        query(LZ0 + l, x, lk_ev[l].z); query(LA0 + l, x, lk_ev[l].a); query(LS0 + l, x, lk_ev[l].s);
-        query(LA0 + l, x_inv, lk_ev[l].a_inv); query(LZ0 + l, x_next, lk_ev[l].z_next);
-    }
-    for (size_t q = 0; q < vk->queries[1].size(); q++) query(F0 + vk->queries[1][q].first, rotate(x, vk->queries[1][q].second), ev[1][q]);
-    for (uint32_t j = 0; j < vk->n_perm; j++) query(S0 + j, x, sigma_ev[j]);
-    query(H, x, h_eval);
-    query(RND, x, random_ev);
-    if (clash) return fail("two different evaluations claimed for one (commitment, point)");
+    const std::vector<PlkOpening> queries = plk_opening_queries(sl, vk->queries[0], vk->queries[1], vk->bf, rotate, x);
+    const PlkRotationSets plan(queries, sl.count);
+    for (size_t q = 0; q < queries.size(); q++)
+        if (claimed(queries[q]) != claimed(queries[plan.same[q]])) return fail("two different evaluations claimed for one (commitment, point)");
 
     // ---- SHPLONK
     const Fr sy = rd.tr.squeeze_challenge();
@@ -321,31 +311,17 @@ bool prepare(const gl355_plonk_vk* vk, const uint64_t* instances, const uint32_t
 #undef RP
 #undef RS
     if (rd.pos != proof_len) return fail("trailing bytes in the proof");
-    // rotation sets: commitments grouped by their sorted point sets, in first-appearance order
-    auto sort_with = [](std::vector<Fr>& p, std::vector<Fr>* e) {
-        for (size_t i = 1; i < p.size(); i++)
-            for (size_t j = i; j > 0 && p[j].less_than(p[j - 1]); j--) { std::swap(p[j], p[j - 1]); if (e) std::swap((*e)[j], (*e)[j - 1]); }
-    };
-    struct Set { std::vector<Fr> pts; std::vector<int> coms; };
-    std::vector<Set> sets;
-    for (int ci : order) {
-        Com& c = coms[ci];
-        sort_with(c.pts, &c.evs);
-        size_t si = 0;
-        for (; si < sets.size(); si++) if (sets[si].pts == c.pts) break;
-        if (si == sets.size()) sets.push_back({c.pts, {}});
-        sets[si].coms.push_back(ci);
-    }
+    const std::vector<Fr>& all_points = plan.all_points;
     Fr zt = one;
     for (auto& pt : all_points) zt = zt * (su - pt);
     out.scalars.assign(pts.size(), Fr::zero());
     out.key_scalars.assign(vk->n_fixed + vk->n_perm + 1, Fr::zero());
     Fr outer_r = Fr::zero(), vi = one, z0 = one;
-    std::vector<std::pair<int, Fr>> weights;                              // (commitment, v^i z_i y^j)
-    for (size_t si = 0; si < sets.size(); si++) {
-        const Set& st = sets[si];
+    std::vector<std::pair<uint32_t, Fr>> weights;                         // (slot, v^i z_i y^j)
+    for (size_t si = 0; si < plan.sets.size(); si++) {
+        const PlkRotationSets::Set& st = plan.sets[si];
         Fr zi = one;
-        for (auto& pt : all_points) if (std::find(st.pts.begin(), st.pts.end(), pt) == st.pts.end()) zi = zi * (su - pt);
+        for (auto& pt : all_points) if (!plan.has(st.pts, pt)) zi = zi * (su - pt);
         if (si == 0) z0 = zi;
         // Lagrange basis of the set's points at u, shared by its commitments
         std::vector<Fr> lag(st.pts.size());
@@ -356,10 +332,10 @@ bool prepare(const gl355_plonk_vk* vk, const uint64_t* instances, const uint32_t
         }
         const Fr scale = vi * zi;
         Fr inner_r = Fr::zero(), yj = one;
-        for (int ci : st.coms) {
+        for (size_t ci : st.coms) {
             Fr r_u = Fr::zero();
-            for (size_t i = 0; i < lag.size(); i++) r_u = r_u + coms[ci].evs[i] * lag[i];
-            weights.push_back({ci, scale * yj});
+            for (size_t i = 0; i < lag.size(); i++) r_u = r_u + claimed(queries[plan.coms[ci].first[i]]) * lag[i];
+            weights.push_back({plan.coms[ci].slot, scale * yj});
             inner_r = inner_r + yj * r_u;
             yj = yj * sy;
         }
@@ -373,7 +349,7 @@ bool prepare(const gl355_plonk_vk* vk, const uint64_t* instances, const uint32_t
         if (where >= 0) out.scalars[where] = out.scalars[where] + s;
         else out.key_scalars[-1 - where] = out.key_scalars[-1 - where] + s;
     };
-    for (auto& w : weights) for (auto& part : coms[w.first].parts) add_term(part.where, w.second * part.coef * z0i);
+    for (auto& w : weights) for (auto& part : parts[w.first]) add_term(part.where, w.second * part.coef * z0i);
     add_term(-1 - (int)(vk->n_fixed + vk->n_perm), (outer_r * z0i).neg());
     add_term(h1, (zt * z0i).neg());
     add_term(h2, su);

@@ -162,13 +162,21 @@ def test_k16_short_columns_commit_through_one_window(ctx):
 
 
 def test_a_lookup_input_outside_the_table_is_an_error(gl, ctx):
+    """... an error the library returns, and one it recovers from: the same key and context then prove the good witness to the bytes of a proof
+    made before the refused one, and a quotient export armed for the refused proof is spent with it -- the later proof writes nothing through it"""
     k, tb = 8, 6
     cs, cfg, w, prover = build(ctx, k, tb)
+    seed = bytes(range(32))
+    before = prover.prove(w.advice, w.instance, seed)
     adv = w.advice.copy()
     adv[cfg.arithmetic_config.r_limbs[0].index, 5, 0] = (1 << tb) + 3          # not a tb-bit value
+    out = np.full((prover.info["n_pieces"], 1 << k, 4), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    ctx.check(ctx.lib.gl355_plonk_pk_export_quotient(prover.h, out.ctypes.data))
     with pytest.raises(gl.Gl355Error) as ei:
         prover.prove(adv, w.instance, bytes(32))
     assert ei.value.code == -1 and "lookup" in str(ei.value)
+    assert prover.prove(w.advice, w.instance, seed) == before
+    assert (out == np.uint64(0xA5A5A5A5A5A5A5A5)).all(), "a proof after the refused one wrote through the export hook"
     prover.close()
 
 
