@@ -714,6 +714,33 @@ int32_t gl355_plonk_check_witness(gl355_ctx* ctx, const uint64_t* desc, uint64_t
                                   const uint64_t* advice, const uint64_t* instances, const uint32_t* instance_lens, uint32_t* failures /* capacity x 4 */,
                                   uint64_t capacity, uint64_t* n_failures, double* stage_ms /* 3 doubles or NULL */);
 
+/* ---- SURVEY 8(f) N4, the Halo2 verifier circuit, part 1: witness synthesis from a recorded tape.  `Verifier::synthesize` (verifier_circuit.rs)
+ * assigns its advice cells through ArithmeticChip (chip/native_chip/arithmetic_chip.rs:204-500), AllChip::permute (all_chip.rs:52-89) and, above
+ * them, GoldilocksChip (goldilocks_chip.rs:68-415), HasherChip (hasher_chip.rs:48-150), VectorChip::access (vector_chip.rs:26) and MerkleProofChip
+ * (merkle_proof_chip.rs:39-87).  The layout is fixed per plonky2 circuit, so it is recorded once (stark-verifier_amd/halo2_goldilocks.py) as a
+ * tape of chip-level entries and replayed per proof from the proof's words.
+ *   tape     n_words u64, 8 per entry: op | level << 8, first row, six operand words.  Ops: 1 CONST (assign_constant) 2 VALUE (assign_value)
+ *            3 MULADD (assign) 4 MULADD_EXT (assign_ext) 5 PACK 6 UNPACK 7 PERMUTE (apply_permute, 69 rows of the five state columns)
+ *            8 ASSERT_EQ (assert_equal: writes nothing).  An operand: kind << 60 | aux << 48 | column << 40 | row with kind 1 CELL, 3 BIT (bit
+ *            `aux` of the cell), 4 INV (its Goldilocks inverse, 0 for 0), or 2 << 60 | index for inputs[index].  Entries are stored level-major
+ *            (level = 1 + the largest level that wrote an operand), levels from 1 without gaps.
+ *   advice   [n_advice][2^k][4] plain integers below r, AllChipConfig's columns in configure order (n_advice = 19): exactly what
+ *            gl355_plonk_prove and gl355_plonk_check_witness take.  It is zeroed first; rows no entry writes stay zero.
+ *   status   two u64: the smallest failing entry (~0: none) and the number of failing entries.  An entry fails on the DATA: a VALUE not
+ *            below the Goldilocks prime, an ASSERT_EQ on differing cells (an invalid proof); an UNPACK cannot fail (four base-p digits
+ *            recompose every scalar, utils.rs:25-36).  That is not an error: the call returns GL355_OK and the rows are written all the same, so gl355_plonk_check_witness can name them.
+ *   gl355_halo2_tape_load        validates (entries whole, ops and operand kinds known, rows and input indices in range, every cell operand
+ *                                written by an earlier level, no cell written twice: GL355_E_INVALID_ARG otherwise) and uploads the tape
+ *   gl355_halo2_synthesize       one launch per level on the context's stream, one lane per entry; inputs and advice_out in host or device
+ *                                memory (device: the columns stay resident for the prover, nothing is copied); status in host memory
+ *   gl355_halo2_synthesize_host  the same validation and a sequential replay on the calling thread; needs no device */
+typedef struct gl355_halo2_tape gl355_halo2_tape;
+int32_t gl355_halo2_tape_load(gl355_ctx* ctx, const uint64_t* tape, uint64_t n_words, uint64_t n_inputs, uint32_t k, uint32_t n_advice, gl355_halo2_tape** out);
+int32_t gl355_halo2_tape_free(gl355_halo2_tape* tape);
+int32_t gl355_halo2_synthesize(gl355_ctx* ctx, const gl355_halo2_tape* tape, const uint64_t* inputs, uint64_t* advice_out, uint64_t* status /* 2 */);
+int32_t gl355_halo2_synthesize_host(const uint64_t* tape, uint64_t n_words, uint64_t n_inputs, uint32_t k, uint32_t n_advice, const uint64_t* inputs,
+                                    uint64_t* advice_out, uint64_t* status /* 2 */);
+
 /* ---- SURVEY 8(f) N4, the other half: the BN254 pairing and halo2_proofs' verify_proof::<_, VerifierSHPLONK<_>, _, _, SingleStrategy<_>> as
  * chip/native_chip/test_utils.rs:82-93 runs it on every proof create_proof_checked makes (verifier_api.rs:77-92).  Nothing here takes the
  * SRS secret: the verifier sees the public [s] G2 of the parameter set only, so proofs under ceremony powers

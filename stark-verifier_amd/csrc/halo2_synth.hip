@@ -1,0 +1,153 @@
+// Witness synthesis of a recorded Halo2 circuit ON THE DEVICE (part 1 of the verifier circuit): the tape of halo2_tape.h --
+// what `Verifier::synthesize` assigns through ArithmeticChip / AllChip::permute (verifier_circuit.rs, chip/native_chip/arithmetic_chip.rs:204-500,
+// all_chip.rs:52-89) -- interpreted by the GPU, so the [19][2^k][4] advice columns appear where gl355_plonk_prove and gl355_plonk_check_witness read
+// them: the host uploads the proof's words instead of 19 x 2^k x 32 bytes of columns.
+//
+// Schedule: one launch per LEVEL of the tape's DAG, all on the context's stream (no host round trip between levels: the host only enqueues),
+// one lane per entry.  The entries of a level are independent and write disjoint cells (validated at load), and a level reads only what earlier
+// launches wrote, so stream order is the only synchronisation.  A PERMUTE entry is one lane's whole permutation: the 68 rounds in their dense
+// form (the circuit's gates constrain every round's state, so the sparse partial rounds of bn254_permute_fr cannot be used) over bn254.cuh's
+// Fr arithmetic, each round's state leaving the Montgomery form once to be stored.  What bounds it is the depth of the DAG times the latency of
+// one permutation: a Merkle path is a chain of permutations, however many paths run side by side.
+//
+// Offsets are validated once when the tape is loaded (halo2_tape_validate), so the interpreter does not bounds-check; data-dependent
+// failures (a VALUE not below p, an ASSERT_EQ on differing cells = an invalid proof) are reported as the smallest failing entry and the number of
+// failing entries, exactly like the host replay, and the rows are written all the same.
+#include "gl355_internal.h"
+#include "halo2_tape.h"
+#include "bn254.cuh"
+
+namespace gl355 {
+
+// one dense round (native.rs:45-62): constants, x^5 on every element (full) or on the first, the 5x5 MDS
+GL_DEV void h2_round(fr8 (&s)[5], int rnd) {
+    const bool full = rnd < 4 || rnd >= 64;
+    s[0] = fr_pow5(fr_add(s[0], fr_const(BNT(RC)[5 * rnd])));
+    if (full) {
+        for (int i = 1; i < 5; i++) s[i] = fr_pow5(fr_add(s[i], fr_const(BNT(RC)[5 * rnd + i])));
+    } else {
+#pragma unroll
+        for (int i = 1; i < 5; i++) s[i] = fr_add(s[i], fr_const(BNT(RC)[5 * rnd + i]));
+    }
+    fr8 n[5];
+    for (int i = 0; i < 5; i++) {
+        fr8 acc = fr_mul(s[0], fr_const(BNT(MDS)[5 * i]));
+#pragma unroll
+        for (int j = 1; j < 5; j++) acc = fr_add(acc, fr_mul(s[j], fr_const(BNT(MDS)[5 * i + j])));
+        n[i] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < 5; i++) s[i] = n[i];
+}
+
+GL_DEV void h2_permute_rows(const H2Cols& c, const uint64_t* e) {
+    const uint64_t row = e[1];
+    fr8 s[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const h2_w4 v = h2_operand(c, e[2 + i]);
+        h2_store(c, H2_COL_STATE + i, row, v);
+        s[i] = fr_enter(v.w);
+    }
+#pragma unroll 1
+    for (int rnd = 0; rnd < 68; rnd++) {
+        h2_round(s, rnd);
+#pragma unroll
+        for (int i = 0; i < 5; i++) {
+            h2_w4 v;
+            fr_leave(s[i], v.w);
+            h2_store(c, H2_COL_STATE + i, row + rnd + 1, v);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64) halo2_level_kernel(const uint64_t* tape, uint64_t first, uint64_t count, H2Cols c, unsigned long long* status) {
+    const uint64_t i = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t* e = tape + H2_ENTRY_WORDS * (first + i);
+    int fail = 0;
+    if (((uint32_t)e[0] & 0xFF) == H2_OP_PERMUTE) h2_permute_rows(c, e);
+    else fail = h2_exec(c, e);
+    if (fail) {
+        atomicMin(status, (unsigned long long)(first + i));
+        atomicAdd(status + 1, 1ull);
+    }
+}
+
+}  // namespace gl355
+
+using namespace gl355;
+
+extern "C" int32_t gl355_halo2_tape_load(gl355_ctx* h, const uint64_t* tape, uint64_t n_words, uint64_t n_inputs, uint32_t k, uint32_t n_advice,
+                                         gl355_halo2_tape** out) {
+    Ctx* ctx = ctx_of(h);
+    if (!ctx) return GL355_E_INVALID_ARG;
+    if (!out) return ctx->fail(GL355_E_INVALID_ARG, "halo2_tape_load: null argument");
+    *out = nullptr;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail(GL355_E_HIP, "hipSetDevice failed");
+    std::vector<uint64_t> level_start;
+    gl355_halo2_tape* t = nullptr;
+    try {
+        if (const char* what = halo2_tape_validate(tape, n_words, n_inputs, k, n_advice, &level_start))
+            return ctx->fail(GL355_E_INVALID_ARG, (std::string("halo2_tape_load: ") + what).c_str());
+        t = new gl355_halo2_tape();
+        t->host.assign(tape, tape + n_words);
+    } catch (const std::bad_alloc&) {      // the validator's table of writers (40 bytes a row) or the host copy of the tape
+        delete t;
+        return ctx->fail(GL355_E_OOM, "halo2_tape_load: out of host memory");
+    }
+    t->ctx = ctx; t->k = k; t->n_advice = n_advice; t->n_entries = n_words / H2_ENTRY_WORDS; t->n_inputs = n_inputs;
+    t->level_start.swap(level_start);
+    t->dev = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&t->dev), std::max<size_t>(n_words * 8, 64)) != hipSuccess) { delete t; return ctx->fail(GL355_E_OOM, "halo2_tape_load: hipMalloc failed"); }
+    if (n_words && hipMemcpy(t->dev, tape, n_words * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(t->dev);
+        delete t;
+        return ctx->fail(GL355_E_HIP, "halo2_tape_load: upload failed");
+    }
+    *out = t;
+    return GL355_OK;
+}
+
+extern "C" int32_t gl355_halo2_tape_free(gl355_halo2_tape* t) {
+    if (!t) return GL355_OK;
+    if (t->dev) {
+        (void)hipSetDevice(t->ctx->device);
+        (void)t->ctx->wait();
+        (void)hipFree(t->dev);
+    }
+    delete t;
+    return GL355_OK;
+}
+
+extern "C" int32_t gl355_halo2_synthesize(gl355_ctx* h, const gl355_halo2_tape* t, const uint64_t* inputs, uint64_t* advice_out, uint64_t* status) {
+    Ctx* ctx = ctx_of(h);
+    if (!ctx) return GL355_E_INVALID_ARG;
+    if (!t || t->ctx != ctx || !advice_out || !status || (t->n_inputs && !inputs)) return ctx->fail(GL355_E_INVALID_ARG, "halo2_synthesize: null argument or a tape of another context");
+    if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail(GL355_E_HIP, "hipSetDevice failed");
+    const uint64_t n = 1ull << t->k;
+    const size_t bytes = (size_t)t->n_advice * n * 32;
+    Staged in(ctx), adv(ctx);
+    GL355_TRY(in.open(inputs, std::max<size_t>(t->n_inputs * 8, 8), 1));
+    GL355_TRY(adv.open(advice_out, bytes, 2));
+    Scratch st(ctx);
+    GL355_TRY(st.get(64));
+    unsigned long long* d_status = st.as<unsigned long long>();
+    GL355_HIP(ctx, hipMemsetAsync(adv.dev, 0, bytes, ctx->stream));
+    GL355_HIP(ctx, hipMemsetAsync(d_status, 0xFF, 8, ctx->stream));
+    GL355_HIP(ctx, hipMemsetAsync(d_status + 1, 0, 8, ctx->stream));
+    const H2Cols c = {adv.as<uint64_t>(), n, in.as<uint64_t>()};
+    {
+        ProfScope ps(ctx, "halo2_synthesize", bytes);
+        for (size_t l = 0; l + 1 < t->level_start.size(); l++) {
+            const uint64_t first = t->level_start[l], count = t->level_start[l + 1] - first;
+            if (!count) continue;
+            hipLaunchKernelGGL(halo2_level_kernel, dim3((uint32_t)((count + 63) / 64)), dim3(64), 0, ctx->stream, t->dev, first, count, c, d_status);
+            GL355_HIP(ctx, hipGetLastError());
+        }
+    }
+    GL355_HIP(ctx, ctx->d2h(status, d_status, 16));
+    GL355_HIP(ctx, ctx->wait());
+    GL355_TRY(adv.finish());
+    return GL355_OK;
+}

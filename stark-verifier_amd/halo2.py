@@ -727,6 +727,12 @@ class MockProver:
             name, pos = repr(self.cs.permutation[index]), None
         return Failure(kind, index, row, aux, name, pos)
 
+    @classmethod
+    def from_artifact(cls, ctx, artifact):
+        """the checker of a recorded circuit (halo2_goldilocks.Artifact)"""
+        lay = artifact.layout
+        return cls(ctx, lay.cs, lay.k, lay.fixed_array(), lay.mapping_array())
+
     def check(self, advice, instances, capacity=1 << 16):
         """-> (the first min(capacity, total) records as a [.][4] uint32 array in (kind, index, row) order, the exact total)"""
         import ctypes as C
@@ -773,6 +779,8 @@ class PlonkProver:
         # prove(check=True) needs the circuit's side again: kept only on request (at k = 23 the host arrays are several GB a caller may want to free)
         self._check_args = (fixed, mapping) if checkable else None
         self._mock = None
+        self.tape = None            # from_artifact: the recorded circuit's tape on this context (prove_from_inputs)
+        self._cols = None           # prove_from_inputs' device buffer for the advice columns, kept until close()
         ptr = lambda a: a if isinstance(a, int) else a.ctypes.data       # noqa: E731
         self.h = C.c_void_p()
         ctx.check(ctx.lib.gl355_plonk_keygen(ctx.h, self.desc.ctypes.data, self.desc.size, ptr(g), ptr(g_lagrange), fixed.ctypes.data, mapping.ctypes.data, C.byref(self.h)))
@@ -794,6 +802,14 @@ class PlonkProver:
         self.ctx.check(self.ctx.lib.gl355_plonk_pk_set_digest(self.h, d.ctypes.data))
         self.digest = digest
 
+    def mock_prover(self):
+        """the MockProver of this prover's circuit (a prover built with checkable=True), made on first use"""
+        if self._mock is None:
+            if self._check_args is None:
+                raise ValueError("prove(check=True) needs a PlonkProver built with checkable=True (it keeps the fixed columns and the mapping)")
+            self._mock = MockProver(self.ctx, self.cs, self.k, *self._check_args)
+        return self._mock
+
     def prove(self, advice, instances, seed, want_trace=False, timed=False, check=False):
         """advice: [num_advice][n][4] uint64 (numpy, or a device pointer as int); instances: per instance column a list of integers;
         seed: 32 bytes.  check (a prover built with checkable=True): run MockProver.assert_satisfied on the witness first and raise
@@ -802,11 +818,7 @@ class PlonkProver:
         import ctypes as C
         ctx = self.ctx
         if check:
-            if self._mock is None:
-                if self._check_args is None:
-                    raise ValueError("prove(check=True) needs a PlonkProver built with checkable=True (it keeps the fixed columns and the mapping)")
-                self._mock = MockProver(ctx, self.cs, self.k, *self._check_args)
-            self._mock.assert_satisfied(advice, instances)
+            self.mock_prover().assert_satisfied(advice, instances)
         if not isinstance(advice, int):
             advice = np.ascontiguousarray(advice, dtype=np.uint64)
             assert advice.shape == (self.cs.num_advice, self.n, 4)
@@ -828,6 +840,30 @@ class PlonkProver:
             out.append(dict(zip(STAGES, (float(v) for v in ms))))
         return out[0] if len(out) == 1 else tuple(out)
 
+    @classmethod
+    def from_artifact(cls, ctx, artifact, g, g_lagrange, digest=None, checkable=False):
+        """the prover of a recorded circuit (halo2_goldilocks.Artifact: layout + tape): keygen from the layout's fixed columns and copy constraints,
+        the tape loaded on the context for prove_from_inputs"""
+        from . import halo2_goldilocks as hg
+        lay = artifact.layout
+        self = cls(ctx, lay.cs, lay.k, g, g_lagrange, lay.fixed_array(), lay.mapping_array(), digest=digest, checkable=checkable)
+        self.tape = hg.DeviceTape(ctx, artifact.tape, lay.k, lay.n_inputs)
+        return self
+
+    def prove_from_inputs(self, inputs, instances, seed, **kw):
+        """gl355_halo2_synthesize -> gl355_plonk_prove on the resident columns: inputs (the proof's words, numpy or a device pointer) -> the advice
+        columns in device memory -> the proof.  -> (what prove() returns, (first failing tape entry or 2^64 - 1, failing entries))"""
+        import ctypes as C
+        ctx = self.ctx
+        if self.tape is None:
+            raise ValueError("prove_from_inputs needs a PlonkProver made by from_artifact (it loads the tape)")
+        if self._cols is None:
+            cols = C.c_void_p()
+            ctx.check(ctx.lib.gl355_malloc(ctx.h, self.cs.num_advice * self.n * 32, C.byref(cols)))
+            self._cols = cols
+        _, status = self.tape.synthesize(inputs, out=self._cols.value)
+        return self.prove(self._cols.value, instances, seed, **kw), status
+
     def verifying_key(self, s_g2):
         """the PlonkVerifier of this key (its descriptor, commitments and current digest) under the parameter set's [s] G2"""
         import ctypes as C
@@ -837,6 +873,12 @@ class PlonkProver:
         return PlonkVerifier(self.cs, self.k, None, None, None, _handle=h)
 
     def close(self):
+        if getattr(self, "tape", None) is not None:
+            self.tape.close()
+            self.tape = None
+        if getattr(self, "_cols", None) is not None:
+            self.ctx.lib.gl355_free(self.ctx.h, self._cols)
+            self._cols = None
         if getattr(self, "h", None):
             self.ctx.lib.gl355_plonk_pk_destroy(self.h)
             self.h = None

@@ -8,7 +8,11 @@ device, warm, best of five, once clean and once with one advice cell broken: che
 of its inputs on its own, and the ratio to create_proof + native verify -- the only way to tell a bad witness without it (the restated Python
 verifier is skipped in this mode).
 `--batch` instead of k values: the batch verifier's numbers at k = 12 (batches of 32 and 256, device against host MSM, the MSM alone over a
-range of term counts) and gl355_kzg_params_check at k = 20 and 23, one JSON line."""
+range of term counts) and gl355_kzg_params_check at k = 20 and 23, one JSON line.
+`--synth` instead of k values: witness synthesis of FriOpeningsCircuit (halo2_verifier_circuit.py) over a wrap proof: gl355_halo2_synthesize
+with the inputs and the columns resident (one warm-up, best of five) against gl355_halo2_synthesize_host on one thread plus the upload of the
+same columns from pageable host memory -- what a caller without the device path pays; rows, k, levels and their widths; create_proof on the
+synthesised witness against synthetic_circuit at the same k.  One JSON line."""
 import importlib
 import json
 import os
@@ -181,6 +185,65 @@ def run_batch(gl, ctx, k=12):
     return out
 
 
+def run_synth(gl, ctx):
+    import torch
+    from oracle_lib import rand_field
+    from test_gpu_prover import make_access_set
+    h2 = importlib.import_module("stark-verifier_amd.halo2")
+    hg = importlib.import_module("stark-verifier_amd.halo2_goldilocks")
+    vc = importlib.import_module("stark-verifier_amd.halo2_verifier_circuit")
+    rcn = importlib.import_module("stark-verifier_amd.recursion")
+    aset, sks, rng = make_access_set(gl, ctx, 3, 0x2542)
+    sig, data = aset.make_signal_fast(sks[4], rand_field(rng, 4), 4, 3, flat_only=True)
+    inner = (sig.proof, np.concatenate([aset.tree.cap[0], sig.nullifier[0], sig.topics[0]]))
+    wc = rcn.WrapperCircuit(ctx, data.common()).build([inner], rng)
+    flat, _ = wc.prove_flat([inner], seed=17)
+    circuit = vc.FriOpeningsCircuit(wc.data.common())
+    inputs = circuit.inputs(flat)
+    t0 = time.perf_counter()
+    rec = circuit.record(inputs)
+    out = {"wrap_degree_bits": int(wc.data.degree_bits), "proof_words": int(flat.size), "record_s": round(time.perf_counter() - t0, 1)}
+    widths = rec.level_widths()
+    k, tape = rec.k, rec.tape()
+    out.update({"k": k, "rows_used": rec.rows_used, "query_rounds": len(circuit.queries), "tape_entries": len(rec.entries), "tape_MB": round(tape.nbytes / 1e6, 1),
+                "levels": len(widths), "entries_per_level": {"min": int(min(widths)), "median": int(np.median(widths)), "max": int(max(widths))},
+                "instances": len(rec.instance)})
+    dt = hg.DeviceTape(ctx, tape, k, inputs.size)
+    d_in = torch.from_numpy(inputs.view(np.int64)).cuda()
+    dev = torch.empty((hg.N_ADVICE, 1 << k, 4), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    _, status = dt.synthesize(d_in.data_ptr(), out=dev.data_ptr())                 # warm
+    _, out["device_synthesis_ms"] = timed(lambda: dt.synthesize(d_in.data_ptr(), out=dev.data_ptr()), 5)
+    out["status"] = [int(status[0]) if status[0] != hg.NO_FAILURE else -1, status[1]]
+    hg.synthesize_host(tape, k, inputs)                                            # warm
+    (host, _), out["host_replay_ms"] = timed(lambda: hg.synthesize_host(tape, k, inputs), 5)       # one thread; validates the tape on every call
+    out["device_equals_host"] = bool(np.array_equal(dev.cpu().numpy().view(np.uint64), host))
+
+    def upload():
+        t = torch.from_numpy(host.view(np.int64)).cuda()
+        torch.cuda.synchronize()
+        return t
+    upload()
+    _, out["upload_pageable_ms"] = timed(upload, 5)
+    out["host_replay_plus_upload_ms"] = round(out["host_replay_ms"] + out["upload_pageable_ms"], 3)
+    out["device_speedup"] = round(out["host_replay_plus_upload_ms"] / out["device_synthesis_ms"], 1)
+    g, gl_ = h2.kzg_setup(ctx, k, TAU % h2.R)
+    t0 = time.perf_counter()
+    prover = h2.PlonkProver.from_artifact(ctx, rec.artifact(), g, gl_)
+    out["layout_and_keygen_s"] = round(time.perf_counter() - t0, 1)
+    prover.prove(dev.data_ptr(), [rec.instance], bytes(32))                        # warm
+    proof, ms = timed(lambda: prover.prove(dev.data_ptr(), [rec.instance], bytes([1] * 32)), 5)
+    out["create_proof_ms"] = ms
+    nv = prover.verifying_key(h2.kzg_setup_g2(TAU % h2.R))
+    out["native_verified"] = bool(nv.verify([rec.instance], proof))
+    nv.close()
+    prover.close()
+    del dev, d_in, g, gl_
+    torch.cuda.empty_cache()
+    out["create_proof_synthetic_circuit_ms"] = round(run(gl, ctx, k, verify=False, reps=5)["create_proof_s"] * 1e3, 1)
+    return out
+
+
 if __name__ == "__main__":
     import torch
     torch.cuda.init()            # torch's bundled ROCm runtime first, then libgl355.so (tests/conftest.py has the reason)
@@ -188,6 +251,10 @@ if __name__ == "__main__":
     ctx = gl.Context(0)
     if sys.argv[1:] == ["--batch"]:
         print(json.dumps(run_batch(gl, ctx)), flush=True)
+        ctx.close()
+        sys.exit(0)
+    if sys.argv[1:] == ["--synth"]:
+        print(json.dumps(run_synth(gl, ctx)), flush=True)
         ctx.close()
         sys.exit(0)
     check = "--check" in sys.argv[1:]
