@@ -714,7 +714,7 @@ int32_t gl355_plonk_check_witness(gl355_ctx* ctx, const uint64_t* desc, uint64_t
                                   const uint64_t* advice, const uint64_t* instances, const uint32_t* instance_lens, uint32_t* failures /* capacity x 4 */,
                                   uint64_t capacity, uint64_t* n_failures, double* stage_ms /* 3 doubles or NULL */);
 
-/* ---- SURVEY 8(f) N4, the Halo2 verifier circuit, part 1: witness synthesis from a recorded tape.  `Verifier::synthesize` (verifier_circuit.rs)
+/* ---- SURVEY 8(f) N4, the Halo2 verifier circuit, parts 1 and 2: witness synthesis from a recorded tape.  `Verifier::synthesize` (verifier_circuit.rs)
  * assigns its advice cells through ArithmeticChip (chip/native_chip/arithmetic_chip.rs:204-500), AllChip::permute (all_chip.rs:52-89) and, above
  * them, GoldilocksChip (goldilocks_chip.rs:68-415), HasherChip (hasher_chip.rs:48-150), VectorChip::access (vector_chip.rs:26) and MerkleProofChip
  * (merkle_proof_chip.rs:39-87).  The layout is fixed per plonky2 circuit, so it is recorded once (stark-verifier_amd/halo2_goldilocks.py) as a
@@ -722,7 +722,10 @@ int32_t gl355_plonk_check_witness(gl355_ctx* ctx, const uint64_t* desc, uint64_t
  *   tape     n_words u64, 8 per entry: op | level << 8, first row, six operand words.  Ops: 1 CONST (assign_constant) 2 VALUE (assign_value)
  *            3 MULADD (assign) 4 MULADD_EXT (assign_ext) 5 PACK 6 UNPACK 7 PERMUTE (apply_permute, 69 rows of the five state columns)
  *            8 ASSERT_EQ (assert_equal: writes nothing).  An operand: kind << 60 | aux << 48 | column << 40 | row with kind 1 CELL, 3 BIT (bit
- *            `aux` of the cell), 4 INV (its Goldilocks inverse, 0 for 0), or 2 << 60 | index for inputs[index].  Entries are stored level-major
+ *            `aux` of the cell), 4 INV (its Goldilocks inverse, 0 for 0), or 2 << 60 | index for inputs[index].  5 INV_EXT (part 2:
+ *            GoldilocksExtensionChip::div_extension's y_inv) is component `aux` (0 or 1) of the inverse of y0 + y1 X in GF(p)[X] / (X^2 - 7),
+ *            (0, 0) for (0, 0), with y0 the cell this word names and y1 the CELL in the NEXT operand word; it may only be the first operand of
+ *            a VALUE entry, and both cells must be written by earlier levels.  Entries are stored level-major
  *            (level = 1 + the largest level that wrote an operand), levels from 1 without gaps.
  *   advice   [n_advice][2^k][4] plain integers below r, AllChipConfig's columns in configure order (n_advice = 19): exactly what
  *            gl355_plonk_prove and gl355_plonk_check_witness take.  It is zeroed first; rows no entry writes stay zero.
@@ -731,7 +734,9 @@ int32_t gl355_plonk_check_witness(gl355_ctx* ctx, const uint64_t* desc, uint64_t
  *            recompose every scalar, utils.rs:25-36).  That is not an error: the call returns GL355_OK and the rows are written all the same, so gl355_plonk_check_witness can name them.
  *   gl355_halo2_tape_load        validates (entries whole, ops and operand kinds known, rows and input indices in range, every cell operand
  *                                written by an earlier level, no cell written twice: GL355_E_INVALID_ARG otherwise) and uploads the tape
- *   gl355_halo2_synthesize       one launch per level on the context's stream, one lane per entry; inputs and advice_out in host or device
+ *   gl355_halo2_synthesize       one launch per level on the context's stream, one lane per entry, or eight lanes per entry with a PERMUTE
+ *                                spread over five of them when the level holds one and is narrow enough to leave lanes idle (the columns
+ *                                are the same either way; GL355_HALO2_SPREAD_MAX=N overrides the bound, 0 = never); inputs and advice_out in host or device
  *                                memory (device: the columns stay resident for the prover, nothing is copied); status in host memory
  *   gl355_halo2_synthesize_host  the same validation and a sequential replay on the calling thread; needs no device */
 typedef struct gl355_halo2_tape gl355_halo2_tape;

@@ -10,6 +10,13 @@
 // Fr arithmetic, each round's state leaving the Montgomery form once to be stored.  What bounds it is the depth of the DAG times the latency of
 // one permutation: a Merkle path is a chain of permutations, however many paths run side by side.
 //
+// A level with few PERMUTE entries (the transcript: a chain of single permutations everything else waits for; the small Merkle levels) runs
+// the SPREAD form of the kernel instead: eight lanes per entry, and a permutation over five of them, one state element per lane.  In a full
+// round every lane adds its constant and takes x^5, in a partial round only lane 0 does; for the MDS row lane i forms sum_j M[i][j] s_j from the
+// other lanes' limbs, read by cross-lane moves (__shfl: ds_bpermute, no LDS planes), and stores its own state column.  The operations on every
+// element are h2_round's, in the same order, so the limbs and the stored columns are the same.  Per round a lane's chain is 3 + 5 + 1 products
+// instead of 15 + 25 + 5 (full) or 3 + 25 + 5 (partial).  The rule for choosing the form is halo2_spread_level below.
+//
 // Offsets are validated once when the tape is loaded (halo2_tape_validate), so the interpreter does not bounds-check; data-dependent
 // failures (a VALUE not below p, an ASSERT_EQ on differing cells = an invalid proof) are reported as the smallest failing entry and the number of
 // failing entries, exactly like the host replay, and the rows are written all the same.
@@ -61,17 +68,67 @@ GL_DEV void h2_permute_rows(const H2Cols& c, const uint64_t* e) {
     }
 }
 
+// element j of the group's state: every limb from lane j of this lane's group of eight
+GL_DEV fr8 h2_from_lane(const fr8& x, int j) {
+    fr8 r;
+#pragma unroll
+    for (int l = 0; l < FR_W; l++) r.l[l] = (uint32_t)__shfl((int)x.l[l], j, H2_SPREAD_LANES);
+    return r;
+}
+
+// h2_permute_rows over the lanes of a group: lane i < 5 holds state element i (lanes 5 .. 7 shadow element 4 and store nothing).  All eight
+// lanes of a group take every branch together except the x^5 of a partial round, which has no cross-lane move inside it
+GL_DEV void h2_permute_rows_spread(const H2Cols& c, const uint64_t* e, int lane) {
+    const uint64_t row = e[1];
+    const int i = lane < 5 ? lane : 4;
+    const bool stores = lane < 5;
+    h2_w4 v = h2_operand(c, e[2 + i]);
+    if (stores) h2_store(c, H2_COL_STATE + i, row, v);
+    fr8 s = fr_enter(v.w);
+    fr8 m[5];                                          // row i of the MDS matrix
+#pragma unroll
+    for (int j = 0; j < 5; j++) m[j] = fr_const(BNT(MDS)[5 * i + j]);
+    fr8 rc = fr_const(BNT(RC)[i]);
+#pragma unroll 1
+    for (int rnd = 0; rnd < 68; rnd++) {
+        const bool full = rnd < 4 || rnd >= 64;
+        fr8 t = fr_add(s, rc);
+        rc = fr_const(BNT(RC)[5 * (rnd < 67 ? rnd + 1 : rnd) + i]);      // the next round's constant, loaded under this round's products
+        if (full || lane == 0) t = fr_pow5(t);
+        fr8 acc = fr_mul(h2_from_lane(t, 0), m[0]);
+#pragma unroll
+        for (int j = 1; j < 5; j++) acc = fr_add(acc, fr_mul(h2_from_lane(t, j), m[j]));
+        s = acc;
+        fr_leave(s, v.w);
+        if (stores) h2_store(c, H2_COL_STATE + i, row + rnd + 1, v);
+    }
+}
+
+// SPREAD: eight lanes per entry (a PERMUTE entry over five of them, any other entry on the first); otherwise one lane per entry
+template <bool SPREAD>
 __global__ void __launch_bounds__(64) halo2_level_kernel(const uint64_t* tape, uint64_t first, uint64_t count, H2Cols c, unsigned long long* status) {
-    const uint64_t i = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    const uint64_t t = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+    const uint64_t i = SPREAD ? t / H2_SPREAD_LANES : t;
+    const int lane = SPREAD ? (int)(threadIdx.x % H2_SPREAD_LANES) : 0;
     if (i >= count) return;
     const uint64_t* e = tape + H2_ENTRY_WORDS * (first + i);
     int fail = 0;
-    if (((uint32_t)e[0] & 0xFF) == H2_OP_PERMUTE) h2_permute_rows(c, e);
-    else fail = h2_exec(c, e);
+    if (((uint32_t)e[0] & 0xFF) == H2_OP_PERMUTE) {
+        if (SPREAD) h2_permute_rows_spread(c, e, lane);
+        else h2_permute_rows(c, e);
+    } else if (lane == 0) fail = h2_exec(c, e);
     if (fail) {
         atomicMin(status, (unsigned long long)(first + i));
         atomicAdd(status + 1, 1ull);
     }
+}
+
+// The form of a level.  SPREAD gives an entry eight lanes, so it is taken while the level still leaves lanes idle that way -- at most one wave
+// per SIMD (4 SIMDs a CU) -- and has a PERMUTE entry to gain from it; beyond that the lanes are worth more as entries.  GL355_HALO2_SPREAD_MAX
+// (entries of a level) overrides the bound: 0 turns the form off (profiles/halo2_synth_fri.txt has the figures with and without)
+uint64_t halo2_spread_max(int compute_units) {
+    const char* v = getenv("GL355_HALO2_SPREAD_MAX");
+    return v && *v ? strtoull(v, nullptr, 10) : (uint64_t)compute_units * 4 * (64 / H2_SPREAD_LANES);
 }
 
 }  // namespace gl355
@@ -98,7 +155,13 @@ extern "C" int32_t gl355_halo2_tape_load(gl355_ctx* h, const uint64_t* tape, uin
     }
     t->ctx = ctx; t->k = k; t->n_advice = n_advice; t->n_entries = n_words / H2_ENTRY_WORDS; t->n_inputs = n_inputs;
     t->level_start.swap(level_start);
+    t->level_permutes.assign(t->level_start.size() - 1, 0);
+    for (size_t l = 0; l + 1 < t->level_start.size(); l++)
+        for (uint64_t i = t->level_start[l]; i < t->level_start[l + 1]; i++) t->level_permutes[l] += ((uint32_t)tape[H2_ENTRY_WORDS * i] & 0xFF) == H2_OP_PERMUTE;
     t->dev = nullptr;
+    int n_cu = 0;
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) { delete t; return ctx->fail(GL355_E_HIP, "halo2_tape_load: hipDeviceGetAttribute failed"); }
+    t->spread_max = halo2_spread_max(n_cu);
     if (hipMalloc(reinterpret_cast<void**>(&t->dev), std::max<size_t>(n_words * 8, 64)) != hipSuccess) { delete t; return ctx->fail(GL355_E_OOM, "halo2_tape_load: hipMalloc failed"); }
     if (n_words && hipMemcpy(t->dev, tape, n_words * 8, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(t->dev);
@@ -142,7 +205,10 @@ extern "C" int32_t gl355_halo2_synthesize(gl355_ctx* h, const gl355_halo2_tape* 
         for (size_t l = 0; l + 1 < t->level_start.size(); l++) {
             const uint64_t first = t->level_start[l], count = t->level_start[l + 1] - first;
             if (!count) continue;
-            hipLaunchKernelGGL(halo2_level_kernel, dim3((uint32_t)((count + 63) / 64)), dim3(64), 0, ctx->stream, t->dev, first, count, c, d_status);
+            if (t->level_permutes[l] && count <= t->spread_max)
+                hipLaunchKernelGGL(halo2_level_kernel<true>, dim3((uint32_t)((count * H2_SPREAD_LANES + 63) / 64)), dim3(64), 0, ctx->stream, t->dev, first, count, c, d_status);
+            else
+                hipLaunchKernelGGL(halo2_level_kernel<false>, dim3((uint32_t)((count + 63) / 64)), dim3(64), 0, ctx->stream, t->dev, first, count, c, d_status);
             GL355_HIP(ctx, hipGetLastError());
         }
     }

@@ -82,7 +82,7 @@ const char* halo2_tape_validate(const uint64_t* tape, uint64_t n_words, uint64_t
         uint64_t span = 1;
         switch (op) {
         case H2_OP_CONST: n_ops = 0; w[0] = {0, 1, 1u << H2_COL_A}; break;
-        case H2_OP_VALUE: n_ops = 1; w[0] = {0, 1, MASK_QR}; break;
+        case H2_OP_VALUE: n_ops = h2_kind(e[2]) == H2_K_INV_EXT ? 2 : 1; w[0] = {0, 1, MASK_QR}; break;      // an INV_EXT's second cell is the next word
         case H2_OP_MULADD: n_ops = 3; w[0] = {0, 1, MASK_ARITH}; break;
         case H2_OP_MULADD_EXT: n_ops = 6; span = 2; w[0] = {0, 2, MASK_ARITH}; break;
         case H2_OP_PACK: n_ops = 3; span = 3; w[0] = {0, 3, MASK_ABCQR}; break;
@@ -96,12 +96,17 @@ const char* halo2_tape_validate(const uint64_t* tape, uint64_t n_words, uint64_t
             const uint64_t o = e[2 + i];
             const uint32_t kind = h2_kind(o);
             if (kind == H2_K_INPUT) {
-                if (op != H2_OP_VALUE && op != H2_OP_MULADD && op != H2_OP_MULADD_EXT) return "an input operand where a cell is required";
+                if ((op != H2_OP_VALUE || i) && op != H2_OP_MULADD && op != H2_OP_MULADD_EXT) return "an input operand where a cell is required";
                 if (h2_row(o) >= n_inputs) return "an input index is out of range";
                 continue;
             }
-            if (kind != H2_K_CELL && kind != H2_K_BIT && kind != H2_K_INV) return "unknown operand kind";
-            if (kind != H2_K_CELL && op != H2_OP_MULADD && op != H2_OP_MULADD_EXT) return "a derived operand outside a MULADD entry";
+            if (kind != H2_K_CELL && kind != H2_K_BIT && kind != H2_K_INV && kind != H2_K_INV_EXT) return "unknown operand kind";
+            if (kind == H2_K_INV_EXT) {
+                if (op != H2_OP_VALUE || i != 0) return "an INV_EXT operand that is not the first of a VALUE entry";
+                if (h2_aux(o) > 1) return "an INV_EXT component is out of range";
+            } else if (op == H2_OP_VALUE && i == 1) {
+                if (kind != H2_K_CELL) return "the second operand of an INV_EXT is not a cell";
+            } else if (kind != H2_K_CELL && op != H2_OP_MULADD && op != H2_OP_MULADD_EXT) return "a derived operand outside a MULADD entry";
             if (kind == H2_K_BIT && h2_aux(o) >= 64) return "a bit index is out of range";
             const uint32_t col = h2_col(o);
             if (col >= H2_N_ADVICE || slot_of[col] < 0) return "an operand's column is out of range";

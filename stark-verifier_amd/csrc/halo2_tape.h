@@ -4,14 +4,17 @@
 // everything in this header except the Poseidon rounds.
 //
 // An entry is 8 words:  w0 = op | level << 8,  w1 = first row,  w2..w7 = operands (CONST: the value's four words in w2..w5).
-// An operand is one word: kind << 60 | aux << 48 | column << 40 | row (CELL, BIT, INV) or kind << 60 | index (INPUT).
+// An operand is one word: kind << 60 | aux << 48 | column << 40 | row (CELL, BIT, INV, INV_EXT) or kind << 60 | index (INPUT).
 //   CELL   the four words of an advice cell an EARLIER LEVEL wrote
 //   INPUT  inputs[index] (a proof word)
 //   BIT    bit `aux` of the low word of a cell      (GoldilocksChip::to_bits' unassigned bits, goldilocks_chip.rs:317-332)
 //   INV    the Goldilocks inverse of a cell, 0 for 0 (GoldilocksChip::is_zero's unassigned a_inv, goldilocks_chip.rs:285-292)
+//   INV_EXT  component `aux` (0 or 1) of the inverse of y0 + y1 X in GF(p)[X] / (X^2 - 7), (0, 0) for (0, 0): y0 is the cell this word
+//          names, y1 the CELL operand in the NEXT word.  Only the first operand of a VALUE entry may be one
+//          (GoldilocksExtensionChip::div_extension's unassigned y_inv, goldilocks_extension_chip.rs:83-98)
 // The advice columns are AllChipConfig's, in configure order: a b c q r | q_limbs[5] | r_limbs[4] | state[5].
 //   CONST       assign_constant (arithmetic_chip.rs:236-253): a = the constant
-//   VALUE       assign_value (:256-268): r = the operand, q = p - r, both in 16-bit limbs.  FAILS for r >= p.
+//   VALUE       assign_value (:256-268): r = the operand (w2; an INV_EXT takes w3 as well), q = p - r, both in 16-bit limbs.  FAILS for r >= p.
 //   MULADD      assign (:281-308): a b c from the operands' low words, a b + c = q p + r, limbs
 //   MULADD_EXT  assign_ext (:310-349), two rows: (a0 + a1 X)(b0 + b1 X) + (c0 + c1 X) in GF(p)[X] / (X^2 - 7)
 //   PACK        pack (:454-463), three mul_add_no_mod rows (:414-437): b = p^i, c = the sum so far, q = 0, r = c + a p^i
@@ -35,8 +38,8 @@ namespace gl355 {
 struct Ctx;
 
 enum { H2_OP_CONST = 1, H2_OP_VALUE = 2, H2_OP_MULADD = 3, H2_OP_MULADD_EXT = 4, H2_OP_PACK = 5, H2_OP_UNPACK = 6, H2_OP_PERMUTE = 7, H2_OP_ASSERT_EQ = 8 };
-enum { H2_K_NONE = 0, H2_K_CELL = 1, H2_K_INPUT = 2, H2_K_BIT = 3, H2_K_INV = 4 };
-enum { H2_ENTRY_WORDS = 8, H2_N_ADVICE = 19, H2_PERMUTE_ROWS = 69 };
+enum { H2_K_NONE = 0, H2_K_CELL = 1, H2_K_INPUT = 2, H2_K_BIT = 3, H2_K_INV = 4, H2_K_INV_EXT = 5 };
+enum { H2_ENTRY_WORDS = 8, H2_N_ADVICE = 19, H2_PERMUTE_ROWS = 69, H2_SPREAD_LANES = 8 };
 enum { H2_COL_A = 0, H2_COL_B = 1, H2_COL_C = 2, H2_COL_Q = 3, H2_COL_R = 4, H2_COL_QL = 5, H2_COL_RL = 10, H2_COL_STATE = 14 };
 
 typedef unsigned __int128 h2_u128;
@@ -105,6 +108,18 @@ GL_HD h2_w4 h2_operand(const H2Cols& c, uint64_t o) {
     if (kind == H2_K_CELL) { v.w[0] = p[0]; v.w[1] = p[1]; v.w[2] = p[2]; v.w[3] = p[3]; }
     else if (kind == H2_K_BIT) v.w[0] = (p[0] >> h2_aux(o)) & 1;
     else if (kind == H2_K_INV) v.w[0] = h2_inverse(p[0]);
+    return v;
+}
+
+// INV_EXT: (y0 - y1 X) / (y0^2 - 7 y1^2); 7 is no square, so the norm is 0 only for (0, 0), whose "inverse" is then (0, 0)
+GL_HD h2_w4 h2_inv_ext(const H2Cols& c, uint64_t o, uint64_t o1) {
+    uint64_t y0 = h2_cell(c, h2_col(o), h2_row(o))[0], y1 = h2_cell(c, h2_col(o1), h2_row(o1))[0];
+    y0 = y0 >= GL_P ? y0 - GL_P : y0;
+    y1 = y1 >= GL_P ? y1 - GL_P : y1;
+    const uint64_t s0 = h2_mulmod(y0, y0), s1 = h2_mulmod(h2_mulmod(y1, y1), 7);
+    const uint64_t inv = h2_inverse(s0 >= s1 ? s0 - s1 : s0 + (GL_P - s1));
+    h2_w4 v = {{0, 0, 0, 0}};
+    v.w[0] = h2_aux(o) ? h2_mulmod(y1 ? GL_P - y1 : 0, inv) : h2_mulmod(y0, inv);
     return v;
 }
 
@@ -201,7 +216,7 @@ GL_HD int h2_exec(const H2Cols& c, const uint64_t* e) {
         return 0;
     }
     case H2_OP_VALUE:
-        return h2_value_row(c, row, h2_operand(c, e[2]));
+        return h2_value_row(c, row, h2_kind(e[2]) == H2_K_INV_EXT ? h2_inv_ext(c, e[2], e[3]) : h2_operand(c, e[2]));
     case H2_OP_MULADD: {
         const uint64_t a = h2_operand(c, e[2]).w[0], b = h2_operand(c, e[3]).w[0], cc = h2_operand(c, e[4]).w[0];
         const h2_u128 t = (h2_u128)a * b + cc;
@@ -268,6 +283,8 @@ struct gl355_halo2_tape {
     uint64_t n_entries, n_inputs;
     std::vector<uint64_t> host;
     std::vector<uint64_t> level_start;      // [levels + 1] entry indices
+    std::vector<uint32_t> level_permutes;   // [levels] PERMUTE entries of each level (device tapes: the kernel's form depends on it)
+    uint64_t spread_max;                    // a level of at most this many entries with a PERMUTE among them runs the kernel's spread form
     uint64_t* dev;
 };
 

@@ -13,9 +13,12 @@ rows, selectors, fixed cells and copy constraints the Rust emits, in the same or
   HasherChip                        chip/hasher_chip.rs:30-171 (rate 8, overwrite mode)
   VectorChip.access                 chip/vector_chip.rs:26-48
   MerkleProofChip                   chip/merkle_proof_chip.rs:39-87
+  GoldilocksExtensionChip           chip/goldilocks_extension_chip.rs:56-416
+  TranscriptChip                    chip/transcript_chip.rs:17-74
+  FriVerifierChip                   chip/fri_chip.rs:58-376
 
 A term of `apply` is a Cell (Term::Assigned: copied into the row) or an unassigned value the prover derives: Input(i) (a proof word), BitOf(cell, i),
-InvOf(cell).  Cells that take part in Goldilocks arithmetic hold values below 2^64; only the packed scalars (pack's result, the Poseidon state)
+InvOf(cell); assign_value also takes InvExtOf(cell0, cell1, component), a component of a quadratic-extension inverse.  Cells that take part in Goldilocks arithmetic hold values below 2^64; only the packed scalars (pack's result, the Poseidon state)
 are wider, and they only ever feed PACK / UNPACK / PERMUTE entries and copy constraints."""
 import hashlib
 import io
@@ -28,7 +31,8 @@ from . import halo2_chips as hc
 P = hc.GOLDILOCKS_MODULUS
 R = h2.R
 (OP_CONST, OP_VALUE, OP_MULADD, OP_MULADD_EXT, OP_PACK, OP_UNPACK, OP_PERMUTE, OP_ASSERT_EQ) = range(1, 9)
-K_CELL, K_INPUT, K_BIT, K_INV = 1, 2, 3, 4
+K_CELL, K_INPUT, K_BIT, K_INV, K_INV_EXT = 1, 2, 3, 4, 5
+W = 7                               # GF(p)[X] / (X^2 - W)
 ENTRY_WORDS, N_ADVICE, PERMUTE_ROWS = 8, 19, 69
 NO_FAILURE = (1 << 64) - 1
 
@@ -57,6 +61,19 @@ class BitOf:
 class InvOf:
     def __init__(self, cell):
         self.cell = cell
+
+
+class InvExtOf:
+    """component `component` of 1 / (cell0 + cell1 X), (0, 0) for (0, 0): an assign_value term only (its VALUE entry names cell1 in a second word)"""
+
+    def __init__(self, cell0, cell1, component):
+        self.cell0, self.cell1, self.component = cell0, cell1, component
+
+
+def ext_inverse(y0, y1):
+    """(y0 - y1 X) / (y0^2 - 7 y1^2) in GF(p)[X] / (X^2 - 7): the norm is 0 only for (0, 0), which gives (0, 0)"""
+    inv = pow((y0 * y0 - W * y1 * y1) % P, P - 2, P)
+    return (y0 * inv % P, (P - y1) % P * inv % P)
 
 
 class Recorder:
@@ -119,6 +136,9 @@ class Recorder:
 
     def term(self, t):
         """-> (operand word, eager value, level of its writer)"""
+        if isinstance(t, InvExtOf):
+            y0, y1 = ((c.value & ((1 << 64) - 1)) % P for c in (t.cell0, t.cell1))
+            return t.cell0.word(K_INV_EXT, t.component), ext_inverse(y0, y1)[t.component], max(t.cell0.level, t.cell1.level)
         if isinstance(t, Cell):
             return t.word(), t.value, t.level
         if isinstance(t, Input):
@@ -390,14 +410,15 @@ class ArithmeticChip:
         ctx.constants[constant] = cell
         return cell
 
-    def assign_value(self, unassigned):                              # :256-268; unassigned: Input or a Cell whose value is taken
+    def assign_value(self, unassigned):                              # :256-268; unassigned: Input, InvExtOf or a Cell whose value is taken
         ctx, cfg = self.ctx, self.cfg
         word, r, level = ctx.term(unassigned)
+        words = [word, unassigned.cell1.word()] if isinstance(unassigned, InvExtOf) else [word]
         row = ctx.offset
         ctx.enable(cfg.s_limb)
         ctx.enable(cfg.s_range)
         self._q_and_r(row, (P - r) % R, r)
-        ctx.emit(OP_VALUE, row, [word], level + 1, failed=r >= P)
+        ctx.emit(OP_VALUE, row, words, level + 1, failed=r >= P)
         ctx.next()
         return Cell(cfg.r.index, row, r, level + 1)
 
@@ -411,6 +432,7 @@ class ArithmeticChip:
 
     def apply(self, a, b, c):                                        # assign + apply, :281-308, :351-379
         ctx, cfg = self.ctx, self.cfg
+        assert not any(isinstance(t, InvExtOf) for t in (a, b, c)), "an InvExtOf is a term of assign_value only"
         terms = [ctx.term(t) for t in (a, b, c)]
         vals = [t[1] for t in terms]
         assert all(v < (1 << 64) for v in vals), "a Goldilocks row takes values below 2^64"
@@ -780,3 +802,285 @@ class MerkleProofChip:
         for i in range(4):
             cap_i = VectorChip(self.ctx, [h[i] for h in merkle_cap]).access(cap_index)
             g.assert_equal(cap_i, state[i])
+
+
+# ---- GoldilocksExtensionChip ---------------------------------------------------------------------------------------------------------------
+class GoldilocksExtensionChip:
+    """goldilocks_extension_chip.rs:56-416; an extension element is a list of two cells.  The wasteful forms are the reference's (a subtraction
+    multiplies by one, exp multiplies `power` times): the layout is the reference's"""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.goldilocks_chip = GoldilocksChip(ctx)
+        self.arithmetic_chip = self.goldilocks_chip.arithmetic_chip
+
+    def mul_add_extension(self, a, b, c):                            # :56-70
+        return self.arithmetic_chip.apply_ext(a, b, c).r
+
+    def div_extension(self, x, y):                                   # :72-106; y = (0, 0) fails the assert_one below instead of the Rust's assert!
+        g = self.goldilocks_chip
+        y_inv = [g.assign_value(InvExtOf(y[0], y[1], 0)), g.assign_value(InvExtOf(y[0], y[1], 1))]
+        yy_inv = self.mul_extension(y, y_inv)
+        self.assert_one_extension(yy_inv)
+        return self.mul_extension(x, y_inv)
+
+    def div_add_extension(self, x, y, z):                            # :108-117
+        return self.add_extension(self.div_extension(x, y), z)
+
+    def add_extension(self, addend_0, addend_1):                     # :119-133
+        g = self.goldilocks_chip
+        return [g.add(a, b) for a, b in zip(addend_0, addend_1)]
+
+    def scalar_mul(self, multiplicand, scalar):                      # :135-149
+        g = self.goldilocks_chip
+        assigned_scalar = g.assign_constant(scalar)
+        return [g.mul(v, assigned_scalar) for v in multiplicand]
+
+    def arithmetic_extension(self, const_0, const_1, multiplicand_0, multiplicand_1, addend):      # :151-168
+        term_1 = self.mul_extension(multiplicand_0, multiplicand_1)
+        term_1 = self.scalar_mul(term_1, const_0)
+        term_2 = self.scalar_mul(addend, const_1)
+        return self.add_extension(term_1, term_2)
+
+    def zero_extension(self):                                        # :170-179
+        g = self.goldilocks_chip
+        return [g.assign_constant(0) for _ in range(2)]
+
+    def one_extension(self):                                         # :181-191
+        g = self.goldilocks_chip
+        return [g.assign_constant(1), g.assign_constant(0)]
+
+    def two_extension(self):                                         # :193-203
+        g = self.goldilocks_chip
+        return [g.assign_constant(2), g.assign_constant(0)]
+
+    def mul_extension_with_const(self, const_0, multiplicand_0, multiplicand_1):      # :205-221
+        zero = self.zero_extension()
+        return self.arithmetic_extension(const_0, 0, multiplicand_0, multiplicand_1, zero)
+
+    def mul_extension(self, multiplicand_0, multiplicand_1):         # :223-231
+        zero = self.zero_extension()
+        return self.mul_add_extension(multiplicand_0, multiplicand_1, zero)
+
+    def mul_sub_extension(self, a, b, c):                            # :233-242
+        return self.arithmetic_extension(1, P - 1, a, b, c)
+
+    def square_extension(self, x):                                   # :244-250
+        return self.mul_extension(x, x)
+
+    def exp_power_of_2_extension(self, base, power_log):             # :252-262
+        for _ in range(power_log):
+            base = self.square_extension(base)
+        return base
+
+    def exp(self, base, power):                                      # :264-281
+        if power == 0:
+            return self.one_extension()
+        if power == 1:
+            return list(base)
+        if power == 2:
+            return self.square_extension(base)
+        product = self.one_extension()
+        for _ in range(power):
+            product = self.mul_extension(product, base)
+        return product
+
+    def mul_many_extension(self, terms):                             # :283-293
+        result = self.one_extension()
+        for term in terms:
+            result = self.mul_extension(result, term)
+        return result
+
+    def sub_extension(self, lhs, rhs):                               # :295-304
+        one_extension = self.one_extension()
+        return self.arithmetic_extension(1, P - 1, lhs, one_extension, rhs)
+
+    def constant_extension(self, constant):                          # :306-317
+        g = self.goldilocks_chip
+        return [g.assign_constant(c) for c in constant]
+
+    def convert_to_extension(self, value):                           # :319-329
+        return [value, self.goldilocks_chip.assign_constant(0)]
+
+    def reduce_extension(self, base, terms):                         # :331-342
+        result = self.zero_extension()
+        for term in reversed(terms):
+            result = self.mul_add_extension(result, base, term)
+        return result
+
+    def reduce_base_field_terms_extension(self, base, terms):        # :344-355
+        terms = [self.convert_to_extension(t) for t in terms]
+        return self.reduce_extension(base, terms)
+
+    def reduce_extension_field_terms_base(self, base, terms):        # :357-365
+        base = self.convert_to_extension(base)
+        return self.reduce_extension(base, terms)
+
+    def shift(self, factor, power, shifted):                         # :367-377: shifted * factor^power
+        exp = self.exp(factor, power)
+        return self.mul_extension(exp, shifted)
+
+    def assert_equal_extension(self, lhs, rhs):                      # :379-389
+        g = self.goldilocks_chip
+        g.assert_equal(lhs[0], rhs[0])
+        g.assert_equal(lhs[1], rhs[1])
+
+    def assert_one_extension(self, a):                               # :391-400
+        g = self.goldilocks_chip
+        g.assert_one(a[0])
+        g.assert_zero(a[1])
+
+    def select(self, cond, a, b):                                    # :402-416: cond (a - b) + b
+        a_minus_b = self.sub_extension(a, b)
+        return self.arithmetic_extension(1, 1, cond, a_minus_b, b)
+
+
+# ---- TranscriptChip -------------------------------------------------------------------------------------------------------------------------
+class TranscriptChip:
+    def __init__(self, ctx):                                         # transcript_chip.rs:17-23
+        self.hasher_chip = HasherChip(ctx)
+
+    def write_scalar(self, scalar):                                  # :26-32
+        self.hasher_chip.update(scalar)
+
+    def write_extension(self, extension):                            # :34-43
+        for scalar in extension:
+            self.write_scalar(scalar)
+
+    def write_hash(self, hash_):                                     # :45-54
+        for scalar in hash_:
+            self.write_scalar(scalar)
+
+    def write_cap(self, cap):                                        # :56-65
+        for hash_ in cap:
+            self.write_hash(hash_)
+
+    def squeeze(self, num_outputs):                                  # :68-74
+        return self.hasher_chip.squeeze(num_outputs)
+
+
+# ---- FriVerifierChip ------------------------------------------------------------------------------------------------------------------------
+GENERATOR = 7                                                        # GoldilocksField::MULTIPLICATIVE_GROUP_GENERATOR
+
+
+def primitive_root_of_unity(bits):
+    """MULTIPLICATIVE_GROUP_GENERATOR.exp_u64(NEG_ONE / 2^bits), as fri_chip.rs:162-163 and :182-183 derive their roots"""
+    return pow(GENERATOR, (P - 1) >> bits, P)
+
+
+class FriInstanceInfo:
+    """types/fri.rs:49-72 with common_data's fri_oracles / fri_all_polys / fri_zs_polys: four oracles (constants and sigmas unblinded), every
+    polynomial opened at zeta, the Zs also at g zeta.  widths: the polynomials of each oracle"""
+
+    def __init__(self, zeta, zeta_next, widths, num_challenges):
+        self.oracles_blinding = [False, True, True, True]
+        self.batches = [(zeta, [(o, i) for o in range(4) for i in range(widths[o])]), (zeta_next, [(2, i) for i in range(num_challenges)])]
+
+
+class FriVerifierChip:
+    """fri_chip.rs:34-376.  A proof's parts come as cells: fri_proof = dict(commit_phase_merkle_caps, query_round_proofs, final_poly) with a
+    round = dict(initial_trees=[(evals, siblings)], steps=[(evals as extension elements, siblings)]); a cap is a list of 4-cell hashes"""
+
+    def __init__(self, ctx, offset, lde_bits, cap_height, reduction_arity_bits, hiding, proof_of_work_bits):      # construct, :35-46
+        self.ctx, self.offset = ctx, offset
+        self.lde_bits, self.cap_height, self.reduction_arity_bits = lde_bits, cap_height, list(reduction_arity_bits)
+        self.hiding, self.proof_of_work_bits = hiding, proof_of_work_bits
+        self.goldilocks_chip = GoldilocksChip(ctx)
+        self.goldilocks_extension_chip = GoldilocksExtensionChip(ctx)
+        self.round_rows = []
+
+    def compute_reduced_openings(self, fri_alpha, fri_openings):     # :58-70; fri_openings: the batches' values
+        return [self.goldilocks_extension_chip.reduce_extension(fri_alpha, values) for values in fri_openings]
+
+    def calculate_cap_index(self, x_index_bits):                     # :72-82
+        return self.goldilocks_chip.from_bits(x_index_bits[len(x_index_bits) - self.cap_height:])
+
+    def verify_initial_merkle_proof(self, x_index_bits, cap_index, initial_merkle_caps, initial_trees_proof):      # :85-110
+        merkle_proof_chip = MerkleProofChip(self.ctx)
+        for (evals, merkle_proof), cap in zip(initial_trees_proof, initial_merkle_caps):
+            merkle_proof_chip.verify_merkle_proof_to_cap_with_cap_index(evals, x_index_bits, cap_index, cap, merkle_proof)
+
+    @staticmethod
+    def unsalted_eval(initial_trees_proof, oracle_index, poly_index, salted):      # types/assigned.rs:58-71
+        evals = initial_trees_proof[oracle_index][0]
+        return evals[:len(evals) - (4 if salted else 0)][poly_index]
+
+    def batch_initial_polynomials(self, fri_instance_info, fri_alpha, x, initial_trees_proof, reduced_openings):      # :112-149
+        ge = self.goldilocks_extension_chip
+        x = ge.convert_to_extension(x)
+        total = ge.zero_extension()
+        for (point, polynomials), reduced in zip(fri_instance_info.batches, reduced_openings):
+            evals = [self.unsalted_eval(initial_trees_proof, o, i, self.hiding and fri_instance_info.oracles_blinding[o]) for o, i in polynomials]
+            reduced_evals = ge.reduce_base_field_terms_extension(fri_alpha, evals)
+            numerator = ge.sub_extension(reduced_evals, reduced)
+            denominator = ge.sub_extension(x, point)
+            total = ge.shift(fri_alpha, len(evals), total)
+            total = ge.div_add_extension(numerator, denominator, total)
+        return total
+
+    def x_from_subgroup(self, x_index_bits):                         # :151-166
+        return self.goldilocks_chip.exp_from_bits(primitive_root_of_unity(self.lde_bits), x_index_bits)
+
+    def next_eval(self, x_index_within_coset_bits, x, evals, arity_bits, beta):      # :168-226
+        g_chip, ge = self.goldilocks_chip, self.goldilocks_extension_chip
+        assert arity_bits == 1, "only arity 2 is supported, as in the reference (:211)"
+        g = primitive_root_of_unity(arity_bits)
+        g_inv = pow(g, P - 2, P)
+        g = g_chip.assign_constant(g)
+        evals = list(evals)                                          # reverse_index_bits_in_place: the identity on two elements
+        start = g_chip.exp_from_bits(g_inv, list(reversed(x_index_within_coset_bits)))
+        coset_start = g_chip.mul(start, x)
+        g_power = g_chip.assign_constant(1)
+        points = []
+        for ev in evals:
+            xi = g_chip.mul(coset_start, g_power)
+            xi = ge.convert_to_extension(xi)
+            g_power = g_chip.mul(g_power, g)
+            points.append((xi, ev))
+        (a0, a1), (b0, b1) = points                                  # a1 + (beta - a0) (b1 - a1) / (b0 - a0)
+        x_minus_a0 = ge.sub_extension(beta, a0)
+        b1_minus_a1 = ge.sub_extension(b1, a1)
+        numerator = ge.mul_extension(x_minus_a0, b1_minus_a1)
+        denominator = ge.sub_extension(b0, a0)
+        return ge.div_add_extension(numerator, denominator, a1)
+
+    def check_consistency(self, initial_merkle_caps, fri_instance_info, fri_alpha, fri_betas, fri_proof, x_index, round_proof, reduced_openings):      # :228-327
+        g_chip, ge = self.goldilocks_chip, self.goldilocks_extension_chip
+        x_index_bits = g_chip.to_bits(x_index, 64)[:self.lde_bits]
+        cap_index = self.calculate_cap_index(x_index_bits)
+        self.verify_initial_merkle_proof(x_index_bits, cap_index, initial_merkle_caps, round_proof["initial_trees"])
+        x_from_subgroup = self.x_from_subgroup(list(reversed(x_index_bits)))
+        x_from_subgroup = g_chip.mul(self.offset, x_from_subgroup)
+        prev_eval = self.batch_initial_polynomials(fri_instance_info, fri_alpha, x_from_subgroup, round_proof["initial_trees"], reduced_openings)
+        for i, arity_bits in enumerate(self.reduction_arity_bits):
+            evals, siblings = round_proof["steps"][i]
+            coset_index_bits = x_index_bits[arity_bits:]
+            x_index_within_coset_bits = x_index_bits[:arity_bits]
+            x_index_within_coset = g_chip.from_bits(x_index_within_coset_bits)
+            for j in range(2):
+                next_eval_j = VectorChip(self.ctx, [ev[j] for ev in evals]).access(x_index_within_coset)
+                g_chip.assert_equal(prev_eval[j], next_eval_j)
+            prev_eval = self.next_eval(x_index_within_coset_bits, x_from_subgroup, evals, arity_bits, fri_betas[i])
+            MerkleProofChip(self.ctx).verify_merkle_proof_to_cap_with_cap_index([c for ev in evals for c in ev], coset_index_bits, cap_index,
+                                                                                fri_proof["commit_phase_merkle_caps"][i], siblings)
+            x_from_subgroup = g_chip.exp_power_of_2(x_from_subgroup, arity_bits)
+            x_index_bits = coset_index_bits
+        final_poly_eval = ge.reduce_extension_field_terms_base(x_from_subgroup, fri_proof["final_poly"])
+        ge.assert_equal_extension(prev_eval, final_poly_eval)
+
+    def verify_fri_proof(self, initial_merkle_caps, fri_challenges, fri_openings, fri_proof, fri_instance_info):      # :329-362
+        """fri_challenges: dict(fri_alpha, fri_betas, fri_pow_response, fri_query_indices).  round_rows gets one half-open row range per round"""
+        self.fri_verify_proof_of_work(fri_challenges["fri_pow_response"])
+        reduced_openings = self.compute_reduced_openings(fri_challenges["fri_alpha"], fri_openings)
+        self.round_rows = []
+        for i, round_proof in enumerate(fri_proof["query_round_proofs"]):
+            start = self.ctx.offset
+            self.check_consistency(initial_merkle_caps, fri_instance_info, fri_challenges["fri_alpha"], fri_challenges["fri_betas"], fri_proof,
+                                   fri_challenges["fri_query_indices"][i], round_proof, reduced_openings)
+            self.round_rows.append((start, self.ctx.offset))
+
+    def fri_verify_proof_of_work(self, fri_pow_response):            # :364-376
+        g_chip = self.goldilocks_chip
+        bits = g_chip.to_bits(fri_pow_response, 64)
+        for b in list(reversed(bits))[:self.proof_of_work_bits]:
+            g_chip.assert_zero(b)

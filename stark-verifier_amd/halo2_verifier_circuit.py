@@ -1,5 +1,7 @@
-"""Part 1 of the Halo2 verifier circuit: every Merkle opening of a plonky2 proof's FRI query rounds, verified in circuit against
-its caps under Bn254PoseidonHash, recorded over the chips of halo2_goldilocks.py.
+"""Parts 1 and 2 of the Halo2 verifier circuit, recorded over the chips of halo2_goldilocks.py.
+
+FriOpeningsCircuit (part 1): every Merkle opening of a plonky2 proof's FRI query rounds, verified in circuit against its caps under
+Bn254PoseidonHash.
 
   the proof's shape                 types/proof.rs:317-403 (caps, openings, the FRI proof), types/fri.rs:50-73 (query rounds, steps)
   the Merkle calls and the indices  chip/fri_chip.rs:72-110 (cap index, the four initial trees), :228-327 (check_consistency: to_bits on the
@@ -8,7 +10,19 @@ its caps under Bn254PoseidonHash, recorded over the chips of halo2_goldilocks.py
 The input vector is the flat proof of gl355_prove (include/gl355.h; plonk.parse_proof reads the same layout) followed by the circuit's
 constants_sigmas cap, which the proof does not carry.  The caps and the query indices are exposed through the instance column, caps first: the
 circuit is sound on its own until part 2's transcript derives them.  The arithmetic of batch_initial_polynomials / next_eval, the transcript and
-the gate constraints are part 2 and reuse the recorder and the tape unchanged."""
+the gate constraints come after it.
+
+FriVerifierCircuit (part 2): the reference's get_challenges followed by FriVerifierChip::verify_fri_proof, i.e. the transcript derives alpha, the
+betas, the proof-of-work response and the query indices from the proof itself, and the committed polynomials are proved to open to the claimed
+values at zeta and g zeta.
+
+  the order of assignment           verifier_circuit.rs:81-127 (assign_proof_with_pis, assign_verification_key), types/proof.rs:58-109, :237-280,
+                                    :345-377 (openings; a round's evaluations before its Merkle proofs; caps, rounds, final polynomial, witness)
+  the challenges                    chip/plonk/plonk_verifier_chip.rs:55-154
+  FRI                               chip/plonk/plonk_verifier_chip.rs:212-240, chip/fri_chip.rs:329-376
+
+What part 3 still owes: eval_vanishing_poly with the 12 gate constrainers and the quotient identity (plonk_verifier_chip.rs:165-210), and
+PublicInputsHasherChip; until then the public-inputs hash is four input words, exposed as the instances."""
 import numpy as np
 
 from . import halo2_goldilocks as hg
@@ -97,5 +111,111 @@ class FriOpeningsCircuit:
             self.round_rows.append((start, rec.offset))
         for row, cell in enumerate(public):
             ar.expose_public(cell, row)
+        rec.shrink_to_fit(min_k)
+        return rec
+
+
+class FriVerifierCircuit:
+    """The input vector is the flat proof of gl355_prove followed by the four words of the public-inputs hash; the circuit digest and the
+    constants_sigmas cap are constants of the recording (they are fixed per plonky2 circuit, and so is the recording).  Neither the proof's
+    stored index words nor a stored proof-of-work response are read: both come out of the transcript."""
+
+    def __init__(self, common_data):
+        cd = common_data
+        self.cd = cd
+        shape = FriOpeningsCircuit(cd)                                # the positions of the flat proof's parts
+        self.arity_bits, self.cap_height, self.n_cap, self.lde_bits = shape.arity_bits, shape.cap_height, shape.n_cap, shape.lde_bits
+        self.n_queries, self.n_layers, self.leaf_len = shape.n_queries, shape.n_layers, shape.leaf_len
+        self.proof_caps, self.layer_caps, self.queries, self.proof_words = shape.initial_caps[1:], shape.layer_caps, shape.queries, shape.proof_words
+        nch = self.nch = cd["num_challenges"]
+        n_const = cd["num_selectors"] + cd["num_constants"]
+        self.widths = [n_const + cd["num_routed_wires"], cd["num_wires"], nch * (1 + cd["num_partial_products"]), nch * cd["quotient_degree_factor"]]
+        pos = self.proof_caps[-1][-1][-1] + 1                        # the openings follow the three caps, in plonk.parse_proof's order
+        self.openings = {}
+        for name, count in (("constants", n_const), ("plonk_sigmas", cd["num_routed_wires"]), ("wires", cd["num_wires"]), ("plonk_zs", nch),
+                            ("partial_products", nch * cd["num_partial_products"]), ("quotient_polys", nch * cd["quotient_degree_factor"]), ("plonk_zs_next", nch)):
+            self.openings[name] = [[pos + 2 * i, pos + 2 * i + 1] for i in range(count)]
+            pos += 2 * count
+        assert pos == self.layer_caps[0][0][0] if self.n_layers else True
+        pos += 4 * self.n_cap * self.n_layers
+        n_final = (1 << cd["degree_bits"]) >> self.n_layers
+        self.final_poly = [[pos + 2 * i, pos + 2 * i + 1] for i in range(n_final)]
+        self.pow_witness = pos + 2 * n_final
+        assert self.pow_witness + 1 == self.queries[0][0]
+        self.pi_hash = list(range(self.proof_words, self.proof_words + 4))
+        self.n_inputs = self.proof_words + 4
+        self.round_rows, self.challenge_cells = [], {}
+
+    def inputs(self, flat, public_inputs_hash):
+        flat = np.ascontiguousarray(flat, dtype=np.uint64).reshape(-1)
+        assert flat.size == self.proof_words == int(flat[0]), "not a proof of this circuit"
+        out = np.concatenate([flat, np.asarray(public_inputs_hash, dtype=np.uint64).reshape(-1)])
+        assert out.size == self.n_inputs
+        return out
+
+    def record(self, inputs, min_k=17):
+        """-> the Recorder of the circuit at the smallest k that holds it; round_rows[i] is the half-open row range of query round i and
+        challenge_cells holds the cells of fri_alpha, fri_betas, pow_response and indices"""
+        cd = self.cd
+        rec = hg.Recorder(28, inputs)
+        g = hg.GoldilocksChip(rec)
+        ge = hg.GoldilocksExtensionChip(rec)
+        g.load_table()
+        value = lambda words: [g.assign_value(hg.Input(w)) for w in words]                            # noqa: E731
+        # assign_proof_with_pis (the public inputs' place is taken by their hash), then assign_verification_key
+        public_inputs_hash = value(self.pi_hash)
+        wires_cap, zs_cap, quotient_cap = [[value(h) for h in cap] for cap in self.proof_caps]
+        op = {name: [value(e) for e in self.openings[name]]
+              for name in ("constants", "plonk_sigmas", "wires", "plonk_zs", "plonk_zs_next", "partial_products", "quotient_polys")}
+        layer_caps = [[value(h) for h in cap] for cap in self.layer_caps]
+        rounds = []
+        for _, initial, steps in self.queries:
+            evals = [value(leaf) for leaf, _ in initial]
+            proofs = [[value(s) for s in siblings] for _, siblings in initial]
+            steps = [([value(ev[0:2]), value(ev[2:4])], [value(s) for s in siblings]) for ev, siblings in steps]
+            rounds.append(dict(initial_trees=list(zip(evals, proofs)), steps=steps))
+        final_poly = [value(e) for e in self.final_poly]
+        pow_witness = g.assign_value(hg.Input(self.pow_witness))
+        fri_proof = dict(commit_phase_merkle_caps=layer_caps, query_round_proofs=rounds, final_poly=final_poly)
+        constants_sigmas_cap = [[g.assign_constant(int(w)) for w in h] for h in np.asarray(cd["constants_sigmas_cap"], dtype=np.uint64).reshape(-1, 4)]
+        circuit_digest = [g.assign_constant(int(w)) for w in cd["circuit_digest"]]
+        # get_challenges, plonk_verifier_chip.rs:55-154
+        tr = hg.TranscriptChip(rec)
+        for e in circuit_digest + public_inputs_hash:
+            tr.write_scalar(e)
+        tr.write_cap(wires_cap)
+        tr.squeeze(self.nch)                                         # the plonk betas, gammas and alphas: part 3's
+        tr.squeeze(self.nch)
+        tr.write_cap(zs_cap)
+        tr.squeeze(self.nch)
+        tr.write_cap(quotient_cap)
+        plonk_zeta = tr.squeeze(2)
+        fri_openings = [op["constants"] + op["plonk_sigmas"] + op["wires"] + op["plonk_zs"] + op["partial_products"] + op["quotient_polys"],
+                        op["plonk_zs_next"]]                         # to_fri_openings, types/assigned.rs:26-44
+        for values in fri_openings:
+            for e in values:
+                tr.write_extension(e)
+        fri_alpha = tr.squeeze(2)
+        fri_betas = []
+        for cap in layer_caps:
+            tr.write_cap(cap)
+            fri_betas.append(tr.squeeze(2))
+        for e in final_poly:
+            tr.write_extension(e)
+        tr.write_scalar(pow_witness)
+        fri_pow_response = tr.squeeze(1)[0]
+        fri_query_indices = tr.squeeze(self.n_queries)
+        self.challenge_cells = dict(fri_alpha=fri_alpha, fri_betas=fri_betas, pow_response=fri_pow_response, indices=fri_query_indices)
+        # verify_proof_with_challenges from zeta_next on, plonk_verifier_chip.rs:212-240
+        merkle_caps = [constants_sigmas_cap, wires_cap, zs_cap, quotient_cap]
+        zeta_next = ge.scalar_mul(plonk_zeta, hg.primitive_root_of_unity(cd["degree_bits"]))
+        info = hg.FriInstanceInfo(plonk_zeta, zeta_next, self.widths, self.nch)
+        offset = g.assign_constant(hg.GENERATOR)
+        fri = hg.FriVerifierChip(rec, offset, self.lde_bits, self.cap_height, self.arity_bits, bool(cd["hiding"]), cd["pow_bits"])
+        fri.verify_fri_proof(merkle_caps, dict(fri_alpha=fri_alpha, fri_betas=fri_betas, fri_pow_response=fri_pow_response,
+                                               fri_query_indices=fri_query_indices), fri_openings, fri_proof, info)
+        self.round_rows = fri.round_rows
+        for row, cell in enumerate(public_inputs_hash):
+            g.arithmetic_chip.expose_public(cell, row)
         rec.shrink_to_fit(min_k)
         return rec

@@ -9,10 +9,13 @@ of its inputs on its own, and the ratio to create_proof + native verify -- the o
 verifier is skipped in this mode).
 `--batch` instead of k values: the batch verifier's numbers at k = 12 (batches of 32 and 256, device against host MSM, the MSM alone over a
 range of term counts) and gl355_kzg_params_check at k = 20 and 23, one JSON line.
-`--synth` instead of k values: witness synthesis of FriOpeningsCircuit (halo2_verifier_circuit.py) over a wrap proof: gl355_halo2_synthesize
-with the inputs and the columns resident (one warm-up, best of five) against gl355_halo2_synthesize_host on one thread plus the upload of the
-same columns from pageable host memory -- what a caller without the device path pays; rows, k, levels and their widths; create_proof on the
-synthesised witness against synthetic_circuit at the same k.  One JSON line."""
+`--synth [openings] [fri] [--levels DIR] [--no-synthetic]` instead of k values: witness synthesis of FriOpeningsCircuit and FriVerifierCircuit
+(halo2_verifier_circuit.py) over one wrap proof: gl355_halo2_synthesize with the inputs and the columns resident (one warm-up, best of five, all
+five kept) against gl355_halo2_synthesize_host on one thread plus the upload of the same columns from pageable host memory -- what a caller
+without the device path pays; rows, k, entries, levels and their widths; the status must be NO_FAILURE and gl355_plonk_check_witness must find
+nothing; create_proof on the synthesised witness against synthetic_circuit at the same k (--no-synthetic leaves that out).  One JSON line per
+circuit.  --levels DIR also writes per level [entries, PERMUTE entries] (the launches of one synthesis, in order) and the tape with its inputs
+there: what a kernel trace of the run is joined with (profiles/halo2_synth_fri.txt)."""
 import importlib
 import json
 import os
@@ -185,36 +188,58 @@ def run_batch(gl, ctx, k=12):
     return out
 
 
-def run_synth(gl, ctx):
-    import torch
+def wrap_proof(gl, ctx):
+    """a Semaphore proof wrapped under the BN254-Poseidon config (wrapper.rs:35-56) -> (the wrap circuit, its flat proof, its public inputs)"""
     from oracle_lib import rand_field
     from test_gpu_prover import make_access_set
-    h2 = importlib.import_module("stark-verifier_amd.halo2")
-    hg = importlib.import_module("stark-verifier_amd.halo2_goldilocks")
-    vc = importlib.import_module("stark-verifier_amd.halo2_verifier_circuit")
     rcn = importlib.import_module("stark-verifier_amd.recursion")
     aset, sks, rng = make_access_set(gl, ctx, 3, 0x2542)
     sig, data = aset.make_signal_fast(sks[4], rand_field(rng, 4), 4, 3, flat_only=True)
     inner = (sig.proof, np.concatenate([aset.tree.cap[0], sig.nullifier[0], sig.topics[0]]))
     wc = rcn.WrapperCircuit(ctx, data.common()).build([inner], rng)
-    flat, _ = wc.prove_flat([inner], seed=17)
-    circuit = vc.FriOpeningsCircuit(wc.data.common())
-    inputs = circuit.inputs(flat)
+    flat, pis = wc.prove_flat([inner], seed=17)
+    return wc, flat, pis
+
+
+def level_table(rec):
+    """per level of the tape: [entries, PERMUTE entries] (the order of gl355_halo2_synthesize's launches)"""
+    hg = importlib.import_module("stark-verifier_amd.halo2_goldilocks")
+    t = rec.tape().reshape(-1, 8)
+    level, op = (t[:, 0] >> np.uint64(8)).astype(np.int64), (t[:, 0] & np.uint64(0xFF)).astype(np.int64)
+    return np.stack([np.bincount(level)[1:], np.bincount(level, weights=(op == hg.OP_PERMUTE))[1:].astype(np.int64)], axis=1)
+
+
+def synth_circuit(gl, ctx, name, circuit, inputs, out, levels_dir=None):
+    """record `circuit` from `inputs`, then: device synthesis against host replay + upload, the status, gl355_plonk_check_witness on the resident
+    columns, create_proof at that k and the native verifier"""
+    import torch
+    h2 = importlib.import_module("stark-verifier_amd.halo2")
+    hg = importlib.import_module("stark-verifier_amd.halo2_goldilocks")
     t0 = time.perf_counter()
     rec = circuit.record(inputs)
-    out = {"wrap_degree_bits": int(wc.data.degree_bits), "proof_words": int(flat.size), "record_s": round(time.perf_counter() - t0, 1)}
+    out["record_s"] = round(time.perf_counter() - t0, 1)
     widths = rec.level_widths()
     k, tape = rec.k, rec.tape()
-    out.update({"k": k, "rows_used": rec.rows_used, "query_rounds": len(circuit.queries), "tape_entries": len(rec.entries), "tape_MB": round(tape.nbytes / 1e6, 1),
+    levels = level_table(rec)
+    assert [int(w) for w in levels[:, 0]] == widths
+    with_permute = levels[:, 1] > 0
+    out.update({"circuit": name, "k": k, "rows_used": rec.rows_used, "query_rounds": len(circuit.queries), "tape_entries": len(rec.entries), "tape_MB": round(tape.nbytes / 1e6, 1),
                 "levels": len(widths), "entries_per_level": {"min": int(min(widths)), "median": int(np.median(widths)), "max": int(max(widths))},
-                "instances": len(rec.instance)})
+                "levels_with_permute": int(with_permute.sum()), "levels_of_one_permute": int((levels[:, 1] == 1).sum()),
+                "levels_one_entry_wide": int((levels[:, 0] <= 2).sum()), "instances": len(rec.instance)})
+    if levels_dir:
+        os.makedirs(levels_dir, exist_ok=True)
+        np.save(os.path.join(levels_dir, "levels_%s.npy" % name), levels)
+        np.savez(os.path.join(levels_dir, "tape_%s.npz" % name), tape=tape, inputs=inputs, k=np.array([k]))
     dt = hg.DeviceTape(ctx, tape, k, inputs.size)
     d_in = torch.from_numpy(inputs.view(np.int64)).cuda()
     dev = torch.empty((hg.N_ADVICE, 1 << k, 4), dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
     _, status = dt.synthesize(d_in.data_ptr(), out=dev.data_ptr())                 # warm
-    _, out["device_synthesis_ms"] = timed(lambda: dt.synthesize(d_in.data_ptr(), out=dev.data_ptr()), 5)
+    runs = sorted(timed(lambda: dt.synthesize(d_in.data_ptr(), out=dev.data_ptr()), 1)[1] for _ in range(5))
+    out["device_synthesis_ms"], out["device_synthesis_ms_runs"] = runs[0], runs
     out["status"] = [int(status[0]) if status[0] != hg.NO_FAILURE else -1, status[1]]
+    assert status == (hg.NO_FAILURE, 0), "the circuit refuses the wrap proof: %r" % (status,)
     hg.synthesize_host(tape, k, inputs)                                            # warm
     (host, _), out["host_replay_ms"] = timed(lambda: hg.synthesize_host(tape, k, inputs), 5)       # one thread; validates the tape on every call
     out["device_equals_host"] = bool(np.array_equal(dev.cpu().numpy().view(np.uint64), host))
@@ -226,11 +251,14 @@ def run_synth(gl, ctx):
     upload()
     _, out["upload_pageable_ms"] = timed(upload, 5)
     out["host_replay_plus_upload_ms"] = round(out["host_replay_ms"] + out["upload_pageable_ms"], 3)
-    out["device_speedup"] = round(out["host_replay_plus_upload_ms"] / out["device_synthesis_ms"], 1)
+    out["device_speedup"] = round(out["host_replay_plus_upload_ms"] / out["device_synthesis_ms"], 2)
     g, gl_ = h2.kzg_setup(ctx, k, TAU % h2.R)
     t0 = time.perf_counter()
-    prover = h2.PlonkProver.from_artifact(ctx, rec.artifact(), g, gl_)
+    prover = h2.PlonkProver.from_artifact(ctx, rec.artifact(), g, gl_, checkable=True)
     out["layout_and_keygen_s"] = round(time.perf_counter() - t0, 1)
+    fails = prover.mock_prover().verify(dev.data_ptr(), [rec.instance], 8)         # gl355_plonk_check_witness on the synthesised columns
+    out["check_witness_failures"] = len(fails)
+    assert not fails, [h2.describe_failure(f) for f in fails]
     prover.prove(dev.data_ptr(), [rec.instance], bytes(32))                        # warm
     proof, ms = timed(lambda: prover.prove(dev.data_ptr(), [rec.instance], bytes([1] * 32)), 5)
     out["create_proof_ms"] = ms
@@ -238,10 +266,32 @@ def run_synth(gl, ctx):
     out["native_verified"] = bool(nv.verify([rec.instance], proof))
     nv.close()
     prover.close()
+    dt.close()
     del dev, d_in, g, gl_
     torch.cuda.empty_cache()
-    out["create_proof_synthetic_circuit_ms"] = round(run(gl, ctx, k, verify=False, reps=5)["create_proof_s"] * 1e3, 1)
     return out
+
+
+def run_synth(gl, ctx, which=("openings", "fri"), levels_dir=None, synthetic=True):
+    """-> one dict per circuit of `which`: FriOpeningsCircuit (part 1) and FriVerifierCircuit (part 2) over the same wrap proof"""
+    vc = importlib.import_module("stark-verifier_amd.halo2_verifier_circuit")
+    plonk = importlib.import_module("stark-verifier_amd.plonk")
+    wc, flat, pis = wrap_proof(gl, ctx)
+    cd = wc.data.common()
+    outs = []
+    for name in which:
+        out = {"wrap_degree_bits": int(wc.data.degree_bits), "proof_words": int(flat.size)}
+        if name == "openings":
+            circuit = vc.FriOpeningsCircuit(cd)
+            inputs = circuit.inputs(flat)
+        else:
+            circuit = vc.FriVerifierCircuit(cd)
+            inputs = circuit.inputs(flat, plonk.host_hash_no_pad(pis))
+        synth_circuit(gl, ctx, name, circuit, inputs, out, levels_dir)
+        if synthetic:
+            out["create_proof_synthetic_circuit_ms"] = round(run(gl, ctx, out["k"], verify=False, reps=5)["create_proof_s"] * 1e3, 1)
+        outs.append(out)
+    return outs
 
 
 if __name__ == "__main__":
@@ -253,8 +303,12 @@ if __name__ == "__main__":
         print(json.dumps(run_batch(gl, ctx)), flush=True)
         ctx.close()
         sys.exit(0)
-    if sys.argv[1:] == ["--synth"]:
-        print(json.dumps(run_synth(gl, ctx)), flush=True)
+    if sys.argv[1:2] == ["--synth"]:
+        rest = sys.argv[2:]
+        levels_dir = rest[rest.index("--levels") + 1] if "--levels" in rest else None
+        which = [a for a in rest if a in ("openings", "fri")] or ["openings", "fri"]
+        for out in run_synth(gl, ctx, which, levels_dir, synthetic="--no-synthetic" not in rest):
+            print(json.dumps(out), flush=True)
         ctx.close()
         sys.exit(0)
     check = "--check" in sys.argv[1:]
