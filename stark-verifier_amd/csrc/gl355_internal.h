@@ -185,7 +185,6 @@ struct NttPlan {
     const uint64_t* post_hi = nullptr;
     uint64_t scale = 1;
 };
-int32_t ntt_init_constants(Ctx* ctx);
 int32_t ntt_run(Ctx* ctx, const NttPlan& p);
 int32_t bitrev_permute(Ctx* ctx, const uint64_t* in, uint64_t* out, uint32_t log_n, uint32_t width,
                        uint64_t in_col_stride, uint64_t out_col_stride, uint32_t batch);

@@ -34,10 +34,6 @@
 
 namespace gl355 {
 
-// the 24-bit-limb passes of the LDE (ntt_l24.hip)
-hipError_t launch_rows_l24(const PassArgs& a, hipStream_t s);
-hipError_t launch_cols_l24_cosets(const PassArgs& a, hipStream_t s);
-hipError_t launch_cols_small_cosets(const PassArgs& a, uint32_t log_t, hipStream_t s);
 // out[c][i] = in[c][bitrev(i)] over 2^log_n entries of `width` u64 each (a5:
 // reverse_index_bits_in_place; out-of-place, or in place via swap when in == out).
 __global__ void bitrev_permute_kernel(const uint64_t* in, uint64_t* out, uint32_t log_n, uint32_t width,
@@ -493,16 +489,6 @@ int32_t Ctx::nat_step_table(const uint64_t* lo, const uint64_t* hi, uint32_t l1,
     GL355_HIP(this, hipGetLastError());
     full_cache[key] = d;
     *out = d;
-    return GL355_OK;
-}
-
-int32_t ntt_init_constants(Ctx* ctx) {
-    uint64_t w16[2][8];
-    const uint64_t w = gl_root_of_unity(4), wi = gl_inv(w);
-    uint64_t x = 1, y = 1;
-    for (int j = 0; j < 8; j++) { w16[0][j] = gl_canon(x); w16[1][j] = gl_canon(y); x = gl_mul(x, w); y = gl_mul(y, wi); }
-    GL355_HIP(ctx, hipMemcpyToSymbolAsync(HIP_SYMBOL(c_w16), w16, sizeof w16, 0, hipMemcpyHostToDevice, ctx->stream));
-    GL355_HIP(ctx, ctx->wait());
     return GL355_OK;
 }
 

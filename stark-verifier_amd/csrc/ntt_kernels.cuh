@@ -3,16 +3,6 @@
 // experiments on exactly this code).  Conventions and the design notes are at the top of ntt.hip.
 #pragma once
 #include "gl355_internal.h"
-// GL355_NTT_KO (tools/ubench only; results are wrong with any bit set): 1 = twiddles from a register instead of the table,
-// 2 = no global loads of the tile, 4 = no twiddle products, 8 = no butterfly network, 16 = pre / step multipliers from registers
-// instead of their tables, 32 = no pre / step products, 64 = column pass writes rows at a padded stride
-#ifndef GL355_NTT_KO
-#define GL355_NTT_KO 0
-#endif
-// 1 (default): the radix-8 rounds run the lazily reduced butterfly network (dif8_lazy); 0: the reduce-every-time network (A/B in the ubench)
-#ifndef GL355_NTT_R8_LAZY
-#define GL355_NTT_R8_LAZY 1
-#endif
 
 namespace gl355 {
 
@@ -35,9 +25,6 @@ GL_DEV uint64_t pow2lvl(const uint64_t* __restrict__ lo, const uint64_t* __restr
     return v;
 }
 
-// omega_16^j for the in-register radix-16 butterflies (forward / inverse), filled at ctx creation
-__constant__ uint64_t c_w16[2][8];
-
 // (a - b) * omega_16^(+-E) with shifts only: omega_16 = 2^156 = -2^60, omega_16^-1 = 2^36, so
 //   forward  E=1..7: -2^60, -2^24, +2^84, +2^48, +2^12, -2^72, -2^36
 //   inverse  E=1..7: +2^36, +2^72, -2^12, -2^48, -2^84, +2^24, +2^60
@@ -52,28 +39,6 @@ GL_DEV uint64_t sub_mul_w16(uint64_t a, uint64_t b) {
     constexpr bool NEG = INV ? INV_NEG[E] : FWD_NEG[E];
     const uint64_t d = NEG ? gl_sub(b, a) : gl_sub(a, b);
     return gl_mul_2exp<S>(d);
-}
-
-// In-register DIF butterfly network on 2^RHO values: x[pos] <- X[bitrev(pos)].
-template <int RHO, bool INV>
-GL_DEV void dif_regs_generic(uint64_t (&x)[16]) {
-#pragma unroll
-    for (int s = 0; s < RHO; s++) {
-        const int half = 1 << (RHO - 1 - s);
-#pragma unroll
-        for (int blk = 0; blk < (1 << s); blk++) {
-#pragma unroll
-            for (int j = 0; j < half; j++) {
-                const int i0 = blk * 2 * half + j, i1 = i0 + half;
-                uint64_t a = x[i0], b = x[i1];
-                x[i0] = gl_add(a, b);
-                uint64_t d = gl_sub(a, b);
-                // twiddle omega_{2*half}^j = omega_16^(j * 8 / half)
-                const int e = j * (8 / half);
-                x[i1] = (e == 0) ? d : gl_mul(d, c_w16[INV ? 1 : 0][e]);
-            }
-        }
-    }
 }
 
 template <bool INV, int HALF, int J>
@@ -96,7 +61,7 @@ GL_DEV void dif_stage_blocks(uint64_t (&x)[16]) {
         dif_stage_blocks<INV, HALF, NBLK, BLK + 1>(x);
     }
 }
-// shift-twiddle version of the same network (all internal twiddles are powers of two)
+// In-register DIF butterfly network on 2^RHO values, x[pos] <- X[bitrev(pos)]: all internal twiddles are powers of two (shifts)
 template <int RHO, bool INV>
 GL_DEV void dif_regs(uint64_t (&x)[16]) {
     if constexpr (RHO >= 4) dif_stage_blocks<INV, 8, 1, 0>(x);
@@ -171,7 +136,7 @@ GL_DEV void dif8_lazy(uint64_t (&x)[16]) {
 // radix and direction (Ctx::twr): tw[2^m + (k0 << (m - RHO)) + r] = omega_{2^m}^(+-r * k0), so that the 64 lanes of a wave
 // (consecutive r) read 64 consecutive words per register q.  With the plain omega_{2^14}^e table the same loads were gathers
 // at a stride of k0 * 2^(14-m) words -- up to 64 cache lines per wave instruction, and a third of the row pass's time
-// (tools/ubench/ubench_ntt_rows.hip, knock-out 1).
+// (profiles/r02_ubench_ntt_knockout.txt, knock-out 1).
 template <int LT, int RHO, bool INV, bool LAZY = false, int PAD = 0>
 GL_DEV void dif_round(uint64_t* lds, const uint64_t* __restrict__ tw, int m, int LO, int tid, int nthreads) {
     constexpr int R = 1 << RHO;
@@ -183,19 +148,16 @@ GL_DEV void dif_round(uint64_t* lds, const uint64_t* __restrict__ tw, int m, int
         uint64_t x[16];
 #pragma unroll
         for (int q = 0; q < R; q++) x[q] = lds[lds_phys_t<PAD>(idx0 + ((uint32_t)q << fbit))];
-        if constexpr (!(GL355_NTT_KO & 8)) {
-            if constexpr (LAZY && RHO == 3) dif8_lazy<INV>(x);
-            else dif_regs<RHO, INV>(x);
-        }
-        if ((GL355_NTT_KO & 4) == 0 && m > RHO) {
+        if constexpr (LAZY && RHO == 3) dif8_lazy<INV>(x);
+        else dif_regs<RHO, INV>(x);
+        if (m > RHO) {
             // output k0 = bitrev(q) of this butterfly is multiplied by omega_{2^m}^(r*k0)
             const uint32_t r = (idx0 >> LO) & ((1u << (m - RHO)) - 1);
             const uint64_t* __restrict__ twm = tw + (1u << m) + r;   // round-major table: lanes with consecutive r read consecutive words
 #pragma unroll
             for (int q = 1; q < R; q++) {
                 const uint32_t k0 = brev(q, RHO);
-                if constexpr (GL355_NTT_KO & 1) x[q] = gl_mul(x[q], x[0] + r * k0);
-                else x[q] = gl_mul(x[q], twm[k0 << (m - RHO)]);
+                x[q] = gl_mul(x[q], twm[k0 << (m - RHO)]);
             }
         }
 #pragma unroll
@@ -270,6 +232,10 @@ hipError_t launch_rows_r8(const PassArgs& a, uint32_t log_t, bool inv, hipStream
 hipError_t launch_cols_r8(const PassArgs& a, uint32_t log_t, bool inv, hipStream_t s);
 hipError_t launch_cols_r8_big(const PassArgs& a, uint32_t log_t, uint32_t lt, hipStream_t s);
 hipError_t launch_cols_r8_cosets(const PassArgs& a, uint32_t log_t, hipStream_t s);
+// the 24-bit-limb passes of the LDE (ntt_l24.cuh), compiled in ntt_l24.hip
+hipError_t launch_rows_l24(const PassArgs& a, hipStream_t s);
+hipError_t launch_cols_l24_cosets(const PassArgs& a, hipStream_t s);
+hipError_t launch_cols_small_cosets(const PassArgs& a, uint32_t log_t, hipStream_t s);
 
 // Row pass: each row = 2^LOG_T contiguous elements; a tile packs 2^(LT-LOG_T) rows.
 // FAST = the commit-path shape with every optional multiplier compiled out: rows pass = no pre / post multiplier, no scaling,
@@ -297,8 +263,7 @@ __global__ void __launch_bounds__(1 << (LT - 4)) __attribute__((amdgpu_waves_per
         uint64_t v = 0;
         if (row < total_rows) {
             const uint64_t col = row >> a.log_rows, rin = row & (rows_per_col - 1);
-            if constexpr (GL355_NTT_KO & 2) v = col * a.in_col_stride + (rin << LOG_T) + e;
-            else v = a.in[col * a.in_col_stride + (rin << LOG_T) + e];
+            v = a.in[col * a.in_col_stride + (rin << LOG_T) + e];
             if constexpr (!FAST) {
                 if (a.pre_full) v = gl_mul(v, a.pre_full[(uint64_t)coset * a.pre_full_stride + (rin << LOG_T) + e]);
                 else if (pre_lo) v = gl_mul(v, pow2lvl(pre_lo, pre_hi, (rin << LOG_T) + e));
@@ -342,7 +307,7 @@ GL_DEV void dif_tile_r8(uint64_t* lds, const uint64_t* __restrict__ tw, int LO, 
     int m = LOG_T;
 #pragma unroll
     for (int round = 0; round < LOG_T / 3; round++) {
-        dif_round<LT, 3, INV, GL355_NTT_R8_LAZY != 0, PAD>(lds, tw, m, LO, tid, nthreads);
+        dif_round<LT, 3, INV, true, PAD>(lds, tw, m, LO, tid, nthreads);
         m -= 3;
         __syncthreads();
     }
@@ -354,26 +319,17 @@ GL_DEV void dif_tile_r8(uint64_t* lds, const uint64_t* __restrict__ tw, int LO, 
 // The first radix-8 round straight from the registers that loaded the tile, and the last round straight to its consumer: a thread that
 // loaded tile elements tid + q * NT (q < 8, NT = 2^(LT-3) threads) holds exactly the operands of its own first-round butterfly (the first
 // DIF round pairs elements 2^(LT-3) apart), so the load -> LDS -> barrier -> LDS -> registers detour is skipped; and the last round's
-// results (no twiddles follow) can go to `sink(tile index, value)` instead of back to LDS.  GL355_NTT_R8_DIRECT=0 keeps the staged form (A/B).
-#ifndef GL355_NTT_R8_DIRECT
-#define GL355_NTT_R8_DIRECT 1
-#endif
+// results (no twiddles follow) can go to `sink(tile index, value)` instead of back to LDS.
 template <int LT, int LOG_T, bool INV, int PAD = 0>
 GL_DEV void dif_first_round_regs(uint64_t (&x)[16], uint64_t* lds, const uint64_t* __restrict__ tw, int LO, int tid) {
     static_assert(LOG_T >= 3, "needs a radix-8 first round");
     constexpr int fbit = LT - 3;
-    if constexpr (!(GL355_NTT_KO & 8)) {
-        if constexpr (GL355_NTT_R8_LAZY != 0) dif8_lazy<INV>(x);
-        else dif_regs<3, INV>(x);
-    }
-    if constexpr (LOG_T > 3 && (GL355_NTT_KO & 4) == 0) {
+    dif8_lazy<INV>(x);
+    if constexpr (LOG_T > 3) {
         const uint32_t r = ((uint32_t)tid >> LO) & ((1u << (LOG_T - 3)) - 1);
         const uint64_t* __restrict__ twm = tw + (1u << LOG_T) + r;
 #pragma unroll
-        for (int q = 1; q < 8; q++) {
-            if constexpr (GL355_NTT_KO & 1) x[q] = gl_mul(x[q], x[0] + r * brev(q, 3));
-            else x[q] = gl_mul(x[q], twm[brev(q, 3) << (LOG_T - 3)]);
-        }
+        for (int q = 1; q < 8; q++) x[q] = gl_mul(x[q], twm[brev(q, 3) << (LOG_T - 3)]);
     }
 #pragma unroll
     for (int q = 0; q < 8; q++) lds[lds_phys_t<PAD>((uint32_t)tid + ((uint32_t)q << fbit))] = x[q];
@@ -393,10 +349,8 @@ GL_DEV void dif_last_round_sink(const uint64_t* lds, int LO, int tid, int nthrea
         uint64_t x[16];
 #pragma unroll
         for (int q = 0; q < R; q++) x[q] = lds[lds_phys_t<PAD>(idx0 + ((uint32_t)q << fbit))];
-        if constexpr (!(GL355_NTT_KO & 8)) {
-            if constexpr (GL355_NTT_R8_LAZY != 0 && RHO == 3) dif8_lazy<INV>(x);
-            else dif_regs<RHO, INV>(x);
-        }
+        if constexpr (RHO == 3) dif8_lazy<INV>(x);
+        else dif_regs<RHO, INV>(x);
 #pragma unroll
         for (int q = 0; q < R; q++) sink(idx0 + ((uint32_t)q << fbit), x[q]);
     }
@@ -405,38 +359,37 @@ GL_DEV void dif_last_round_sink(const uint64_t* lds, int LO, int tid, int nthrea
 // network and the stores.  Written as `out[go] = v * table[go]` inside the sink, every table load sat behind the previous output's store (the
 // compiler cannot prove that `out` and the table do not alias) and was waited for with vmcnt(0), which also drains that store: eight exposed load
 // latencies per thread and tile (round 6; the all-cosets column kernels always held their eight step words in registers).
-template <int LT, int RHO, bool INV, int PAD, class Fetch, class Sink>
-GL_DEV void dif_last_round_sink_tab(const uint64_t* lds, int LO, int tid, int nthreads, Fetch fetch, Sink sink) {
+// NT threads.  All of a thread's table words are held at once: an instantiation that would need more than MAXW of them does not compile.
+template <int LT, int RHO, bool INV, int PAD, int NT, class Fetch, class Sink>
+GL_DEV void dif_last_round_sink_tab(const uint64_t* lds, int LO, int tid, Fetch fetch, Sink sink) {
     constexpr int R = 1 << RHO;
-    const int tasks = (1 << LT) >> RHO;
+    constexpr int tasks = (1 << LT) >> RHO;
     const int fbit = LO;
-    constexpr int MAXW = 16;                                 // table words a thread holds at once
+    constexpr int MAXW = 16;                                 // table words a thread may hold at once
+    constexpr int trips = (tasks + NT - 1) / NT;
+    static_assert(trips * R <= MAXW, "too many table words per thread to fetch them all first");
     uint64_t w[MAXW];
-    const int trips = (tasks + nthreads - 1) / nthreads;     // compile-time at every call site
-    const bool all_first = trips * R <= MAXW;
-    if (all_first) {
 #pragma unroll
-        for (int k = 0; k < MAXW / R; k++) {
-            const int t = tid + k * nthreads;
-            if (k < trips && t < tasks) {
-                const uint32_t idx0 = ((uint32_t)(t >> fbit) << (fbit + RHO)) | (t & ((1u << fbit) - 1));
+    for (int k = 0; k < MAXW / R; k++) {
+        const int t = tid + k * NT;
+        if (k < trips && t < tasks) {
+            const uint32_t idx0 = ((uint32_t)(t >> fbit) << (fbit + RHO)) | (t & ((1u << fbit) - 1));
 #pragma unroll
-                for (int q = 0; q < R; q++) w[k * R + q] = fetch(idx0 + ((uint32_t)q << fbit));
-            }
+            for (int q = 0; q < R; q++) w[k * R + q] = fetch(idx0 + ((uint32_t)q << fbit));
         }
     }
 #pragma unroll
-    for (int k = 0; k < (all_first ? MAXW / R : 64); k++) {
-        const int t = tid + k * nthreads;
+    for (int k = 0; k < MAXW / R; k++) {
+        const int t = tid + k * NT;
         if (k >= trips || t >= tasks) break;
         const uint32_t low = t & ((1u << fbit) - 1), high = t >> fbit;
         const uint32_t idx0 = (high << (fbit + RHO)) | low;
         uint64_t x[16], wk[R];
 #pragma unroll
-        for (int q = 0; q < R; q++) wk[q] = all_first ? w[(k * R + q) % MAXW] : fetch(idx0 + ((uint32_t)q << fbit));
+        for (int q = 0; q < R; q++) wk[q] = w[k * R + q];
 #pragma unroll
         for (int q = 0; q < R; q++) x[q] = lds[lds_phys_t<PAD>(idx0 + ((uint32_t)q << fbit))];
-        if constexpr (GL355_NTT_R8_LAZY != 0 && RHO == 3) dif8_lazy<INV>(x);
+        if constexpr (RHO == 3) dif8_lazy<INV>(x);
         else dif_regs<RHO, INV>(x);
 #pragma unroll
         for (int q = 0; q < R; q++) sink(idx0 + ((uint32_t)q << fbit), x[q], wk[q]);
@@ -453,7 +406,7 @@ GL_DEV void dif_tile_r8_regs(uint64_t (&x)[16], uint64_t* lds, const uint64_t* _
     constexpr int MID = FULL - 1 - ((KEEP_LAST && REM == 0) ? 1 : 0);       // radix-8 rounds done here after the first
 #pragma unroll
     for (int round = 0; round < MID; round++) {
-        dif_round<LT, 3, INV, GL355_NTT_R8_LAZY != 0, PAD>(lds, tw, m, LO, tid, nthreads);
+        dif_round<LT, 3, INV, true, PAD>(lds, tw, m, LO, tid, nthreads);
         m -= 3;
         __syncthreads();
     }
@@ -481,12 +434,12 @@ __global__ void __launch_bounds__(LT >= 13 ? 1024 : 512) __attribute__((amdgpu_w
     const uint64_t* pre = PRE ? a.pre_full + (uint64_t)coset * a.pre_full_stride + (rin << LT) : nullptr;
     uint64_t* out = a.out + (uint64_t)a.coset_slot[coset] * a.coset_out_stride + col * a.out_col_stride + (rin << LT);
     // measured: 8192-point tiles gain 5 % from the register-fed first round, 4096-point tiles at 64 VGPRs lose 4 % (more spilled registers)
-    if constexpr (EPT == 8 && LT == 13 && GL355_NTT_R8_DIRECT != 0) {
+    if constexpr (EPT == 8 && LT == 13) {
         uint64_t x[16];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             const uint32_t g = tid + i * NT;
-            x[i] = (GL355_NTT_KO & 2) ? (uint64_t)g + row : in[g];
+            x[i] = in[g];
             if constexpr (PRE) x[i] = gl_mul(x[i], pre[g]);
         }
         dif_tile_r8_regs<LT, LT, INV, false>(x, lds, a.tw_r8, 0, tid, NT);
@@ -494,7 +447,7 @@ __global__ void __launch_bounds__(LT >= 13 ? 1024 : 512) __attribute__((amdgpu_w
 #pragma unroll
         for (int i = 0; i < EPT; i++) {
             const uint32_t g = tid + i * NT;
-            uint64_t v = (GL355_NTT_KO & 2) ? (uint64_t)g + row : in[g];
+            uint64_t v = in[g];
             if constexpr (PRE) v = gl_mul(v, pre[g]);
             lds[lds_phys(g)] = v;
         }
@@ -604,34 +557,29 @@ __global__ void __launch_bounds__(LT == 12 ? 512 : 1024) __attribute__((amdgpu_w
     auto store = [&](uint32_t g, uint64_t v) {
         const uint32_t r = g >> LOG_TC, cc = g & (TC - 1);
         const uint64_t go = ((uint64_t)r << log_n2) + c0 + cc;
-        if constexpr (!(GL355_NTT_KO & 32)) v = gl_mul(v, (GL355_NTT_KO & 16) ? go + 5 : a.step_full[go]);
-        if constexpr (GL355_NTT_KO & 64) out[go + r * 16] = v;      // padded row stride (timing experiment: channel camping?)
-        else out[go] = v;
+        out[go] = gl_mul(v, a.step_full[go]);
     };
-    if constexpr (LOG_T >= 4 && GL355_NTT_R8_DIRECT != 0 && EPT == 8) {
+    if constexpr (LOG_T >= 4 && EPT == 8) {
         uint64_t x[16];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             const uint32_t g = tid + i * NT;
             const uint64_t gi = ((uint64_t)(g >> LOG_TC) << log_n2) + c0 + (g & (TC - 1));
-            x[i] = (GL355_NTT_KO & 2) ? gi : in[gi];
-            if constexpr (PRE && !(GL355_NTT_KO & 32)) x[i] = gl_mul(x[i], (GL355_NTT_KO & 16) ? gi + 3 : pre[gi]);
+            x[i] = in[gi];
+            if constexpr (PRE) x[i] = gl_mul(x[i], pre[gi]);
         }
         dif_tile_r8_regs<LT, LOG_T, INV, true>(x, lds, a.tw_r8, LOG_TC, tid, NT);
-        if constexpr (GL355_NTT_KO & (16 | 32 | 64)) dif_last_round_sink<LT, R8Last<LOG_T>::RHO, INV>(lds, LOG_TC, tid, NT, store);
-        else {
-            auto addr = [&](uint32_t g) { return ((uint64_t)(g >> LOG_TC) << log_n2) + c0 + (g & (TC - 1)); };
-            dif_last_round_sink_tab<LT, R8Last<LOG_T>::RHO, INV, 0>(lds, LOG_TC, tid, NT, [&](uint32_t g) { return a.step_full[addr(g)]; },
+        auto addr = [&](uint32_t g) { return ((uint64_t)(g >> LOG_TC) << log_n2) + c0 + (g & (TC - 1)); };
+        dif_last_round_sink_tab<LT, R8Last<LOG_T>::RHO, INV, 0, NT>(lds, LOG_TC, tid, [&](uint32_t g) { return a.step_full[addr(g)]; },
                                                                    [&](uint32_t g, uint64_t v, uint64_t w) { out[addr(g)] = gl_mul(v, w); });
-        }
     } else {
 #pragma unroll
         for (int i = 0; i < EPT; i++) {
             const uint32_t g = tid + i * NT;
             const uint32_t r = g >> LOG_TC, cc = g & (TC - 1);
             const uint64_t gi = ((uint64_t)r << log_n2) + c0 + cc;
-            uint64_t v = (GL355_NTT_KO & 2) ? gi : in[gi];
-            if constexpr (PRE && !(GL355_NTT_KO & 32)) v = gl_mul(v, (GL355_NTT_KO & 16) ? gi + 3 : pre[gi]);
+            uint64_t v = in[gi];
+            if constexpr (PRE) v = gl_mul(v, pre[gi]);
             lds[lds_phys(g)] = v;
         }
         __syncthreads();
@@ -741,7 +689,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE)))
             const uint64_t go = ((uint64_t)(g >> LOG_TC) << log_n2) + c0 + (g & (TC - 1));
             out[go] = gl_mul(val, a.step_full[go]);
         };
-        if constexpr (LOG_T >= 4 && GL355_NTT_R8_DIRECT != 0) {
+        if constexpr (LOG_T >= 4) {
             uint64_t x[16];
 #pragma unroll
             for (int i = 0; i < 8; i++) x[i] = v[i];

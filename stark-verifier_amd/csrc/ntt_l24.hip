@@ -9,7 +9,7 @@
 namespace gl355 {
 
 // mid[64 u + v] = omega_4096^(bitrev6(u) v): cell (u, v) of the row tile holds output kA = bitrev6(u) of the first radix-64
-// super-round (ntt_rows_l24_kernel)
+// super-round (ntt_rows_l24s_kernel)
 __global__ void build_mid_kernel(uint64_t root4096, uint64_t* out) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= 4096) return;
@@ -31,8 +31,8 @@ int32_t Ctx::l24_mid_table(const uint64_t** out) {
 }
 
 // rows of 4096 points: a.batch << a.log_rows of them (forward, natural order in, bit-reversed canonical out, no multiplier tables).
-// The split-exchange kernel, one row per block, 33 KB of LDS.  (The persistent limb-quad kernel of the first version, ntt_rows_l24_kernel, and the
-// prefetching variants stay in ntt_l24.cuh for tools/ubench/ubench_ntt_l24.hip: profiles/r03_ubench_ntt_l24s.txt, r05_ubench_ntt_l24s.txt.)
+// The split-exchange kernel, one row per block, 33 KB of LDS.  (Its other launch shapes and the prefetching instantiation are timed in
+// profiles/r03_ubench_ntt_l24s.txt and r05_ubench_ntt_l24s.txt; the kernels it was measured against are in tools/ubench/ntt_l24_experiments.cuh.)
 hipError_t launch_rows_l24(const PassArgs& a, hipStream_t s) {
     const uint64_t total = ((uint64_t)a.batch) << a.log_rows;
     auto k = ntt_rows_l24s_kernel<5, false>;

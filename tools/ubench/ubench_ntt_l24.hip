@@ -1,15 +1,19 @@
-// Timing experiments on the 24-bit-limb LDE passes as shipped (csrc/ntt_l24.cuh), outside the library: the row pass (135 x 256 rows of
-// 4096 points, in place) and the all-cosets column pass of the 2^17 -> 2^20 x 135 LDE.  Random operands and table words (only the access
-// pattern matters for the time; parity is the library's tests').  Build variants with -DGL355_L24_KO=mask:
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I stark-verifier_amd/csrc -DGL_MUL_VARIANT=1 tools/ubench/ubench_ntt_l24.hip -o ...
+// Timing experiments on the 24-bit-limb LDE passes, outside the library: the row pass (135 x 256 rows of 4096 points, in place) and the
+// all-cosets column pass of the 2^17 -> 2^20 x 135 LDE, the shipped kernels (csrc/ntt_l24.cuh) in several launch shapes against the
+// earlier forms (ntt_l24_experiments.cuh).  Random operands and table words (only the access pattern matters for the time; parity is the
+// library's tests').
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I stark-verifier_amd/csrc -DGL_MUL_VARIANT=1 tools/ubench/ubench_ntt_l24.hip -o tools/ubench/bin/ubench_ntt_l24
+// The knock-out builds (-DGL355_L24_KO=mask: no global loads / no global stores / mid twiddles from constants) are closed: their results are in
+// profiles/r03_ubench_ntt_l24*.txt and DESIGN 4.1, and the branches are gone from the kernels.  Whoever needs one again builds commit
+// 3078612b24feca10eb94eb4f48929c71f94663bf, the last one that has them.
 #ifndef GL_MUL_VARIANT
 #define GL_MUL_VARIANT 1
 #endif
-#include "ntt_l24.cuh"
+#include "ntt_l24_experiments.cuh"
 #include <cstdio>
 #include <cstdlib>
 using namespace gl355;
-namespace gl355 {   // declared by the headers for the library build; not used here
+namespace gl355 {   // declared by ntt_kernels.cuh for the library build; not used here
 hipError_t launch_rows_r8(const PassArgs&, uint32_t, bool, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_cols_r8(const PassArgs&, uint32_t, bool, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_cols_r8_cosets(const PassArgs&, uint32_t, hipStream_t) { return hipErrorNotSupported; }
@@ -34,7 +38,7 @@ template <typename F> static float timeit(F f, int reps) {
     return t / reps;
 }
 static void report(const char* what, float ms, double gb) {
-    printf("KO=%-2d %-24s %.3f ms  %.0f GB/s moved\n", GL355_L24_KO, what, ms, gb / ms * 1e3);
+    printf("%-24s %.3f ms  %.0f GB/s moved\n", what, ms, gb / ms * 1e3);
 }
 template <int WPE> static void rows(const PassArgs& a, uint32_t blocks, double gb) {
     auto k = ntt_rows_l24_kernel<WPE>;

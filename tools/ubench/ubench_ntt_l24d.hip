@@ -1,16 +1,16 @@
 // Round 6 A/B: the row pass of the 2^17 -> 2^20 x 135 LDE as shipped (ntt_rows_l24s_kernel<5, false>, one row per block) against the LDS-DMA variant
-// (ntt_rows_l24d_kernel: persistent blocks, the next row fetched global -> LDS by global_load_lds_dwordx4 while this one is transformed, mid twiddles in
+// (ntt_rows_l24d_kernel, ntt_l24_experiments.cuh: persistent blocks, the next row fetched global -> LDS by global_load_lds_dwordx4 while this one is transformed, mid twiddles in
 // registers).  Checks the two outputs word for word on random input first, then times both: alone (200 launches) and alternating with the column pass.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I stark-verifier_amd/csrc tools/ubench/ubench_ntt_l24d.hip -o tools/ubench/bin/ubench_ntt_l24d
 #ifndef GL_MUL_VARIANT
 #define GL_MUL_VARIANT 1
 #endif
-#include "ntt_l24.cuh"
+#include "ntt_l24_experiments.cuh"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 using namespace gl355;
-namespace gl355 {
+namespace gl355 {   // declared by ntt_kernels.cuh for the library build; not used here
 hipError_t launch_rows_r8(const PassArgs&, uint32_t, bool, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_cols_r8(const PassArgs&, uint32_t, bool, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_cols_r8_cosets(const PassArgs&, uint32_t, hipStream_t) { return hipErrorNotSupported; }

@@ -3,9 +3,9 @@
 //   * the in-proof single-pass LDEs (8 units x 135 columns of 2^13 / 2^14 coefficients -> 8 cosets),
 // radix-16 against radix-8 kernels.  Random operands (the clocks follow the data's toggle rate); the twiddle tables hold random words
 // too -- only the access pattern matters for the time.
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I stark-verifier_amd/csrc [-DGL_MUL_VARIANT=1|2] [-DGL355_NTT_KO=mask] tools/ubench/ubench_ntt_rows.hip
-// GL355_NTT_KO knocks parts of the kernels out (ntt_kernels.cuh; results are wrong then, only the time means something): this is how
-// the scattered twiddle gathers of the first version were found to cost a third of the row pass.
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I stark-verifier_amd/csrc [-DGL_MUL_VARIANT=1|2] tools/ubench/ubench_ntt_rows.hip -o tools/ubench/bin/ubench_ntt_rows
+// (The knock-out builds that found the scattered twiddle gathers of the first version to cost a third of the row pass are recorded in
+// profiles/r02_ubench_ntt_knockout.txt; the kernels no longer carry those branches.)
 #ifndef GL_MUL_VARIANT
 #define GL_MUL_VARIANT 2
 #endif
@@ -14,7 +14,7 @@
 #include <cstdlib>
 #include <vector>
 using namespace gl355;
-namespace gl355 {   // declared by the header for the library build; not used here
+namespace gl355 {   // declared by ntt_kernels.cuh for the library build; not used here
 hipError_t launch_rows_r8(const PassArgs&, uint32_t, bool, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_cols_r8(const PassArgs&, uint32_t, bool, hipStream_t) { return hipErrorNotSupported; }
 }
@@ -38,7 +38,7 @@ template <typename F> static float timeit(F f, int reps) {
     return t / reps;
 }
 static void report(const char* what, float ms, double gb) {
-    printf("MV=%d KO=%-2d %-28s %.3f ms  %.0f GB/s\n", GL_MUL_VARIANT, GL355_NTT_KO, what, ms, gb / ms * 1e3);
+    printf("MV=%d %-28s %.3f ms  %.0f GB/s\n", GL_MUL_VARIANT, what, ms, gb / ms * 1e3);
 }
 
 template <int LT>
