@@ -285,11 +285,22 @@ static int32_t create_common(int32_t device, void* stream, bool external, gl355_
 int32_t gl355_runtime_config(int32_t device, uint32_t contexts, int32_t sleeping_waits) {
     if (device < 0) return GL355_E_INVALID_ARG;
     if (contexts) {
-        char buf[16];
         // a context owns two streams: the proving stream and the side stream of the batch runtime (witness generation, uploads).  A
         // long interpreter kernel sharing a hardware queue with another context's proving stream would hold that stream up.
-        snprintf(buf, sizeof buf, "%u", 2 * contexts < 4 ? 4u : 2 * contexts);
-        setenv("GPU_MAX_HW_QUEUES", buf, 0);      // read by the HIP runtime when it initialises
+        // Launchers often export a small value (the runtime's own default is 4) in front of every command: a lower value is
+        // raised, a higher one is kept, and the request stops at 32 queues.
+        const unsigned long need = contexts >= 16 ? 32ul : contexts < 2 ? 4ul : 2ul * contexts;
+        unsigned long have = 0;                   // 0: unset, empty or not a positive integer
+        if (const char* cur = getenv("GPU_MAX_HW_QUEUES")) {
+            char* end = nullptr;
+            const unsigned long v = strtoul(cur, &end, 10);   // saturates, so an absurdly large value still counts as "more"
+            if (*cur >= '0' && *cur <= '9' && *end == '\0') have = v;
+        }
+        if (have < need) {
+            char buf[16];
+            snprintf(buf, sizeof buf, "%lu", need);
+            setenv("GPU_MAX_HW_QUEUES", buf, 1);  // read by the HIP runtime when it initialises
+        }
     }
     if (sleeping_waits) {
         if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return GL355_E_HIP; }

@@ -622,7 +622,8 @@ class NativeCircuit:
 
 def semaphore_units(ctxs, sem, rec, private_keys, topic, tree_digests, member_indices, seed_base, want_proofs=False):
     """gl355_semaphore_units: the native batch runtime (recursion.rs:300-308 `par_iter` of make_signal + the verification
-    circuit per signal): one host thread per context inside the library, unit j on context j mod len(ctxs).
+    circuit per signal): one host thread per context inside the library; a context takes the next GL355_OPT_BATCH_UNITS
+    units whenever it is free and proves them in lock-step.
     -> leaves [count][8] (nullifier | topic), proofs [count][words] or None, units proven per context"""
     lib = ctxs[0].lib
     hs = (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
