@@ -147,39 +147,70 @@ __global__ void alpha_table_kernel(AlphaTabArgs a) {
 }
 
 // a point's wire row: column j of the wires LDE at this lane's row (global memory), or of the LDS copy of the row (STAGE variant)
-struct WireSrc { const uint64_t* p; uint64_t stride, idx; };
+struct WireSrc { const uint64_t* p; uint64_t stride, idx, cs_stride; };    // cs_stride: of the constants_sigmas oracle (global memory)
 #define WIRE(j) (w.p[(uint64_t)(j) * w.stride + w.idx])
-#define CONST(j) (a.cs[(uint64_t)(j) * a.lde_stride + t])
+#define CONST(j) (a.cs[(uint64_t)(j) * w.cs_stride + t])
 
-// PoseidonGate: 123 constraints (gates/poseidon.rs:592-698); wire layout :329-380
+// GROUPED COLUMN READS.  A column value is an Infinity-Cache hit (~545 clk idle) and with three waves per SIMD a read that is
+// waited for on the spot is a bubble nobody fills, so the evaluators request their columns K at a time: the K loads are issued
+// back to back into a register array (no wait, no branch between them) and the evaluator consumes from the registers -- one
+// round trip per group.  A run-time loop runs over groups; the short last group CLAMPS its column indices to `last` (the last
+// column the evaluator owns, so never past the oracle) and the surplus registers are ignored.
+constexpr int QG = 8;
+template <int K>
+GL_DEV void wire_group(const WireSrc& w, uint32_t first, uint32_t last, uint64_t* v) {
+#pragma unroll
+    for (int i = 0; i < K; i++) { const uint32_t j = first + i; v[i] = WIRE(j < last ? j : last); }
+}
+template <int K>
+GL_DEV void const_group(const QuotArgs& a, const WireSrc& w, uint64_t t, uint32_t first, uint32_t last, uint64_t* v) {
+#pragma unroll
+    for (int i = 0; i < K; i++) { const uint32_t j = first + i; v[i] = CONST(j < last ? j : last); }
+}
+
+// PoseidonGate: 123 constraints (gates/poseidon.rs:592-698); wire layout :329-380.  The first PSD_AHEAD S-box-input wires of a
+// full round are requested one round ahead (in flight over the S-boxes and the MDS layer of the round before; all twelve do
+// not fit next to the state at three waves), the rest in one group when the round starts; a partial round's wire four rounds ahead.
+constexpr int PSD_AHEAD = 6;
+template <class GateAcc>
+GL_DEV void psd_round_wires(const WireSrc& w, GateAcc& g, uint64_t* s, uint64_t* sin, uint32_t first) {
+    constexpr int PF = PSD_AHEAD;
+    if constexpr (PF < 12) wire_group<12 - PF>(w, first + PF, first + 11, sin + PF);
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        g.push(gl_sub(s[i], sin[i]));
+        s[i] = sin[i];
+    }
+}
 template <class GateAcc>
 GL_DEV void gate_poseidon(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g) {
-    const uint64_t swap = WIRE(24);
-    g.push(gl_sub(gl_mul(swap, swap), swap));
-    uint64_t s[12];
+    constexpr int PF = PSD_AHEAD;
+    uint64_t s[12], sin[12], pin[4];
+    {
+        uint64_t in[12], sd[5];                     // inputs 0..11, swap 24, delta 25..28: one group
+        wire_group<12>(w, 0, 11, in);
+        wire_group<5>(w, 24, 28, sd);
+        const uint64_t swap = sd[0];
+        g.push(gl_sub(gl_mul(swap, swap), swap));
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint64_t lhs = WIRE(i), rhs = WIRE(i + 4), delta = WIRE(25 + i);
-        g.push(gl_sub(gl_mul(swap, gl_sub(rhs, lhs)), delta));
-        s[i] = gl_add(lhs, delta);
-        s[i + 4] = gl_sub(rhs, delta);
+        for (int i = 0; i < 4; i++) {
+            const uint64_t lhs = in[i], rhs = in[i + 4], delta = sd[1 + i];
+            g.push(gl_sub(gl_mul(swap, gl_sub(rhs, lhs)), delta));
+            s[i] = gl_add(lhs, delta);
+            s[i + 4] = gl_sub(rhs, delta);
+        }
+#pragma unroll
+        for (int i = 8; i < 12; i++) s[i] = in[i];
     }
-#pragma unroll
-    for (int i = 8; i < 12; i++) s[i] = WIRE(i);
     // every MDS layer also adds the NEXT round's constants (psd_mds; row 30 of the table is zero), so s is "state + constants",
     // the quantity the S-box-input wires are constrained to, whenever a round starts
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = gl_add_canonical(s[i], PSD_ALL_RC[i]);
 #pragma unroll 1
     for (int r = 0; r < 4; r++) {
-        if (r != 0) {
-#pragma unroll
-            for (int i = 0; i < 12; i++) {
-                const uint64_t sin = WIRE(29 + 12 * (r - 1) + i);
-                g.push(gl_sub(s[i], sin));
-                s[i] = sin;
-            }
-        }
+        if (r != 0) psd_round_wires(w, g, s, sin, 29 + 12 * (r - 1));
+        if (r < 3) wire_group<PF>(w, 29 + 12 * r, 64, sin);      // round r + 1's
+        else wire_group<4>(w, 65, 86, pin);                      // the first four partial rounds'
 #pragma unroll
         for (int i = 0; i < 12; i += 4) psd_sbox4(s[i], s[i + 1], s[i + 2], s[i + 3]);       // four S-boxes in lock-step (poseidon.cuh)
         psd_mds(s, &PSD_ALL_RC[12 * (r + 1)]);
@@ -188,56 +219,89 @@ GL_DEV void gate_poseidon(const QuotArgs& a, const WireSrc& w, uint64_t t, GateA
     // 22 constraints (and the state handed to the closing full rounds) are the same polynomials in the wires
     // as in the reference's sparse formulation (gates/poseidon.rs:652-673), at fewer VALU cycles
 #pragma unroll 1
-    for (int r = 0; r < 22; r++) {
-        const uint64_t sin = WIRE(65 + r);
-        g.push(gl_sub(s[0], sin));
-        s[0] = psd_sbox(sin);
-        psd_mds(s, &PSD_ALL_RC[12 * (5 + r)]);
+    for (int r0 = 0; r0 < 24; r0 += 4) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (r0 + i < 22) {
+                const uint64_t sin0 = pin[i];
+                pin[i] = WIRE(r0 + i + 4 < 22 ? 65 + r0 + i + 4 : 86);       // round r + 4's (clamped: never used past round 21)
+                g.push(gl_sub(s[0], sin0));
+                s[0] = psd_sbox(sin0);
+                if (r0 + i == 21) wire_group<PF>(w, 87, 98, sin);            // the first closing full round's
+                psd_mds(s, &PSD_ALL_RC[12 * (5 + r0 + i)]);
+            }
+        }
     }
 #pragma unroll 1
     for (int r = 0; r < 4; r++) {
-#pragma unroll
-        for (int i = 0; i < 12; i++) {
-            const uint64_t sin = WIRE(87 + 12 * r + i);
-            g.push(gl_sub(s[i], sin));
-            s[i] = sin;
-        }
+        psd_round_wires(w, g, s, sin, 87 + 12 * r);
+        if (r < 3) wire_group<PF>(w, 87 + 12 * (r + 1), 134, sin);
+        else wire_group<PF>(w, 12, 23, sin);                     // the first PF outputs; the other 12 - PF are read behind the loop
 #pragma unroll
         for (int i = 0; i < 12; i += 4) psd_sbox4(s[i], s[i + 1], s[i + 2], s[i + 3]);
         psd_mds(s, &PSD_ALL_RC[12 * (27 + r)]);
     }
+    if constexpr (PF < 12) wire_group<12 - PF>(w, 12 + PF, 23, sin + PF);
 #pragma unroll
-    for (int i = 0; i < 12; i++) g.push(gl_sub(s[i], WIRE(12 + i)));
+    for (int i = 0; i < 12; i++) g.push(gl_sub(s[i], sin[i]));
 }
 
 // BaseSumGate<2>{num_limbs}: sum_i limb_i 2^i - sum ; limb (limb - 1)   (gates/base_sum.rs:37-60)
 template <class GateAcc>
 GL_DEV void gate_base_sum(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g, uint32_t num_limbs) {
+    const uint64_t sum = WIRE(0);
+    const uint32_t groups = (num_limbs + QG - 1) / QG;
     uint64_t acc = 0;
-    for (uint32_t i = num_limbs; i-- > 0;) acc = gl_add(gl_add(acc, acc), WIRE(1 + i));
-    g.push(gl_sub(acc, WIRE(0)));
-    for (uint32_t i = 0; i < num_limbs; i++) {
-        const uint64_t l = WIRE(1 + i);
-        g.push(gl_sub(gl_mul(l, l), l));
+    for (uint32_t gr = groups; gr-- > 0;) {
+        uint64_t v[QG];
+        wire_group<QG>(w, 1 + gr * QG, num_limbs, v);
+#pragma unroll
+        for (int i = QG - 1; i >= 0; i--)
+            if (gr * QG + i < num_limbs) acc = gl_add(gl_add(acc, acc), v[i]);
+    }
+    g.push(gl_sub(acc, sum));
+    for (uint32_t gr = 0; gr < groups; gr++) {
+        uint64_t v[QG];
+        wire_group<QG>(w, 1 + gr * QG, num_limbs, v);
+#pragma unroll
+        for (int i = 0; i < QG; i++)
+            if (gr * QG + i < num_limbs) g.push(gl_sub(gl_mul(v[i], v[i]), v[i]));
     }
 }
 // ConstantGate{n}: const_i - wire_i   (gates/constant.rs:31-36); gate constants follow the selectors
 template <class GateAcc>
 GL_DEV void gate_constant(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g, uint32_t n) {
-    for (uint32_t i = 0; i < n; i++) g.push(gl_sub(CONST(a.c.num_selectors + i), WIRE(i)));
+    for (uint32_t i0 = 0; i0 < n; i0 += 4) {
+        uint64_t c[4], v[4];
+        const_group<4>(a, w, t, a.c.num_selectors + i0, a.c.num_selectors + n - 1, c);
+        wire_group<4>(w, i0, n - 1, v);
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (i0 + i < n) g.push(gl_sub(c[i], v[i]));
+    }
 }
 // PublicInputGate: wire_i - pi_hash_i   (gates/public_input.rs:32-39)
 template <class GateAcc>
 GL_DEV void gate_public_input(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g, uint32_t unit) {
-    for (uint32_t i = 0; i < 4; i++) g.push(gl_sub(WIRE(i), a.pi_hash[unit * 4 + i]));
+    uint64_t v[4];
+    wire_group<4>(w, 0, 3, v);
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) g.push(gl_sub(v[i], a.pi_hash[unit * 4 + i]));
 }
 // ArithmeticGate{num_ops}: out - (c0 m0 m1 + c1 addend)   (gates/arithmetic.rs:47-68)
 template <class GateAcc>
 GL_DEV void gate_arithmetic(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g, uint32_t num_ops) {
     const uint64_t c0 = CONST(a.c.num_selectors), c1 = CONST(a.c.num_selectors + 1);
-    for (uint32_t i = 0; i < num_ops; i++) {
-        const uint64_t m0 = WIRE(4 * i), m1 = WIRE(4 * i + 1), ad = WIRE(4 * i + 2), out = WIRE(4 * i + 3);
-        g.push(gl_sub(out, gl_add(gl_mul(gl_mul(m0, m1), c0), gl_mul(ad, c1))));
+    for (uint32_t i0 = 0; i0 < num_ops; i0 += 2) {           // two operations = one group
+        uint64_t v[8];
+        wire_group<8>(w, 4 * i0, 4 * num_ops - 1, v);
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            if (i0 + i < num_ops) {
+                const uint64_t m0 = v[4 * i], m1 = v[4 * i + 1], ad = v[4 * i + 2], out = v[4 * i + 3];
+                g.push(gl_sub(out, gl_add(gl_mul(gl_mul(m0, m1), c0), gl_mul(ad, c1))));
+            }
+        }
     }
 }
 
@@ -252,8 +316,16 @@ GL_DEV void push2(GateAcc& g, gl2 v) { g.push(v.c0); g.push(v.c1); }
 template <class GateAcc>
 GL_DEV void gate_arithmetic_ext(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g, uint32_t num_ops) {
     const uint64_t c0 = CONST(a.c.num_selectors), c1 = CONST(a.c.num_selectors + 1);
-    for (uint32_t i = 0; i < num_ops; i++) {
-        const gl2 m0 = WIRE2(8 * i), m1 = WIRE2(8 * i + 2), ad = WIRE2(8 * i + 4), out = WIRE2(8 * i + 6);
+    if (num_ops == 0) return;
+    const uint32_t last = 8 * num_ops - 1;
+    uint64_t nx[8];
+    wire_group<8>(w, 0, last, nx);
+    for (uint32_t i = 0; i < num_ops; i++) {                 // one operation = one group, requested an operation ahead
+        uint64_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = nx[k];
+        wire_group<8>(w, 8 * (i + 1), last, nx);
+        const gl2 m0 = gl2_make(v[0], v[1]), m1 = gl2_make(v[2], v[3]), ad = gl2_make(v[4], v[5]), out = gl2_make(v[6], v[7]);
         const gl2 comp = gl2_add(gl2_mul_base(gl2_mul(m0, m1), c0), gl2_mul_base(ad, c1));
         push2(g, gl2_sub(out, comp));
     }
@@ -262,26 +334,50 @@ GL_DEV void gate_arithmetic_ext(const QuotArgs& a, const WireSrc& w, uint64_t t,
 template <class GateAcc>
 GL_DEV void gate_mul_ext(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g, uint32_t num_ops) {
     const uint64_t c0 = CONST(a.c.num_selectors);
+    if (num_ops == 0) return;
+    const uint32_t last = 6 * num_ops - 1;
+    uint64_t nx[6];
+    wire_group<6>(w, 0, last, nx);
     for (uint32_t i = 0; i < num_ops; i++) {
-        const gl2 m0 = WIRE2(6 * i), m1 = WIRE2(6 * i + 2), out = WIRE2(6 * i + 4);
+        uint64_t v[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) v[k] = nx[k];
+        wire_group<6>(w, 6 * (i + 1), last, nx);
+        const gl2 m0 = gl2_make(v[0], v[1]), m1 = gl2_make(v[2], v[3]), out = gl2_make(v[4], v[5]);
         push2(g, gl2_sub(out, gl2_mul_base(gl2_mul(m0, m1), c0)));
     }
 }
-// PoseidonMdsGate: out_r - sum_i CIRC[i] in[(i+r)%12] - DIAG[r] in[r]   (gates/poseidon_mds.rs:26-126)
+// PoseidonMdsGate: out_r - sum_i CIRC[i] in[(i+r)%12] - DIAG[r] in[r]   (gates/poseidon_mds.rs:26-126).  The 24 input wires are
+// read once into registers; four output rows per pass of the loop, after which the inputs are rotated by four elements, so
+// that every register index is a compile-time one.  A row's two output wires are read when the row is pushed (a group of them does not fit next to the inputs at three waves).
 template <class GateAcc>
 GL_DEV void gate_poseidon_mds(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g) {
     constexpr uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-    for (uint32_t r = 0; r < 12; r++) {
-        gl2 acc = gl2_make(0, 0);
-        for (uint32_t i = 0; i < 12; i++) {
-            const gl2 in = WIRE2(2 * ((i + r) % 12));
-            acc = gl2_add(acc, gl2_make(gl_mul_small(in.c0, CIRC[i]), gl_mul_small(in.c1, CIRC[i])));
+    uint64_t in[24];
+    wire_group<24>(w, 0, 23, in);
+#pragma unroll 1
+    for (uint32_t r0 = 0; r0 < 12; r0 += 4) {
+#pragma unroll
+        for (uint32_t r = 0; r < 4; r++) {
+            gl2 acc = gl2_make(0, 0);
+#pragma unroll
+            for (uint32_t i = 0; i < 12; i++) {
+                const gl2 x = gl2_make(in[2 * ((i + r) % 12)], in[2 * ((i + r) % 12) + 1]);
+                acc = gl2_add(acc, gl2_make(gl_mul_small(x.c0, CIRC[i]), gl_mul_small(x.c1, CIRC[i])));
+            }
+            if (r0 + r == 0) {
+                const gl2 x = gl2_make(in[0], in[1]);
+                acc = gl2_add(acc, gl2_make(gl_mul_small(x.c0, 8), gl_mul_small(x.c1, 8)));
+            }
+            push2(g, gl2_sub(WIRE2(2 * (12 + r0 + r)), acc));
         }
-        if (r == 0) {
-            const gl2 in = WIRE2(0);
-            acc = gl2_add(acc, gl2_make(gl_mul_small(in.c0, 8), gl_mul_small(in.c1, 8)));
-        }
-        push2(g, gl2_sub(WIRE2(2 * (12 + r)), acc));
+        uint64_t rot[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) rot[k] = in[k];
+#pragma unroll
+        for (int k = 0; k < 16; k++) in[k] = in[k + 8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) in[16 + k] = rot[k];
     }
 }
 // RandomAccessGate{bits, copies, extra}   (gates/random_access.rs:27-147)
@@ -291,40 +387,73 @@ GL_DEV void gate_random_access(const QuotArgs& a, const WireSrc& w, uint64_t t, 
     const uint32_t vec = 1u << bits, routed = (2 + vec) * copies + extra;
     for (uint32_t c = 0; c < copies; c++) {
         const uint32_t base = (2 + vec) * c;
+        // a copy's wires in one go: its bit wires (<= 4) once, the claimed index and element, the list (<= 16 items)
+        uint64_t b[4], hd[2], items[16];
+        wire_group<4>(w, routed + c * bits, routed + c * bits + bits - 1, b);      // 1 <= bits <= 4 (checked at launch)
+        wire_group<2>(w, base, base + 1, hd);
+        wire_group<8>(w, base + 2, base + 1 + vec, &items[0]);
+        if (vec > 8) wire_group<8>(w, base + 10, base + 1 + vec, &items[8]);
         uint64_t recon = 0;
-        for (uint32_t i = 0; i < bits; i++) {
-            const uint64_t b = WIRE(routed + c * bits + i);
-            g.push(gl_sub(gl_mul(b, b), b));
-        }
-        for (uint32_t i = bits; i-- > 0;) recon = gl_add(gl_add(recon, recon), WIRE(routed + c * bits + i));
-        g.push(gl_sub(recon, WIRE(base)));
-        // fold the list: item = x + b (y - x) per pair, one bit per level (bits <= 4 => <= 16 items)
-        uint64_t items[16];
-        for (uint32_t i = 0; i < 16; i++) items[i] = i < vec ? WIRE(base + 2 + i) : 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if ((uint32_t)i < bits) g.push(gl_sub(gl_mul(b[i], b[i]), b[i]));
+#pragma unroll
+        for (int i = 3; i >= 0; i--)
+            if ((uint32_t)i < bits) recon = gl_add(gl_add(recon, recon), b[i]);
+        g.push(gl_sub(recon, hd[0]));
+        // fold the list: item = x + b (y - x) per pair, one bit per level (bits <= 4 => <= 16 items; entries past the list
+        // hold clamped re-reads and are never folded in)
         uint32_t len = vec;
         for (uint32_t lvl = 0; lvl < bits; lvl++) {
-            const uint64_t b = WIRE(routed + c * bits + lvl);
+            const uint64_t bl = b[0];                // the level's bit; the rest move down one place
+            b[0] = b[1]; b[1] = b[2]; b[2] = b[3];
             for (uint32_t k = 0; k < 8; k++) {
-                if (k < len / 2) items[k] = gl_add(gl_mul(b, gl_sub(items[2 * k + 1], items[2 * k])), items[2 * k]);
+                if (k < len / 2) items[k] = gl_add(gl_mul(bl, gl_sub(items[2 * k + 1], items[2 * k])), items[2 * k]);
             }
             len >>= 1;
         }
-        g.push(gl_sub(items[0], WIRE(base + 1)));
+        g.push(gl_sub(items[0], hd[1]));
     }
-    for (uint32_t i = 0; i < extra; i++) g.push(gl_sub(CONST(a.c.num_selectors + i), WIRE((2 + vec) * copies + i)));
+    if (extra != 0) {
+        for (uint32_t i0 = 0; i0 < extra; i0 += 4) {
+            uint64_t cv[4], v[4];
+            const_group<4>(a, w, t, a.c.num_selectors + i0, a.c.num_selectors + extra - 1, cv);
+            wire_group<4>(w, (2 + vec) * copies + i0, (2 + vec) * copies + extra - 1, v);
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i0 + i < extra) g.push(gl_sub(cv[i], v[i]));
+        }
+    }
 }
 // ReducingGate{n} / ReducingExtensionGate{n}: acc*alpha + coeff - acc_i   (gates/reducing.rs:20-85,
 // gates/reducing_extension.rs:20-87); the last accumulator is the output (wires 0..1)
 template <bool EXT, class GateAcc>
 GL_DEV void gate_reducing(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g, uint32_t n) {
-    const gl2 alpha = WIRE2(2);
-    gl2 acc = WIRE2(4);
+    constexpr int CW = EXT ? 8 : 4;                          // coefficient wires of four steps
+    if (n == 0) return;
+    uint64_t hd[6];                                          // output, alpha, initial accumulator
+    wire_group<6>(w, 0, 5, hd);
+    const gl2 alpha = gl2_make(hd[2], hd[3]);
+    gl2 acc = gl2_make(hd[4], hd[5]);
     const uint32_t start_accs = 6 + (EXT ? 2 * n : n);
-    for (uint32_t i = 0; i < n; i++) {
-        const gl2 coeff = EXT ? WIRE2(6 + 2 * i) : gl2_make(WIRE(6 + i), 0);
-        const gl2 acc_i = (i == n - 1) ? WIRE2(0) : WIRE2(start_accs + 2 * i);
-        push2(g, gl2_sub(gl2_add(gl2_mul(acc, alpha), coeff), acc_i));
-        acc = acc_i;
+    // four steps = one group of coefficients + one group of old accumulators; the last step's accumulator is the output, so the
+    // accumulator columns end at start_accs + 2 (n - 1) - 1 (for n = 1 that clamps onto the coefficient wire in front of them)
+    const uint32_t last_coeff = start_accs - 1, last_acc = start_accs + 2 * (n - 1) - 1;
+    for (uint32_t i0 = 0; i0 < n; i0 += 4) {
+        uint64_t cf[CW], ac[8];
+        wire_group<CW>(w, 6 + (EXT ? 2 : 1) * i0, last_coeff, cf);
+        wire_group<8>(w, start_accs + 2 * i0, last_acc, ac);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (i0 + i < n) {
+                gl2 coeff;
+                if constexpr (EXT) coeff = gl2_make(cf[2 * i], cf[2 * i + 1]);
+                else coeff = gl2_make(cf[i], 0);
+                const gl2 acc_i = (i0 + i == n - 1) ? gl2_make(hd[0], hd[1]) : gl2_make(ac[2 * i], ac[2 * i + 1]);
+                push2(g, gl2_sub(gl2_add(gl2_mul(acc, alpha), coeff), acc_i));
+                acc = acc_i;
+            }
+        }
     }
 }
 
@@ -338,10 +467,10 @@ __global__ void __launch_bounds__(STAGE ? 64 : 128) __attribute__((amdgpu_waves_
     if (t >= nq) return;
     const uint32_t unit = blockIdx.y;
     const uint64_t* __restrict__ wglob = a.wires + (uint64_t)unit * a.wires_us;
-    WireSrc w{wglob, a.lde_stride, t};
+    WireSrc w{wglob, a.lde_stride, t, a.lde_stride};
     if constexpr (STAGE) {
         for (uint32_t j = 0; j < a.c.num_wires; j++) wire_lds[j * 64 + threadIdx.x] = wglob[(uint64_t)j * a.lde_stride + t];
-        w = WireSrc{wire_lds, 64, threadIdx.x};        // one wave per block: no barrier needed, each lane reads only its own column entries
+        w = WireSrc{wire_lds, 64, threadIdx.x, a.lde_stride};        // one wave per block: no barrier needed, each lane reads only its own column entries
     }
     const uint64_t* __restrict__ zs = a.zs + (uint64_t)unit * a.zs_us;
     const uint32_t qdb = a.qbits - a.c.degree_bits;
@@ -358,7 +487,6 @@ __global__ void __launch_bounds__(STAGE ? 64 : 128) __attribute__((amdgpu_waves_
     AlphaAcc<NCH> total;
     total.init(a, unit);
     // ---- L0(x) (Z_c(x) - 1);  L0(x) = (x^n - 1) / (n (x - 1))  (vanishing_poly.rs:155-178) ---------
-    const uint64_t zh_inv = a.zh_inv[iq & ((1u << qdb) - 1)];
     const uint64_t zh = a.zh[iq & ((1u << qdb) - 1)];  // x^n - 1 (never zero on the coset)
     const uint64_t l0 = gl_mul(gl_mul(zh, a.n_inv), gl_inv(gl_sub(x, 1)));
     for (uint32_t c = 0; c < nch; c++) {
@@ -377,12 +505,18 @@ __global__ void __launch_bounds__(STAGE ? 64 : 128) __attribute__((amdgpu_waves_
             bx[c] = gl_mul(a.betas[unit * 4 + c], x);
         }
         const uint32_t first = total.idx;
+        // wire j + 1, its sigma and its k are requested before the eight products of wire j (the index is clamped to the last
+        // routed wire: sigma_{routed-1} is the last column of its batch)
+        const uint32_t sig0 = n_sel + n_cst;
+        uint64_t wn = WIRE(0), sn = CONST(sig0), kn = a.k_is[0];
         for (uint32_t ch = 0; ch < n_chunks; ch++) {
             uint64_t num[NCH], den[NCH];
 #pragma unroll
             for (int c = 0; c < NCH; c++) { num[c] = 1; den[c] = 1; }
             for (uint32_t j = ch * chunk; j < (ch + 1) * chunk && j < routed; j++) {
-                const uint64_t wj = WIRE(j), sj = CONST(n_sel + n_cst + j), kj = a.k_is[j];
+                const uint64_t wj = wn, sj = sn, kj = kn;
+                const uint32_t jn = j + 1 < routed ? j + 1 : routed - 1;
+                wn = WIRE(jn); sn = CONST(sig0 + jn); kn = a.k_is[jn];
                 if constexpr (NCH == 2) {
                     // the eight products of a wire in two lock-step groups of four (gl_mul_multi: partners fill the carry wait states)
                     const uint64_t a1[4] = {bx[0], bx[1], a.betas[unit * 4], a.betas[unit * 4 + 1]}, b1[4] = {kj, kj, sj, sj};
@@ -420,19 +554,25 @@ __global__ void __launch_bounds__(STAGE ? 64 : 128) __attribute__((amdgpu_waves_
         const gl355_gate gt = a.c.gates[gi];
         if (gt.type == GL355_GATE_NOOP) continue;
         GateAccT<NCH> g;
+        // every column address of an evaluator is invariant in this loop; left visible, the compiler forms them all in front of
+        // the loop and spills them, so each gate starts from strides and a row index it cannot see through
+        WireSrc wg = w;
+        uint64_t tg = t;
+        asm volatile("" : "+s"(wg.stride), "+s"(wg.cs_stride), "+v"(tg));
+        wg.idx = STAGE ? w.idx : tg;
         g.init(a, unit, total.idx);
         switch (gt.type) {
-            case GL355_GATE_POSEIDON: gate_poseidon(a, w, t, g); break;
-            case GL355_GATE_BASE_SUM: gate_base_sum(a, w, t, g, gt.param); break;
-            case GL355_GATE_CONSTANT: gate_constant(a, w, t, g, gt.param); break;
-            case GL355_GATE_PUBLIC_INPUT: gate_public_input(a, w, t, g, unit); break;
-            case GL355_GATE_ARITHMETIC: gate_arithmetic(a, w, t, g, gt.param); break;
-            case GL355_GATE_ARITHMETIC_EXT: gate_arithmetic_ext(a, w, t, g, gt.param); break;
-            case GL355_GATE_MUL_EXT: gate_mul_ext(a, w, t, g, gt.param); break;
-            case GL355_GATE_POSEIDON_MDS: gate_poseidon_mds(a, w, t, g); break;
-            case GL355_GATE_RANDOM_ACCESS: gate_random_access(a, w, t, g, gt.param); break;
-            case GL355_GATE_REDUCING: gate_reducing<false>(a, w, t, g, gt.param); break;
-            case GL355_GATE_REDUCING_EXT: gate_reducing<true>(a, w, t, g, gt.param); break;
+            case GL355_GATE_POSEIDON: gate_poseidon(a, wg, tg, g); break;
+            case GL355_GATE_BASE_SUM: gate_base_sum(a, wg, tg, g, gt.param); break;
+            case GL355_GATE_CONSTANT: gate_constant(a, wg, tg, g, gt.param); break;
+            case GL355_GATE_PUBLIC_INPUT: gate_public_input(a, wg, tg, g, unit); break;
+            case GL355_GATE_ARITHMETIC: gate_arithmetic(a, wg, tg, g, gt.param); break;
+            case GL355_GATE_ARITHMETIC_EXT: gate_arithmetic_ext(a, wg, tg, g, gt.param); break;
+            case GL355_GATE_MUL_EXT: gate_mul_ext(a, wg, tg, g, gt.param); break;
+            case GL355_GATE_POSEIDON_MDS: gate_poseidon_mds(a, wg, tg, g); break;
+            case GL355_GATE_RANDOM_ACCESS: gate_random_access(a, wg, tg, g, gt.param); break;
+            case GL355_GATE_REDUCING: gate_reducing<false>(a, wg, tg, g, gt.param); break;
+            case GL355_GATE_REDUCING_EXT: gate_reducing<true>(a, wg, tg, g, gt.param); break;
             default: break;
         }
         const uint64_t sel = CONST(gt.selector_index);
@@ -443,6 +583,7 @@ __global__ void __launch_bounds__(STAGE ? 64 : 128) __attribute__((amdgpu_waves_
 #pragma unroll
         for (uint32_t c = 0; c < nch; c++) gate_sum[c] = gl_add(gate_sum[c], gl_mul(filter, g.value(c)));
     }
+    const uint64_t zh_inv = a.zh_inv[iq & ((1u << qdb) - 1)];
     for (uint32_t c = 0; c < nch; c++) {
         const uint64_t v = gl_mul(gl_add(total.acc[c], gate_sum[c]), zh_inv);
         a.out[((uint64_t)unit * nch + c) * nq + t] = gl_canon(v);
@@ -499,6 +640,9 @@ int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const u
     uint32_t longest = 0;
     for (uint32_t g = 0; g < c->num_gates; g++) {
         const uint32_t p = c->gates[g].param;
+        // the evaluator keeps a copy's bit wires in four registers and its list in sixteen
+        if (c->gates[g].type == GL355_GATE_RANDOM_ACCESS && ((p & 0xFF) < 1 || (p & 0xFF) > 4))
+            return ctx->fail(GL355_E_UNSUPPORTED, "quotient: RandomAccessGate with 1..4 bits");
         uint32_t k = 0;
         switch (c->gates[g].type) {
             case GL355_GATE_CONSTANT: k = p; break;
@@ -526,6 +670,8 @@ int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const u
     ProfScope ps(ctx, "quotient_kernel", (uint64_t)B * nq * 8 * ((uint64_t)c->num_selectors + c->num_constants + c->num_routed_wires + c->num_wires +
                                                    (uint64_t)c->num_challenges * (2 + c->num_partial_products)));
     // (the LDS-staged variant quotient_kernel<NCH, true> measured slower -- profiles/r02_quotient_ab.txt -- and is no longer instantiated)
+    // three and four challenges: no circuit of the project has them; those instantiations do not fit 168 registers with the grouped
+    // reads and spill (156 / 372 bytes of scratch per lane) -- correct, slower than they could be
     const dim3 grid((uint32_t)((nq + 127) / 128), B);
     switch (c->num_challenges) {
         case 1: hipLaunchKernelGGL(quotient_kernel<1>, grid, dim3(128), 0, ctx->stream, a); break;

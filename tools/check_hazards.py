@@ -54,7 +54,9 @@ def sdst_index(op):
 def check_listing(txt, name):
     bad = []
     n_checked = 0
-    for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)(?:s_endpgm|s_setpc_b64)", txt, re.S | re.M):
+    # a function runs to its .Lfunc_end label: s_endpgm can sit in the middle, and a kernel too large for 16-bit branch offsets has
+    # s_setpc_b64 long branches inside (like every branch they end a block below)
+    for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", txt, re.S | re.M):
         fn, body = m.group(1), m.group(2)
         last_write = {}          # scalar register -> wait states issued since its last VALU write
         for raw in body.split("\n"):
