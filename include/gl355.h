@@ -810,7 +810,9 @@ int32_t gl355_plonk_verify_stage_ms(double ms[3]);
 int32_t gl355_kzg_params_check(gl355_ctx* ctx, const uint64_t* g /* n_points x 8 */, uint64_t n_points, const uint64_t* g_lagrange /* 2^log_n x 8 or NULL */,
                                uint32_t log_n, const uint64_t s_g2[16], const uint8_t seed[32], int32_t* ok);
 
-/* ---- a9: wires_permutation_partial_products_and_zs (vanishing_poly.rs:54-108,183-218) --------- */
+/* ---- a9: wires_permutation_partial_products_and_zs (vanishing_poly.rs:54-108,183-218) ---------
+ * One unit and one challenge through the lock-step prover's kernels, which hold the chunk products of a row in registers:
+ * more than 16 chunks (ceil(n_routed / max_degree) > 16) is GL355_E_UNSUPPORTED, as it is in gl355_prove. */
 int32_t gl355_zs_partial_products(gl355_ctx* ctx, const uint64_t* wires, const uint64_t* sigmas,
                                   const uint64_t* k_is, uint32_t log_n, uint32_t n_routed,
                                   uint32_t max_degree, uint64_t beta, uint64_t gamma,

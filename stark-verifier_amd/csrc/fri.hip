@@ -1,13 +1,13 @@
-// DEEP quotient, openings, FRI fold / layer commit, permutation-argument Z and the element-wise field
-// entry points for gfx950 (a1, a9, a11, a12 of SURVEY.md 8).
+// DEEP quotient, openings, FRI fold / layer commit and the element-wise field entry points for gfx950
+// (a1, a11, a12 of SURVEY.md 8), on interleaved F_p^2 data and pointer tables: the staged surface of the
+// C ABI.  The prover's own copies of these stages, with a unit dimension, are in prover_batch.hip.
 //
 // Replaces PolynomialBatch::prove_openings (ReducingFactor::reduce_polys_base,
 // PolynomialCoeffs::divide_by_linear, shift_poly), OpeningSet::new's polynomial evaluations,
-// fri_committed_trees' reduce_with_powers fold and wires_permutation_partial_products_and_zs,
+// and fri_committed_trees' reduce_with_powers fold,
 // all reached from the reference through CircuitData::prove (src/plonky2_semaphore/access_set.rs:94,
 // recursion.rs:168, wrapper.rs:55).  Formulas pinned by the reference's verifier:
-// chip/fri_chip.rs:112-149 (batch combine), :168-226 (arity-2 fold), types/fri.rs:50-73 (batches),
-// chip/plonk/vanishing_poly.rs:54-108,183-218 (Z / partial products).
+// chip/fri_chip.rs:112-149 (batch combine), :168-226 (arity-2 fold), types/fri.rs:50-73 (batches).
 //
 // These are streaming kernels: every polynomial coefficient is read exactly once, lane k handles
 // coefficient k so each wave reads 512 contiguous bytes per column.
@@ -250,6 +250,12 @@ __global__ void ext_join_kernel(const uint64_t* c0, const uint64_t* c1, uint64_t
     if (k >= n) return;
     *reinterpret_cast<ulonglong2*>(ext + 2 * k) = make_ulonglong2(c0[k], c1[k]);
 }
+int32_t ext_split_dev(Ctx* ctx, const uint64_t* ext, uint64_t n, uint64_t* c0, uint64_t* c1) {
+    ProfScope ps(ctx, "ext_split_join", n * 32);
+    hipLaunchKernelGGL(ext_split_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, ext, n, c0, c1);
+    GL355_HIP(ctx, hipGetLastError());
+    return GL355_OK;
+}
 int32_t lde_ext_dev(Ctx* ctx, const uint64_t* coeffs, uint32_t log_n, uint32_t rate_bits, uint64_t shift, uint64_t* out,
                     bool out_bitrev) {
     const uint64_t n = 1ull << log_n, N = n << rate_bits;
@@ -257,93 +263,10 @@ int32_t lde_ext_dev(Ctx* ctx, const uint64_t* coeffs, uint32_t log_n, uint32_t r
     GL355_TRY(sc.get((2 * n + 2 * N) * 8));
     uint64_t* cols = sc.as<uint64_t>();
     uint64_t* res = cols + 2 * n;
-    { ProfScope ps(ctx, "ext_split_join", n * 32);
-    hipLaunchKernelGGL(ext_split_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, coeffs, n, cols, cols + n);
-    GL355_HIP(ctx, hipGetLastError()); }
+    GL355_TRY(ext_split_dev(ctx, coeffs, n, cols, cols + n));
     GL355_TRY(lde_dev(ctx, cols, n, log_n, rate_bits, shift, 2, res, N, out_bitrev));
     ProfScope ps(ctx, "ext_split_join", N * 32);
     hipLaunchKernelGGL(ext_join_kernel, dim3((uint32_t)((N + 255) / 256)), dim3(256), 0, ctx->stream, res, res + N, N, out);
-    GL355_HIP(ctx, hipGetLastError());
-    return GL355_OK;
-}
-
-// ---- a9: permutation argument ---------------------------------------------------------------------
-// kernel 1: per row, the n_chunks chunk quotients prod(num)/prod(den) and their product
-__global__ void zs_rows_kernel(const uint64_t* wires, const uint64_t* sigmas, const uint64_t* k_is, uint32_t log_n,
-                               uint32_t n_routed, uint32_t max_degree, uint64_t beta, uint64_t gamma, uint64_t g,
-                               uint64_t* chunk_q /* [n_chunks][n] */, uint64_t* row_prod /* [n] */) {
-    const uint64_t n = 1ull << log_n;
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t x = gl_pow(g, i);
-    const uint64_t bx = gl_mul(beta, x);
-    const uint32_t n_chunks = (n_routed + max_degree - 1) / max_degree;
-    uint64_t rp = 1;
-    for (uint32_t ch = 0; ch < n_chunks; ch++) {
-        uint64_t num = 1, den = 1;
-        for (uint32_t j = ch * max_degree; j < (ch + 1) * max_degree && j < n_routed; j++) {
-            const uint64_t w = wires[(uint64_t)j * n + i];
-            num = gl_mul(num, gl_add(gl_add(w, gl_mul(bx, k_is[j])), gamma));
-            den = gl_mul(den, gl_add(gl_add(w, gl_mul(beta, sigmas[(uint64_t)j * n + i])), gamma));
-        }
-        const uint64_t q = gl_mul(num, gl_inv(den));
-        chunk_q[(uint64_t)ch * n + i] = q;
-        rp = gl_mul(rp, q);
-    }
-    row_prod[i] = rp;
-}
-// kernel 2 (one workgroup): z[i] = prod_{j<i} row_prod[j], tile-by-tile log-step product scan
-__global__ void __launch_bounds__(1024) zs_scan_kernel(const uint64_t* row_prod, uint64_t n, uint64_t* z) {
-    __shared__ uint64_t sh[1024];
-    const int tid = threadIdx.x;
-    uint64_t running = 1;
-    for (uint64_t base = 0; base < n; base += 1024) {
-        const uint64_t i = base + tid;
-        uint64_t v = i < n ? row_prod[i] : 1;
-        sh[tid] = v;
-        __syncthreads();
-        for (int s = 1; s < 1024; s <<= 1) {
-            uint64_t o = tid >= s ? sh[tid - s] : 1;
-            __syncthreads();
-            v = gl_mul(v, o);
-            sh[tid] = v;
-            __syncthreads();
-        }
-        // v = inclusive product of the tile up to tid; exclusive = product up to tid-1
-        const uint64_t excl = tid ? sh[tid - 1] : 1;
-        if (i < n) z[i] = gl_canon(gl_mul(running, excl));
-        const uint64_t tile_total = sh[1023];
-        __syncthreads();
-        running = gl_mul(running, tile_total);
-    }
-}
-// kernel 3: partial products: acc = z[i]; acc *= q[ch][i]; pp[ch][i] = acc  (ch < n_chunks-1)
-__global__ void zs_partials_kernel(const uint64_t* z, const uint64_t* chunk_q, uint64_t n, uint32_t n_chunks, uint64_t* pp) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint64_t acc = z[i];
-    for (uint32_t ch = 0; ch + 1 < n_chunks; ch++) {
-        acc = gl_mul(acc, chunk_q[(uint64_t)ch * n + i]);
-        pp[(uint64_t)ch * n + i] = gl_canon(acc);
-    }
-}
-int32_t zs_partial_products_dev(Ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, const uint64_t* k_is,
-                                uint32_t log_n, uint32_t n_routed, uint32_t max_degree, uint64_t beta, uint64_t gamma,
-                                uint64_t* z_out, uint64_t* pp_out) {
-    const uint64_t n = 1ull << log_n;
-    const uint32_t n_chunks = (n_routed + max_degree - 1) / max_degree;
-    Scratch sc(ctx);
-    GL355_TRY(sc.get(((uint64_t)n_chunks + 1) * n * 8));
-    uint64_t* d_q = sc.as<uint64_t>();
-    uint64_t* d_rp = d_q + (uint64_t)n_chunks * n;
-    const uint32_t blocks = (uint32_t)((n + 255) / 256);
-    ProfScope ps(ctx, "zs_partial_products", (uint64_t)n_routed * n * 16 + (uint64_t)n_chunks * n * 8);
-    hipLaunchKernelGGL(zs_rows_kernel, dim3(blocks), dim3(256), 0, ctx->stream, wires, sigmas, k_is, log_n, n_routed,
-                       max_degree, gl_canon(beta), gl_canon(gamma), gl_root_of_unity(log_n), d_q, d_rp);
-    GL355_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(zs_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_rp, n, z_out);
-    GL355_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(zs_partials_kernel, dim3(blocks), dim3(256), 0, ctx->stream, z_out, d_q, n, n_chunks, pp_out);
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }

@@ -212,9 +212,6 @@ int32_t two_to_one_dev(Ctx* ctx, const uint64_t* l, const uint64_t* r, uint64_t 
 int32_t open_batch_dev(Ctx* ctx, const uint64_t* lde, uint64_t stride, uint32_t leaf_len, const uint64_t* digests,
                        uint32_t log_n, uint32_t cap_height, const uint64_t* idx_dev, uint32_t n_idx, uint64_t* leaves_out,
                        uint64_t* sib_out);
-int32_t open_batch_ex_dev(Ctx* ctx, const uint64_t* leaves, uint64_t stride, uint32_t leaf_len, const uint64_t* digests,
-                          uint32_t log_n, uint32_t cap_height, const uint64_t* idx_dev, uint32_t idx_shift, uint32_t n_idx,
-                          uint64_t* leaves_out, uint64_t leaf_out_stride, uint64_t* sib_out, uint64_t sib_out_stride);
 // second hash back-end (merkle_bn254.hip, host_bn254.cpp)
 void host_bn254_permute(uint64_t state[12]);
 // Merkle tree / PoW with the hasher chosen at run time
@@ -233,6 +230,10 @@ int32_t oracle_open_batch_on(Ctx* ctx, const gl355_oracle* o, const uint64_t* in
                              uint64_t* siblings);
 int32_t pow_grind_dev(Ctx* ctx, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start,
                       uint64_t* witness_host);
+// the Poseidon grinder for B <= GL355_MAX_UNITS sponge states at once (pow_grind_dev is its B = 1 call): the smallest passing
+// candidate >= start of every unit; `landing` is a host area of B words for the device's answers (pinned: no hidden wait)
+int32_t pow_grind_units_dev(Ctx* ctx, uint32_t B, const uint64_t* states /* [B][12] */, const uint32_t* pos /* [B] */, uint32_t bits,
+                            uint64_t start, uint64_t* landing, uint64_t* const* witness_host /* [B] */);
 
 // ---- fri.hip -------------------------------------------------------------------------------
 int32_t deep_batch_dev(Ctx* ctx, const uint64_t* const* poly_ptrs_host, uint32_t n_polys, uint32_t log_n,
@@ -243,6 +244,7 @@ int32_t fri_fold_dev(Ctx* ctx, const uint64_t* coeffs, uint64_t n, const uint64_
 int32_t fri_layer_leaves_dev(Ctx* ctx, const uint64_t* values, uint64_t n, uint64_t* leaves);
 int32_t lde_ext_dev(Ctx* ctx, const uint64_t* coeffs, uint32_t log_n, uint32_t rate_bits, uint64_t shift, uint64_t* out,
                     bool out_bitrev);
+int32_t ext_split_dev(Ctx* ctx, const uint64_t* ext, uint64_t n, uint64_t* c0, uint64_t* c1);
 int32_t field_batch_dev(Ctx* ctx, int32_t op, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n);
 int32_t zs_partial_products_dev(Ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, const uint64_t* k_is,
                                 uint32_t log_n, uint32_t n_routed, uint32_t max_degree, uint64_t beta, uint64_t gamma,
@@ -281,6 +283,60 @@ uint64_t circuit_rows_words(const gl355_circuit_handle* ch);
 int32_t circuit_replay_units(const gl355_circuit_handle* ch, uint32_t threads, uint32_t n_units, const uint64_t* inputs, uint64_t* rows, uint64_t* pis_out,
                              uint64_t* failed_unit, uint64_t* failed_op);
 int32_t resolve_blinding_key_words(Ctx* ctx, const uint8_t* key, uint32_t out[8]);
+
+// The flat proof (layout in include/gl355.h) as numbers, computed once from the prover data: gl355_proof_words, the prover's
+// staging and device open buffers and its assembly loop all read this.
+// FRI layer l's Merkle path starts at off[l] words inside a query's layer siblings; returns their total
+static inline uint64_t fri_sibling_offsets(uint32_t lde_bits, uint32_t cap_height, uint32_t n_layers, uint64_t off[32]) {
+    uint64_t total = 0;
+    for (uint32_t l = 0; l < n_layers; l++) {
+        if (l < 32) off[l] = total;
+        total += (uint64_t)(lde_bits - 1 - l - cap_height) * 4;
+    }
+    return total;
+}
+struct ProofLayout {
+    uint32_t leaf_len[4];              // constants_sigmas | wires | Z and partial products | quotient chunks (salt included)
+    uint32_t depth0;                   // digests of a path in one of those four trees
+    uint64_t sib_off[32], sib_total;   // fri_sibling_offsets
+    uint64_t n_open;                   // polynomials opened at zeta (the num_challenges Z polynomials also at g * zeta)
+    uint64_t query_words;              // index | 4 x (leaf, path) | n_fri_layers x (pair, path)
+    uint64_t words;                    // the whole proof, header included
+    explicit ProofLayout(const gl355_prover_data& pd) {
+        const gl355_circuit& c = *pd.circuit;
+        const uint32_t nch = c.num_challenges, lde_bits = c.degree_bits + c.rate_bits, L = pd.n_fri_layers;
+        const uint64_t n_cap = 1ull << pd.cap_height;
+        const uint32_t widths[4] = {c.num_selectors + c.num_constants + c.num_routed_wires, c.num_wires, nch * (1 + c.num_partial_products), nch * c.max_degree};
+        depth0 = lde_bits - pd.cap_height;
+        sib_total = fri_sibling_offsets(lde_bits, pd.cap_height, L, sib_off);
+        n_open = 0;
+        query_words = 1 + (uint64_t)L * 4 + sib_total;
+        for (int o = 0; o < 4; o++) {
+            n_open += widths[o];
+            leaf_len[o] = widths[o] + ((pd.zero_knowledge && o > 0) ? GL355_SALT_SIZE : 0);
+            query_words += leaf_len[o] + (uint64_t)depth0 * 4;
+        }
+        words = 8 + 3 * n_cap * 4                              // header; wires / zs / quotient caps
+                + 2 * (n_open + nch)                           // openings (ext)
+                + (uint64_t)L * n_cap * 4                      // commit-phase caps
+                + 2 * ((1ull << c.degree_bits) >> L) + 1       // final polynomial (ext), PoW witness
+                + query_words * pd.num_queries;
+    }
+};
+
+// ---- the FRI tail of a proof (prover_batch.hip): commit phase, final polynomial, proof of work, query indices, layer openings ----
+struct FriShape { uint32_t log_n, rate_bits, cap_height, n_layers, pow_bits, n_queries; int32_t hasher; };
+struct FriUnitOut { uint64_t* caps /* [n_layers][2^cap_height][4] */; uint64_t* final_poly /* [n >> n_layers] ext */; uint64_t* pow_witness; };
+// words of host staging fri_tail_units needs
+static inline uint64_t fri_tail_stage_words(const FriShape& s, uint32_t B) {
+    return (uint64_t)B * std::max<uint64_t>({4ull << s.cap_height, 2 * ((1ull << s.log_n) >> s.n_layers), 1});
+}
+// B units, each a polynomial of n = 2^log_n F_p^2 coefficients held as two base columns: cols [B][2][n] (consumed), cols2 [B][n] and
+// vals [B][2][n << rate_bits] are work space.  ch[u] is advanced as the verifier replays it; caps, final polynomial and PoW witness go
+// to out[u], the query indices to q_idx [B][n_queries] (host, must outlive the stream's work) and d_idx (device); the layer openings
+// stay on the device: d_evals [B][n_queries][n_layers][4], d_sibs [B][n_queries][sum of fri_sibling_offsets].  `stage`: pinned host.
+int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, uint64_t* cols2, uint64_t* vals, uint64_t* stage,
+                       gl355_challenger* ch, const FriUnitOut* out, uint64_t* q_idx, uint64_t* d_idx, uint64_t* d_evals, uint64_t* d_sibs);
 int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const uint64_t* cs_lde, const uint64_t* wires_lde, uint64_t wires_us,
                            const uint64_t* zs_lde, uint64_t zs_us, uint64_t lde_stride, const uint64_t* k_is_dev, const uint64_t* betas /* [B][4] */,
                            const uint64_t* gammas, const uint64_t* alphas, const uint64_t* pi_hashes /* [B][4] */, uint64_t* out_values /* [B][nch][nq] */);

@@ -270,39 +270,43 @@ __global__ void __launch_bounds__(256) two_to_one_kernel(const uint64_t* l, cons
     for (int k = 0; k < 4; k++) out[4 * i + k] = gl_canon(s[k]);
 }
 
-// proof of work: candidates start + g; the smallest passing candidate of the launch wins (atomicMin)
-__global__ void __launch_bounds__(256) pow_grind_kernel(const uint64_t* state, uint32_t pos, uint32_t bits,
-                                                       uint64_t start, unsigned long long* best) {
-    const uint64_t w = start + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (w > __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;      // cannot be the smallest witness any more
+// proof of work of every unit that still lacks a witness: candidates start + g, the smallest passing one of the launch wins
+struct PowArgs { uint64_t state[GL355_MAX_UNITS * 12]; uint32_t pos[GL355_MAX_UNITS]; uint32_t todo[GL355_MAX_UNITS]; uint32_t bits; uint64_t start; unsigned long long* best; };
+__global__ void __launch_bounds__(256) pow_grind_units_kernel(PowArgs a) {
+    const uint32_t u = blockIdx.y;
+    if (!a.todo[u]) return;
+    const uint64_t w = a.start + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    // the smallest witness wins, so a candidate above the best one found so far cannot matter: workgroups are dispatched in
+    // roughly increasing order, and once a witness is known the rest of the launch exits here (expected work ~2^bits instead of the
+    // 2^(bits+1) candidates of the launch); candidates below the current best are never skipped, so the result is still the minimum
+    if (w > __hip_atomic_load(a.best + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
     uint64_t s[12];
 #pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = state[k];
+    for (int k = 0; k < 12; k++) s[k] = a.state[u * 12 + k];
 #pragma unroll
-    for (int k = 0; k < 12; k++) if ((uint32_t)k == pos) s[k] = w;
+    for (int k = 0; k < 12; k++) if ((uint32_t)k == a.pos[u]) s[k] = w;
     psd_permute(s);
     const uint64_t resp = gl_canon(s[7]);
-    if (bits == 0 || (resp >> (64 - bits)) == 0) atomicMin(best, (unsigned long long)w);
+    if (a.bits == 0 || (resp >> (64 - a.bits)) == 0) atomicMin(a.best + u, (unsigned long long)w);
 }
 
 // query openings: block q copies row idx[q] of a column-major matrix and its Merkle path (siblings
 // leaf -> cap, MerkleTree::prove's index walk) into dense output buffers -- one launch + one D2H per
 // oracle for all FRI queries instead of (1 + depth) tiny copies per query.
 __global__ void open_batch_kernel(const uint64_t* lde, uint64_t stride, uint32_t leaf_len, const uint64_t* digests,
-                                  uint32_t log_n, uint32_t cap_height, const uint64_t* idx, uint32_t idx_shift,
-                                  uint64_t* leaves_out, uint64_t leaf_out_stride, uint64_t* sib_out, uint64_t sib_out_stride) {
+                                  uint32_t log_n, uint32_t cap_height, const uint64_t* idx, uint64_t* leaves_out, uint64_t* sib_out) {
     // stride == 0: leaves are row-major [n][leaf_len]; otherwise column-major with that column stride
-    const uint64_t index = idx[blockIdx.x] >> idx_shift;
+    const uint64_t index = idx[blockIdx.x];
     const uint32_t layers = log_n - cap_height;
     for (uint32_t c = threadIdx.x; c < leaf_len; c += blockDim.x)
-        leaves_out[(uint64_t)blockIdx.x * leaf_out_stride + c] = stride ? lde[(uint64_t)c * stride + index] : lde[index * leaf_len + c];
+        leaves_out[(uint64_t)blockIdx.x * leaf_len + c] = stride ? lde[(uint64_t)c * stride + index] : lde[index * leaf_len + c];
     const uint64_t sub_leaves = 1ull << layers;
     const uint64_t* tree = digests + (index >> layers) * 2 * (sub_leaves - 1) * 4;
     const uint64_t k0 = index & (sub_leaves - 1);
     for (uint32_t e = threadIdx.x; e < layers * 4; e += blockDim.x) {
         const uint32_t layer = e >> 2;
         const uint64_t k = (k0 >> layer) ^ 1;  // sibling of the node on the path at this layer
-        sib_out[(uint64_t)blockIdx.x * sib_out_stride + layer * 4 + (e & 3)] = tree[digest_slot(layer, k) * 4 + (e & 3)];
+        sib_out[(uint64_t)blockIdx.x * layers * 4 + e] = tree[digest_slot(layer, k) * 4 + (e & 3)];
     }
 }
 
@@ -312,18 +316,7 @@ int32_t open_batch_dev(Ctx* ctx, const uint64_t* lde, uint64_t stride, uint32_t 
     if (n_idx == 0) return GL355_OK;
     ProfScope ps(ctx, "open_batch", (uint64_t)n_idx * (leaf_len * 16 + (log_n - cap_height) * 64));
     hipLaunchKernelGGL(open_batch_kernel, dim3(n_idx), dim3(64), 0, ctx->stream, lde, stride, leaf_len, digests, log_n,
-                       cap_height, idx_dev, 0u, leaves_out, (uint64_t)leaf_len, sib_out, (uint64_t)(log_n - cap_height) * 4);
-    GL355_HIP(ctx, hipGetLastError());
-    return GL355_OK;
-}
-// general form: index = idx[q] >> idx_shift, explicit output strides (FRI layer trees share one output row per query)
-int32_t open_batch_ex_dev(Ctx* ctx, const uint64_t* leaves, uint64_t stride, uint32_t leaf_len, const uint64_t* digests,
-                          uint32_t log_n, uint32_t cap_height, const uint64_t* idx_dev, uint32_t idx_shift, uint32_t n_idx,
-                          uint64_t* leaves_out, uint64_t leaf_out_stride, uint64_t* sib_out, uint64_t sib_out_stride) {
-    if (n_idx == 0) return GL355_OK;
-    ProfScope ps(ctx, "open_batch", (uint64_t)n_idx * (leaf_len * 16 + (log_n - cap_height) * 64));
-    hipLaunchKernelGGL(open_batch_kernel, dim3(n_idx), dim3(64), 0, ctx->stream, leaves, stride, leaf_len, digests, log_n,
-                       cap_height, idx_dev, idx_shift, leaves_out, leaf_out_stride, sib_out, sib_out_stride);
+                       cap_height, idx_dev, leaves_out, sib_out);
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }
@@ -428,36 +421,45 @@ int32_t merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_t* dig
     return GL355_OK;
 }
 
-int32_t pow_grind_dev(Ctx* ctx, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start,
-                      uint64_t* witness_host) {
-    if (pos >= 8) return ctx->fail(GL355_E_INVALID_ARG, "pow: witness position must be in the rate part");
+int32_t pow_grind_units_dev(Ctx* ctx, uint32_t B, const uint64_t* states, const uint32_t* pos, uint32_t bits, uint64_t start, uint64_t* landing,
+                            uint64_t* const* witness_host) {
     if (bits > 40) return ctx->fail(GL355_E_UNSUPPORTED, "pow: more than 40 bits of grinding refused");
-    Scratch sc(ctx);
-    GL355_TRY(sc.get(13 * sizeof(uint64_t)));
-    uint64_t* d_state = sc.as<uint64_t>();
-    unsigned long long* d_best = reinterpret_cast<unsigned long long*>(d_state + 12);
-    uint64_t host[13];
-    for (int i = 0; i < 12; i++) host[i] = gl_canon(state[i]);
-    host[12] = ~0ull;
-    GL355_HIP(ctx, hipMemcpyAsync(d_state, host, sizeof host, hipMemcpyHostToDevice, ctx->stream));
-    // batches of 2^20 candidates until one launch contains a solution; within a launch the
-    // minimum wins, and earlier launches found nothing, so the result is the global minimum.
-    // a launch of 2^(bits+1) candidates contains a solution with probability 1 - e^-2; grow when unlucky
+    PowArgs pa;
+    memset(&pa, 0, sizeof pa);
+    for (uint32_t u = 0; u < B; u++) {
+        for (int k = 0; k < 12; k++) pa.state[u * 12 + k] = gl_canon(states[u * 12 + k]);
+        pa.pos[u] = pos[u]; pa.todo[u] = 1;
+    }
+    Scratch pb(ctx);
+    GL355_TRY(pb.get(GL355_MAX_UNITS * 8));
+    pa.best = reinterpret_cast<unsigned long long*>(pb.p);
+    pa.bits = bits;
+    GL355_HIP(ctx, hipMemsetAsync(pb.p, 0xFF, GL355_MAX_UNITS * 8, ctx->stream));
+    // within a launch the minimum wins, and earlier launches found nothing for that unit, so the result is the global minimum.
+    // a launch of 2^(bits+1) candidates holds a solution with probability 1 - e^-2; units without one go again, with a larger window
     uint64_t per_launch = 1ull << std::min<uint32_t>(std::max<uint32_t>(bits + 1, 12), 22);
     uint64_t base = start;
-    for (;;) {
+    for (uint32_t left = B; left;) {
         ProfScope ps(ctx, "pow_grind", 0);   // pure compute: one permutation per candidate, no HBM traffic
-        hipLaunchKernelGGL(pow_grind_kernel, dim3((uint32_t)(per_launch / 256)), dim3(256), 0, ctx->stream, d_state, pos,
-                           bits, base, d_best);
+        pa.start = base;
+        hipLaunchKernelGGL(pow_grind_units_kernel, dim3((uint32_t)(per_launch / 256), B), dim3(256), 0, ctx->stream, pa);
         GL355_HIP(ctx, hipGetLastError());
-        unsigned long long best;
-        GL355_HIP(ctx, ctx->d2h(&best, d_best, sizeof best));
+        GL355_HIP(ctx, ctx->d2h(landing, pb.p, (uint64_t)B * 8));
         GL355_HIP(ctx, ctx->wait());
-        if (best != ~0ull) { *witness_host = best; return GL355_OK; }
+        for (uint32_t u = 0; u < B; u++)
+            if (pa.todo[u] && landing[u] != ~0ull) { *witness_host[u] = landing[u]; pa.todo[u] = 0; left--; }
         base += per_launch;
         if (per_launch < (1ull << 22)) per_launch <<= 1;
         if (base - start > (1ull << 44)) return ctx->fail(GL355_E_UNSUPPORTED, "pow: no witness found in 2^44 candidates");
     }
+    return GL355_OK;
+}
+
+int32_t pow_grind_dev(Ctx* ctx, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start,
+                      uint64_t* witness_host) {
+    if (pos >= 8) return ctx->fail(GL355_E_INVALID_ARG, "pow: witness position must be in the rate part");
+    uint64_t landing;
+    return pow_grind_units_dev(ctx, 1, state, &pos, bits, start, &landing, &witness_host);
 }
 
 }  // namespace gl355

@@ -1,5 +1,6 @@
 // FRI prover loop in one call (a12 + a13 + a14 of SURVEY.md 8): commit phase, proof of work and the
-// layer openings of every query, with the polynomial resident on the device throughout.
+// layer openings of every query, with the polynomial resident on the device throughout: one unit
+// through fri_tail_units (prover_batch.hip), the routine the lock-step prover runs.
 //
 // Replaces plonky2::fri::prover::{fri_proof, fri_committed_trees, fri_proof_of_work,
 // fri_prover_query_rounds} (reached through CircuitData::prove, src/plonky2_semaphore/access_set.rs:94).
@@ -31,87 +32,29 @@ extern "C" int32_t gl355_fri_prove(gl355_ctx* h, const uint64_t* final_coeffs, u
     for (uint32_t l = 0; l < n_layers; l++)
         if (arity_bits[l] != 1) return ctx->fail(GL355_E_UNSUPPORTED, "fri_prove: arity-2 folding only (fri_chip.rs:211)");
     if (lde_bits - n_layers < cap_height + 0u) return ctx->fail(GL355_E_INVALID_ARG, "fri_prove: too many layers for the cap height");
-    const uint64_t n = 1ull << log_n, N = 1ull << lde_bits, n_cap = 1ull << cap_height;
+    const uint64_t n = 1ull << log_n, N = 1ull << lde_bits;
 
-    // device buffers: coefficients (N ext, zero padded), values (N ext), per-layer leaves + digests
+    // the interleaved coefficients as the two base columns the shared FRI tail folds, then that tail for one unit
+    const FriShape shape{log_n, rate_bits, cap_height, n_layers, pow_bits, num_queries, ch->hasher};
+    uint64_t sib_off[32];
+    const uint64_t sib_total = fri_sibling_offsets(lde_bits, cap_height, n_layers, sib_off);
     Staged sc(ctx);
     GL355_TRY(sc.open(final_coeffs, n * 16, 1));
-    Scratch work(ctx), trees(ctx);
-    GL355_TRY(work.get((2 * N + 2 * N + 2 * N) * 8 + 64));
-    uint64_t* coeffs = work.as<uint64_t>();       // 2N u64
-    uint64_t* values = coeffs + 2 * N;           // 2N u64
-    uint64_t* coeffs2 = values + 2 * N;          // fold target
-    // tree storage: layer l has N/2^(l+1) leaves of 4 u64 and 2*(leaves - n_cap) digests of 4 u64
-    std::vector<uint64_t> leaf_off(n_layers), dig_off(n_layers);
-    uint64_t total = 0;
-    for (uint32_t l = 0; l < n_layers; l++) {
-        const uint64_t nl = N >> (l + 1);
-        if (nl < n_cap) return ctx->fail(GL355_E_INVALID_ARG, "fri_prove: layer smaller than the cap");
-        leaf_off[l] = total; total += nl * 4;
-        dig_off[l] = total; total += 2 * (nl - n_cap) * 4;
-    }
-    GL355_TRY(trees.get((total + n_cap * 4 + 16) * 8));
-    uint64_t* tree_buf = trees.as<uint64_t>();
-    uint64_t* d_cap = tree_buf + total;
-
-    GL355_HIP(ctx, hipMemcpyAsync(coeffs, sc.as<uint64_t>(), n * 16, hipMemcpyDeviceToDevice, ctx->stream));
-    GL355_HIP(ctx, hipMemsetAsync(coeffs + 2 * n, 0, (N - n) * 16, ctx->stream));
-    GL355_TRY(lde_ext_dev(ctx, coeffs, log_n, rate_bits, GL355_COSET_SHIFT, values, false));
-
-    uint64_t shift = GL355_COSET_SHIFT;
-    uint64_t len = N;  // current number of ext coefficients / values
-    std::vector<uint64_t> cap_host(n_cap * 4);
-    for (uint32_t l = 0; l < n_layers; l++) {
-        uint64_t* lv = tree_buf + leaf_off[l];
-        uint64_t* dg = tree_buf + dig_off[l];
-        GL355_TRY(fri_layer_leaves_dev(ctx, values, len, lv));
-        GL355_TRY(merkle_build_any(ctx, ch->hasher, lv, len / 2, 4, false, 0, cap_height, dg, d_cap));
-        GL355_HIP(ctx, ctx->d2h(cap_host.data(), d_cap, n_cap * 32));
-        GL355_HIP(ctx, ctx->wait());
-        memcpy(caps_out + (uint64_t)l * n_cap * 4, cap_host.data(), n_cap * 32);
-        gl355_challenger_observe(ch, cap_host.data(), n_cap * 4);
-        uint64_t beta[2];
-        gl355_challenger_squeeze(ch, beta, 2);
-        GL355_TRY(fri_fold_dev(ctx, coeffs, len, beta, coeffs2));
-        std::swap(coeffs, coeffs2);
-        len >>= 1;
-        shift = gl_mul(shift, shift);
-        if (l + 1 < n_layers) {
-            const uint32_t lg = log2_u64(len);
-            GL355_TRY(lde_ext_dev(ctx, coeffs, lg, 0, gl_canon(shift), values, false));
-        }
-    }
-    // final polynomial: the upper (1 - 2^-rate_bits) of the coefficients is zero by construction
-    const uint64_t final_len = len >> rate_bits;
-    GL355_HIP(ctx, ctx->d2h(final_poly_out, coeffs, final_len * 16));
-    GL355_HIP(ctx, ctx->wait());
-    gl355_challenger_observe(ch, final_poly_out, final_len * 2);
-    // proof of work
-    uint64_t st[12];
-    uint32_t pos;
-    if (gl355_challenger_pow_state(ch, st, &pos) != GL355_OK) return ctx->fail(GL355_E_INVALID_ARG, "fri_prove: challenger state");
-    GL355_TRY(pow_grind_any(ctx, ch->hasher, st, pos, pow_bits, 0, pow_witness));
-    gl355_challenger_observe(ch, pow_witness, 1);
-    uint64_t resp;
-    gl355_challenger_squeeze(ch, &resp, 1);
-    if (pow_bits && (resp >> (64 - pow_bits)) != 0) return ctx->fail(GL355_E_HIP, "fri_prove: proof-of-work response check failed");
-    // queries: x_index = challenge mod N; layer l opens index x_index >> (l + 1)
-    gl355_challenger_squeeze(ch, query_indices, num_queries);
-    for (uint32_t q = 0; q < num_queries; q++) query_indices[q] &= (N - 1);
-    uint64_t sib_total = 0;
-    std::vector<uint64_t> sib_off(n_layers);
-    for (uint32_t l = 0; l < n_layers; l++) { sib_off[l] = sib_total; sib_total += (uint64_t)(lde_bits - 1 - l - cap_height) * 4; }
-    Scratch outb(ctx);
+    Scratch work(ctx), outb(ctx);
+    GL355_TRY(work.get((2 * n + n + 8 + 2 * N) * 8));
     GL355_TRY(outb.get(((uint64_t)num_queries * (1 + n_layers * 4 + sib_total) + 16) * 8));
+    uint64_t* cols = work.as<uint64_t>();
+    uint64_t* cols2 = cols + 2 * n;
+    uint64_t* vals = cols2 + n + 8;
     uint64_t* d_idx = outb.as<uint64_t>();
     uint64_t* d_ev = d_idx + num_queries;
     uint64_t* d_sib = d_ev + (uint64_t)num_queries * n_layers * 4;
-    GL355_HIP(ctx, hipMemcpyAsync(d_idx, query_indices, (uint64_t)num_queries * 8, hipMemcpyHostToDevice, ctx->stream));
-    for (uint32_t l = 0; l < n_layers; l++) {
-        GL355_TRY(open_batch_ex_dev(ctx, tree_buf + leaf_off[l], 0, 4, tree_buf + dig_off[l], lde_bits - 1 - l, cap_height, d_idx,
-                                    l + 1, num_queries, d_ev + (uint64_t)l * 4, (uint64_t)n_layers * 4, d_sib + sib_off[l], sib_total));
-    }
-    GL355_HIP(ctx, ctx->d2h(step_evals, d_ev, (uint64_t)num_queries * n_layers * 32));
+    uint64_t* stage = nullptr;
+    GL355_TRY(ctx->pinned(fri_tail_stage_words(shape, 1) * 8, reinterpret_cast<void**>(&stage)));
+    GL355_TRY(ext_split_dev(ctx, sc.as<uint64_t>(), n, cols, cols + n));
+    const FriUnitOut out{caps_out, final_poly_out, pow_witness};
+    GL355_TRY(fri_tail_units(ctx, shape, 1, cols, cols2, vals, stage, ch, &out, query_indices, d_idx, d_ev, d_sib));
+    if (n_layers) GL355_HIP(ctx, ctx->d2h(step_evals, d_ev, (uint64_t)num_queries * n_layers * 32));
     if (sib_total) GL355_HIP(ctx, ctx->d2h(step_siblings, d_sib, (uint64_t)num_queries * sib_total * 8));
     GL355_HIP(ctx, ctx->wait());
     return GL355_OK;
@@ -165,28 +108,7 @@ int32_t resolve_blinding_key_words(Ctx* ctx, const uint8_t* key, uint32_t out[8]
 
 extern "C" uint64_t gl355_proof_words(const gl355_prover_data* pd) {
     if (!pd || !pd->circuit) return 0;
-    const gl355_circuit& c = *pd->circuit;
-    const uint64_t n_cap = 1ull << pd->cap_height;
-    const uint32_t nch = c.num_challenges, qdf = c.max_degree;
-    const uint32_t lde_bits = c.degree_bits + c.rate_bits;
-    const uint32_t widths[4] = {c.num_selectors + c.num_constants + c.num_routed_wires, c.num_wires,
-                                nch * (1 + c.num_partial_products), nch * qdf};
-    uint64_t w = 8;                                            // header
-    w += 3 * n_cap * 4;                                        // wires / zs / quotient caps
-    uint64_t n_open = 0;
-    for (int o = 0; o < 4; o++) n_open += widths[o];
-    w += 2 * (n_open + nch);                                   // openings at zeta, Z at g*zeta (ext)
-    w += (uint64_t)pd->n_fri_layers * n_cap * 4;               // commit-phase caps
-    w += 2 * ((1ull << c.degree_bits) >> pd->n_fri_layers);    // final polynomial (ext)
-    w += 1;                                                    // pow witness
-    uint64_t per_q = 1;
-    for (int o = 0; o < 4; o++) {
-        const uint32_t leaf = widths[o] + ((pd->zero_knowledge && o > 0) ? GL355_SALT_SIZE : 0);
-        per_q += leaf + (uint64_t)(lde_bits - pd->cap_height) * 4;
-    }
-    for (uint32_t l = 0; l < pd->n_fri_layers; l++) per_q += 4 + (uint64_t)(lde_bits - 1 - l - pd->cap_height) * 4;
-    w += per_q * pd->num_queries;
-    return w;
+    return ProofLayout(*pd).words;
 }
 
 // ---- single-proof entries: one unit through the lock-step prover (prover_batch.hip) ---------------------------------------

@@ -399,25 +399,6 @@ __global__ void fri_fold_units_kernel(const uint64_t* cols /* [B][2][len] */, ui
     uint64_t* o0 = out + (uint64_t)u * 2 * half;
     o0[k] = r.c0; o0[half + k] = r.c1;
 }
-// proof of work of every unit that still lacks a witness: candidates start + g, the smallest passing one of the launch wins
-struct PowArgs { uint64_t state[MAXB * 12]; uint32_t pos[MAXB]; uint32_t todo[MAXB]; uint32_t bits; uint64_t start; unsigned long long* best; };
-__global__ void __launch_bounds__(256) pow_grind_units_kernel(PowArgs a) {
-    const uint32_t u = blockIdx.y;
-    if (!a.todo[u]) return;
-    const uint64_t w = a.start + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    // the smallest witness wins, so a candidate above the best one found so far cannot matter: workgroups are dispatched in
-    // roughly increasing order, and once a witness is known the rest of the launch exits here (expected work ~2^bits instead of the
-    // 2^(bits+1) candidates of the launch); candidates below the current best are never skipped, so the result is still the minimum
-    if (w > __hip_atomic_load(a.best + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    uint64_t s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = a.state[u * 12 + k];
-#pragma unroll
-    for (int k = 0; k < 12; k++) if ((uint32_t)k == a.pos[u]) s[k] = w;
-    psd_permute(s);
-    const uint64_t resp = gl_canon(s[7]);
-    if (a.bits == 0 || (resp >> (64 - a.bits)) == 0) atomicMin(a.best + u, (unsigned long long)w);
-}
 
 // ---- a14: query openings ---------------------------------------------------------------------------------------------------------
 // block (q, u): row idx[u][q] of unit u's column-major LDE (+ salt segment) and its Merkle path, dense per-unit outputs
@@ -491,6 +472,434 @@ static int32_t commit_units(Ctx* ctx, int32_t hasher, BOracle& o, bool is_coeffs
     return merkle_build_args_any(ctx, hasher, a, lde_bits - o.cap_height, o.digests, o.cap);
 }
 
+
+// caps [B][n_cap][4] on the device -> dst[u] on the host, each absorbed by its unit's transcript
+static int32_t observe_caps_units(Ctx* ctx, uint32_t B, uint64_t n_cap, const uint64_t* d_caps, uint64_t* stage, gl355_challenger* ch, uint64_t* const* dst) {
+    GL355_HIP(ctx, ctx->d2h(stage, d_caps, (uint64_t)B * n_cap * 32));
+    GL355_HIP(ctx, ctx->wait());
+    for (uint32_t u = 0; u < B; u++) {
+        memcpy(dst[u], stage + (uint64_t)u * n_cap * 4, n_cap * 32);
+        gl355_challenger_observe(&ch[u], dst[u], n_cap * 4);
+    }
+    return GL355_OK;
+}
+// two canonical words of unit u's next extension challenge
+static void squeeze_ext(gl355_challenger* ch, uint64_t* v) {
+    gl355_challenger_squeeze(ch, v, 2);
+    v[0] = gl_canon(v[0]); v[1] = gl_canon(v[1]);
+}
+
+// the permutation argument of n_inst = B * nch instances: unit u's Z_0..Z_{nch-1} and then its partial products go to zbuf + u * z_us
+static int32_t zs_units_dev(Ctx* ctx, uint32_t B, uint32_t nch, const uint64_t* wires, uint64_t wires_us, const uint64_t* sigmas, const uint64_t* k_is,
+                            uint32_t log_n, uint32_t routed, uint32_t max_degree, const UnitVals& betas, const UnitVals& gammas, uint64_t* zbuf, uint64_t z_us) {
+    const uint64_t n = 1ull << log_n;
+    const uint32_t n_inst = B * nch, n_chunks = (routed + max_degree - 1) / max_degree;
+    Scratch zs_tmp(ctx);
+    GL355_TRY(zs_tmp.get((uint64_t)n_inst * (n_chunks + 1) * n * 8));
+    ZsArgs za;
+    memset(&za, 0, sizeof za);
+    za.wires = wires; za.wires_us = wires_us; za.sigmas = sigmas; za.k_is = k_is;
+    za.log_n = log_n; za.n_routed = routed; za.max_degree = max_degree; za.nch = nch; za.n_chunks = n_chunks; za.npp = n_chunks - 1;
+    za.g = gl_root_of_unity(log_n);
+    za.chunk_q = zs_tmp.as<uint64_t>(); za.row_prod = za.chunk_q + (uint64_t)n_inst * n_chunks * n;
+    za.zbuf = zbuf; za.z_us = z_us;
+    for (uint32_t i = 0; i < MAXB * 4; i++) { za.betas.v[i] = gl_canon(betas.v[i]); za.gammas.v[i] = gl_canon(gammas.v[i]); }
+    ProfScope ps(ctx, "zs_partial_products", (uint64_t)n_inst * ((uint64_t)routed * n * 16 + (uint64_t)n_chunks * n * 8));
+    const uint32_t blocks = (uint32_t)((n + 255) / 256);
+    hipLaunchKernelGGL(zs_rows_units_kernel, dim3(blocks, n_inst), dim3(256), 0, ctx->stream, za);
+    LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(zs_scan_units_kernel, dim3(n_inst), dim3(1024), 0, ctx->stream, za);
+    LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(zs_partials_units_kernel, dim3(blocks, n_inst), dim3(256), 0, ctx->stream, za);
+    LAUNCH_CHECK(ctx);
+    return GL355_OK;
+}
+// gl355_zs_partial_products: one unit, one challenge
+int32_t zs_partial_products_dev(Ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, const uint64_t* k_is, uint32_t log_n, uint32_t n_routed,
+                                uint32_t max_degree, uint64_t beta, uint64_t gamma, uint64_t* z_out, uint64_t* pp_out) {
+    const uint64_t n = 1ull << log_n;
+    const uint32_t n_chunks = (n_routed + max_degree - 1) / max_degree;
+    if (n_chunks > ZS_MAX_CHUNKS) return ctx->fail(GL355_E_UNSUPPORTED, "zs_partial_products: at most 16 partial-product chunks");
+    Scratch zb(ctx);       // [Z | pp_0 .. pp_{n_chunks-2}][n], as a unit of the prover lays them out
+    GL355_TRY(zb.get((uint64_t)n_chunks * n * 8));
+    UnitVals betas, gammas;
+    memset(&betas, 0, sizeof betas); memset(&gammas, 0, sizeof gammas);
+    betas.v[0] = beta; gammas.v[0] = gamma;
+    GL355_TRY(zs_units_dev(ctx, 1, 1, wires, 0, sigmas, k_is, log_n, n_routed, max_degree, betas, gammas, zb.as<uint64_t>(), (uint64_t)n_chunks * n));
+    GL355_HIP(ctx, hipMemcpyAsync(z_out, zb.p, n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    if (n_chunks > 1) GL355_HIP(ctx, hipMemcpyAsync(pp_out, zb.as<uint64_t>() + n, (uint64_t)(n_chunks - 1) * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return GL355_OK;
+}
+
+// ---- the FRI tail (fri_committed_trees, final polynomial, fri_proof_of_work, query indices, layer openings): gl355_internal.h ----------
+int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, uint64_t* cols2, uint64_t* vals, uint64_t* stage,
+                       gl355_challenger* ch, const FriUnitOut* out, uint64_t* q_idx, uint64_t* d_idx, uint64_t* d_evals, uint64_t* d_sibs) {
+    const uint32_t L = s.n_layers, lde_bits = s.log_n + s.rate_bits;
+    const uint64_t N = 1ull << lde_bits, n_cap = 1ull << s.cap_height;
+    OpenFriArgs fa;         // the layer trees: leaves [B][nl][4] and digests [B][2(nl - n_cap)][4] of layer l, one after the other
+    memset(&fa, 0, sizeof fa);
+    uint64_t tree_words = 0;
+    for (uint32_t l = 0; l < L; l++) {
+        const uint64_t nl = N >> (l + 1);
+        if (nl < n_cap) return ctx->fail(GL355_E_INVALID_ARG, "fri: layer smaller than the cap");
+        fa.leaf_off[l] = tree_words; tree_words += (uint64_t)B * nl * 4;
+        fa.dig_off[l] = tree_words; tree_words += (uint64_t)B * 2 * (nl - n_cap) * 4;
+    }
+    Scratch trees(ctx);
+    GL355_TRY(trees.get((tree_words + (uint64_t)B * n_cap * 4 + 16) * 8));
+    uint64_t* tree_buf = trees.as<uint64_t>();
+    uint64_t* d_cap = tree_buf + tree_words;
+    uint64_t shift = GL355_COSET_SHIFT, len_c = 1ull << s.log_n;
+    for (uint32_t l = 0; l < L; l++) {
+        const uint64_t len_v = len_c << s.rate_bits, nl = len_v / 2;
+        GL355_TRY(lde_dev(ctx, cols, len_c, log2_u64(len_c), s.rate_bits, gl_canon(shift), 2 * B, vals, len_v, true));
+        uint64_t* lv = tree_buf + fa.leaf_off[l];
+        {
+            ProfScope ps(ctx, "fri_layer_leaves", (uint64_t)B * len_v * 32);
+            hipLaunchKernelGGL(fri_leaves_units_kernel, dim3((uint32_t)((nl + 255) / 256), B), dim3(256), 0, ctx->stream, vals, len_v, lv);
+            LAUNCH_CHECK(ctx);
+        }
+        LeafArgs la;
+        memset(&la, 0, sizeof la);
+        la.leaves = lv; la.n_leaves = (uint64_t)B * nl; la.leaf_len = 4; la.col_major = 0; la.stride = 4;
+        GL355_TRY(merkle_build_args_any(ctx, s.hasher, la, log2_u64(nl) - s.cap_height, tree_buf + fa.dig_off[l], d_cap));
+        uint64_t* cap_dst[MAXB];
+        for (uint32_t u = 0; u < B; u++) cap_dst[u] = out[u].caps + (uint64_t)l * n_cap * 4;
+        GL355_TRY(observe_caps_units(ctx, B, n_cap, d_cap, stage, ch, cap_dst));
+        UnitVals beta;
+        memset(&beta, 0, sizeof beta);
+        for (uint32_t u = 0; u < B; u++) squeeze_ext(&ch[u], &beta.v[u * 4]);
+        {
+            ProfScope ps(ctx, "fri_fold", (uint64_t)B * (len_c * 16 + len_c * 8));
+            hipLaunchKernelGGL(fri_fold_units_kernel, dim3((uint32_t)((len_c / 2 + 255) / 256), B), dim3(256), 0, ctx->stream, cols, len_c, beta, cols2);
+            LAUNCH_CHECK(ctx);
+        }
+        std::swap(cols, cols2);
+        len_c >>= 1;
+        shift = gl_mul(shift, shift);
+    }
+    // final polynomial: len_c = n >> L extension coefficients per unit, two columns each
+    GL355_HIP(ctx, ctx->d2h(stage, cols, (uint64_t)B * 2 * len_c * 8));
+    GL355_HIP(ctx, ctx->wait());
+    uint64_t pow_state[MAXB * 12];
+    uint32_t pow_pos[MAXB];
+    uint64_t* p_pow[MAXB];
+    for (uint32_t u = 0; u < B; u++) {
+        const uint64_t* c0 = stage + (uint64_t)u * 2 * len_c;
+        uint64_t* fp = out[u].final_poly;
+        for (uint64_t k = 0; k < len_c; k++) { fp[2 * k] = c0[k]; fp[2 * k + 1] = c0[len_c + k]; }
+        gl355_challenger_observe(&ch[u], fp, 2 * len_c);
+        if (gl355_challenger_pow_state(&ch[u], &pow_state[u * 12], &pow_pos[u]) != GL355_OK) return ctx->fail(GL355_E_INVALID_ARG, "fri: challenger state");
+        for (int k = 0; k < 12; k++) pow_state[u * 12 + k] = gl_canon(pow_state[u * 12 + k]);
+        p_pow[u] = out[u].pow_witness;
+    }
+    // proof of work: the smallest witness of every unit
+    if (s.hasher == GL355_HASH_POSEIDON) GL355_TRY(pow_grind_units_dev(ctx, B, pow_state, pow_pos, s.pow_bits, 0, stage, p_pow));
+    else for (uint32_t u = 0; u < B; u++) GL355_TRY(pow_grind_any(ctx, s.hasher, &pow_state[u * 12], pow_pos[u], s.pow_bits, 0, p_pow[u]));
+    // queries: x_index = challenge mod N; layer l opens the pair at x_index >> (l + 1) and its path
+    for (uint32_t u = 0; u < B; u++) {
+        gl355_challenger_observe(&ch[u], p_pow[u], 1);
+        uint64_t resp;
+        gl355_challenger_squeeze(&ch[u], &resp, 1);
+        if (s.pow_bits && (resp >> (64 - s.pow_bits)) != 0) return ctx->fail(GL355_E_HIP, "fri: proof-of-work response check failed");
+        uint64_t* qi = q_idx + (uint64_t)u * s.n_queries;
+        gl355_challenger_squeeze(&ch[u], qi, s.n_queries);
+        for (uint32_t q = 0; q < s.n_queries; q++) qi[q] &= (N - 1);
+    }
+    GL355_HIP(ctx, hipMemcpyAsync(d_idx, q_idx, (uint64_t)B * s.n_queries * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (L) {
+        fa.trees = tree_buf;
+        fa.sib_total = fri_sibling_offsets(lde_bits, s.cap_height, L, fa.sib_off);
+        fa.lde_bits = lde_bits; fa.cap_height = s.cap_height; fa.n_idx = s.n_queries; fa.n_layers = L; fa.idx = d_idx;
+        fa.evals = d_evals; fa.sibs = d_sibs;
+        ProfScope ps(ctx, "open_batch", (uint64_t)B * s.n_queries * (L * 64 + fa.sib_total * 16));
+        hipLaunchKernelGGL(open_fri_units_kernel, dim3(s.n_queries, B, L), dim3(64), 0, ctx->stream, fa);
+        LAUNCH_CHECK(ctx);
+    }
+    return GL355_OK;
+}
+
+// ---- one run of the lock-step prover: what its stages share --------------------------------------------------------------------------
+struct ProveRun {
+    Ctx* ctx; const gl355_prover_data* pd; const gl355_circuit& c; const gl355_oracle* cs; const ProveUnit* io;
+    // shape
+    const uint32_t B, nch, qdf, npp, routed, nw, z_width, lde_bits, cap_h, L, nq_idx;
+    const uint64_t n, N, n_cap;
+    const int32_t hasher; const bool zk;
+    const ProofLayout lay;
+    // per unit: transcript, write cursor into its proof, blinding key, public-input hash, query indices
+    std::vector<gl355_challenger> ch;
+    std::vector<uint64_t*> out;
+    std::vector<uint64_t> q_idx;
+    UnitKeys keys;
+    UnitVals pi_hashes;
+    uint64_t* stage = nullptr;      // pinned staging for everything that crosses PCIe (caps, openings, final polynomials, query openings)
+    // wires | Z and partial products | quotient chunks, and the four opened oracles as the kernels see them
+    BOracle o_w, o_z, o_q;
+    OView views[4];
+    PolySet all, zsset;             // every polynomial (opened at zeta); the Z polynomials (also at g * zeta)
+    // challenges, [u * 4 + k]; zetas: [u*4+0..1] = zeta, [u*4+2..3] = g * zeta
+    UnitVals betas, gammas, alphas, zetas, fri_alpha;
+    // device buffers that outlive the stage that fills them
+    Scratch wires_keep;             // the wire VALUES, needed again for the permutation argument
+    Staged s_sig, s_k;
+    Scratch evb, colsA, colsB, fri_vals, ob;
+    uint64_t *d_idx = nullptr, *d_open = nullptr;      // ob: query indices [B][nq_idx] | the openings below
+    uint64_t off_leaf[4], off_sib[4], off_ev = 0, off_fsib = 0, open_words = 0;   // word offsets in d_open (and in `stage` after the copy)
+
+    ProveRun(Ctx* cx, const gl355_prover_data* p, uint32_t b, const ProveUnit* units)
+        : ctx(cx), pd(p), c(*p->circuit), cs(p->constants_sigmas), io(units), B(b), nch(c.num_challenges), qdf(c.max_degree), npp(c.num_partial_products),
+          routed(c.num_routed_wires), nw(c.num_wires), z_width(nch * (1 + npp)), lde_bits(c.degree_bits + c.rate_bits), cap_h(p->cap_height),
+          L(p->n_fri_layers), nq_idx(p->num_queries), n(1ull << c.degree_bits), N(1ull << lde_bits), n_cap(1ull << cap_h), hasher(p->hasher),
+          zk(p->zero_knowledge != 0), lay(*p), ch(b), out(b), q_idx((uint64_t)b * p->num_queries), wires_keep(cx), s_sig(cx), s_k(cx), evb(cx), colsA(cx),
+          colsB(cx), fri_vals(cx), ob(cx) {
+        memset(&pi_hashes, 0, sizeof pi_hashes);
+        for (UnitVals* v : {&betas, &gammas, &alphas, &zetas, &fri_alpha}) memset(v, 0, sizeof *v);
+    }
+    // a committed batch's caps: into every unit's proof and transcript
+    int32_t observe_caps(const BOracle& o) {
+        GL355_TRY(observe_caps_units(ctx, B, n_cap, o.cap, stage, ch.data(), out.data()));
+        for (uint32_t u = 0; u < B; u++) out[u] += n_cap * 4;
+        return GL355_OK;
+    }
+    int32_t commit(BOracle& o, bool is_coeffs, bool canonical, uint32_t salt_stream) { return commit_units(ctx, hasher, o, is_coeffs, canonical, &keys, salt_stream); }
+};
+
+// proof headers, one transcript per unit (host) started with the circuit digest and the public-input hash, the staging buffer
+static int32_t begin_units(ProveRun& r) {
+    for (uint32_t u = 0; u < r.B; u++) {
+        uint64_t* hdr = r.io[u].proof;
+        hdr[0] = r.lay.words; hdr[1] = r.c.degree_bits; hdr[2] = r.L; hdr[3] = r.nq_idx; hdr[4] = r.io[u].n_public_inputs; hdr[5] = r.zk; hdr[6] = r.cap_h; hdr[7] = r.nch;
+        r.out[u] = hdr + 8;
+        gl355_challenger_init_h(&r.ch[u], r.hasher);
+        gl355_host_hash_no_pad(r.io[u].public_inputs, r.io[u].n_public_inputs, &r.pi_hashes.v[u * 4]);
+        gl355_challenger_observe(&r.ch[u], r.pd->circuit_digest, 4);
+        gl355_challenger_observe(&r.ch[u], &r.pi_hashes.v[u * 4], 4);
+        memcpy(r.keys.k[u].w, r.io[u].key, 32);
+    }
+    const uint64_t stage_words = (uint64_t)r.B * std::max<uint64_t>({r.n_cap * 4, 2 * (r.lay.n_open + r.nch), 2 * (r.n >> r.L) + 8,
+                                                                     (r.lay.query_words - 1) * r.nq_idx, 16});
+    return r.ctx->pinned(stage_words * 8, reinterpret_cast<void**>(&r.stage));
+}
+
+// 1. witness: the wire values [B][num_wires][n], dense from the caller or scattered from its sparse rows plus the blinding rows
+static int32_t stage_witness(ProveRun& r, const uint64_t* d_wires_dense, const uint32_t* row_idx, const uint64_t* rows_host, uint32_t n_rows,
+                             uint32_t blind_start, uint32_t n_blind, uint32_t z_start, uint32_t n_z_pairs) {
+    Ctx* ctx = r.ctx;
+    const uint32_t B = r.B, nw = r.nw;
+    const uint64_t n = r.n;
+    GL355_TRY(r.o_w.alloc(ctx, B, r.c.degree_bits, r.c.rate_bits, nw, r.zk, r.cap_h));
+    GL355_TRY(r.wires_keep.get((uint64_t)B * nw * n * 8));
+    uint64_t* wires = r.wires_keep.as<uint64_t>();
+    if (d_wires_dense) {
+        GL355_HIP(ctx, hipMemcpyAsync(wires, d_wires_dense, (uint64_t)B * nw * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        return GL355_OK;
+    }
+    GL355_HIP(ctx, hipMemsetAsync(wires, 0, (uint64_t)B * nw * n * 8, ctx->stream));
+    Scratch rbuf(ctx);
+    if (n_rows) {
+        const uint64_t per = (uint64_t)n_rows * nw;
+        const bool rows_on_device = ptr_is_device(rows_host);       // the batch runtime uploads the next batch's rows on its copy stream
+        GL355_TRY(rbuf.get((rows_on_device ? 0 : (uint64_t)B * per * 8) + (uint64_t)n_rows * 4 + 16));
+        const uint64_t* d_vals = rows_on_device ? rows_host : rbuf.as<uint64_t>();
+        uint32_t* d_idx = reinterpret_cast<uint32_t*>(rbuf.as<uint64_t>() + (rows_on_device ? 0 : (uint64_t)B * per));
+        if (!rows_on_device) GL355_HIP(ctx, hipMemcpyAsync(rbuf.p, rows_host, (uint64_t)B * per * 8, hipMemcpyHostToDevice, ctx->stream));
+        GL355_HIP(ctx, hipMemcpyAsync(d_idx, row_idx, (uint64_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
+        ProfScope ps(ctx, "witness_scatter", (uint64_t)B * per * 16);
+        hipLaunchKernelGGL(witness_rows_units_kernel, dim3((uint32_t)((per + 255) / 256), B), dim3(256), 0, ctx->stream, wires, n, nw, d_idx, d_vals, n_rows);
+        LAUNCH_CHECK(ctx);
+    }
+    const uint64_t cnt_b = (uint64_t)n_blind * nw + (uint64_t)n_z_pairs * r.routed;
+    if (cnt_b) {
+        ProfScope ps(ctx, "witness_blind", (uint64_t)B * cnt_b * 8);
+        hipLaunchKernelGGL(witness_blind_units_kernel, dim3((uint32_t)((cnt_b / 4 + 256) / 256), B), dim3(256), 0, ctx->stream, wires, n, nw, r.routed, blind_start,
+                           n_blind, z_start, n_z_pairs, r.keys);
+        LAUNCH_CHECK(ctx);
+    }
+    GL355_HIP(ctx, ctx->wait());      // the caller's host row buffers may be reused; rbuf is released after its last use
+    return GL355_OK;
+}
+
+// 2. wires commitment; beta and gamma of every challenge
+static int32_t stage_wires_commit(ProveRun& r) {
+    GL355_HIP(r.ctx, hipMemcpyAsync(r.o_w.coeffs, r.wires_keep.p, (uint64_t)r.B * r.nw * r.n * 8, hipMemcpyDeviceToDevice, r.ctx->stream));
+    GL355_TRY(r.commit(r.o_w, false, false, GL355_BLIND_STREAM_WIRES_SALT));
+    GL355_TRY(r.observe_caps(r.o_w));
+    for (uint32_t u = 0; u < r.B; u++) {
+        gl355_challenger_squeeze(&r.ch[u], &r.betas.v[u * 4], r.nch);
+        gl355_challenger_squeeze(&r.ch[u], &r.gammas.v[u * 4], r.nch);
+    }
+    return GL355_OK;
+}
+
+// 3. permutation argument: Z and partial products of every (unit, challenge), committed; alpha of every challenge
+static int32_t stage_permutation(ProveRun& r) {
+    Ctx* ctx = r.ctx;
+    GL355_TRY(r.o_z.alloc(ctx, r.B, r.c.degree_bits, r.c.rate_bits, r.z_width, r.zk, r.cap_h));
+    GL355_TRY(r.s_sig.open(r.pd->sigmas, (uint64_t)r.routed * r.n * 8, 1));
+    GL355_TRY(r.s_k.open(r.pd->k_is, (uint64_t)r.routed * 8, 1));
+    GL355_TRY(zs_units_dev(ctx, r.B, r.nch, r.wires_keep.as<uint64_t>(), (uint64_t)r.nw * r.n, r.s_sig.as<uint64_t>(), r.s_k.as<uint64_t>(), r.c.degree_bits, r.routed,
+                           r.qdf, r.betas, r.gammas, r.o_z.coeffs, (uint64_t)r.z_width * r.n));
+    GL355_TRY(r.commit(r.o_z, false, false, GL355_BLIND_STREAM_ZS_SALT));
+    r.wires_keep.reset();      // the wire values are not needed any more
+    GL355_TRY(r.observe_caps(r.o_z));
+    for (uint32_t u = 0; u < r.B; u++) gl355_challenger_squeeze(&r.ch[u], &r.alphas.v[u * 4], r.nch);
+    return GL355_OK;
+}
+
+// 4. quotient: its values on the coset of size n * 2^qdb, back to coefficients, committed as max_degree chunks; zeta
+static int32_t stage_quotient(ProveRun& r) {
+    Ctx* ctx = r.ctx;
+    uint32_t qdb = 0;
+    while ((1u << qdb) < r.qdf) qdb++;
+    const uint64_t nq = r.n << qdb;
+    GL355_TRY(r.o_q.alloc(ctx, r.B, r.c.degree_bits, r.c.rate_bits, r.nch * r.qdf, r.zk, r.cap_h));
+    {
+        Scratch qv(ctx);
+        GL355_TRY(qv.get((uint64_t)r.B * r.nch * nq * 8));
+        GL355_TRY(quotient_units_dev(ctx, &r.c, r.B, r.cs->lde, r.o_w.lde, (uint64_t)r.nw * r.N, r.o_z.lde, (uint64_t)r.z_width * r.N, r.N, r.s_k.as<uint64_t>(),
+                                     r.betas.v, r.gammas.v, r.alphas.v, r.pi_hashes.v, qv.as<uint64_t>()));
+        GL355_TRY(intt_from_bitrev_dev(ctx, qv.as<uint64_t>(), nq, r.o_q.coeffs, nq, r.c.degree_bits + qdb, r.B * r.nch, GL355_COSET_SHIFT));
+    }
+    GL355_TRY(r.commit(r.o_q, true, true, GL355_BLIND_STREAM_QUOTIENT_SALT));
+    GL355_TRY(r.observe_caps(r.o_q));
+    const uint64_t g = gl_root_of_unity(r.c.degree_bits);
+    for (uint32_t u = 0; u < r.B; u++) {
+        uint64_t* z = &r.zetas.v[u * 4];
+        squeeze_ext(&r.ch[u], z);
+        z[2] = gl_canon(gl_mul(z[0], g)); z[3] = gl_canon(gl_mul(z[1], g));
+    }
+    return GL355_OK;
+}
+
+// 5. openings (OpeningSet::new): every polynomial at zeta, the Z polynomials at g * zeta; the FRI batching challenge
+static int32_t stage_openings(ProveRun& r) {
+    Ctx* ctx = r.ctx;
+    const uint32_t B = r.B, nch = r.nch, n_open = (uint32_t)r.lay.n_open;
+    r.views[0] = view_of(r.cs); r.views[1] = view_of(r.o_w); r.views[2] = view_of(r.o_z); r.views[3] = view_of(r.o_q);
+    memset(&r.all, 0, sizeof r.all); memset(&r.zsset, 0, sizeof r.zsset);
+    for (int o = 0; o < 4; o++) { r.all.base[o] = r.views[o].coeffs; r.all.us[o] = r.views[o].coeffs_us; r.all.count[o] = r.views[o].batch; }
+    r.all.n_sets = 4; r.all.log_n = r.c.degree_bits;
+    r.zsset.base[0] = r.views[2].coeffs; r.zsset.us[0] = r.views[2].coeffs_us; r.zsset.count[0] = nch; r.zsset.n_sets = 1; r.zsset.log_n = r.c.degree_bits;
+    GL355_TRY(r.evb.get((uint64_t)B * (n_open + nch) * 16));
+    {
+        EvalArgs ea;
+        ea.all = r.all; ea.zs = r.zsset; ea.n_all = n_open; ea.zeta = r.zetas; ea.out = r.evb.as<uint64_t>(); ea.out_us = 2 * (n_open + nch);
+        ProfScope ps(ctx, "eval_polys", (uint64_t)B * ((uint64_t)(n_open + nch) << r.c.degree_bits) * 8);
+        hipLaunchKernelGGL(eval_polys_units_kernel, dim3(n_open + nch, B), dim3(256), 0, ctx->stream, ea);
+        LAUNCH_CHECK(ctx);
+    }
+    GL355_HIP(ctx, ctx->d2h(r.stage, r.evb.as<uint64_t>(), (uint64_t)B * (n_open + nch) * 16));
+    GL355_HIP(ctx, ctx->wait());
+    for (uint32_t u = 0; u < B; u++) {
+        const uint64_t w = 2ull * (n_open + nch);
+        memcpy(r.out[u], r.stage + (uint64_t)u * w, w * 8);
+        gl355_challenger_observe(&r.ch[u], r.out[u], w);
+        r.out[u] += w;
+        squeeze_ext(&r.ch[u], &r.fri_alpha.v[u * 4]);
+    }
+    return GL355_OK;
+}
+
+// 6. DEEP quotient (prove_openings): acc = Q_zeta * alpha^nch + Q_{g zeta}, two base columns per unit in colsA
+static int32_t stage_deep(ProveRun& r) {
+    Ctx* ctx = r.ctx;
+    const uint32_t B = r.B, n_open = (uint32_t)r.lay.n_open;
+    const uint64_t n = r.n;
+    GL355_TRY(r.colsA.get((uint64_t)B * 2 * n * 8));
+    GL355_TRY(r.colsB.get((uint64_t)B * n * 8 + 64));
+    GL355_TRY(r.fri_vals.get((uint64_t)B * 2 * r.N * 8));
+    const uint64_t n_blocks = (n + DEEP_BLK - 1) / DEEP_BLK;
+    Scratch tab(ctx), vbuf(ctx);
+    GL355_TRY(tab.get((uint64_t)B * deep_tab_len(n_open) * 16));
+    GL355_TRY(vbuf.get((uint64_t)B * (2 * n + 4 * n_blocks + 8) * 8));
+    DeepTabArgs ta;
+    ta.tab = tab.as<uint64_t>(); ta.n_alpha = n_open; ta.alpha = r.fri_alpha; ta.zeta = r.zetas;
+    hipLaunchKernelGGL(deep_tables_kernel, dim3(B), dim3(256), 0, ctx->stream, ta);
+    LAUNCH_CHECK(ctx);
+    GL355_HIP(ctx, hipMemsetAsync(r.colsA.p, 0, (uint64_t)B * 2 * n * 8, ctx->stream));
+    DeepArgs da;
+    memset(&da, 0, sizeof da);
+    da.tab = tab.as<uint64_t>(); da.n_alpha = n_open; da.n = n; da.n_blocks = n_blocks;
+    da.v = vbuf.as<uint64_t>(); da.totals = da.v + (uint64_t)B * 2 * n; da.carry = da.totals + (uint64_t)B * 2 * n_blocks;
+    da.acc = r.colsA.as<uint64_t>();
+    for (int pass = 0; pass < 2; pass++) {
+        da.polys = pass ? r.zsset : r.all; da.n_polys = pass ? r.nch : n_open; da.point = pass;
+        ProfScope ps(ctx, "deep_batch", (uint64_t)B * ((uint64_t)da.n_polys * n * 8 + n * 32));
+        hipLaunchKernelGGL(deep_reduce_scan_units_kernel, dim3((uint32_t)n_blocks, B), dim3(DEEP_BLK), 0, ctx->stream, da);
+        LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL(deep_carry_units_kernel, dim3(B), dim3(64), 0, ctx->stream, da);
+        LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL(deep_finish_units_kernel, dim3((uint32_t)n_blocks, B), dim3(DEEP_BLK), 0, ctx->stream, da);
+        LAUNCH_CHECK(ctx);
+    }
+    return GL355_OK;
+}
+
+// 7. FRI: the device buffer of every query opening (the four oracles', then the layers'), and the shared tail, which writes caps, final
+// polynomial and PoW witness into the proofs and leaves the layer openings in that buffer
+static int32_t stage_fri(ProveRun& r) {
+    const uint64_t per_oracle = (uint64_t)r.B * r.nq_idx;
+    uint64_t woff = 0;
+    for (int o = 0; o < 4; o++) {
+        r.off_leaf[o] = woff; woff += per_oracle * r.lay.leaf_len[o];
+        r.off_sib[o] = woff; woff += per_oracle * r.lay.depth0 * 4;
+    }
+    r.off_ev = woff; woff += per_oracle * r.L * 4;
+    r.off_fsib = woff; woff += per_oracle * r.lay.sib_total;
+    r.open_words = woff;
+    GL355_TRY(r.ob.get((per_oracle + r.open_words + 16) * 8));
+    r.d_idx = r.ob.as<uint64_t>();
+    r.d_open = r.d_idx + per_oracle;
+    const uint64_t final_words = 2 * (r.n >> r.L);
+    FriUnitOut fo[MAXB];
+    for (uint32_t u = 0; u < r.B; u++) {
+        fo[u].caps = r.out[u]; r.out[u] += (uint64_t)r.L * r.n_cap * 4;
+        fo[u].final_poly = r.out[u]; r.out[u] += final_words;
+        fo[u].pow_witness = r.out[u]; r.out[u] += 1;
+    }
+    const FriShape shape{r.c.degree_bits, r.c.rate_bits, r.cap_h, r.L, r.pd->pow_bits, r.nq_idx, r.hasher};
+    return fri_tail_units(r.ctx, shape, r.B, r.colsA.as<uint64_t>(), r.colsB.as<uint64_t>(), r.fri_vals.as<uint64_t>(), r.stage, r.ch.data(), fo, r.q_idx.data(),
+                          r.d_idx, r.d_open + r.off_ev, r.d_open + r.off_fsib);
+}
+
+// 8. the four oracles' rows and paths at every query; ONE copy brings all query openings back; the proofs' query rounds
+static int32_t stage_queries(ProveRun& r) {
+    Ctx* ctx = r.ctx;
+    const uint32_t B = r.B, nq_idx = r.nq_idx, depth0 = r.lay.depth0;
+    for (int o = 0; o < 4; o++) {
+        OpenArgs oa;
+        oa.o = r.views[o]; oa.N = r.N; oa.lde_bits = r.lde_bits; oa.cap_height = r.cap_h; oa.n_idx = nq_idx; oa.idx = r.d_idx;
+        oa.leaves = r.d_open + r.off_leaf[o]; oa.sibs = r.d_open + r.off_sib[o];
+        if (oa.o.leaf_len != r.lay.leaf_len[o]) return ctx->fail(GL355_E_HIP, "prove: internal leaf-length mismatch");
+        ProfScope ps(ctx, "open_batch", (uint64_t)B * nq_idx * (r.lay.leaf_len[o] * 16 + depth0 * 64));
+        hipLaunchKernelGGL(open_units_kernel, dim3(nq_idx, B), dim3(64), 0, ctx->stream, oa);
+        LAUNCH_CHECK(ctx);
+    }
+    GL355_HIP(ctx, ctx->d2h(r.stage, r.d_open, r.open_words * 8));
+    GL355_HIP(ctx, ctx->wait());
+    const uint64_t* st = r.stage;
+    for (uint32_t u = 0; u < B; u++) {
+        uint64_t* o_ = r.out[u];
+        for (uint32_t q = 0; q < nq_idx; q++) {
+            const uint64_t uq = (uint64_t)u * nq_idx + q;
+            *o_++ = r.q_idx[uq];
+            for (int o = 0; o < 4; o++) {
+                const uint32_t ll = r.lay.leaf_len[o];
+                memcpy(o_, st + r.off_leaf[o] + uq * ll, (uint64_t)ll * 8); o_ += ll;
+                memcpy(o_, st + r.off_sib[o] + uq * depth0 * 4, (uint64_t)depth0 * 32); o_ += (uint64_t)depth0 * 4;
+            }
+            for (uint32_t l = 0; l < r.L; l++) {
+                memcpy(o_, st + r.off_ev + (uq * r.L + l) * 4, 32); o_ += 4;
+                const uint64_t d = (uint64_t)(r.lde_bits - 1 - l - r.cap_h) * 4;
+                memcpy(o_, st + r.off_fsib + uq * r.lay.sib_total + r.lay.sib_off[l], d * 8); o_ += d;
+            }
+        }
+        if ((uint64_t)(o_ - r.io[u].proof) != r.lay.words) return ctx->fail(GL355_E_HIP, "prove: internal proof-size mismatch");
+    }
+    return GL355_OK;
+}
+
 int32_t prove_units(Ctx* ctx, const gl355_prover_data* pd, uint32_t B, const uint64_t* d_wires_dense, const uint32_t* row_idx,
                     const uint64_t* rows_host, uint32_t n_rows, uint32_t blind_start, uint32_t n_blind, uint32_t z_start, uint32_t n_z_pairs,
                     const ProveUnit* io) {
@@ -502,379 +911,34 @@ int32_t prove_units(Ctx* ctx, const gl355_prover_data* pd, uint32_t B, const uin
         ~CpuScope() { if (c->prof_on) { c->prove_cpu_ns += thread_cpu_ns() - t0; c->prove_calls++; } }
     } cpu_scope(ctx);
     const gl355_circuit& c = *pd->circuit;
-    const uint32_t nch = c.num_challenges, qdf = c.max_degree, npp = c.num_partial_products, routed = c.num_routed_wires, nw = c.num_wires;
-    const uint32_t lde_bits = c.degree_bits + c.rate_bits, cap_h = pd->cap_height, L = pd->n_fri_layers, nq_idx = pd->num_queries;
-    const uint64_t n = 1ull << c.degree_bits, N = 1ull << lde_bits, n_cap = 1ull << cap_h;
+    const gl355_oracle* cs = pd->constants_sigmas;
+    const uint32_t nch = c.num_challenges, lde_bits = c.degree_bits + c.rate_bits, cap_h = pd->cap_height, L = pd->n_fri_layers;
     if (nch == 0 || nch > 4 || L > 32 || lde_bits > 27) return ctx->fail(GL355_E_UNSUPPORTED, "prove: unsupported shape");
     if (L >= c.degree_bits) return ctx->fail(GL355_E_UNSUPPORTED, "prove: the final polynomial must keep at least two coefficients");
     if (lde_bits - L < cap_h + 1u) return ctx->fail(GL355_E_INVALID_ARG, "prove: too many FRI layers for the cap height");
-    const uint32_t n_chunks = (routed + qdf - 1) / qdf;
-    if (n_chunks > ZS_MAX_CHUNKS || npp + 1 != n_chunks) return ctx->fail(GL355_E_UNSUPPORTED, "prove: at most 16 partial-product chunks");
-    const gl355_oracle* cs = pd->constants_sigmas;
+    const uint32_t n_chunks = (c.num_routed_wires + c.max_degree - 1) / c.max_degree;
+    if (n_chunks > ZS_MAX_CHUNKS || c.num_partial_products + 1 != n_chunks) return ctx->fail(GL355_E_UNSUPPORTED, "prove: at most 16 partial-product chunks");
     if (cs->log_n != c.degree_bits || cs->rate_bits != c.rate_bits || cs->cap_height != cap_h)
         return ctx->fail(GL355_E_INVALID_ARG, "prove: constants_sigmas oracle does not match the circuit");
-    const int32_t hasher = pd->hasher;
-    if (hasher != GL355_HASH_POSEIDON && hasher != GL355_HASH_BN254_POSEIDON) return ctx->fail(GL355_E_INVALID_ARG, "prove: unknown hasher");
-    if (cs->hasher != hasher) return ctx->fail(GL355_E_INVALID_ARG, "prove: constants_sigmas was committed with another hasher");
-    const bool zk = pd->zero_knowledge != 0;
-    const uint64_t need = gl355_proof_words(pd);
+    if (pd->hasher != GL355_HASH_POSEIDON && pd->hasher != GL355_HASH_BN254_POSEIDON) return ctx->fail(GL355_E_INVALID_ARG, "prove: unknown hasher");
+    if (cs->hasher != pd->hasher) return ctx->fail(GL355_E_INVALID_ARG, "prove: constants_sigmas was committed with another hasher");
+    ProveRun r(ctx, pd, B, io);
     for (uint32_t u = 0; u < B; u++) {
         if (!io[u].proof || (!io[u].public_inputs && io[u].n_public_inputs)) return ctx->fail(GL355_E_INVALID_ARG, "prove: null argument");
-        if (io[u].proof_capacity_words < need) return ctx->fail(GL355_E_INVALID_ARG, "prove: proof buffer too small (see gl355_proof_words)");
+        if (io[u].proof_capacity_words < r.lay.words) return ctx->fail(GL355_E_INVALID_ARG, "prove: proof buffer too small (see gl355_proof_words)");
     }
-    uint32_t qdb = 0;
-    while ((1u << qdb) < qdf) qdb++;
-    const uint64_t nq = n << qdb;
-
-    // ---- transcripts, one per unit (host) ---------------------------------------------------------------------------------
-    std::vector<gl355_challenger> ch(B);
-    std::vector<uint64_t*> out(B);
-    UnitKeys keys;
-    UnitVals pi_hashes;
-    memset(&pi_hashes, 0, sizeof pi_hashes);
-    for (uint32_t u = 0; u < B; u++) {
-        uint64_t* hdr = io[u].proof;
-        hdr[0] = need; hdr[1] = c.degree_bits; hdr[2] = L; hdr[3] = nq_idx; hdr[4] = io[u].n_public_inputs; hdr[5] = zk; hdr[6] = cap_h; hdr[7] = nch;
-        out[u] = hdr + 8;
-        gl355_challenger_init_h(&ch[u], hasher);
-        gl355_host_hash_no_pad(io[u].public_inputs, io[u].n_public_inputs, &pi_hashes.v[u * 4]);
-        gl355_challenger_observe(&ch[u], pd->circuit_digest, 4);
-        gl355_challenger_observe(&ch[u], &pi_hashes.v[u * 4], 4);
-        memcpy(keys.k[u].w, io[u].key, 32);
-    }
-    // pinned staging for everything that crosses PCIe (caps, openings, final polynomials, query openings)
-    const uint64_t n_open_all = (uint64_t)cs->batch + nw + (uint64_t)nch * (1 + npp) + (uint64_t)nch * qdf;
-    const uint32_t depth0 = lde_bits - cap_h;
-    uint64_t sib_total = 0;
-    for (uint32_t l = 0; l < L; l++) sib_total += (uint64_t)(lde_bits - 1 - l - cap_h) * 4;
-    const uint32_t leaf_lens[4] = {cs->leaf_len, nw + (zk ? GL355_SALT_SIZE : 0u), nch * (1 + npp) + (zk ? GL355_SALT_SIZE : 0u), nch * qdf + (zk ? GL355_SALT_SIZE : 0u)};
-    uint64_t open_words = 0;
-    for (int o = 0; o < 4; o++) open_words += (uint64_t)nq_idx * (leaf_lens[o] + (uint64_t)depth0 * 4);
-    open_words += (uint64_t)nq_idx * (L * 4 + sib_total);
-    const uint64_t stage_words = (uint64_t)B * std::max<uint64_t>({n_cap * 4, 2 * (n_open_all + nch), 2 * (n >> L) + 8, open_words, 16});
-    uint64_t* stage = nullptr;
-    GL355_TRY(ctx->pinned(stage_words * 8, reinterpret_cast<void**>(&stage)));
-
-    auto observe_caps = [&](const uint64_t* d_caps) -> int32_t {        // d_caps: [B][n_cap][4]
-        GL355_HIP(ctx, ctx->d2h(stage, d_caps, (uint64_t)B * n_cap * 32));
-        GL355_HIP(ctx, ctx->wait());
-        for (uint32_t u = 0; u < B; u++) {
-            memcpy(out[u], stage + (uint64_t)u * n_cap * 4, n_cap * 32);
-            gl355_challenger_observe(&ch[u], out[u], n_cap * 4);
-            out[u] += n_cap * 4;
-        }
-        return GL355_OK;
-    };
-
-    // ---- wires ------------------------------------------------------------------------------------------------------------------
-    BOracle o_w, o_z, o_q;
-    GL355_TRY(o_w.alloc(ctx, B, c.degree_bits, c.rate_bits, nw, zk, cap_h));
-    Scratch wires_keep(ctx);                    // the wire VALUES are needed again for the permutation argument
-    GL355_TRY(wires_keep.get((uint64_t)B * nw * n * 8));
-    uint64_t* wires = wires_keep.as<uint64_t>();
-    if (d_wires_dense) {
-        GL355_HIP(ctx, hipMemcpyAsync(wires, d_wires_dense, (uint64_t)B * nw * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    } else {
-        GL355_HIP(ctx, hipMemsetAsync(wires, 0, (uint64_t)B * nw * n * 8, ctx->stream));
-        Scratch rbuf(ctx);
-        if (n_rows) {
-            const uint64_t per = (uint64_t)n_rows * nw;
-            const bool rows_on_device = ptr_is_device(rows_host);       // the batch runtime uploads the next batch's rows on its copy stream
-            GL355_TRY(rbuf.get((rows_on_device ? 0 : (uint64_t)B * per * 8) + (uint64_t)n_rows * 4 + 16));
-            const uint64_t* d_vals = rows_on_device ? rows_host : rbuf.as<uint64_t>();
-            uint32_t* d_idx = reinterpret_cast<uint32_t*>(rbuf.as<uint64_t>() + (rows_on_device ? 0 : (uint64_t)B * per));
-            if (!rows_on_device) GL355_HIP(ctx, hipMemcpyAsync(rbuf.p, rows_host, (uint64_t)B * per * 8, hipMemcpyHostToDevice, ctx->stream));
-            GL355_HIP(ctx, hipMemcpyAsync(d_idx, row_idx, (uint64_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
-            ProfScope ps(ctx, "witness_scatter", (uint64_t)B * per * 16);
-            hipLaunchKernelGGL(witness_rows_units_kernel, dim3((uint32_t)((per + 255) / 256), B), dim3(256), 0, ctx->stream, wires, n, nw, d_idx, d_vals, n_rows);
-            LAUNCH_CHECK(ctx);
-        }
-        const uint64_t cnt_b = (uint64_t)n_blind * nw + (uint64_t)n_z_pairs * routed;
-        if (cnt_b) {
-            ProfScope ps(ctx, "witness_blind", (uint64_t)B * cnt_b * 8);
-            hipLaunchKernelGGL(witness_blind_units_kernel, dim3((uint32_t)((cnt_b / 4 + 256) / 256), B), dim3(256), 0, ctx->stream, wires, n, nw, routed, blind_start,
-                               n_blind, z_start, n_z_pairs, keys);
-            LAUNCH_CHECK(ctx);
-        }
-        GL355_HIP(ctx, ctx->wait());      // the caller's host row buffers may be reused; rbuf is released after its last use
-    }
-    GL355_HIP(ctx, hipMemcpyAsync(o_w.coeffs, wires, (uint64_t)B * nw * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    GL355_TRY(commit_units(ctx, hasher, o_w, false, false, &keys, GL355_BLIND_STREAM_WIRES_SALT));
-    GL355_TRY(observe_caps(o_w.cap));
-    UnitVals betas, gammas, alphas;
-    memset(&betas, 0, sizeof betas); memset(&gammas, 0, sizeof gammas); memset(&alphas, 0, sizeof alphas);
-    for (uint32_t u = 0; u < B; u++) {
-        gl355_challenger_squeeze(&ch[u], &betas.v[u * 4], nch);
-        gl355_challenger_squeeze(&ch[u], &gammas.v[u * 4], nch);
-    }
-    // ---- Z / partial products --------------------------------------------------------------------------------------------------
-    const uint32_t z_width = nch * (1 + npp);
-    GL355_TRY(o_z.alloc(ctx, B, c.degree_bits, c.rate_bits, z_width, zk, cap_h));
-    Staged s_sig(ctx), s_k(ctx);
-    GL355_TRY(s_sig.open(pd->sigmas, (uint64_t)routed * n * 8, 1));
-    GL355_TRY(s_k.open(pd->k_is, (uint64_t)routed * 8, 1));
-    {
-        Scratch zs_tmp(ctx);
-        const uint32_t n_inst = B * nch;
-        GL355_TRY(zs_tmp.get((uint64_t)n_inst * (n_chunks + 1) * n * 8));
-        ZsArgs za;
-        memset(&za, 0, sizeof za);
-        za.wires = wires; za.wires_us = (uint64_t)nw * n; za.sigmas = s_sig.as<uint64_t>(); za.k_is = s_k.as<uint64_t>();
-        za.log_n = c.degree_bits; za.n_routed = routed; za.max_degree = qdf; za.nch = nch; za.n_chunks = n_chunks; za.npp = npp;
-        za.g = gl_root_of_unity(c.degree_bits);
-        za.chunk_q = zs_tmp.as<uint64_t>(); za.row_prod = za.chunk_q + (uint64_t)n_inst * n_chunks * n;
-        za.zbuf = o_z.coeffs; za.z_us = (uint64_t)z_width * n;
-        for (uint32_t i = 0; i < MAXB * 4; i++) { za.betas.v[i] = gl_canon(betas.v[i]); za.gammas.v[i] = gl_canon(gammas.v[i]); }
-        ProfScope ps(ctx, "zs_partial_products", (uint64_t)n_inst * ((uint64_t)routed * n * 16 + (uint64_t)n_chunks * n * 8));
-        const uint32_t blocks = (uint32_t)((n + 255) / 256);
-        hipLaunchKernelGGL(zs_rows_units_kernel, dim3(blocks, n_inst), dim3(256), 0, ctx->stream, za);
-        LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(zs_scan_units_kernel, dim3(n_inst), dim3(1024), 0, ctx->stream, za);
-        LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(zs_partials_units_kernel, dim3(blocks, n_inst), dim3(256), 0, ctx->stream, za);
-        LAUNCH_CHECK(ctx);
-    }
-    GL355_TRY(commit_units(ctx, hasher, o_z, false, false, &keys, GL355_BLIND_STREAM_ZS_SALT));
-    wires_keep.reset();      // the wire values are not needed any more
-    GL355_TRY(observe_caps(o_z.cap));
-    for (uint32_t u = 0; u < B; u++) gl355_challenger_squeeze(&ch[u], &alphas.v[u * 4], nch);
-    // ---- quotient --------------------------------------------------------------------------------------------------------------------
-    GL355_TRY(o_q.alloc(ctx, B, c.degree_bits, c.rate_bits, nch * qdf, zk, cap_h));
-    {
-        Scratch qv(ctx);
-        GL355_TRY(qv.get((uint64_t)B * nch * nq * 8));
-        GL355_TRY(quotient_units_dev(ctx, &c, B, cs->lde, o_w.lde, (uint64_t)nw * N, o_z.lde, (uint64_t)z_width * N, N, s_k.as<uint64_t>(), betas.v, gammas.v,
-                                     alphas.v, pi_hashes.v, qv.as<uint64_t>()));
-        GL355_TRY(intt_from_bitrev_dev(ctx, qv.as<uint64_t>(), nq, o_q.coeffs, nq, c.degree_bits + qdb, B * nch, GL355_COSET_SHIFT));
-    }
-    GL355_TRY(commit_units(ctx, hasher, o_q, true, true, &keys, GL355_BLIND_STREAM_QUOTIENT_SALT));
-    GL355_TRY(observe_caps(o_q.cap));
-    UnitVals zetas, fri_alpha;                  // zetas: [u*4+0..1] = zeta, [u*4+2..3] = g * zeta
-    memset(&zetas, 0, sizeof zetas); memset(&fri_alpha, 0, sizeof fri_alpha);
-    const uint64_t g = gl_root_of_unity(c.degree_bits);
-    for (uint32_t u = 0; u < B; u++) {
-        gl355_challenger_squeeze(&ch[u], &zetas.v[u * 4], 2);
-        zetas.v[u * 4] = gl_canon(zetas.v[u * 4]); zetas.v[u * 4 + 1] = gl_canon(zetas.v[u * 4 + 1]);
-        zetas.v[u * 4 + 2] = gl_canon(gl_mul(zetas.v[u * 4], g)); zetas.v[u * 4 + 3] = gl_canon(gl_mul(zetas.v[u * 4 + 1], g));
-    }
-    // ---- openings (OpeningSet::new): every polynomial at zeta, the Z polynomials at g * zeta ------------------------------------------
-    const OView v_cs = view_of(cs), v_w = view_of(o_w), v_z = view_of(o_z), v_q = view_of(o_q);
-    PolySet all, zsset;
-    memset(&all, 0, sizeof all); memset(&zsset, 0, sizeof zsset);
-    const OView* vs[4] = {&v_cs, &v_w, &v_z, &v_q};
-    for (int o = 0; o < 4; o++) { all.base[o] = vs[o]->coeffs; all.us[o] = vs[o]->coeffs_us; all.count[o] = vs[o]->batch; }
-    all.n_sets = 4; all.log_n = c.degree_bits;
-    zsset.base[0] = v_z.coeffs; zsset.us[0] = v_z.coeffs_us; zsset.count[0] = nch; zsset.n_sets = 1; zsset.log_n = c.degree_bits;
-    const uint32_t n_open = (uint32_t)n_open_all;
-    Scratch evb(ctx);
-    GL355_TRY(evb.get((uint64_t)B * (n_open + nch) * 16));
-    {
-        EvalArgs ea;
-        ea.all = all; ea.zs = zsset; ea.n_all = n_open; ea.zeta = zetas; ea.out = evb.as<uint64_t>(); ea.out_us = 2 * (n_open + nch);
-        ProfScope ps(ctx, "eval_polys", (uint64_t)B * ((uint64_t)(n_open + nch) << c.degree_bits) * 8);
-        hipLaunchKernelGGL(eval_polys_units_kernel, dim3(n_open + nch, B), dim3(256), 0, ctx->stream, ea);
-        LAUNCH_CHECK(ctx);
-    }
-    GL355_HIP(ctx, ctx->d2h(stage, evb.as<uint64_t>(), (uint64_t)B * (n_open + nch) * 16));
-    GL355_HIP(ctx, ctx->wait());
-    for (uint32_t u = 0; u < B; u++) {
-        const uint64_t w = 2ull * (n_open + nch);
-        memcpy(out[u], stage + (uint64_t)u * w, w * 8);
-        gl355_challenger_observe(&ch[u], out[u], w);
-        out[u] += w;
-        gl355_challenger_squeeze(&ch[u], &fri_alpha.v[u * 4], 2);
-        fri_alpha.v[u * 4] = gl_canon(fri_alpha.v[u * 4]); fri_alpha.v[u * 4 + 1] = gl_canon(fri_alpha.v[u * 4 + 1]);
-    }
-    // ---- DEEP quotient (prove_openings): acc = Q_zeta * alpha^nch + Q_{g zeta}, two base columns per unit ----------------------------------
-    Scratch colsA(ctx), colsB(ctx), fri_vals(ctx);
-    GL355_TRY(colsA.get((uint64_t)B * 2 * n * 8));
-    GL355_TRY(colsB.get((uint64_t)B * n * 8 + 64));
-    GL355_TRY(fri_vals.get((uint64_t)B * 2 * N * 8));
-    {
-        const uint64_t n_blocks = (n + DEEP_BLK - 1) / DEEP_BLK;
-        Scratch tab(ctx), vbuf(ctx);
-        GL355_TRY(tab.get((uint64_t)B * deep_tab_len(n_open) * 16));
-        GL355_TRY(vbuf.get((uint64_t)B * (2 * n + 4 * n_blocks + 8) * 8));
-        DeepTabArgs ta;
-        ta.tab = tab.as<uint64_t>(); ta.n_alpha = n_open; ta.alpha = fri_alpha; ta.zeta = zetas;
-        hipLaunchKernelGGL(deep_tables_kernel, dim3(B), dim3(256), 0, ctx->stream, ta);
-        LAUNCH_CHECK(ctx);
-        GL355_HIP(ctx, hipMemsetAsync(colsA.p, 0, (uint64_t)B * 2 * n * 8, ctx->stream));
-        DeepArgs da;
-        memset(&da, 0, sizeof da);
-        da.tab = tab.as<uint64_t>(); da.n_alpha = n_open; da.n = n; da.n_blocks = n_blocks;
-        da.v = vbuf.as<uint64_t>(); da.totals = da.v + (uint64_t)B * 2 * n; da.carry = da.totals + (uint64_t)B * 2 * n_blocks;
-        da.acc = colsA.as<uint64_t>();
-        for (int pass = 0; pass < 2; pass++) {
-            da.polys = pass ? zsset : all; da.n_polys = pass ? nch : n_open; da.point = pass;
-            ProfScope ps(ctx, "deep_batch", (uint64_t)B * ((uint64_t)da.n_polys * n * 8 + n * 32));
-            hipLaunchKernelGGL(deep_reduce_scan_units_kernel, dim3((uint32_t)n_blocks, B), dim3(DEEP_BLK), 0, ctx->stream, da);
-            LAUNCH_CHECK(ctx);
-            hipLaunchKernelGGL(deep_carry_units_kernel, dim3(B), dim3(64), 0, ctx->stream, da);
-            LAUNCH_CHECK(ctx);
-            hipLaunchKernelGGL(deep_finish_units_kernel, dim3((uint32_t)n_blocks, B), dim3(DEEP_BLK), 0, ctx->stream, da);
-            LAUNCH_CHECK(ctx);
-        }
-    }
-    // ---- FRI commit phase (fri_committed_trees) ----------------------------------------------------------------------------------------
-    std::vector<uint64_t> leaf_off(L), dig_off(L);
-    uint64_t tree_words = 0;
-    for (uint32_t l = 0; l < L; l++) {
-        const uint64_t nl = N >> (l + 1);
-        if (nl < n_cap) return ctx->fail(GL355_E_INVALID_ARG, "prove: FRI layer smaller than the cap");
-        leaf_off[l] = tree_words; tree_words += (uint64_t)B * nl * 4;
-        dig_off[l] = tree_words; tree_words += (uint64_t)B * 2 * (nl - n_cap) * 4;
-    }
-    Scratch trees(ctx);
-    GL355_TRY(trees.get((tree_words + (uint64_t)B * n_cap * 4 + 16) * 8));
-    uint64_t* tree_buf = trees.as<uint64_t>();
-    uint64_t* d_cap = tree_buf + tree_words;
-    uint64_t* cols = colsA.as<uint64_t>();
-    uint64_t* cols2 = colsB.as<uint64_t>();
-    uint64_t shift = GL355_COSET_SHIFT, len_c = n;
-    std::vector<uint64_t*> p_fri_caps(B);
-    for (uint32_t u = 0; u < B; u++) { p_fri_caps[u] = out[u]; out[u] += (uint64_t)L * n_cap * 4; }
-    for (uint32_t l = 0; l < L; l++) {
-        const uint64_t len_v = len_c << c.rate_bits, nl = len_v / 2;
-        GL355_TRY(lde_dev(ctx, cols, len_c, log2_u64(len_c), c.rate_bits, gl_canon(shift), 2 * B, fri_vals.as<uint64_t>(), len_v, true));
-        uint64_t* lv = tree_buf + leaf_off[l];
-        {
-            ProfScope ps(ctx, "fri_layer_leaves", (uint64_t)B * len_v * 32);
-            hipLaunchKernelGGL(fri_leaves_units_kernel, dim3((uint32_t)((nl + 255) / 256), B), dim3(256), 0, ctx->stream, fri_vals.as<uint64_t>(), len_v, lv);
-            LAUNCH_CHECK(ctx);
-        }
-        LeafArgs la;
-        memset(&la, 0, sizeof la);
-        la.leaves = lv; la.n_leaves = (uint64_t)B * nl; la.leaf_len = 4; la.col_major = 0; la.stride = 4;
-        GL355_TRY(merkle_build_args_any(ctx, hasher, la, log2_u64(nl) - cap_h, tree_buf + dig_off[l], d_cap));
-        GL355_HIP(ctx, ctx->d2h(stage, d_cap, (uint64_t)B * n_cap * 32));
-        GL355_HIP(ctx, ctx->wait());
-        UnitVals beta;
-        memset(&beta, 0, sizeof beta);
-        for (uint32_t u = 0; u < B; u++) {
-            uint64_t* dst = p_fri_caps[u] + (uint64_t)l * n_cap * 4;
-            memcpy(dst, stage + (uint64_t)u * n_cap * 4, n_cap * 32);
-            gl355_challenger_observe(&ch[u], dst, n_cap * 4);
-            gl355_challenger_squeeze(&ch[u], &beta.v[u * 4], 2);
-            beta.v[u * 4] = gl_canon(beta.v[u * 4]); beta.v[u * 4 + 1] = gl_canon(beta.v[u * 4 + 1]);
-        }
-        {
-            ProfScope ps(ctx, "fri_fold", (uint64_t)B * (len_c * 16 + len_c * 8));
-            hipLaunchKernelGGL(fri_fold_units_kernel, dim3((uint32_t)((len_c / 2 + 255) / 256), B), dim3(256), 0, ctx->stream, cols, len_c, beta, cols2);
-            LAUNCH_CHECK(ctx);
-        }
-        std::swap(cols, cols2);
-        len_c >>= 1;
-        shift = gl_mul(shift, shift);
-    }
-    // final polynomial (len_c = n >> L extension coefficients per unit, two columns each)
-    GL355_HIP(ctx, ctx->d2h(stage, cols, (uint64_t)B * 2 * len_c * 8));
-    GL355_HIP(ctx, ctx->wait());
-    PowArgs pa;
-    memset(&pa, 0, sizeof pa);
-    std::vector<uint64_t*> p_pow(B);
-    for (uint32_t u = 0; u < B; u++) {
-        const uint64_t* c0 = stage + (uint64_t)u * 2 * len_c;
-        for (uint64_t k = 0; k < len_c; k++) { out[u][2 * k] = c0[k]; out[u][2 * k + 1] = c0[len_c + k]; }
-        gl355_challenger_observe(&ch[u], out[u], 2 * len_c);
-        out[u] += 2 * len_c;
-        p_pow[u] = out[u]; out[u] += 1;
-        uint64_t st[12];
-        uint32_t pos;
-        if (gl355_challenger_pow_state(&ch[u], st, &pos) != GL355_OK) return ctx->fail(GL355_E_INVALID_ARG, "prove: challenger state");
-        for (int k = 0; k < 12; k++) pa.state[u * 12 + k] = gl_canon(st[k]);
-        pa.pos[u] = pos; pa.todo[u] = 1;
-    }
-    // ---- proof of work (fri_proof_of_work): smallest witness per unit ---------------------------------------------------------------------------
-    if (hasher == GL355_HASH_POSEIDON) {
-        if (pd->pow_bits > 40) return ctx->fail(GL355_E_UNSUPPORTED, "pow: more than 40 bits of grinding refused");
-        Scratch pb(ctx);
-        GL355_TRY(pb.get(MAXB * 8));
-        pa.best = reinterpret_cast<unsigned long long*>(pb.p);
-        pa.bits = pd->pow_bits;
-        GL355_HIP(ctx, hipMemsetAsync(pb.p, 0xFF, MAXB * 8, ctx->stream));
-        // a launch of 2^(bits+1) candidates holds a solution with probability 1 - e^-2; units without one go again
-        uint64_t per_launch = 1ull << std::min<uint32_t>(std::max<uint32_t>(pd->pow_bits + 1, 12), 22);
-        uint64_t base = 0;
-        for (uint32_t left = B; left;) {
-            ProfScope ps(ctx, "pow_grind", 0);
-            pa.start = base;
-            hipLaunchKernelGGL(pow_grind_units_kernel, dim3((uint32_t)(per_launch / 256), B), dim3(256), 0, ctx->stream, pa);
-            LAUNCH_CHECK(ctx);
-            GL355_HIP(ctx, ctx->d2h(stage, pb.p, (uint64_t)B * 8));
-            GL355_HIP(ctx, ctx->wait());
-            for (uint32_t u = 0; u < B; u++)
-                if (pa.todo[u] && stage[u] != ~0ull) { *p_pow[u] = stage[u]; pa.todo[u] = 0; left--; }
-            base += per_launch;
-            if (per_launch < (1ull << 22)) per_launch <<= 1;
-            if (base > (1ull << 44)) return ctx->fail(GL355_E_UNSUPPORTED, "pow: no witness found in 2^44 candidates");
-        }
-    } else {
-        for (uint32_t u = 0; u < B; u++) GL355_TRY(pow_grind_any(ctx, hasher, &pa.state[u * 12], pa.pos[u], pd->pow_bits, 0, p_pow[u]));
-    }
-    // ---- query indices, then every opening of every query in five launches -----------------------------------------------------------------------
-    std::vector<uint64_t> q_idx((uint64_t)B * nq_idx);
-    for (uint32_t u = 0; u < B; u++) {
-        gl355_challenger_observe(&ch[u], p_pow[u], 1);
-        uint64_t resp;
-        gl355_challenger_squeeze(&ch[u], &resp, 1);
-        if (pd->pow_bits && (resp >> (64 - pd->pow_bits)) != 0) return ctx->fail(GL355_E_HIP, "prove: proof-of-work response check failed");
-        gl355_challenger_squeeze(&ch[u], &q_idx[(uint64_t)u * nq_idx], nq_idx);
-        for (uint32_t q = 0; q < nq_idx; q++) q_idx[(uint64_t)u * nq_idx + q] &= (N - 1);
-    }
-    Scratch ob(ctx);
-    GL355_TRY(ob.get(((uint64_t)B * nq_idx + (uint64_t)B * open_words + 16) * 8));
-    uint64_t* d_idx = ob.as<uint64_t>();
-    uint64_t* d_open = d_idx + (uint64_t)B * nq_idx;
-    GL355_HIP(ctx, hipMemcpyAsync(d_idx, q_idx.data(), (uint64_t)B * nq_idx * 8, hipMemcpyHostToDevice, ctx->stream));
-    uint64_t off_leaf[4], off_sib[4], woff = 0;
-    for (int o = 0; o < 4; o++) {
-        off_leaf[o] = woff; woff += (uint64_t)B * nq_idx * leaf_lens[o];
-        off_sib[o] = woff; woff += (uint64_t)B * nq_idx * depth0 * 4;
-        OpenArgs oa;
-        oa.o = *vs[o]; oa.N = N; oa.lde_bits = lde_bits; oa.cap_height = cap_h; oa.n_idx = nq_idx; oa.idx = d_idx;
-        oa.leaves = d_open + off_leaf[o]; oa.sibs = d_open + off_sib[o];
-        if (oa.o.leaf_len != leaf_lens[o]) return ctx->fail(GL355_E_HIP, "prove: internal leaf-length mismatch");
-        ProfScope ps(ctx, "open_batch", (uint64_t)B * nq_idx * (leaf_lens[o] * 16 + depth0 * 64));
-        hipLaunchKernelGGL(open_units_kernel, dim3(nq_idx, B), dim3(64), 0, ctx->stream, oa);
-        LAUNCH_CHECK(ctx);
-    }
-    const uint64_t off_ev = woff; woff += (uint64_t)B * nq_idx * L * 4;
-    const uint64_t off_fsib = woff; woff += (uint64_t)B * nq_idx * sib_total;
-    if (L) {
-        OpenFriArgs fa;
-        memset(&fa, 0, sizeof fa);
-        fa.trees = tree_buf;
-        uint64_t so = 0;
-        for (uint32_t l = 0; l < L; l++) { fa.leaf_off[l] = leaf_off[l]; fa.dig_off[l] = dig_off[l]; fa.sib_off[l] = so; so += (uint64_t)(lde_bits - 1 - l - cap_h) * 4; }
-        fa.sib_total = sib_total; fa.lde_bits = lde_bits; fa.cap_height = cap_h; fa.n_idx = nq_idx; fa.n_layers = L; fa.idx = d_idx;
-        fa.evals = d_open + off_ev; fa.sibs = d_open + off_fsib;
-        ProfScope ps(ctx, "open_batch", (uint64_t)B * nq_idx * (L * 64 + sib_total * 16));
-        hipLaunchKernelGGL(open_fri_units_kernel, dim3(nq_idx, B, L), dim3(64), 0, ctx->stream, fa);
-        LAUNCH_CHECK(ctx);
-    }
-    GL355_HIP(ctx, ctx->d2h(stage, d_open, woff * 8));
-    GL355_HIP(ctx, ctx->wait());
-    for (uint32_t u = 0; u < B; u++) {
-        uint64_t* o_ = out[u];
-        for (uint32_t q = 0; q < nq_idx; q++) {
-            *o_++ = q_idx[(uint64_t)u * nq_idx + q];
-            for (int o = 0; o < 4; o++) {
-                const uint32_t ll = leaf_lens[o];
-                memcpy(o_, stage + off_leaf[o] + ((uint64_t)u * nq_idx + q) * ll, (uint64_t)ll * 8); o_ += ll;
-                memcpy(o_, stage + off_sib[o] + ((uint64_t)u * nq_idx + q) * depth0 * 4, (uint64_t)depth0 * 32); o_ += (uint64_t)depth0 * 4;
-            }
-            uint64_t so = 0;
-            for (uint32_t l = 0; l < L; l++) {
-                memcpy(o_, stage + off_ev + (((uint64_t)u * nq_idx + q) * L + l) * 4, 32); o_ += 4;
-                const uint64_t d = (uint64_t)(lde_bits - 1 - l - cap_h) * 4;
-                memcpy(o_, stage + off_fsib + ((uint64_t)u * nq_idx + q) * sib_total + so, d * 8); o_ += d;
-                so += d;
-            }
-        }
-        if ((uint64_t)(o_ - io[u].proof) != need) return ctx->fail(GL355_E_HIP, "prove: internal proof-size mismatch");
-    }
-    return GL355_OK;
+    // a constants_sigmas batch of another width than the circuit's would only show as a size mismatch after the whole proof
+    if (cs->batch != r.lay.leaf_len[0] || cs->leaf_len != r.lay.leaf_len[0])
+        return ctx->fail(GL355_E_HIP, "prove: internal leaf-length mismatch");
+    GL355_TRY(begin_units(r));
+    GL355_TRY(stage_witness(r, d_wires_dense, row_idx, rows_host, n_rows, blind_start, n_blind, z_start, n_z_pairs));
+    GL355_TRY(stage_wires_commit(r));
+    GL355_TRY(stage_permutation(r));
+    GL355_TRY(stage_quotient(r));
+    GL355_TRY(stage_openings(r));
+    GL355_TRY(stage_deep(r));
+    GL355_TRY(stage_fri(r));
+    return stage_queries(r);
 }
 
 }  // namespace gl355

@@ -291,7 +291,7 @@ def test_pow_grind(ctx, orc):
 
 
 # ---- a9 ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("log_n,n_routed,max_degree", [(3, 8, 8), (5, 80, 8), (11, 80, 8), (6, 10, 3)])
+@pytest.mark.parametrize("log_n,n_routed,max_degree", [(3, 8, 8), (5, 80, 8), (11, 80, 8), (6, 10, 3), (4, 128, 8)])
 def test_zs_partial_products(ctx, orc, log_n, n_routed, max_degree):
     rng = np.random.default_rng(0x435 + log_n)
     n = 1 << log_n
@@ -302,6 +302,17 @@ def test_zs_partial_products(ctx, orc, log_n, n_routed, max_degree):
     zw, ppw = orc.zs_partial_products(wires, sigmas, k_is, max_degree, beta, gamma)
     eq(z, zw)
     eq(pp, ppw)
+
+
+def test_zs_partial_products_chunk_bound(gl, ctx):
+    """16 chunks (the case (4, 128, 8) above) is what the kernel's register arrays hold: one more is refused, as gl355_prove refuses it"""
+    rng = np.random.default_rng(0x436)
+    wires, sigmas, k_is = rand_field(rng, (129, 16)), rand_field(rng, (129, 16)), rand_field(rng, 129)
+    with pytest.raises(gl.Gl355Error) as e:
+        ctx.zs_partial_products(wires, sigmas, k_is, 8, 3, 5)
+    assert e.value.code == -5       # GL355_E_UNSUPPORTED
+    # the context stays usable after the error
+    assert ctx.hash_no_pad(np.arange(1, 9, dtype=np.uint64))[0] == 0xD110AA6A46373941
 
 
 # ---- error behaviour: codes, never aborts ----------------------------------------------------------

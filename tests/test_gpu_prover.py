@@ -143,6 +143,19 @@ def test_wrong_witness_fails_quotient(gl, ctx, orc):
             pv.verify(orc, data.common(), proof)
 
 
+def test_staged_prover_gives_a_valid_proof(gl, ctx, orc):
+    """the stage-by-stage sequencing over the individual C entry points (gl355_zs_partial_products, gl355_quotient, gl355_deep_batch,
+    gl355_fri_prove, oracle openings) on a valid witness: the verifier accepts the proof"""
+    plonk = importlib.import_module("stark-verifier_amd.plonk")
+    aset, sks, rng = make_access_set(gl, ctx, 3, 0x35B)
+    data, rows = aset.build(rng)
+    assert data.degree_bits == 13
+    wires, pi = aset.fill_semaphore_targets(data, rows, sks[6], rand_field(rng, 4), 6, rng)
+    proof = plonk.prove_staged(ctx, data, wires, pi, np.random.default_rng(2))
+    ch = pv.verify(orc, data.common(), proof)
+    assert len(ch["query_indices"]) == data.config.num_query_rounds
+
+
 def test_quotient_kernel_pointwise(gl, ctx, orc):
     """a10: vanishing(x)/Z_H(x) from the HIP kernel == big-integer evaluation of vanishing_poly.rs at sample points."""
     import ctypes as C
