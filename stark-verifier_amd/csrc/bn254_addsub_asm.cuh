@@ -1,5 +1,5 @@
-// 256-bit modular sums and differences for the BN254 fields as written-out carry chains (device only).  Shared by bn254_field.cuh (m_add /
-// m_sub over both fields) and bn254.cuh (the BN254-Poseidon hasher).  Operands and results are 8 x 32-bit limbs, values < 2m; T = 2m.
+// 256-bit modular sums and differences for the BN254 fields as written-out carry chains (device only): m_add / m_sub of bn254_field.cuh over
+// both fields.  Operands and results are 8 x 32-bit limbs, values < 2m; T = 2m.
 //
 // Sum: 8 v_add_co / v_addc_co + the conditional subtraction of 2m as a second chain on its own carry register, interleaved with the first,
 // + 8 selects (24 instructions).  Difference: a borrow chain, a lane mask from the last borrow, 8 masked constants and one more chain (25).
@@ -10,7 +10,6 @@
 #include "gl355_internal.h"
 
 namespace gl355 {
-#if defined(__HIP_DEVICE_COMPILE__)
 struct bn_limbs { uint32_t l[8]; };
 GL_DEV bn_limbs bn254_add_asm(const uint32_t (&al)[8], const uint32_t (&bl)[8], const uint32_t* T) {
     struct { const uint32_t (&l)[8]; } a{al}, b{bl};
@@ -80,5 +79,4 @@ GL_DEV bn_limbs bn254_sub_asm(const uint32_t (&al)[8], const uint32_t (&bl)[8], 
         : "vcc");
     return d;
 }
-#endif
 }  // namespace gl355

@@ -68,18 +68,14 @@ GL_DEV u256 u_cond_sub(const u256& a, const uint32_t* m) {
 }
 // a * b * R^-1 (mod m), result < 2m for a, b < 2m
 //
-// Device build: one asm statement (bn254_mmul_asm.inc, written by tools/gen_mmul_asm.py, which explains the scheme): independent
-// multiply-adds against a bank of {t_j, 0} pairs + one carry chain per half-row, 128 v_mad_u64_u32 + 128 carry adds + 8 v_mul_lo, where
-// the compiled C below spends 128 + 118 64-bit adds + 268 moves.  GL355_BN254_MMUL_ASM=0 builds the C form (the A/B of DESIGN 4.8).
-#ifndef GL355_BN254_MMUL_ASM
-#define GL355_BN254_MMUL_ASM 1
-#endif
+// One asm statement (bn254_mmul_asm.inc, written by tools/gen_mmul_asm.py, which explains the scheme): the CIOS product of a and b with the
+// Montgomery reduction by M folded into each row, as independent multiply-adds against a bank of {t_j, 0} pairs + one carry chain per half-row:
+// 128 v_mad_u64_u32 + 128 carry adds + 8 v_mul_lo, where the same loop compiled from C spends 128 + 118 64-bit adds + 268 moves.
 #include "bn254_mmul_asm.inc"
 template <int F>
 __device__ __noinline__ u256 m_mul(u256 a, u256 b) {
     const uint32_t* M = f_mod<F>();
     const uint32_t n0 = F == F_Q ? BN254C_FQ_N0INV : BN254C_FR_N0INV;
-#if GL355_BN254_MMUL_ASM && defined(__HIP_DEVICE_COMPILE__)
     u256 r;
     uint32_t u8, mm;
     uint64_t sd;
@@ -92,88 +88,23 @@ __device__ __noinline__ u256 m_mul(u256 a, u256 b) {
           [M6] "s"(M[6]), [M7] "s"(M[7]), [n0] "s"(n0)
         : GL355_MMUL_ASM_CLOBBERS);
     return r;
-#else
-    uint32_t t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t t9 = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        uint64_t c = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            c = (uint64_t)a.l[j] * b.l[i] + ((uint64_t)t[j] + c);
-            t[j] = (uint32_t)c;
-            c >>= 32;
-        }
-        c += t[8];
-        t[8] = (uint32_t)c;
-        t9 = (uint32_t)(c >> 32);
-        const uint32_t m = t[0] * n0;
-        c = ((uint64_t)m * M[0] + t[0]) >> 32;
-#pragma unroll
-        for (int j = 1; j < 8; j++) {
-            c = (uint64_t)m * M[j] + ((uint64_t)t[j] + c);
-            t[j - 1] = (uint32_t)c;
-            c >>= 32;
-        }
-        c += t[8];
-        t[7] = (uint32_t)c;
-        t[8] = t9 + (uint32_t)(c >> 32);
-    }
-    u256 r;
-#pragma unroll
-    for (int j = 0; j < 8; j++) r.l[j] = t[j];
-    return r;
-#endif
 }
-// Sums and differences (results < 2m for operands < 2m): bn254_addsub_asm.cuh on the device, the plain C below with GL355_BN254_MMUL_ASM=0
+// Sums and differences (results < 2m for operands < 2m): the carry chains of bn254_addsub_asm.cuh
 template <int F> GL_DEV u256 m_add(const u256& a, const u256& b) {
-#if GL355_BN254_MMUL_ASM && defined(__HIP_DEVICE_COMPILE__)
     const bn_limbs q = bn254_add_asm(a.l, b.l, f_two_mod<F>());
     u256 r;
 #pragma unroll
     for (int j = 0; j < 8; j++) r.l[j] = q.l[j];
     return r;
-#else
-    u256 s;
-    uint64_t c = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        c += (uint64_t)a.l[j] + b.l[j];
-        s.l[j] = (uint32_t)c;
-        c >>= 32;
-    }
-    return u_cond_sub(s, f_two_mod<F>());
-#endif
 }
 template <int F> GL_DEV u256 m_sub(const u256& a, const u256& b) {
     const uint32_t* tm = f_two_mod<F>();
-#if GL355_BN254_MMUL_ASM && defined(__HIP_DEVICE_COMPILE__)
-    // a - b, plus 2m where that borrowed: a representative in [0, 2m) as the C form gives (not always the same one; every consumer
-    // either multiplies on or canonicalises)
+    // a - b, plus 2m where that borrowed: a representative in [0, 2m) (every consumer either multiplies on or canonicalises)
     const bn_limbs q = bn254_sub_asm(a.l, b.l, tm);
     u256 d;
 #pragma unroll
     for (int j = 0; j < 8; j++) d.l[j] = q.l[j];
     return d;
-#else
-    u256 nb;
-    uint64_t br = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const uint64_t v = (uint64_t)tm[j] - b.l[j] - br;
-        nb.l[j] = (uint32_t)v;
-        br = (v >> 32) & 1;
-    }
-    u256 s;
-    uint64_t c = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        c += (uint64_t)a.l[j] + nb.l[j];
-        s.l[j] = (uint32_t)c;
-        c >>= 32;
-    }
-    return u_cond_sub(s, f_two_mod<F>());
-#endif
 }
 template <int F> GL_DEV u256 m_canon(const u256& a) { return u_cond_sub(a, f_mod<F>()); }       // < 2m -> < m
 template <int F> GL_DEV bool m_is_zero(const u256& a) { return u_is_zero(m_canon<F>(a)); }

@@ -72,13 +72,18 @@ GL_HD uint64_t gl_neg(uint64_t a) { return gl_sub(0, a); }
 #ifndef GL_MUL_VARIANT
 #define GL_MUL_VARIANT 1
 #endif
+#if GL_MUL_VARIANT != 1 && GL_MUL_VARIANT != 2
+#error "GL_MUL_VARIANT is 1 (carry steps in inline asm) or 2 (compiler-scheduled)"
+#endif
 // two wait states between a VALU write of an SGPR / VCC and the VALU instruction that reads it (carry-in, select mask)
 #ifdef GL_EXPERIMENT_NO_HAZARD_NOP   // timing experiments only: results are undefined without the wait states
 #define GL_HAZARD_NOP ""
 #else
 #define GL_HAZARD_NOP "s_nop 1\n\t"
 #endif
-#if defined(__HIP_DEVICE_COMPILE__)
+// device-only helpers, declared in both passes of a HIP compile (device-only callers name them without a guard; the host pass does not look inside
+// the asm of a __device__ function).  The host-only .cpp units never see them.
+#if defined(__HIPCC__)
 #if GL_MUL_VARIANT == 1
 // x = lo - sub32: a borrow is repaid with -EPS (the wrapped x is >= p then, so no second borrow)
 GL_DEV uint64_t gl_dev_sub32(uint32_t lo0, uint32_t lo1, uint32_t sub32) {
@@ -129,7 +134,7 @@ GL_DEV uint64_t gl_dev_mid(uint32_t a1, uint32_t b0, uint64_t u, uint32_t* v0) {
 
 // (lo, hi) = hi*2^64 + lo  ->  lo - hi_hi + hi_lo*(2^32 - 1)      [2^64 = 2^32-1, 2^96 = -1 mod p]
 GL_HD uint64_t gl_reduce128(uint64_t lo, uint64_t hi) {
-#if defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT != 0
+#if defined(__HIP_DEVICE_COMPILE__)
     return gl_dev_add_mul_eps(gl_dev_sub32((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)(hi >> 32)), (uint32_t)hi);
 #else
     uint32_t hi_hi = (uint32_t)(hi >> 32), hi_lo = (uint32_t)hi;
@@ -143,7 +148,7 @@ GL_HD uint64_t gl_reduce128(uint64_t lo, uint64_t hi) {
 }
 
 GL_HD uint64_t gl_mul(uint64_t a, uint64_t b) {
-#if defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT != 0
+#if defined(__HIP_DEVICE_COMPILE__)
     // four 32x32+64 multiply-adds (v_mad_u64_u32): t and u cannot overflow, the third sum is taken with its carry
     const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
     const uint64_t t = (uint64_t)a0 * b0;
@@ -152,14 +157,6 @@ GL_HD uint64_t gl_mul(uint64_t a, uint64_t b) {
     const uint64_t mid = gl_dev_mid(a1, b0, u, &v0);
     const uint64_t w = (uint64_t)a1 * b1 + mid;
     return gl_dev_add_mul_eps(gl_dev_sub32((uint32_t)t, v0, (uint32_t)(w >> 32)), (uint32_t)w);
-#elif defined(__HIP_DEVICE_COMPILE__)
-    uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
-    uint64_t t = (uint64_t)a0 * b0;
-    uint64_t u = (uint64_t)a0 * b1 + (t >> 32);
-    uint64_t v = (uint64_t)a1 * b0 + (uint32_t)u;
-    uint64_t w = (uint64_t)a1 * b1 + (u >> 32) + (v >> 32);
-    uint64_t lo = (v << 32) | (uint32_t)t;
-    return gl_reduce128(lo, w);
 #else
     unsigned __int128 pr = (unsigned __int128)a * b;
     return gl_reduce128((uint64_t)pr, (uint64_t)(pr >> 64));
@@ -175,13 +172,18 @@ GL_HD uint64_t gl_sqr(uint64_t a) { return gl_mul(a, a); }
 // intermediates for free), pinned in this order by scheduling barriers; N = 2 needs one extra wait state in front of the first product's readers
 // (its writer is one instruction back; the second product then has the first one's nop + instruction behind its writer), N >= 3 none.  Anything
 // the compiler adds between two statements only adds wait states.  Each product keeps its carry in its own SGPR pair.
-#if defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT == 1
+#if defined(__HIPCC__) && GL_MUL_VARIANT == 1
 template <int N>
 GL_DEV void gl_mul_multi(const uint64_t (&a)[N], const uint64_t (&b)[N], uint64_t (&r)[N]) {
     static_assert(N >= 1 && N <= 4, "1 .. 4 products");
 #define GL_MM_SB() __builtin_amdgcn_sched_barrier(0)
-    // the nop in front of a carry READER of product j
-#define GL_MM_NOP(j) (N == 1 ? "s_nop 1\n\t" : (N == 2 && (j) == 0 ? "s_nop 0\n\t" : ""))
+    // a carry READER of product j, behind the wait states its form still needs (an asm template is a string literal: the three cases are three statements)
+#define GL_MM_READ(INS, ...)                                               \
+    do {                                                                   \
+        if (N == 1) asm("s_nop 1\n\t" INS : __VA_ARGS__);                  \
+        else if (N == 2 && j == 0) asm("s_nop 0\n\t" INS : __VA_ARGS__);   \
+        else asm(INS : __VA_ARGS__);                                       \
+    } while (0)
     uint32_t a0[N], a1[N], b0[N], b1[N], ch[N], x0[N], x1[N], m[N];
     uint64_t t[N], u[N], v[N], w[N], c[N];
 #pragma unroll
@@ -192,12 +194,7 @@ GL_DEV void gl_mul_multi(const uint64_t (&a)[N], const uint64_t (&b)[N], uint64_
 #pragma unroll
     for (int j = 0; j < N; j++) { asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(v[j]), "=s"(c[j]) : "v"(a1[j]), "v"(b0[j]), "v"(u[j])); GL_MM_SB(); }
 #pragma unroll
-    for (int j = 0; j < N; j++) {
-        if (N == 1) asm("s_nop 1\n\tv_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(ch[j]) : "s"(c[j]));
-        else if (N == 2 && j == 0) asm("s_nop 0\n\tv_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(ch[j]) : "s"(c[j]));
-        else asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(ch[j]) : "s"(c[j]));
-        GL_MM_SB();
-    }
+    for (int j = 0; j < N; j++) { GL_MM_READ("v_cndmask_b32_e64 %0, 0, 1, %1", "=v"(ch[j]) : "s"(c[j])); GL_MM_SB(); }
 #pragma unroll
     for (int j = 0; j < N; j++) w[j] = (uint64_t)a1[j] * b1[j] + (((uint64_t)ch[j] << 32) | (v[j] >> 32));
     GL_MM_SB();
@@ -205,28 +202,13 @@ GL_DEV void gl_mul_multi(const uint64_t (&a)[N], const uint64_t (&b)[N], uint64_
 #pragma unroll
     for (int j = 0; j < N; j++) { asm("v_sub_co_u32_e64 %0, %1, %2, %3" : "=v"(x0[j]), "=s"(c[j]) : "v"((uint32_t)t[j]), "v"((uint32_t)(w[j] >> 32))); GL_MM_SB(); }
 #pragma unroll
-    for (int j = 0; j < N; j++) {
-        if (N == 1) asm("s_nop 1\n\tv_subb_co_u32_e64 %0, %1, %2, 0, %1" : "=v"(x1[j]), "+s"(c[j]) : "v"((uint32_t)v[j]));
-        else if (N == 2 && j == 0) asm("s_nop 0\n\tv_subb_co_u32_e64 %0, %1, %2, 0, %1" : "=v"(x1[j]), "+s"(c[j]) : "v"((uint32_t)v[j]));
-        else asm("v_subb_co_u32_e64 %0, %1, %2, 0, %1" : "=v"(x1[j]), "+s"(c[j]) : "v"((uint32_t)v[j]));
-        GL_MM_SB();
-    }
+    for (int j = 0; j < N; j++) { GL_MM_READ("v_subb_co_u32_e64 %0, %1, %2, 0, %1", "=v"(x1[j]), "+s"(c[j]) : "v"((uint32_t)v[j])); GL_MM_SB(); }
 #pragma unroll
-    for (int j = 0; j < N; j++) {
-        if (N == 1) asm("s_nop 1\n\tv_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(m[j]) : "s"(c[j]));
-        else if (N == 2 && j == 0) asm("s_nop 0\n\tv_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(m[j]) : "s"(c[j]));
-        else asm("v_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(m[j]) : "s"(c[j]));
-        GL_MM_SB();
-    }
+    for (int j = 0; j < N; j++) { GL_MM_READ("v_cndmask_b32_e64 %0, 0, -1, %1", "=v"(m[j]) : "s"(c[j])); GL_MM_SB(); }
 #pragma unroll
     for (int j = 0; j < N; j++) { asm("v_sub_co_u32_e64 %0, %1, %0, %2" : "+v"(x0[j]), "=s"(c[j]) : "v"(m[j])); GL_MM_SB(); }
 #pragma unroll
-    for (int j = 0; j < N; j++) {
-        if (N == 1) asm("s_nop 1\n\tv_subb_co_u32_e64 %0, %1, %0, 0, %1" : "+v"(x1[j]), "+s"(c[j]));
-        else if (N == 2 && j == 0) asm("s_nop 0\n\tv_subb_co_u32_e64 %0, %1, %0, 0, %1" : "+v"(x1[j]), "+s"(c[j]));
-        else asm("v_subb_co_u32_e64 %0, %1, %0, 0, %1" : "+v"(x1[j]), "+s"(c[j]));
-        GL_MM_SB();
-    }
+    for (int j = 0; j < N; j++) { GL_MM_READ("v_subb_co_u32_e64 %0, %1, %0, 0, %1", "+v"(x1[j]), "+s"(c[j])); GL_MM_SB(); }
     // + w_lo * EPS, the carry-out repaid with +EPS.  The repayment is a second multiply-add (carry in {0, 1} times EPS): as a 64-bit add every product
     // in flight needs a zero-extended register pair of its own for the addend, i.e. a register move each
 #pragma unroll
@@ -236,15 +218,10 @@ GL_DEV void gl_mul_multi(const uint64_t (&a)[N], const uint64_t (&b)[N], uint64_
         GL_MM_SB();
     }
 #pragma unroll
-    for (int j = 0; j < N; j++) {
-        if (N == 1) asm("s_nop 1\n\tv_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(m[j]) : "s"(c[j]));
-        else if (N == 2 && j == 0) asm("s_nop 0\n\tv_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(m[j]) : "s"(c[j]));
-        else asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(m[j]) : "s"(c[j]));
-        GL_MM_SB();
-    }
+    for (int j = 0; j < N; j++) { GL_MM_READ("v_cndmask_b32_e64 %0, 0, 1, %1", "=v"(m[j]) : "s"(c[j])); GL_MM_SB(); }
 #pragma unroll
     for (int j = 0; j < N; j++) asm("v_mad_u64_u32 %0, %1, %2, -1, %0" : "+v"(r[j]), "=s"(c[j]) : "v"(m[j]));
-#undef GL_MM_NOP
+#undef GL_MM_READ
 #undef GL_MM_SB
 }
 // ONE product (and a lock-step PAIR) whose carry wait states are filled by the CALLER's instructions (round 6): fill(k), k = 0 .. 4, is invoked between the
@@ -323,14 +300,7 @@ GL_DEV void gl_mul2_fill(const uint64_t (&a)[2], const uint64_t (&b)[2], uint64_
     for (int j = 0; j < 2; j++) asm("v_mad_u64_u32 %0, %1, %2, -1, %0" : "+v"(r[j]), "=s"(c[j]) : "v"(m[j]));
 #undef GL_MF_SB
 }
-#else
-// host pass / compiler-scheduled product: one after the other
-template <int N>
-GL_HD void gl_mul_multi(const uint64_t (&a)[N], const uint64_t (&b)[N], uint64_t (&r)[N]) {
-    for (int j = 0; j < N; j++) r[j] = gl_mul(a[j], b[j]);
-}
 #endif
-
 
 // a * c for a small constant c < 2^32 (MDS entries, W = 7, ...): two mads instead of four
 GL_HD uint64_t gl_mul_small(uint64_t a, uint32_t c) {
@@ -339,7 +309,7 @@ GL_HD uint64_t gl_mul_small(uint64_t a, uint32_t c) {
     uint64_t u = (uint64_t)a1 * c + (t >> 32);   // < 2^64
     uint64_t lo = (u << 32) | (uint32_t)t;
     uint32_t hi = (uint32_t)(u >> 32);           // product = hi*2^64 + lo, hi < 2^32
-#if defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT != 0
+#if defined(__HIP_DEVICE_COMPILE__)
     return gl_dev_add_mul_eps(lo, hi);
 #endif
     uint64_t t1 = ((uint64_t)hi << 32) - hi;
@@ -358,7 +328,7 @@ GL_HD uint64_t gl_mul_2exp(uint64_t x) {
     } else if constexpr (S <= 32) {
         const uint32_t hi = (uint32_t)(x >> (64 - S));       // < 2^S <= 2^32
         const uint64_t lo = x << S;
-#if defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT != 0
+#if defined(__HIP_DEVICE_COMPILE__)
         return gl_dev_add_mul_eps(lo, hi);
 #endif
         const uint64_t t = (uint64_t)hi * 0xFFFFFFFFu;        // hi * 2^64 == hi * EPS
@@ -395,7 +365,7 @@ GL_HD gl2 gl2_make(uint64_t a, uint64_t b) { gl2 r; r.c0 = a; r.c1 = b; return r
 GL_HD gl2 gl2_add(gl2 a, gl2 b) { return gl2_make(gl_add(a.c0, b.c0), gl_add(a.c1, b.c1)); }
 GL_HD gl2 gl2_sub(gl2 a, gl2 b) { return gl2_make(gl_sub(a.c0, b.c0), gl_sub(a.c1, b.c1)); }
 GL_HD gl2 gl2_mul(gl2 a, gl2 b) {
-#if defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT == 1 && !defined(GL2_MUL_SEQUENTIAL)
+#if defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT == 1
     // the four base-field products in lock-step: they fill each other's carry wait states (gl_mul_multi)
     const uint64_t x[4] = {a.c0, a.c1, a.c0, a.c1}, y[4] = {b.c0, b.c1, b.c1, b.c0};
     uint64_t p[4];

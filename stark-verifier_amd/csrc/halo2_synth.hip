@@ -29,18 +29,18 @@ namespace gl355 {
 // one dense round (native.rs:45-62): constants, x^5 on every element (full) or on the first, the 5x5 MDS
 GL_DEV void h2_round(fr8 (&s)[5], int rnd) {
     const bool full = rnd < 4 || rnd >= 64;
-    s[0] = fr_pow5(fr_add(s[0], fr_const(BNT(RC)[5 * rnd])));
+    s[0] = fr_pow5(fr_add(s[0], fr_const(BN254F_RC[5 * rnd])));
     if (full) {
-        for (int i = 1; i < 5; i++) s[i] = fr_pow5(fr_add(s[i], fr_const(BNT(RC)[5 * rnd + i])));
+        for (int i = 1; i < 5; i++) s[i] = fr_pow5(fr_add(s[i], fr_const(BN254F_RC[5 * rnd + i])));
     } else {
 #pragma unroll
-        for (int i = 1; i < 5; i++) s[i] = fr_add(s[i], fr_const(BNT(RC)[5 * rnd + i]));
+        for (int i = 1; i < 5; i++) s[i] = fr_add(s[i], fr_const(BN254F_RC[5 * rnd + i]));
     }
     fr8 n[5];
     for (int i = 0; i < 5; i++) {
-        fr8 acc = fr_mul(s[0], fr_const(BNT(MDS)[5 * i]));
+        fr8 acc = fr_mul(s[0], fr_const(BN254F_MDS[5 * i]));
 #pragma unroll
-        for (int j = 1; j < 5; j++) acc = fr_add(acc, fr_mul(s[j], fr_const(BNT(MDS)[5 * i + j])));
+        for (int j = 1; j < 5; j++) acc = fr_add(acc, fr_mul(s[j], fr_const(BN254F_MDS[5 * i + j])));
         n[i] = acc;
     }
 #pragma unroll
@@ -87,13 +87,13 @@ GL_DEV void h2_permute_rows_spread(const H2Cols& c, const uint64_t* e, int lane)
     fr8 s = fr_enter(v.w);
     fr8 m[5];                                          // row i of the MDS matrix
 #pragma unroll
-    for (int j = 0; j < 5; j++) m[j] = fr_const(BNT(MDS)[5 * i + j]);
-    fr8 rc = fr_const(BNT(RC)[i]);
+    for (int j = 0; j < 5; j++) m[j] = fr_const(BN254F_MDS[5 * i + j]);
+    fr8 rc = fr_const(BN254F_RC[i]);
 #pragma unroll 1
     for (int rnd = 0; rnd < 68; rnd++) {
         const bool full = rnd < 4 || rnd >= 64;
         fr8 t = fr_add(s, rc);
-        rc = fr_const(BNT(RC)[5 * (rnd < 67 ? rnd + 1 : rnd) + i]);      // the next round's constant, loaded under this round's products
+        rc = fr_const(BN254F_RC[5 * (rnd < 67 ? rnd + 1 : rnd) + i]);      // the next round's constant, loaded under this round's products
         if (full || lane == 0) t = fr_pow5(t);
         fr8 acc = fr_mul(h2_from_lane(t, 0), m[0]);
 #pragma unroll

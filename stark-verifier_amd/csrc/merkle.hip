@@ -36,10 +36,8 @@ __global__ void __launch_bounds__(256) poseidon_permute_kernel(uint64_t* states,
 
 
 // one lane = one leaf: overwrite-mode sponge over ceil(len/8) chunks
-#ifndef PSD_LEAF_WAVES
-#define PSD_LEAF_WAVES 4
-#endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PSD_LEAF_WAVES))) hash_leaves_kernel(LeafArgs a) {
+constexpr int psd_leaf_waves = 4;
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(psd_leaf_waves))) hash_leaves_kernel(LeafArgs a) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (i >= a.n_leaves) return;
     uint64_t s[12];
@@ -117,7 +115,7 @@ __device__ __constant__ const uint32_t PSD_CIRC_DEV[12] = {17, 15, 41, 16, 2, 28
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  \
         __builtin_amdgcn_wave_barrier();                        \
     } while (0)
-// PSD_LANES_FORM (round 6): the 22 PARTIAL rounds of the 16-lane permutation.
+// FORM (round 6): the 22 PARTIAL rounds of the 16-lane permutation.
 //   0  as the full rounds: S-box (only lane 0's matters), the state through the ring, the whole MDS row: S-box + LDS round trip + 24 multiply-adds +
 //      recombination, one after the other on the critical path;
 //   3  only element 0 changes in a partial round's S-box, so the other eleven elements go through the ring BEFORE it (lane 0 publishes a zero), and each
@@ -127,10 +125,7 @@ __device__ __constant__ const uint32_t PSD_CIRC_DEV[12] = {17, 15, 41, 16, 2, 28
 //      row = one state) for the last two multiply-adds.
 // Form 3 is 16 % faster per permutation (tree tops 0.080 -> 0.067 ms, a lone unit 11.7 -> 11.0 ms) and costs 16 more VGPRs: under a lock-step load, where
 // these kernels share the CUs with the hash kernels of nine other contexts, the job measured 0.8 % SLOWER with it (320.8 vs 323.3 units/s) -- so the
-// launch code takes form 3 for a lone proof's forest (fewer than 64 cap subtrees) and form 0 for lock-step batches.  PSD_LANES_FORM = 0 / 3 forces one (A/B).
-#ifndef PSD_LANES_FORM
-#define PSD_LANES_FORM -1
-#endif
+// launch code takes form 3 for a lone proof's forest (fewer than 64 cap subtrees) and form 0 for lock-step batches.
 template <int FORM>
 GL_DEV uint64_t psd_permute_lanes(uint64_t s, int li, uint64_t* ring /* 24 u64 of this 16-lane group */) {
     const bool active = li < 12;
@@ -154,10 +149,6 @@ GL_DEV uint64_t psd_permute_lanes(uint64_t s, int li, uint64_t* ring /* 24 u64 o
         GL_WAVE_LDS_SYNC();
         s = psd_recombine(al, ah);
     };
-#if !defined(__HIP_DEVICE_COMPILE__) || GL_MUL_VARIANT != 1
-#pragma unroll 1
-    for (int r = 0; r < 30; r++) dense_round(r, r < 4 || r >= 26);
-#else
     if constexpr (FORM == 0) {
 #pragma unroll 1
         for (int r = 0; r < 30; r++) dense_round(r, r < 4 || r >= 26);
@@ -194,7 +185,6 @@ GL_DEV uint64_t psd_permute_lanes(uint64_t s, int li, uint64_t* ring /* 24 u64 o
     }
 #pragma unroll 1
     for (int r = 26; r < 30; r++) dense_round(r, true);
-#endif
     return s;
 }
 
@@ -390,7 +380,7 @@ int32_t merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_t* dig
     const uint32_t top_levels_max = (n_leaves >> sub_bits) < 64 ? 6 : MERKLE_TOP_LEVELS;
     // a lone proof's forest (16 cap subtrees) is latency-bound: the partial rounds with the row inside the S-box (psd_permute_lanes<3>); a lock-step batch
     // shares the chip with other contexts' hash kernels, where the 16 extra registers of that form cost more than its shorter chain gains
-    const bool fast_lanes = PSD_LANES_FORM < 0 ? (n_leaves >> sub_bits) < 64 : PSD_LANES_FORM == 3;
+    const bool fast_lanes = (n_leaves >> sub_bits) < 64;
     uint32_t top_levels = std::min<uint32_t>(top_levels_max, sub_bits);
     while (top_levels > 1 && ((n_leaves >> (sub_bits - top_levels + 1)) > lanes_max)) top_levels--;      // a forest of many subtrees: fewer levels each
     uint32_t top_from = sub_bits + 1;

@@ -127,12 +127,12 @@ __global__ void __launch_bounds__(64) bn254_merkle_level_lanes_kernel(uint64_t* 
         e[q] = idx < 8 ? tree[child * 4 + idx] : 0;
     }
     fr8 s = fr_encode3(e[0], e[1], e[2]);            // column 4 (and the padding of column 2, 3) encodes zeros
-    const fr8 m = fr_const(BNT(MDS)[5 * i + j]);
+    const fr8 m = fr_const(BN254F_MDS[5 * i + j]);
     uint32_t* my = tile[grp];
-    fr8 rc = fr_const(BNT(RC)[j]);
+    fr8 rc = fr_const(BN254F_RC[j]);
 #pragma unroll 1
     for (int rnd = 0; rnd < 68; rnd++) {
-        const fr8 rc_next = fr_const(BNT(RC)[5 * (rnd < 67 ? rnd + 1 : 67) + j]);   // prefetch: the index depends on the lane
+        const fr8 rc_next = fr_const(BN254F_RC[5 * (rnd < 67 ? rnd + 1 : 67) + j]);   // prefetch: the index depends on the lane
         s = fr_add(s, rc);
         rc = rc_next;
         const fr8 sb = fr_pow5(s);
@@ -296,7 +296,7 @@ __global__ void bn254_hash_fr_hook_kernel(int32_t leave, const uint32_t* a, uint
         for (int k = 0; k < 4; k++) w[k] = (uint64_t)pa[2 * k] | ((uint64_t)pa[2 * k + 1] << 32);
         const fr8 r = fr_enter(w);
 #pragma unroll
-        for (int j = 0; j < 9; j++) po[j] = j < FR_W ? r.l[j] : 0u;
+        for (int j = 0; j < FR_W; j++) po[j] = r.l[j];
     } else {
         fr8 x;
 #pragma unroll

@@ -86,10 +86,6 @@ template <int M> GL_DEV L96 l96_sub(L96 a, L96 b) {        // a + (M p - b); the
     const gl_u128 mp = ((gl_u128)(M - 1) << 64) | ((uint64_t)(0x100000000ull - M) << 32) | (uint64_t)M;
     return l96_of(l96_int(a) + (mp - l96_int(b)));
 }
-#if !defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the declarations to parse (gl_field.cuh defines these for the device pass)
-GL_DEV uint64_t gl_dev_add_mul_eps(uint64_t x, uint32_t k);
-GL_DEV uint64_t gl_dev_sub32(uint32_t lo0, uint32_t lo1, uint32_t sub32);
-#endif
 GL_DEV uint64_t l96_norm(L96 a) { return gl_dev_add_mul_eps(a.v, a.k); }
 // (v + k 2^64) * 2^S mod p as any u64, for the shifts of the radix-8 network and k < 2^8.  With T = 2^32: T^2 = EPS, T^3 = -1.
 template <int S> GL_DEV uint64_t l96_shift(L96 a) {

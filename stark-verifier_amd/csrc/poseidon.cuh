@@ -8,42 +8,22 @@
 // tables are derived by tools/gen_poseidon_tables.py and equal the reference's literals.
 #pragma once
 #include "gl_field.cuh"
+#if GL_MUL_VARIANT != 1
+#error "poseidon.cuh is written on the inline-asm product and its lock-step groups: GL_MUL_VARIANT 1"
+#endif
 
 #define PSD_TABLE_QUAL __device__ __constant__ const
 #include "poseidon_tables.h"
 
 namespace gl355 {
 
-// x^7 = (x x^2)(x^2 x^2).  PSD_SBOX_INTERLEAVE 1 (default, round 5): x^3 and x^4 of one S-box, and everything of the two S-boxes of psd_sbox2, go
-// through gl_mul_multi, whose products fill each other's carry wait states; 0: one product after the other (A/B).
-#ifndef PSD_SBOX_INTERLEAVE
-#define PSD_SBOX_INTERLEAVE 1
-#endif
-#ifndef PSD_SBOX_WIDTH
-#define PSD_SBOX_WIDTH 4          // S-boxes of a full round per lock-step group: 2 or 4 (4: no wait states at all; -4 % at one wave per SIMD, nothing at full occupancy)
-#endif
+// x^7 = (x x^2)(x^2 x^2): x^3 and x^4 go through gl_mul_multi, whose products fill each other's carry wait states (round 5)
 GL_DEV uint64_t psd_sbox(uint64_t x) {
-#if PSD_SBOX_INTERLEAVE && defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT == 1
     const uint64_t x2 = gl_sqr(x);
     const uint64_t a[2] = {x, x2}, b[2] = {x2, x2};
     uint64_t r[2];
     gl_mul_multi<2>(a, b, r);
     return gl_mul(r[0], r[1]);
-#else
-    uint64_t x2 = gl_sqr(x), x4 = gl_sqr(x2), x3 = gl_mul(x, x2);
-    return gl_mul(x3, x4);
-#endif
-}
-GL_DEV void psd_sbox2(uint64_t& x, uint64_t& y) {
-#if PSD_SBOX_INTERLEAVE && defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT == 1
-    uint64_t sq[2];
-    { const uint64_t a[2] = {x, y}; gl_mul_multi<2>(a, a, sq); }
-    uint64_t r[4];
-    { const uint64_t a[4] = {x, sq[0], y, sq[1]}, b[4] = {sq[0], sq[0], sq[1], sq[1]}; gl_mul_multi<4>(a, b, r); }
-    { const uint64_t a[2] = {r[0], r[2]}, b[2] = {r[1], r[3]}; uint64_t o[2]; gl_mul_multi<2>(a, b, o); x = o[0]; y = o[1]; }
-#else
-    x = psd_sbox(x); y = psd_sbox(y);
-#endif
 }
 
 // al + ah * 2^32  ->  u64 representative, for accumulators whose top word ah1 = ah >> 32 satisfies ah1 + 1 < 2^32: the two chains of an MDS row
@@ -51,26 +31,15 @@ GL_DEV void psd_sbox2(uint64_t& x, uint64_t& y) {
 // the generated tables by tools/gen_poseidon_tables.py and tests/test_tables.py).
 // = al0 + (al1 + ah0) 2^32 + ah1 2^64: one 32-bit add with carry into the top word, then top * EPS with the carry-out repaid.
 GL_DEV uint64_t psd_recombine(uint64_t al, uint64_t ah) {
-#if GL_MUL_VARIANT == 1 && defined(__HIP_DEVICE_COMPILE__)
     uint32_t t1 = (uint32_t)(al >> 32), top;     // t1 is updated in place: (al0, t1) stays the register pair of al
     asm("v_add_co_u32_e32 %0, vcc, %0, %2\n\t" GL_HAZARD_NOP "v_addc_co_u32_e32 %1, vcc, 0, %3, vcc"
         : "+v"(t1), "=v"(top) : "v"((uint32_t)ah), "v"((uint32_t)(ah >> 32)) : "vcc");
     return gl_dev_add_mul_eps(((uint64_t)t1 << 32) | (uint32_t)al, top);
-#else
-    const uint64_t mid = ah << 32;
-    const uint32_t top = (uint32_t)(ah >> 32);
-    const uint64_t r0 = al + mid;
-    const uint64_t carry = r0 < mid ? 1u : 0u;
-    const uint64_t t = (uint64_t)(top + carry) * GL_EPS;  // top + carry < 2^32 (see above): the product fits 64 bits
-    uint64_t r1 = r0 + t;
-    if (r1 < t) r1 += GL_EPS;
-    return r1;
-#endif
 }
 
-// four S-boxes at once: every phase is four products wide, no wait states at all
+// the S-boxes of a full round, four at once: every phase is four products wide, no wait states at all (against two at once: -4 % at one wave per
+// SIMD, nothing at full occupancy)
 GL_DEV void psd_sbox4(uint64_t& x0, uint64_t& x1, uint64_t& x2, uint64_t& x3) {
-#if PSD_SBOX_INTERLEAVE && defined(__HIP_DEVICE_COMPILE__) && GL_MUL_VARIANT == 1
     const uint64_t a[4] = {x0, x1, x2, x3};
     uint64_t sq[4], c3[4], c4[4], o[4];
     gl_mul_multi<4>(a, a, sq);
@@ -78,14 +47,10 @@ GL_DEV void psd_sbox4(uint64_t& x0, uint64_t& x1, uint64_t& x2, uint64_t& x3) {
     gl_mul_multi<4>(sq, sq, c4);
     gl_mul_multi<4>(c3, c4, o);
     x0 = o[0]; x1 = o[1]; x2 = o[2]; x3 = o[3];
-#else
-    x0 = psd_sbox(x0); x1 = psd_sbox(x1); x2 = psd_sbox(x2); x3 = psd_sbox(x3);
-#endif
 }
 // N recombinations in lock-step (the two carry steps of one fill the wait states of the others: see gl_mul_multi)
 template <int N>
 GL_DEV void psd_recombine_multi(const uint64_t (&al)[N], const uint64_t (&ah)[N], uint64_t (&out)[N]) {
-#if GL_MUL_VARIANT == 1 && defined(__HIP_DEVICE_COMPILE__)
     static_assert(N >= 3, "three or more: no wait states of their own");
     uint32_t t1[N], top[N], m[N];
     uint64_t c[N], r[N];
@@ -112,10 +77,6 @@ GL_DEV void psd_recombine_multi(const uint64_t (&al)[N], const uint64_t (&ah)[N]
     }
 #pragma unroll
     for (int j = 0; j < N; j++) out[j] = r[j] + (uint64_t)m[j];
-#else
-#pragma unroll
-    for (int j = 0; j < N; j++) out[j] = psd_recombine(al[j], ah[j]);
-#endif
 }
 
 // Full MDS layer, plus the NEXT round's constants.  Row r: sum_i s[(i+r)%12] * CIRC[i] + 8*s[0] (r == 0) + rc[r].  The entries
@@ -147,7 +108,6 @@ GL_DEV uint64_t psd_mds_chain(const uint32_t (&x)[12], uint64_t addend) {
 template <int R>
 GL_DEV void psd_mds_rows(uint64_t (&s)[12], const uint32_t (&lo)[12], const uint32_t (&hi)[12], const uint64_t* rc) {
     if constexpr (R < 12) {
-#if PSD_SBOX_INTERLEAVE
         // four rows at a time: eight chains, then their recombinations in lock-step
         const uint64_t c0 = rc[R], c1 = rc[R + 1], c2 = rc[R + 2], c3 = rc[R + 3];
         const uint64_t al[4] = {psd_mds_chain<R>(lo, (uint32_t)c0), psd_mds_chain<R + 1>(lo, (uint32_t)c1), psd_mds_chain<R + 2>(lo, (uint32_t)c2),
@@ -159,11 +119,6 @@ GL_DEV void psd_mds_rows(uint64_t (&s)[12], const uint32_t (&lo)[12], const uint
         psd_recombine_multi<4>(al, ah, o);
         s[R] = o[0]; s[R + 1] = o[1]; s[R + 2] = o[2]; s[R + 3] = o[3];
         psd_mds_rows<R + 4>(s, lo, hi, rc);
-#else
-        const uint64_t c = rc[R];
-        s[R] = psd_recombine(psd_mds_chain<R>(lo, (uint32_t)c), psd_mds_chain<R>(hi, c >> 32));
-        psd_mds_rows<R + 1>(s, lo, hi, rc);
-#endif
     }
 }
 // rc: 12 constants at a wave-uniform address (scalar loads)
@@ -202,7 +157,6 @@ GL_DEV void psd_split(uint64_t x, uint32_t (&l)[3]) {
 typedef const __attribute__((address_space(4))) uint64_t* psd_ktab;      // constant address space: wave-uniform reads become scalar loads
 GL_DEV void psd_mac(uint64_t& lo, uint64_t& hi, const uint32_t (&l)[3], const uint64_t (&c)[3]) {
     const uint64_t c0 = c[0], c1 = c[1], c2 = c[2];
-#if defined(__HIP_DEVICE_COMPILE__)
     // written out: in C the compiler keeps one zero-extended 64-bit copy of every limb (a register PAIR each, 132 VGPRs of limbs) and truncates
     // it at each use.  src0 = the constant (SGPR, the one constant-bus operand), src1 = the limb; the carry-out pair is never read.
     uint64_t unused;
@@ -212,16 +166,11 @@ GL_DEV void psd_mac(uint64_t& lo, uint64_t& hi, const uint32_t (&l)[3], const ui
         : "+v"(lo), "+v"(hi), "=&s"(unused)
         : "s"((uint32_t)c0), "s"((uint32_t)(c0 >> 32)), "s"((uint32_t)c1), "s"((uint32_t)(c1 >> 32)), "s"((uint32_t)c2), "s"((uint32_t)(c2 >> 32)),
           "v"(l[0]), "v"(l[1]), "v"(l[2]));
-#else
-    lo += (uint64_t)l[0] * (uint32_t)c0 + (uint64_t)l[1] * (uint32_t)c1 + (uint64_t)l[2] * (uint32_t)c2;
-    hi += (uint64_t)l[0] * (uint32_t)(c0 >> 32) + (uint64_t)l[1] * (uint32_t)(c1 >> 32) + (uint64_t)l[2] * (uint32_t)(c2 >> 32);
-#endif
 }
 // the first multiply-accumulate of an output: the accumulators start from the additive constant's halves.  Inside the statement, so that the
 // constant is read where the group's other constants are (a C initialisation is copied to VGPRs right behind its scalar load: a wait of its own).
 GL_DEV void psd_mac_first(uint64_t& lo, uint64_t& hi, const uint32_t (&l)[3], const uint64_t (&c)[3], const uint64_t (&add)[2]) {
     const uint64_t c0 = c[0], c1 = c[1], c2 = c[2];
-#if defined(__HIP_DEVICE_COMPILE__)
     uint64_t unused;
     asm("v_mov_b64 %0, %12\n\tv_mov_b64 %1, %13\n\t"
         "v_mad_u64_u32 %0, %2, %3, %9, %0\n\tv_mad_u64_u32 %1, %2, %4, %9, %1\n\t"
@@ -230,21 +179,15 @@ GL_DEV void psd_mac_first(uint64_t& lo, uint64_t& hi, const uint32_t (&l)[3], co
         : "=&v"(lo), "=&v"(hi), "=&s"(unused)
         : "s"((uint32_t)c0), "s"((uint32_t)(c0 >> 32)), "s"((uint32_t)c1), "s"((uint32_t)(c1 >> 32)), "s"((uint32_t)c2), "s"((uint32_t)(c2 >> 32)),
           "v"(l[0]), "v"(l[1]), "v"(l[2]), "s"(add[0]), "s"(add[1]));
-#else
-    lo = add[0]; hi = add[1];
-    psd_mac(lo, hi, l, c);
-#endif
 }
-#ifndef PSD_K_GROUP
-#define PSD_K_GROUP 5      // multiply-accumulates per group of scalar loads: 6 SGPRs of constants each, two groups in flight
-#endif
+constexpr int psd_k_group = 5;      // multiply-accumulates per group of scalar loads: 6 SGPRs of constants each, two groups in flight
 // The block's table is consumed front to back.  Scalar loads return out of order, so the only wait is "all of them": a group's constants are
 // therefore requested one group AHEAD -- the first multiply-accumulate of a group waits for the group's constants (requested while the previous
 // group was being consumed), then the next group's loads are issued, then the remaining multiply-accumulates run under their latency.  The
 // scheduling barriers pin that order; without them the scheduler either issues the loads of a whole dot product (132 SGPRs, spilled into VGPR
 // lanes) or waits for each group right after requesting it (a lonely wave then sits through the scalar-cache latency 90 times per block).
 struct PsdK {
-    uint64_t w[PSD_K_GROUP][3];     // (c, 2^22 c, 2^44 c) of the group's multiply-accumulates
+    uint64_t w[psd_k_group][3];     // (c, 2^22 c, 2^44 c) of the group's multiply-accumulates
     uint64_t a[2];                  // when the group opens an output: the output's additive constant (low half, high half)
 };
 template <int N, bool WITH_ADD>
@@ -259,7 +202,7 @@ GL_DEV void psd_kload(PsdK& k, psd_ktab c, psd_ktab add) {
 // earlier); on return the NEXT output's first group (table position c + 3 (11 + NX), additive constant add_next), requested, if HAS_NEXT.
 template <int NX, bool HAS_NEXT, int XCAP>
 GL_DEV void psd_dot(const uint32_t (&ul)[11][3], const uint32_t (&xl)[XCAP][3], psd_ktab c, PsdK& k, psd_ktab add_next, uint64_t& lo, uint64_t& hi) {
-    constexpr int G = PSD_K_GROUP, NT = 11 + NX, NG = (NT + G - 1) / G;
+    constexpr int G = psd_k_group, NT = 11 + NX, NG = (NT + G - 1) / G;
     PsdK cur = k;
 #pragma unroll
     for (int g = 0; g < NG; g++) {
@@ -319,7 +262,7 @@ GL_DEV void psd_partial_rounds_block(uint64_t (&s)[12]) {
         psd_ktab mac = (psd_ktab)PSD_K_MAC;
         asm volatile("" : "+s"(mac));         // re-read per block: hoisted out of this loop the table would sit in ~2 600 SGPRs
         PsdK k;
-        psd_kload<PSD_K_GROUP, true>(k, mac, add);        // y_1's first group, under the first S-box
+        psd_kload<psd_k_group, true>(k, mac, add);        // y_1's first group, under the first S-box
         __builtin_amdgcn_sched_barrier(0);
         uint32_t ul[11][3], xl[B][3];
 #pragma unroll
@@ -332,33 +275,18 @@ GL_DEV void psd_partial_rounds_block(uint64_t (&s)[12]) {
 }
 
 // 30 rounds of (constants, S-box on every element [4 + 4 full rounds] or on element 0 [22 partial rounds], MDS); round r's MDS adds round
-// r+1's constants (PSD_ALL_RC row 30 is zero).  PSD_PARTIAL_FORM 1 (default): the partial rounds in the block form above; 0: the dense form
-// for all 30 rounds (rounds 1-4: a v_mad_u64_u32 by a 6-bit MDS entry beat the 64x64 modular products of the round-by-round factored form,
-// profiles/r01_poseidon_dense_vs_sparse.txt; the block form needs neither -- A/B in profiles/r05_poseidon_block_vs_dense.txt).
-#ifndef PSD_PARTIAL_FORM
-#define PSD_PARTIAL_FORM 1
-#endif
-#ifndef PSD_ROUNDS_PER_ITER
-#define PSD_ROUNDS_PER_ITER 2
-#endif
-template <bool FULL>
+// r+1's constants (PSD_ALL_RC row 30 is zero).  The full rounds are dense (S-boxes, whole MDS layer), the partial rounds run in the block form
+// above (against the dense form for all 30 rounds: profiles/r01_poseidon_dense_vs_sparse.txt, profiles/r05_poseidon_block_vs_dense.txt).
+// Two rounds per iteration (4 + 4: always whole pairs), so the state ping-pongs between two register sets instead of being copied back at the
+// loop edge.
+constexpr int psd_rounds_per_iter = 2;
 GL_DEV void psd_dense_rounds(uint64_t (&s)[12], int r0, int r1) {
-    // two rounds per iteration (4 + 22 + 4: a pair is never mixed), so the state ping-pongs between two register sets
-    // instead of being copied back at the loop edge
 #pragma unroll 1
-    for (int r = r0; r < r1; r += PSD_ROUNDS_PER_ITER) {
+    for (int r = r0; r < r1; r += psd_rounds_per_iter) {
 #pragma unroll
-        for (int h = 0; h < PSD_ROUNDS_PER_ITER; h++) {
-            if (FULL) {
+        for (int h = 0; h < psd_rounds_per_iter; h++) {
 #pragma unroll
-#if PSD_SBOX_WIDTH == 4
-                for (int i = 0; i < 12; i += 4) psd_sbox4(s[i], s[i + 1], s[i + 2], s[i + 3]);
-#else
-                for (int i = 0; i < 12; i += 2) psd_sbox2(s[i], s[i + 1]);
-#endif
-            } else {
-                s[0] = psd_sbox(s[0]);
-            }
+            for (int i = 0; i < 12; i += 4) psd_sbox4(s[i], s[i + 1], s[i + 2], s[i + 3]);
             psd_mds(s, &PSD_ALL_RC[12 * (r + h + 1)]);
         }
     }
@@ -366,13 +294,9 @@ GL_DEV void psd_dense_rounds(uint64_t (&s)[12], int r0, int r1) {
 GL_DEV void psd_permute(uint64_t (&s)[12]) {
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = gl_add_canonical(s[i], PSD_ALL_RC[i]);
-    psd_dense_rounds<true>(s, 0, 4);
-#if PSD_PARTIAL_FORM == 1
+    psd_dense_rounds(s, 0, 4);
     psd_partial_rounds_block(s);
-#else
-    psd_dense_rounds<false>(s, 4, 26);
-#endif
-    psd_dense_rounds<true>(s, 26, 30);
+    psd_dense_rounds(s, 26, 30);
 }
 
 // digest of <= 4 elements is the elements themselves, zero padded (chip/merkle_proof_chip.rs:52-57);

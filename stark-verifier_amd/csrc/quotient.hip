@@ -78,14 +78,10 @@ struct AlphaAcc {
 // The carry-outs live in scalar register pairs; gfx950 wants two wait states between a VALU write of a scalar register and the VALU read
 // of it and the hazard recogniser does not look inside inline asm, so the two challenges' instructions are interleaved (every carry
 // is consumed four instructions after it was produced).
-#ifndef GL355_QUOT_LAZY
-#define GL355_QUOT_LAZY 1
-#endif
 template <int NCH>
 struct LazyAcc : AlphaAcc<NCH> {
     GL_DEV uint64_t value(int c) const { return this->acc[c]; }
 };
-#if GL355_QUOT_LAZY && defined(__HIP_DEVICE_COMPILE__)
 template <>
 struct LazyAcc<2> {
     uint64_t A0[2], A1[2], A2[2];
@@ -134,7 +130,6 @@ struct LazyAcc<2> {
         return gl_sub(r, (uint64_t)k2[c] << 32);
     }
 };
-#endif
 template <int NCH>
 using GateAccT = LazyAcc<NCH>;
 

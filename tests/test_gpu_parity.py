@@ -183,7 +183,10 @@ def test_two_to_one(ctx, orc):
 
 # ---- a8 ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("log_n,leaf_len,cap", [(0, 4, 0), (1, 4, 0), (1, 4, 1), (3, 4, 0), (3, 9, 1), (4, 135, 4), (6, 20, 4),
-                                                (10, 4, 0), (10, 85, 4), (12, 7, 3), (13, 4, 4)])
+                                                (10, 4, 0), (10, 85, 4), (12, 7, 3), (13, 4, 4),
+                                                # 64 cap subtrees and more: form 0 of the 16-lane kernels, which every lock-step batch takes
+                                                # (two levels in the top kernel; four levels kept in LDS; a lanes level of 2^14 nodes, then eight)
+                                                (8, 4, 6), (10, 5, 6), (15, 4, 6)])
 def test_merkle_build_and_prove(gl, ctx, orc, log_n, leaf_len, cap):
     rng = np.random.default_rng(0x3D5 + log_n * 31 + leaf_len)
     n = 1 << log_n
