@@ -734,16 +734,22 @@ int32_t gl355_plonk_check_witness(gl355_ctx* ctx, const uint64_t* desc, uint64_t
  *            below the Goldilocks prime, an ASSERT_EQ on differing cells (an invalid proof); an UNPACK cannot fail (four base-p digits
  *            recompose every scalar, utils.rs:25-36).  That is not an error: the call returns GL355_OK and the rows are written all the same, so gl355_plonk_check_witness can name them.
  *   gl355_halo2_tape_load        validates (entries whole, ops and operand kinds known, rows and input indices in range, every cell operand
- *                                written by an earlier level, no cell written twice: GL355_E_INVALID_ARG otherwise) and uploads the tape
+ *                                written by an earlier level, no cell written twice: GL355_E_INVALID_ARG otherwise) and uploads the tape and the
+ *                                table of its levels' entry ranges
  *   gl355_halo2_synthesize       one launch per level on the context's stream, one lane per entry, or eight lanes per entry with a PERMUTE
  *                                spread over five of them when the level holds one and is narrow enough to leave lanes idle (the columns
- *                                are the same either way; GL355_HALO2_SPREAD_MAX=N overrides the bound, 0 = never); inputs and advice_out in host or device
+ *                                are the same either way; GL355_HALO2_SPREAD_MAX=N overrides the bound, 0 = never); a maximal run of at least two
+ *                                consecutive levels without a PERMUTE and of at most run_max entries each is ONE launch of one workgroup, which
+ *                                replays the run level by level behind workgroup barriers (the same entry routine, so the same columns and status;
+ *                                GL355_HALO2_RUN_MAX=N, read at gl355_halo2_tape_load, overrides run_max, 0 = never); inputs and advice_out in host or device
  *                                memory (device: the columns stay resident for the prover, nothing is copied); status in host memory
  *   gl355_halo2_synthesize_host  the same validation and a sequential replay on the calling thread; needs no device */
 typedef struct gl355_halo2_tape gl355_halo2_tape;
 int32_t gl355_halo2_tape_load(gl355_ctx* ctx, const uint64_t* tape, uint64_t n_words, uint64_t n_inputs, uint32_t k, uint32_t n_advice, gl355_halo2_tape** out);
 int32_t gl355_halo2_tape_free(gl355_halo2_tape* tape);
 int32_t gl355_halo2_synthesize(gl355_ctx* ctx, const gl355_halo2_tape* tape, const uint64_t* inputs, uint64_t* advice_out, uint64_t* status /* 2 */);
+/* the launches gl355_halo2_synthesize makes for this tape, from the list it walks: out = { run_max in force, levels in runs, runs, launches } */
+int32_t gl355_halo2_tape_launches(const gl355_halo2_tape* tape, uint64_t* out /* 4 */);
 int32_t gl355_halo2_synthesize_host(const uint64_t* tape, uint64_t n_words, uint64_t n_inputs, uint32_t k, uint32_t n_advice, const uint64_t* inputs,
                                     uint64_t* advice_out, uint64_t* status /* 2 */);
 

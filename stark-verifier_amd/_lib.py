@@ -81,6 +81,7 @@ SIGNATURES = {
     "gl355_halo2_tape_load": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "gl355_halo2_tape_free": (C.c_int32, [vp]),
     "gl355_halo2_synthesize": (C.c_int32, [vp, vp, vp, vp, vp]),
+    "gl355_halo2_tape_launches": (C.c_int32, [vp, vp]),
     "gl355_halo2_synthesize_host": (C.c_int32, [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp]),
     "gl355_bn254_g2_mul": (C.c_int32, [vp, vp, vp]),
     "gl355_bn254_pairing_check": (C.c_int32, [vp, vp, C.c_uint32, C.POINTER(C.c_int32)]),

@@ -17,6 +17,10 @@
 // element are h2_round's, in the same order, so the limbs and the stored columns are the same.  Per round a lane's chain is 3 + 5 + 1 products
 // instead of 15 + 25 + 5 (full) or 3 + 25 + 5 (partial).  The rule for choosing the form is halo2_spread_level below.
 //
+// A RUN of consecutive narrow levels without a PERMUTE (the public-inputs hasher's serial Goldilocks permutations, the gate constrainers' and
+// the reduce_extension chains: part 3's many-input circuit has 61 501 levels, 61 283 of them such) is one launch of ONE workgroup that replays
+// it level by level behind workgroup barriers: halo2_run_kernel below, where the rule and the guarantees it rests on are.
+//
 // Offsets are validated once when the tape is loaded (halo2_tape_validate), so the interpreter does not bounds-check; data-dependent
 // failures (a VALUE not below p, an ASSERT_EQ on differing cells = an invalid proof) are reported as the smallest failing entry and the number of
 // failing entries, exactly like the host replay, and the rows are written all the same.
@@ -123,6 +127,54 @@ __global__ void __launch_bounds__(64) halo2_level_kernel(const uint64_t* tape, u
     }
 }
 
+// A RUN: consecutive levels, none with a PERMUTE entry and none wider than run_max, replayed by ONE workgroup in one launch instead of one
+// launch each.  The tape is level-major, so the run is the entry range level_start[first_level] .. level_start[first_level + n_levels); a
+// thread takes the entries of a level H2_RUN_THREADS apart and calls the same h2_exec, so the columns and the status words are the level
+// kernel's.  Between two levels stands __syncthreads(): a workgroup-scope release fence, the barrier, a workgroup-scope acquire fence.  What
+// makes a level's stores visible to the next level's loads is that fence pair in the AMDGPU memory model, which for gfx950 outside
+// threadgroup-split mode rests on this: the waves of a workgroup are on ONE CU and send their vector memory operations through that CU's one L1
+// in order, so a load issued after the barrier is served behind every store that a wave of the workgroup issued before it.  No wave has to
+// wait for its stores to complete before it arrives, and the compiled kernel does not (no vmcnt wait stands before its barrier).  The
+// project does not build with tgsplit.  Nothing here relies on visibility ACROSS workgroups (one workgroup per
+// launch, and launches are ordered by the stream).  Hang safety: the level loop's bound is a kernel argument, the entry loop holds no
+// barrier, and no thread returns before the last barrier -- a thread without an entry in a level still arrives, a failing entry goes on.
+__global__ void __launch_bounds__(H2_RUN_THREADS) halo2_run_kernel(const uint64_t* tape, const uint64_t* level_start, uint32_t first_level, uint32_t n_levels,
+                                                                   H2Cols c, unsigned long long* status) {
+    for (uint32_t l = 0; l < n_levels; l++) {
+        const uint64_t first = level_start[first_level + l], end = level_start[first_level + l + 1];
+        for (uint64_t i = first + threadIdx.x; i < end; i += H2_RUN_THREADS)
+            if (h2_exec(c, tape + H2_ENTRY_WORDS * i)) {
+                atomicMin(status, (unsigned long long)i);
+                atomicAdd(status + 1, 1ull);
+            }
+        __syncthreads();
+    }
+}
+
+// GL355_HALO2_RUN_MAX (entries of a level) overrides the bound of a run's levels: 0 turns the form off (profiles/halo2_synth_verifier.txt
+// has the figures with and without)
+uint64_t halo2_run_max() {
+    const char* v = getenv("GL355_HALO2_RUN_MAX");
+    return v && *v ? strtoull(v, nullptr, 10) : H2_RUN_MAX_DEFAULT;
+}
+
+// The launches of one synthesis: a level joins a run when it has no PERMUTE entry and at most run_max entries; a maximal run of at least two
+// such levels is one launch of halo2_run_kernel, every other level that holds an entry is one launch of halo2_level_kernel.  Planned once,
+// at load: gl355_halo2_synthesize walks this list and gl355_halo2_tape_launches counts it, so what is reported is what is launched.
+void halo2_plan_launches(gl355_halo2_tape* t) {
+    const size_t n_levels = t->level_start.size() - 1;
+    const auto in_run = [&](size_t l) { return l < n_levels && !t->level_permutes[l] && t->level_start[l + 1] - t->level_start[l] <= t->run_max; };
+    t->launches.clear();
+    for (size_t l = 0; l < n_levels; l++) {
+        if (t->level_start[l + 1] == t->level_start[l]) continue;
+        size_t end = l + 1;
+        if (t->run_max && in_run(l))
+            while (in_run(end)) end++;
+        t->launches.emplace_back((uint32_t)l, (uint32_t)(end - l));
+        l = end - 1;
+    }
+}
+
 // The form of a level.  SPREAD gives an entry eight lanes, so it is taken while the level still leaves lanes idle that way -- at most one wave
 // per SIMD (4 SIMDs a CU) -- and has a PERMUTE entry to gain from it; beyond that the lanes are worth more as entries.  GL355_HALO2_SPREAD_MAX
 // (entries of a level) overrides the bound: 0 turns the form off (profiles/halo2_synth_fri.txt has the figures with and without)
@@ -159,6 +211,14 @@ extern "C" int32_t gl355_halo2_tape_load(gl355_ctx* h, const uint64_t* tape, uin
     for (size_t l = 0; l + 1 < t->level_start.size(); l++)
         for (uint64_t i = t->level_start[l]; i < t->level_start[l + 1]; i++) t->level_permutes[l] += ((uint32_t)tape[H2_ENTRY_WORDS * i] & 0xFF) == H2_OP_PERMUTE;
     t->dev = nullptr;
+    t->dev_level_start = nullptr;
+    t->run_max = halo2_run_max();
+    try {
+        halo2_plan_launches(t);
+    } catch (const std::bad_alloc&) {
+        delete t;
+        return ctx->fail(GL355_E_OOM, "halo2_tape_load: out of host memory");
+    }
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) { delete t; return ctx->fail(GL355_E_HIP, "halo2_tape_load: hipDeviceGetAttribute failed"); }
     t->spread_max = halo2_spread_max(n_cu);
@@ -167,6 +227,14 @@ extern "C" int32_t gl355_halo2_tape_load(gl355_ctx* h, const uint64_t* tape, uin
         (void)hipFree(t->dev);
         delete t;
         return ctx->fail(GL355_E_HIP, "halo2_tape_load: upload failed");
+    }
+    const size_t ls_bytes = t->level_start.size() * 8;
+    if (hipMalloc(reinterpret_cast<void**>(&t->dev_level_start), ls_bytes) != hipSuccess ||
+        hipMemcpy(t->dev_level_start, t->level_start.data(), ls_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(t->dev_level_start);
+        (void)hipFree(t->dev);
+        delete t;
+        return ctx->fail(GL355_E_HIP, "halo2_tape_load: upload of the level table failed");
     }
     *out = t;
     return GL355_OK;
@@ -178,8 +246,19 @@ extern "C" int32_t gl355_halo2_tape_free(gl355_halo2_tape* t) {
         (void)hipSetDevice(t->ctx->device);
         (void)t->ctx->wait();
         (void)hipFree(t->dev);
+        (void)hipFree(t->dev_level_start);
     }
     delete t;
+    return GL355_OK;
+}
+
+extern "C" int32_t gl355_halo2_tape_launches(const gl355_halo2_tape* t, uint64_t* out) {
+    if (!t || !out) return GL355_E_INVALID_ARG;
+    out[0] = t->run_max;
+    out[1] = out[2] = 0;
+    out[3] = t->launches.size();
+    for (const auto& launch : t->launches)
+        if (launch.second > 1) { out[1] += launch.second; out[2]++; }
     return GL355_OK;
 }
 
@@ -202,10 +281,12 @@ extern "C" int32_t gl355_halo2_synthesize(gl355_ctx* h, const gl355_halo2_tape* 
     const H2Cols c = {adv.as<uint64_t>(), n, in.as<uint64_t>()};
     {
         ProfScope ps(ctx, "halo2_synthesize", bytes);
-        for (size_t l = 0; l + 1 < t->level_start.size(); l++) {
+        for (const auto& launch : t->launches) {
+            const uint32_t l = launch.first;
             const uint64_t first = t->level_start[l], count = t->level_start[l + 1] - first;
-            if (!count) continue;
-            if (t->level_permutes[l] && count <= t->spread_max)
+            if (launch.second > 1)                                // a run: one launch, one workgroup
+                hipLaunchKernelGGL(halo2_run_kernel, dim3(1), dim3(H2_RUN_THREADS), 0, ctx->stream, t->dev, t->dev_level_start, l, launch.second, c, d_status);
+            else if (t->level_permutes[l] && count <= t->spread_max)
                 hipLaunchKernelGGL(halo2_level_kernel<true>, dim3((uint32_t)((count * H2_SPREAD_LANES + 63) / 64)), dim3(64), 0, ctx->stream, t->dev, first, count, c, d_status);
             else
                 hipLaunchKernelGGL(halo2_level_kernel<false>, dim3((uint32_t)((count + 63) / 64)), dim3(64), 0, ctx->stream, t->dev, first, count, c, d_status);

@@ -26,6 +26,8 @@
 // A failing entry still writes its rows (gl355_plonk_check_witness then names the row); the smallest failing entry index and the
 // number of failing entries are the status.  Entries are stored level-major: level = 1 + the largest level among the writers of its
 // CELL / BIT / INV operands, so the entries of one level are independent and the tape order is a topological order.
+// Level-major also means that a RUN of consecutive levels is one contiguous range of entries: the device replays a run of narrow levels
+// without a PERMUTE in one launch (halo2_run_kernel, halo2_synth.hip), from that range and the run's slice of the level table.
 #pragma once
 #include <stdint.h>
 
@@ -39,7 +41,7 @@ struct Ctx;
 
 enum { H2_OP_CONST = 1, H2_OP_VALUE = 2, H2_OP_MULADD = 3, H2_OP_MULADD_EXT = 4, H2_OP_PACK = 5, H2_OP_UNPACK = 6, H2_OP_PERMUTE = 7, H2_OP_ASSERT_EQ = 8 };
 enum { H2_K_NONE = 0, H2_K_CELL = 1, H2_K_INPUT = 2, H2_K_BIT = 3, H2_K_INV = 4, H2_K_INV_EXT = 5 };
-enum { H2_ENTRY_WORDS = 8, H2_N_ADVICE = 19, H2_PERMUTE_ROWS = 69, H2_SPREAD_LANES = 8 };
+enum { H2_ENTRY_WORDS = 8, H2_N_ADVICE = 19, H2_PERMUTE_ROWS = 69, H2_SPREAD_LANES = 8, H2_RUN_THREADS = 256, H2_RUN_MAX_DEFAULT = 256 };
 enum { H2_COL_A = 0, H2_COL_B = 1, H2_COL_C = 2, H2_COL_Q = 3, H2_COL_R = 4, H2_COL_QL = 5, H2_COL_RL = 10, H2_COL_STATE = 14 };
 
 typedef unsigned __int128 h2_u128;
@@ -285,7 +287,11 @@ struct gl355_halo2_tape {
     std::vector<uint64_t> level_start;      // [levels + 1] entry indices
     std::vector<uint32_t> level_permutes;   // [levels] PERMUTE entries of each level (device tapes: the kernel's form depends on it)
     uint64_t spread_max;                    // a level of at most this many entries with a PERMUTE among them runs the kernel's spread form
+    uint64_t run_max;                       // a level of at most this many entries and no PERMUTE joins a run (halo2_run_kernel); 0: no runs
+    std::vector<std::pair<uint32_t, uint32_t>> launches;      // device tapes: (first level, levels) of every launch of one synthesis, in order, planned
+                                                              // at load (halo2_plan_launches); two or more levels: a run
     uint64_t* dev;
+    uint64_t* dev_level_start;              // level_start on the device, uploaded once at load: a run reads its slice of it
 };
 
 namespace gl355 {

@@ -345,6 +345,12 @@ class DeviceTape:
         ctx.check(ctx.lib.gl355_halo2_synthesize(ctx.h, self.h, ptr(inputs), ptr(out), status.ctypes.data))
         return out, (int(status[0]), int(status[1]))
 
+    def launches(self):
+        """-> {run_max, levels_in_runs, runs, launches}: what one synthesize() launches, from the list the library walks (gl355_halo2_tape_launches)"""
+        out = np.zeros(4, dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.gl355_halo2_tape_launches(self.h, out.ctypes.data))
+        return dict(zip(("run_max", "levels_in_runs", "runs", "launches"), (int(v) for v in out)))
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.gl355_halo2_tape_free(self.h)

@@ -1,4 +1,4 @@
-"""Parts 1 and 2 of the Halo2 verifier circuit, recorded over the chips of halo2_goldilocks.py.
+"""The Halo2 verifier circuit, recorded over the chips of halo2_goldilocks.py.
 
 FriOpeningsCircuit (part 1): every Merkle opening of a plonky2 proof's FRI query rounds, verified in circuit against its caps under
 Bn254PoseidonHash.
@@ -21,11 +21,19 @@ values at zeta and g zeta.
   the challenges                    chip/plonk/plonk_verifier_chip.rs:55-154
   FRI                               chip/plonk/plonk_verifier_chip.rs:212-240, chip/fri_chip.rs:329-376
 
-What part 3 still owes: eval_vanishing_poly with the 12 gate constrainers and the quotient identity (plonk_verifier_chip.rs:165-210), and
-PublicInputsHasherChip; until then the public-inputs hash is four input words, exposed as the instances."""
+Plonky2VerifierCircuit (part 3): the whole of Verifier::synthesize.  The public inputs are the instances and are hashed in circuit
+(PublicInputsHasherChip), the plonk betas, gammas and alphas are kept, eval_vanishing_poly with the 12 gate constrainers gives the vanishing
+polynomial at zeta, the quotient identity is asserted, and FRI follows: a Halo2 proof over this circuit proves that the plonky2 proof verifies.
+
+  the order of synthesis            verifier_circuit.rs:148-200
+  the public-inputs hash            chip/plonk/plonk_verifier_chip.rs:42-53, chip/public_inputs_hasher_chip.rs
+  the vanishing identity            chip/plonk/plonk_verifier_chip.rs:156-210, chip/plonk/vanishing_poly.rs, chip/plonk/gates/ (halo2_plonk_chips.py)
+
+The two earlier circuits stay as recorded artifacts may depend on them; the three share the helpers of FriVerifierCircuit."""
 import numpy as np
 
 from . import halo2_goldilocks as hg
+from . import halo2_plonk_chips as hp
 
 SALT_SIZE = 4
 
@@ -153,17 +161,10 @@ class FriVerifierCircuit:
         assert out.size == self.n_inputs
         return out
 
-    def record(self, inputs, min_k=17):
-        """-> the Recorder of the circuit at the smallest k that holds it; round_rows[i] is the half-open row range of query round i and
-        challenge_cells holds the cells of fri_alpha, fri_betas, pow_response and indices"""
-        cd = self.cd
-        rec = hg.Recorder(28, inputs)
-        g = hg.GoldilocksChip(rec)
-        ge = hg.GoldilocksExtensionChip(rec)
-        g.load_table()
+    # ---- the parts of Verifier::synthesize that FriVerifierCircuit and Plonky2VerifierCircuit share ----
+    def _assign_proof(self, g):
+        """assign_proof_with_pis after the public inputs (verifier_circuit.rs:95-100) -> the proof's cells"""
         value = lambda words: [g.assign_value(hg.Input(w)) for w in words]                            # noqa: E731
-        # assign_proof_with_pis (the public inputs' place is taken by their hash), then assign_verification_key
-        public_inputs_hash = value(self.pi_hash)
         wires_cap, zs_cap, quotient_cap = [[value(h) for h in cap] for cap in self.proof_caps]
         op = {name: [value(e) for e in self.openings[name]]
               for name in ("constants", "plonk_sigmas", "wires", "plonk_zs", "plonk_zs_next", "partial_products", "quotient_polys")}
@@ -177,18 +178,27 @@ class FriVerifierCircuit:
         final_poly = [value(e) for e in self.final_poly]
         pow_witness = g.assign_value(hg.Input(self.pow_witness))
         fri_proof = dict(commit_phase_merkle_caps=layer_caps, query_round_proofs=rounds, final_poly=final_poly)
+        return dict(wires_cap=wires_cap, zs_cap=zs_cap, quotient_cap=quotient_cap, openings=op, fri_proof=fri_proof, pow_witness=pow_witness)
+
+    def _assign_verification_key(self, g):
+        """assign_verification_key (verifier_circuit.rs:113-127) -> (constants_sigmas_cap, circuit_digest) as constants"""
+        cd = self.cd
         constants_sigmas_cap = [[g.assign_constant(int(w)) for w in h] for h in np.asarray(cd["constants_sigmas_cap"], dtype=np.uint64).reshape(-1, 4)]
         circuit_digest = [g.assign_constant(int(w)) for w in cd["circuit_digest"]]
-        # get_challenges, plonk_verifier_chip.rs:55-154
+        return constants_sigmas_cap, circuit_digest
+
+    def _get_challenges(self, rec, proof, circuit_digest, public_inputs_hash):
+        """get_challenges, plonk_verifier_chip.rs:55-154 -> every challenge's cells and the FRI openings"""
+        op, fri_proof = proof["openings"], proof["fri_proof"]
         tr = hg.TranscriptChip(rec)
         for e in circuit_digest + public_inputs_hash:
             tr.write_scalar(e)
-        tr.write_cap(wires_cap)
-        tr.squeeze(self.nch)                                         # the plonk betas, gammas and alphas: part 3's
-        tr.squeeze(self.nch)
-        tr.write_cap(zs_cap)
-        tr.squeeze(self.nch)
-        tr.write_cap(quotient_cap)
+        tr.write_cap(proof["wires_cap"])
+        plonk_betas = tr.squeeze(self.nch)
+        plonk_gammas = tr.squeeze(self.nch)
+        tr.write_cap(proof["zs_cap"])
+        plonk_alphas = tr.squeeze(self.nch)
+        tr.write_cap(proof["quotient_cap"])
         plonk_zeta = tr.squeeze(2)
         fri_openings = [op["constants"] + op["plonk_sigmas"] + op["wires"] + op["plonk_zs"] + op["partial_products"] + op["quotient_polys"],
                         op["plonk_zs_next"]]                         # to_fri_openings, types/assigned.rs:26-44
@@ -197,25 +207,104 @@ class FriVerifierCircuit:
                 tr.write_extension(e)
         fri_alpha = tr.squeeze(2)
         fri_betas = []
-        for cap in layer_caps:
+        for cap in fri_proof["commit_phase_merkle_caps"]:
             tr.write_cap(cap)
             fri_betas.append(tr.squeeze(2))
-        for e in final_poly:
+        for e in fri_proof["final_poly"]:
             tr.write_extension(e)
-        tr.write_scalar(pow_witness)
+        tr.write_scalar(proof["pow_witness"])
         fri_pow_response = tr.squeeze(1)[0]
         fri_query_indices = tr.squeeze(self.n_queries)
-        self.challenge_cells = dict(fri_alpha=fri_alpha, fri_betas=fri_betas, pow_response=fri_pow_response, indices=fri_query_indices)
-        # verify_proof_with_challenges from zeta_next on, plonk_verifier_chip.rs:212-240
-        merkle_caps = [constants_sigmas_cap, wires_cap, zs_cap, quotient_cap]
-        zeta_next = ge.scalar_mul(plonk_zeta, hg.primitive_root_of_unity(cd["degree_bits"]))
-        info = hg.FriInstanceInfo(plonk_zeta, zeta_next, self.widths, self.nch)
+        return dict(plonk_betas=plonk_betas, plonk_gammas=plonk_gammas, plonk_alphas=plonk_alphas, plonk_zeta=plonk_zeta, fri_openings=fri_openings,
+                    fri_alpha=fri_alpha, fri_betas=fri_betas, fri_pow_response=fri_pow_response, fri_query_indices=fri_query_indices)
+
+    def _verify_fri(self, rec, g, ge, proof, constants_sigmas_cap, ch):
+        """verify_proof_with_challenges from zeta_next on, plonk_verifier_chip.rs:212-240; sets round_rows"""
+        cd = self.cd
+        merkle_caps = [constants_sigmas_cap, proof["wires_cap"], proof["zs_cap"], proof["quotient_cap"]]
+        zeta_next = ge.scalar_mul(ch["plonk_zeta"], hg.primitive_root_of_unity(cd["degree_bits"]))
+        info = hg.FriInstanceInfo(ch["plonk_zeta"], zeta_next, self.widths, self.nch)
         offset = g.assign_constant(hg.GENERATOR)
         fri = hg.FriVerifierChip(rec, offset, self.lde_bits, self.cap_height, self.arity_bits, bool(cd["hiding"]), cd["pow_bits"])
-        fri.verify_fri_proof(merkle_caps, dict(fri_alpha=fri_alpha, fri_betas=fri_betas, fri_pow_response=fri_pow_response,
-                                               fri_query_indices=fri_query_indices), fri_openings, fri_proof, info)
+        fri.verify_fri_proof(merkle_caps, dict(fri_alpha=ch["fri_alpha"], fri_betas=ch["fri_betas"], fri_pow_response=ch["fri_pow_response"],
+                                               fri_query_indices=ch["fri_query_indices"]), ch["fri_openings"], proof["fri_proof"], info)
         self.round_rows = fri.round_rows
+
+    def record(self, inputs, min_k=17):
+        """-> the Recorder of the circuit at the smallest k that holds it; round_rows[i] is the half-open row range of query round i and
+        challenge_cells holds the cells of fri_alpha, fri_betas, pow_response and indices"""
+        rec = hg.Recorder(28, inputs)
+        g = hg.GoldilocksChip(rec)
+        ge = hg.GoldilocksExtensionChip(rec)
+        g.load_table()
+        # assign_proof_with_pis (the public inputs' place is taken by their hash), then assign_verification_key
+        public_inputs_hash = [g.assign_value(hg.Input(w)) for w in self.pi_hash]
+        proof = self._assign_proof(g)
+        constants_sigmas_cap, circuit_digest = self._assign_verification_key(g)
+        ch = self._get_challenges(rec, proof, circuit_digest, public_inputs_hash)      # the plonk betas, gammas and alphas are not used here
+        self.challenge_cells = dict(fri_alpha=ch["fri_alpha"], fri_betas=ch["fri_betas"], pow_response=ch["fri_pow_response"], indices=ch["fri_query_indices"])
+        self._verify_fri(rec, g, ge, proof, constants_sigmas_cap, ch)
         for row, cell in enumerate(public_inputs_hash):
+            g.arithmetic_chip.expose_public(cell, row)
+        rec.shrink_to_fit(min_k)
+        return rec
+
+
+class Plonky2VerifierCircuit(FriVerifierCircuit):
+    """The whole of Verifier::synthesize (verifier_circuit.rs:148-200).  The input vector is the flat proof of gl355_prove followed by the
+    public inputs themselves, which are the instances; their hash, every challenge, the vanishing polynomial at zeta and the quotient identity
+    are computed and asserted in circuit.  The number of public inputs is a property of the plonky2 circuit that common_data does not carry:
+    it is given here, or taken from the first input vector."""
+
+    def __init__(self, common_data, num_public_inputs=None):
+        super().__init__(common_data)
+        del self.pi_hash
+        self.num_public_inputs = num_public_inputs
+        self.vanishing_cells, self.identity_rows = [], []
+        self._set_inputs()
+
+    def _set_inputs(self):
+        n = self.num_public_inputs or 0
+        self.public_inputs = list(range(self.proof_words, self.proof_words + n))
+        self.n_inputs = self.proof_words + n
+
+    def inputs(self, flat, public_inputs):
+        flat = np.ascontiguousarray(flat, dtype=np.uint64).reshape(-1)
+        public_inputs = np.asarray(public_inputs, dtype=np.uint64).reshape(-1)
+        assert flat.size == self.proof_words == int(flat[0]) and int(flat[4]) == public_inputs.size, "not a proof of this circuit"
+        if self.num_public_inputs is None:
+            self.num_public_inputs = int(public_inputs.size)
+            self._set_inputs()
+        out = np.concatenate([flat, public_inputs])
+        assert out.size == self.n_inputs
+        return out
+
+    def record(self, inputs, min_k=17):
+        """-> the Recorder of the circuit at the smallest k that holds it.  challenge_cells holds the cells of every challenge (betas, gammas,
+        alphas, zeta, fri_alpha, fri_betas, pow_response, indices), vanishing_cells the vanishing polynomial at zeta (one extension element
+        per challenge), identity_rows the rows whose cells the quotient identity's assertions compare, round_rows the FRI query rounds"""
+        if self.num_public_inputs is None:
+            self.num_public_inputs = len(inputs) - self.proof_words
+            self._set_inputs()
+        assert len(inputs) == self.n_inputs
+        rec = hg.Recorder(28, inputs)
+        g = hg.GoldilocksChip(rec)
+        ge = hg.GoldilocksExtensionChip(rec)
+        g.load_table()
+        public_inputs = [g.assign_value(hg.Input(w)) for w in self.public_inputs]      # assign_proof_with_pis, verifier_circuit.rs:81-111
+        proof = self._assign_proof(g)
+        constants_sigmas_cap, circuit_digest = self._assign_verification_key(g)
+        plonk = hp.PlonkVerifierChip(rec, self.cd)
+        public_inputs_hash = plonk.get_public_inputs_hash(public_inputs)
+        ch = self._get_challenges(rec, proof, circuit_digest, public_inputs_hash)
+        self.challenge_cells = dict(betas=ch["plonk_betas"], gammas=ch["plonk_gammas"], alphas=ch["plonk_alphas"], zeta=ch["plonk_zeta"],
+                                    fri_alpha=ch["fri_alpha"], fri_betas=ch["fri_betas"], pow_response=ch["fri_pow_response"], indices=ch["fri_query_indices"])
+        # verify_proof_with_challenges, plonk_verifier_chip.rs:156-242
+        self.vanishing_cells = plonk.verify_vanishing_identity(proof["openings"], public_inputs_hash, ch["plonk_zeta"], ch["plonk_betas"],
+                                                               ch["plonk_gammas"], ch["plonk_alphas"])
+        self.identity_rows = plonk.identity_rows
+        self._verify_fri(rec, g, ge, proof, constants_sigmas_cap, ch)
+        for row, cell in enumerate(public_inputs):                   # verifier_circuit.rs:190-198
             g.arithmetic_chip.expose_public(cell, row)
         rec.shrink_to_fit(min_k)
         return rec

@@ -15,7 +15,13 @@ five kept) against gl355_halo2_synthesize_host on one thread plus the upload of 
 without the device path pays; rows, k, entries, levels and their widths; the status must be NO_FAILURE and gl355_plonk_check_witness must find
 nothing; create_proof on the synthesised witness against synthetic_circuit at the same k (--no-synthetic leaves that out).  One JSON line per
 circuit.  --levels DIR also writes per level [entries, PERMUTE entries] (the launches of one synthesis, in order) and the tape with its inputs
-there: what a kernel trace of the run is joined with (profiles/halo2_synth_fri.txt)."""
+there: what a kernel trace of the run is joined with (profiles/halo2_synth_fri.txt).  `verifier` among the circuits is Plonky2VerifierCircuit (part 3);
+`--aggregate N` takes, instead of the wrap of one Semaphore signal, the wrap of an aggregation of N signals (4 + 8 N public inputs: the
+reference's own benchmark flow with N = 128), the circuits' names then end in _aggN.  Every line also says how many levels fall into runs and
+how many runs and launches there are under the run_max in force, as the library itself reports them (gl355_halo2_tape_launches).
+`--tapes DIR`: device synthesis alone (one warm-up, best of five) of every tape_*.npz a `--synth --levels DIR` run left there, one JSON line per
+tape: cheap enough to start one process per setting of GL355_HALO2_RUN_MAX / GL355_HALO2_SPREAD_MAX and alternate them
+(profiles/halo2_synth_verifier.txt)."""
 import importlib
 import json
 import os
@@ -201,6 +207,64 @@ def wrap_proof(gl, ctx):
     return wc, flat, pis
 
 
+def aggregate_wrap_proof(gl, ctx, n_signals):
+    """n_signals Semaphore signals of one access set -> the aggregation tree (recursion.rs:187-247) -> its BN254-Poseidon wrap
+    -> (the wrap circuit, its flat proof, its 4 + 8 n_signals public inputs)"""
+    from oracle_lib import rand_field
+    rcn = importlib.import_module("stark-verifier_amd.recursion")
+    sem = importlib.import_module("stark-verifier_amd.semaphore")
+    plonk = importlib.import_module("stark-verifier_amd.plonk")
+    assert n_signals >= 2 and n_signals & (n_signals - 1) == 0
+    rng = np.random.default_rng(0x2543)
+    sks = rand_field(rng, (n_signals, 4))
+    keys = ctx.hash_no_pad(np.concatenate([sks, np.zeros_like(sks)], axis=1))
+    aset = sem.AccessSet(ctx, keys)
+    topic = rand_field(rng, 4)
+    data, rows = aset.build(rng)
+    idx, _, _ = aset.witness_rows(rows, sks[0], topic, 0)
+    semc = plonk.NativeCircuit(ctx, data.export_blob(idx))
+    leaves, proofs, _ = plonk.semaphore_units([ctx], semc, None, sks, topic, aset.tree.digests, np.arange(n_signals, dtype=np.uint64), 7000, want_proofs=True)
+    signals = [(proofs[j], np.concatenate([aset.tree.cap[0], leaves[j]])) for j in range(n_signals)]
+    proof, pis, cd = rcn.Aggregator(ctx, data.common()).aggregate(signals, seed=100, rng=rng)
+    wc = rcn.WrapperCircuit(ctx, cd).build([(proof, pis)], rng)
+    flat, wpis = wc.prove_flat([(proof, pis)], seed=17)
+    assert wpis.size == 4 + 8 * n_signals
+    return wc, flat, wpis
+
+
+def time_synthesis(ctx, tape, k, inputs):
+    """one warm-up, five timed calls with the inputs and the columns resident -> (sorted ms, status, the columns on the device, the DeviceTape)"""
+    import torch
+    hg = importlib.import_module("stark-verifier_amd.halo2_goldilocks")
+    dt = hg.DeviceTape(ctx, tape, k, inputs.size)
+    d_in = torch.from_numpy(inputs.view(np.int64)).cuda()
+    dev = torch.empty((hg.N_ADVICE, 1 << k, 4), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    _, status = dt.synthesize(d_in.data_ptr(), out=dev.data_ptr())                 # warm
+    runs = sorted(timed(lambda: dt.synthesize(d_in.data_ptr(), out=dev.data_ptr()), 1)[1] for _ in range(5))
+    return runs, status, dev, d_in, dt
+
+
+def run_tapes(gl, ctx, directory):
+    """device synthesis alone of every tape_*.npz in `directory` -> one dict per tape"""
+    hg = importlib.import_module("stark-verifier_amd.halo2_goldilocks")
+    outs = []
+    for f in sorted(os.listdir(directory)):
+        if not (f.startswith("tape_") and f.endswith(".npz")):
+            continue
+        z = np.load(os.path.join(directory, f))
+        name = f[5:-4]
+        runs, status, dev, d_in, dt = time_synthesis(ctx, z["tape"], int(z["k"][0]), z["inputs"])
+        levels = np.load(os.path.join(directory, "levels_%s.npy" % name))
+        outs.append({"circuit": name, "k": int(z["k"][0]), **dt.launches(),
+                     "spread_max": os.environ.get("GL355_HALO2_SPREAD_MAX", "default"), "levels": len(levels), "device_synthesis_ms": runs[0], "device_synthesis_ms_runs": runs,
+                     "status": [int(status[0]) if status[0] != hg.NO_FAILURE else -1, status[1]],
+                     "columns_word_sum": int(dev.sum().item()) & 0xFFFFFFFFFFFFFFFF})
+        dt.close()
+        del dev, d_in
+    return outs
+
+
 def level_table(rec):
     """per level of the tape: [entries, PERMUTE entries] (the order of gl355_halo2_synthesize's launches)"""
     hg = importlib.import_module("stark-verifier_amd.halo2_goldilocks")
@@ -231,12 +295,8 @@ def synth_circuit(gl, ctx, name, circuit, inputs, out, levels_dir=None):
         os.makedirs(levels_dir, exist_ok=True)
         np.save(os.path.join(levels_dir, "levels_%s.npy" % name), levels)
         np.savez(os.path.join(levels_dir, "tape_%s.npz" % name), tape=tape, inputs=inputs, k=np.array([k]))
-    dt = hg.DeviceTape(ctx, tape, k, inputs.size)
-    d_in = torch.from_numpy(inputs.view(np.int64)).cuda()
-    dev = torch.empty((hg.N_ADVICE, 1 << k, 4), dtype=torch.int64, device="cuda")
-    torch.cuda.synchronize()
-    _, status = dt.synthesize(d_in.data_ptr(), out=dev.data_ptr())                 # warm
-    runs = sorted(timed(lambda: dt.synthesize(d_in.data_ptr(), out=dev.data_ptr()), 1)[1] for _ in range(5))
+    runs, status, dev, d_in, dt = time_synthesis(ctx, tape, k, inputs)
+    out.update(dt.launches())                                        # run_max in force, levels in runs, runs, launches: the library's own list
     out["device_synthesis_ms"], out["device_synthesis_ms_runs"] = runs[0], runs
     out["status"] = [int(status[0]) if status[0] != hg.NO_FAILURE else -1, status[1]]
     assert status == (hg.NO_FAILURE, 0), "the circuit refuses the wrap proof: %r" % (status,)
@@ -272,22 +332,28 @@ def synth_circuit(gl, ctx, name, circuit, inputs, out, levels_dir=None):
     return out
 
 
-def run_synth(gl, ctx, which=("openings", "fri"), levels_dir=None, synthetic=True):
-    """-> one dict per circuit of `which`: FriOpeningsCircuit (part 1) and FriVerifierCircuit (part 2) over the same wrap proof"""
+def run_synth(gl, ctx, which=("openings", "fri"), levels_dir=None, synthetic=True, aggregate=0):
+    """-> one dict per circuit of `which`: FriOpeningsCircuit (part 1), FriVerifierCircuit (part 2) and Plonky2VerifierCircuit (part 3) over
+    the same wrap proof: of one Semaphore signal, or of an aggregation of `aggregate` signals"""
     vc = importlib.import_module("stark-verifier_amd.halo2_verifier_circuit")
     plonk = importlib.import_module("stark-verifier_amd.plonk")
-    wc, flat, pis = wrap_proof(gl, ctx)
+    t0 = time.perf_counter()
+    wc, flat, pis = aggregate_wrap_proof(gl, ctx, aggregate) if aggregate else wrap_proof(gl, ctx)
+    proof_s = round(time.perf_counter() - t0, 1)
     cd = wc.data.common()
     outs = []
     for name in which:
-        out = {"wrap_degree_bits": int(wc.data.degree_bits), "proof_words": int(flat.size)}
+        out = {"wrap_degree_bits": int(wc.data.degree_bits), "proof_words": int(flat.size), "public_inputs": int(len(pis)), "wrap_proof_s": proof_s}
         if name == "openings":
             circuit = vc.FriOpeningsCircuit(cd)
             inputs = circuit.inputs(flat)
-        else:
+        elif name == "fri":
             circuit = vc.FriVerifierCircuit(cd)
             inputs = circuit.inputs(flat, plonk.host_hash_no_pad(pis))
-        synth_circuit(gl, ctx, name, circuit, inputs, out, levels_dir)
+        else:
+            circuit = vc.Plonky2VerifierCircuit(cd)
+            inputs = circuit.inputs(flat, pis)
+        synth_circuit(gl, ctx, name + ("_agg%d" % aggregate if aggregate else ""), circuit, inputs, out, levels_dir)
         if synthetic:
             out["create_proof_synthetic_circuit_ms"] = round(run(gl, ctx, out["k"], verify=False, reps=5)["create_proof_s"] * 1e3, 1)
         outs.append(out)
@@ -303,11 +369,17 @@ if __name__ == "__main__":
         print(json.dumps(run_batch(gl, ctx)), flush=True)
         ctx.close()
         sys.exit(0)
+    if sys.argv[1:2] == ["--tapes"]:
+        for out in run_tapes(gl, ctx, sys.argv[2]):
+            print(json.dumps(out), flush=True)
+        ctx.close()
+        sys.exit(0)
     if sys.argv[1:2] == ["--synth"]:
         rest = sys.argv[2:]
         levels_dir = rest[rest.index("--levels") + 1] if "--levels" in rest else None
-        which = [a for a in rest if a in ("openings", "fri")] or ["openings", "fri"]
-        for out in run_synth(gl, ctx, which, levels_dir, synthetic="--no-synthetic" not in rest):
+        which = [a for a in rest if a in ("openings", "fri", "verifier")] or ["openings", "fri"]
+        aggregate = int(rest[rest.index("--aggregate") + 1]) if "--aggregate" in rest else 0
+        for out in run_synth(gl, ctx, which, levels_dir, synthetic="--no-synthetic" not in rest, aggregate=aggregate):
             print(json.dumps(out), flush=True)
         ctx.close()
         sys.exit(0)
