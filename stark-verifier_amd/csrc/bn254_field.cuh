@@ -9,6 +9,7 @@
 #endif
 #include "bn254_curve_tables.h"
 #include "bn254_addsub_asm.cuh"
+#include "host_mont.h"
 
 // gl355_bn254_g1_msm_prepare's handle (built in bn254_kzg.hip, read by bn254_msm.hip): the window multiples of a base set (device), see msm_table_build_kernel
 struct gl355_msm_bases {
@@ -154,65 +155,12 @@ template <int F> GL_DEV u256 m_inv(const u256& a) {
 }
 
 
-// host-side Fr helpers for the few constants a call needs (omega_n, n^-1): plain 256-bit integers with __int128
-typedef unsigned __int128 u128;
-struct H256 { uint64_t l[4]; };
-static const uint64_t HR[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};   // r
-inline bool h_geq(const H256& a) {
-    for (int i = 3; i >= 0; i--) { if (a.l[i] > HR[i]) return true; if (a.l[i] < HR[i]) return false; }
-    return true;
-}
-inline H256 h_addmod(const H256& a, const H256& b) {
-    H256 r; u128 c = 0;
-    for (int i = 0; i < 4; i++) { c += (u128)a.l[i] + b.l[i]; r.l[i] = (uint64_t)c; c >>= 64; }
-    if (c || h_geq(r)) { u128 br = 0; for (int i = 0; i < 4; i++) { u128 d = (u128)r.l[i] - HR[i] - (uint64_t)br; r.l[i] = (uint64_t)d; br = (d >> 64) & 1; } }
-    return r;
-}
-inline H256 h_mulmod(const H256& a, const H256& b) {          // double-and-add: called a few dozen times per API call
-    H256 r = {{0, 0, 0, 0}};
-    for (int i = 255; i >= 0; i--) {
-        r = h_addmod(r, r);
-        if ((b.l[i >> 6] >> (i & 63)) & 1) r = h_addmod(r, a);
-    }
-    return r;
-}
-inline H256 h_powmod(H256 a, const H256& e) {
-    H256 r = {{1, 0, 0, 0}};
-    for (int i = 255; i >= 0; i--) {
-        r = h_mulmod(r, r);
-        if ((e.l[i >> 6] >> (i & 63)) & 1) r = h_mulmod(r, a);
-    }
-    return r;
-}
-inline u256 to_u256(const H256& a) {
+// A host scalar (host_mont.h's Fr) as a kernel argument: to_u256(x.l) hands over the Montgomery form, to_u256 of x.to_words the plain integer
+inline u256 to_u256(const uint64_t w[4]) {
     u256 r;
-    for (int i = 0; i < 4; i++) { r.l[2 * i] = (uint32_t)a.l[i]; r.l[2 * i + 1] = (uint32_t)(a.l[i] >> 32); }
+    for (int i = 0; i < 4; i++) { r.l[2 * i] = (uint32_t)w[i]; r.l[2 * i + 1] = (uint32_t)(w[i] >> 32); }
     return r;
 }
-
-
-inline H256 h_from_words(const uint64_t w[4]) {
-    H256 a = {{w[0], w[1], w[2], w[3]}};
-    while (h_geq(a)) { u128 br = 0; for (int i = 0; i < 4; i++) { u128 d = (u128)a.l[i] - HR[i] - (uint64_t)br; a.l[i] = (uint64_t)d; br = (d >> 64) & 1; } }
-    return a;
-}
-inline H256 h_submod(const H256& a, const H256& b) {
-    H256 nb; u128 br = 0;
-    for (int i = 0; i < 4; i++) { u128 d = (u128)HR[i] - b.l[i] - (uint64_t)br; nb.l[i] = (uint64_t)d; br = (d >> 64) & 1; }
-    if ((b.l[0] | b.l[1] | b.l[2] | b.l[3]) == 0) nb = H256{{0, 0, 0, 0}};
-    return h_addmod(a, nb);
-}
-inline u256 h_to_mont(const H256& a) {
-    const H256 Rm = {{BN254C_FR_ONE_64[0], BN254C_FR_ONE_64[1], BN254C_FR_ONE_64[2], BN254C_FR_ONE_64[3]}};      // R mod r
-    return to_u256(h_mulmod(a, Rm));
-}
-inline H256 h_root_of_unity(uint32_t log_n) {
-    H256 w = {{BN254C_FR_ROOT_64[0], BN254C_FR_ROOT_64[1], BN254C_FR_ROOT_64[2], BN254C_FR_ROOT_64[3]}};
-    for (uint32_t k = log_n; k < BN254C_FR_S; k++) w = h_mulmod(w, w);
-    return w;
-}
-
-
 
 // ---- bn254_fr_fft.hip / bn254_msm.hip / bn254_kzg.hip: what the curve units call of each other, and the resident building blocks of the PLONK
 // prover (plonk_bn254.hip)
@@ -235,5 +183,5 @@ int32_t bn254_fr_ntt_mont_from_bitrev(Ctx* ctx, const uint64_t* in, uint64_t* ou
 // in: 2^log_in values, out: n_out values of the 2^log_n-point transform, device arrays of plain integers; shift == nullptr: the plain transform
 int32_t fr_ntt_run(Ctx* ctx, const uint64_t* in, uint32_t log_in, uint64_t* out, uint64_t n_out, uint32_t log_n, int32_t inverse, const uint64_t* shift);
 // Q[i] = sum_{j > i} A[j] z^(j - i - 1), E = sum_j A[j] z^j on device arrays (see the division kernels of bn254_kzg.hip)
-int32_t kzg_divide(Ctx* ctx, const uint64_t* A, uint64_t m, const H256& z, int a_is_mont, uint64_t* Q, int q_plain, uint64_t* E_mont);
+int32_t kzg_divide(Ctx* ctx, const uint64_t* A, uint64_t m, const Fr& z, int a_is_mont, uint64_t* Q, int q_plain, uint64_t* E_mont);
 }  // namespace gl355

@@ -205,15 +205,13 @@ __global__ void __launch_bounds__(256) fr_fft_pass_kernel(FrPass a) {
 // `tw` holds n / 2 + 1 elements; scratch for the two seed tables comes from the context.
 int32_t bn254_fr_twiddles(Ctx* ctx, uint32_t log_n, bool inverse, uint64_t* tw) {
     const uint64_t n = 1ull << log_n;
-    H256 w = inverse ? H256{{BN254C_FR_ROOT_INV_64[0], BN254C_FR_ROOT_INV_64[1], BN254C_FR_ROOT_INV_64[2], BN254C_FR_ROOT_INV_64[3]}}
-                     : H256{{BN254C_FR_ROOT_64[0], BN254C_FR_ROOT_64[1], BN254C_FR_ROOT_64[2], BN254C_FR_ROOT_64[3]}};
-    for (uint32_t k = log_n; k < BN254C_FR_S; k++) w = h_mulmod(w, w);
+    const Fr w = inverse ? Fr::root_of_unity(log_n).inv() : Fr::root_of_unity(log_n);
     const uint64_t count = std::max<uint64_t>(1, n / 2), n_hi = (count + 1023) / 1024;
     Scratch seed(ctx);
     GL355_TRY(seed.get((1024 + n_hi) * 32));
     uint64_t* lo = seed.as<uint64_t>();
     uint64_t* hi = lo + 4 * 1024;
-    hipLaunchKernelGGL(fr_twiddle_seed_kernel, dim3((uint32_t)((1024 + n_hi + 255) / 256)), dim3(256), 0, ctx->stream, lo, hi, n_hi, h_to_mont(w));
+    hipLaunchKernelGGL(fr_twiddle_seed_kernel, dim3((uint32_t)((1024 + n_hi + 255) / 256)), dim3(256), 0, ctx->stream, lo, hi, n_hi, to_u256(w.l));
     hipLaunchKernelGGL(fr_twiddle_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, tw, count, lo, hi);
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
@@ -225,9 +223,9 @@ int32_t bn254_fr_power_table(Ctx* ctx, const uint64_t base[4], const uint64_t f[
     GL355_TRY(seed.get((1024 + n_hi) * 32));
     uint64_t* lo = seed.as<uint64_t>();
     uint64_t* hi = lo + 4 * 1024;
-    hipLaunchKernelGGL(fr_twiddle_seed_kernel, dim3((uint32_t)((1024 + n_hi + 255) / 256)), dim3(256), 0, ctx->stream, lo, hi, n_hi, h_to_mont(h_from_words(base)));
+    hipLaunchKernelGGL(fr_twiddle_seed_kernel, dim3((uint32_t)((1024 + n_hi + 255) / 256)), dim3(256), 0, ctx->stream, lo, hi, n_hi, to_u256(Fr::from_words(base).l));
     // (lo hi) R * (f R) * R^-1 = lo hi f R: Montgomery again
-    hipLaunchKernelGGL(fr_power_mont_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, tab, count, lo, hi, h_to_mont(h_from_words(f)));
+    hipLaunchKernelGGL(fr_power_mont_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, tab, count, lo, hi, to_u256(Fr::from_words(f).l));
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }
@@ -278,10 +276,10 @@ int32_t bn254_fr_ntt_mont_coset_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in,
         // gpow[t] = shift^(n / 2^t), t = 1 .. log_n (Montgomery): repeated squaring from the bottom
         std::vector<u256> gp(log_n + 1);
         memset(gp.data(), 0, gp.size() * sizeof(u256));
-        H256 g = h_from_words(shift_plain);
+        Fr g = Fr::from_words(shift_plain);
         for (uint32_t t = log_n; t >= 1; t--) {
-            gp[t] = h_to_mont(g);
-            g = h_mulmod(g, g);
+            gp[t] = to_u256(g.l);
+            g = g * g;
         }
         Scratch d(ctx);
         GL355_TRY(d.get(gp.size() * 32));
@@ -333,7 +331,7 @@ int32_t bn254_fr_ntt_mont_from_bitrev(Ctx* ctx, const uint64_t* in, uint64_t* ou
         pa.out = out;
         pa.tw = tw; pa.log_n = log_n; pa.s0 = s0; pa.ns = ns[k];
         pa.in_mont = 1; pa.out_mont = 1; pa.no_gather = 1;
-        if (scale_plain) { pa.use_scale = 1; pa.scale = h_to_mont(h_from_words(scale_plain)); }
+        if (scale_plain) { pa.use_scale = 1; pa.scale = to_u256(Fr::from_words(scale_plain).l); }
         pa.n_in = n; pa.n_out = pa.last ? n_out : n;
         pa.post = pa.last ? post : nullptr;
         hipLaunchKernelGGL(fr_fft_pass_kernel, dim3(tiles), dim3(256), 0, ctx->stream, pa);
@@ -363,7 +361,7 @@ int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t*
         pa.out = (pa.last && !(pa.first && in == out)) ? out : work;
         pa.tw = tw; pa.log_n = log_n; pa.s0 = s0; pa.ns = ns[k];
         pa.in_mont = 1; pa.out_mont = 1;
-        if (scale_plain) { pa.use_scale = 1; pa.scale = h_to_mont(h_from_words(scale_plain)); }
+        if (scale_plain) { pa.use_scale = 1; pa.scale = to_u256(Fr::from_words(scale_plain).l); }
         pa.n_in = n_in; pa.n_out = pa.out == out ? n_out : n;
         pa.pre = pre;
         pa.post = pa.out == out ? post : nullptr;
@@ -374,7 +372,7 @@ int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t*
     if (ns.size() == 1 && in == out) {
         // single pass in place: the pass wrote `work` without post / scale (bit-reversed reads cannot run in place): apply them in the copy
         hipLaunchKernelGGL(fr_scale_copy_kernel, dim3((uint32_t)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t*)work, out, n_out, post,
-                           scale_plain ? h_to_mont(h_from_words(scale_plain)) : to_u256(H256{{0, 0, 0, 0}}), scale_plain ? 1 : 0);
+                           to_u256((scale_plain ? Fr::from_words(scale_plain) : Fr::zero()).l), scale_plain ? 1 : 0);
     }
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
@@ -383,25 +381,20 @@ int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t*
 // in: n_in = 2^log_in values, out: n_out values of the 2^log_n-point transform; shift == nullptr: the plain transform
 int32_t fr_ntt_run(Ctx* ctx, const uint64_t* in, uint32_t log_in, uint64_t* out, uint64_t n_out, uint32_t log_n, int32_t inverse, const uint64_t* shift) {
     const uint64_t n = 1ull << log_n, n_in = 1ull << log_in;
-    // omega_n = ROOT^(2^(28 - log_n)) (or its inverse), as a plain integer, then to Montgomery form: * R mod r
-    H256 w = inverse ? H256{{BN254C_FR_ROOT_INV_64[0], BN254C_FR_ROOT_INV_64[1], BN254C_FR_ROOT_INV_64[2], BN254C_FR_ROOT_INV_64[3]}}
-                     : H256{{BN254C_FR_ROOT_64[0], BN254C_FR_ROOT_64[1], BN254C_FR_ROOT_64[2], BN254C_FR_ROOT_64[3]}};
-    for (uint32_t k = log_n; k < BN254C_FR_S; k++) w = h_mulmod(w, w);
-    const H256 Rm = {{BN254C_FR_ONE_64[0], BN254C_FR_ONE_64[1], BN254C_FR_ONE_64[2], BN254C_FR_ONE_64[3]}};      // R mod r
-    const u256 w_mont = to_u256(h_mulmod(w, Rm));
-    const H256 e_inv = {{HR[0] - 2, HR[1], HR[2], HR[3]}};
-    H256 scale_h = {{1, 0, 0, 0}};
-    if (inverse) scale_h = h_powmod(H256{{n, 0, 0, 0}}, e_inv);              // n^-1 mod r, plain
-    const u256 scale = to_u256(scale_h);
+    // omega_n = ROOT^(2^(28 - log_n)) (or its inverse), Montgomery
+    const Fr w = inverse ? Fr::root_of_unity(log_n).inv() : Fr::root_of_unity(log_n);
+    const u256 w_mont = to_u256(w.l);
+    uint64_t scale_w[4] = {1, 0, 0, 0};
+    if (inverse) Fr::from_u64(n).inv().to_words(scale_w);                    // n^-1 mod r, plain
+    const u256 scale = to_u256(scale_w);
     // coset: powers of the shift multiply the inputs of the forward form, powers of its inverse (and 1/n) the outputs of the inverse form
-    u256 pow_base = to_u256(H256{{0, 0, 0, 0}});
+    Fr sh = Fr::zero();
     if (shift) {
-        H256 sh = {{shift[0], shift[1], shift[2], shift[3]}};
-        while (h_geq(sh)) { unsigned __int128 br = 0; for (int i = 0; i < 4; i++) { unsigned __int128 dd = (unsigned __int128)sh.l[i] - HR[i] - (uint64_t)br; sh.l[i] = (uint64_t)dd; br = (dd >> 64) & 1; } }
-        if ((sh.l[0] | sh.l[1] | sh.l[2] | sh.l[3]) == 0) return ctx->fail(GL355_E_INVALID_ARG, "bn254_fr_coset_ntt: the shift must not be zero");
-        if (inverse) sh = h_powmod(sh, e_inv);
-        pow_base = to_u256(h_mulmod(sh, Rm));
+        sh = Fr::from_words(shift);
+        if (sh.is_zero()) return ctx->fail(GL355_E_INVALID_ARG, "bn254_fr_coset_ntt: the shift must not be zero");
+        if (inverse) sh = sh.inv();
     }
+    const u256 pow_base = to_u256(sh.l);
     const uint64_t n_pow = shift ? (inverse ? n_out : n_in) : 0;
     Scratch tw(ctx);
     const uint64_t n_hi = (std::max(n / 2, n_pow) + 1023) / 1024;

@@ -137,8 +137,9 @@ static int32_t g1_fft_run(Ctx* ctx, const uint64_t* in, uint64_t* out, uint32_t 
         GL355_HIP(ctx, hipGetLastError());
     }
     {
-        const H256 e_inv = {{HR[0] - 2, HR[1], HR[2], HR[3]}};
-        const u256 scale = to_u256(h_powmod(H256{{n, 0, 0, 0}}, e_inv));          // n^-1 mod r, plain
+        uint64_t n_inv[4];
+        Fr::from_u64(n).inv().to_words(n_inv);
+        const u256 scale = to_u256(n_inv);                                        // n^-1 mod r, plain
         ProfScope ps(ctx, "bn254_g1_fft_store", n * (96 + 64));
         hipLaunchKernelGGL(g1_fft_store_kernel, dim3(blk), dim3(256), 0, ctx->stream, data, out, n, scale, inverse && log_n ? 1 : 0);
         GL355_HIP(ctx, hipGetLastError());

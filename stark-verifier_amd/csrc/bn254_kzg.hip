@@ -228,8 +228,8 @@ __global__ void kzg_from_mont1_kernel(const uint64_t* in, uint64_t* out) {
 
 namespace gl355 {
 // Q and E of the comment above the division kernels, levels chained on the stream; A and Q are device arrays (Q plain at the top level)
-int32_t kzg_divide(Ctx* ctx, const uint64_t* A, uint64_t m, const H256& z, int a_is_mont, uint64_t* Q, int q_plain, uint64_t* E_mont) {
-    const u256 z_mont = h_to_mont(z);
+int32_t kzg_divide(Ctx* ctx, const uint64_t* A, uint64_t m, const Fr& z, int a_is_mont, uint64_t* Q, int q_plain, uint64_t* E_mont) {
+    const u256 z_mont = to_u256(z.l);
     if (m <= KZG_DIV_CHUNK) {
         hipLaunchKernelGGL(kzg_div_walk_kernel, dim3(1), dim3(64), 0, ctx->stream, A, m, z_mont, a_is_mont, (const uint64_t*)nullptr, Q, q_plain, E_mont);
         GL355_HIP(ctx, hipGetLastError());
@@ -242,8 +242,8 @@ int32_t kzg_divide(Ctx* ctx, const uint64_t* A, uint64_t m, const H256& z, int a
     uint64_t* C = H + 4 * chunks;
     hipLaunchKernelGGL(kzg_div_chunk_kernel, dim3((uint32_t)((chunks + 63) / 64)), dim3(64), 0, ctx->stream, A, m, z_mont, a_is_mont, H);
     GL355_HIP(ctx, hipGetLastError());
-    H256 zc = z;                                             // Z = z^chunk
-    for (uint32_t k = 1; k < KZG_DIV_CHUNK; k <<= 1) zc = h_mulmod(zc, zc);
+    Fr zc = z;                                               // Z = z^chunk
+    for (uint32_t k = 1; k < KZG_DIV_CHUNK; k <<= 1) zc = zc * zc;
     GL355_TRY(kzg_divide(ctx, H, chunks, zc, 1, C, 0, nullptr));
     hipLaunchKernelGGL(kzg_div_walk_kernel, dim3((uint32_t)((chunks + 63) / 64)), dim3(64), 0, ctx->stream, A, m, z_mont, a_is_mont, (const uint64_t*)C, Q, q_plain, E_mont);
     GL355_HIP(ctx, hipGetLastError());
@@ -336,13 +336,12 @@ int32_t gl355_kzg_setup(gl355_ctx* h, const uint64_t tau[4], uint32_t log_n, uin
     const uint64_t n = 1ull << log_n;
     uint64_t tau_h[4];                                        // tau may be device memory like every other operand
     if (ptr_is_device(tau)) { GL355_HIP(ctx, hipMemcpy(tau_h, tau, 32, hipMemcpyDeviceToHost)); } else memcpy(tau_h, tau, 32);
-    const H256 t = h_from_words(tau_h);
-    const u256 tau_mont = h_to_mont(t);
-    {   // tau in the 2^log_n domain <=> tau^n = 1: refused whether or not the Lagrange bases are asked for (the header says so)
-        H256 tn = t;
-        for (uint32_t k = 0; k < log_n; k++) tn = h_mulmod(tn, tn);
-        if (tn.l[0] == 1 && (tn.l[1] | tn.l[2] | tn.l[3]) == 0) return ctx->fail(GL355_E_INVALID_ARG, "kzg_setup: tau lies in the evaluation domain");
-    }
+    const Fr t = Fr::from_words(tau_h);
+    const u256 tau_mont = to_u256(t.l);
+    Fr tn = t;                                                // tau^n
+    for (uint32_t k = 0; k < log_n; k++) tn = tn * tn;
+    // tau in the 2^log_n domain <=> tau^n = 1: refused whether or not the Lagrange bases are asked for (the header says so)
+    if (tn == Fr::one()) return ctx->fail(GL355_E_INVALID_ARG, "kzg_setup: tau lies in the evaluation domain");
     Scratch sc(ctx);
     GL355_TRY(sc.get((g_lagrange ? 2 : 1) * n * 32 + 64));
     uint64_t* d_s = sc.as<uint64_t>();
@@ -357,17 +356,14 @@ int32_t gl355_kzg_setup(gl355_ctx* h, const uint64_t tau[4], uint32_t log_n, uin
     GL355_TRY(gl355_bn254_g1_fixed_base_mul(h, gen, d_s, n, g));
     if (g_lagrange) {
         // c = (tau^n - 1) / n
-        H256 tn = t;
-        for (uint32_t k = 0; k < log_n; k++) tn = h_mulmod(tn, tn);
-        const H256 e_inv = {{HR[0] - 2, HR[1], HR[2], HR[3]}};
-        const H256 c = h_mulmod(h_submod(tn, H256{{1, 0, 0, 0}}), h_powmod(H256{{n, 0, 0, 0}}, e_inv));
+        const Fr c = (tn - Fr::one()) * Fr::from_u64(n).inv();
         GL355_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
         {
             ProfScope ps(ctx, "kzg_setup_scalars", n * 32);
             const uint64_t lanes = (n + KZG_LG_CHUNK - 1) / KZG_LG_CHUNK;
-            const H256 w = h_root_of_unity(log_n);
-            hipLaunchKernelGGL(kzg_lagrange_kernel, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, ctx->stream, tau_mont, h_to_mont(w),
-                               h_to_mont(h_powmod(w, e_inv)), h_to_mont(c), n, d_s, d_pre, d_bad);
+            const Fr w = Fr::root_of_unity(log_n);
+            hipLaunchKernelGGL(kzg_lagrange_kernel, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, ctx->stream, tau_mont, to_u256(w.l),
+                               to_u256(w.inv().l), to_u256(c.l), n, d_s, d_pre, d_bad);
             GL355_HIP(ctx, hipGetLastError());
         }
         uint32_t bad = 0;
@@ -419,7 +415,7 @@ int32_t gl355_kzg_open(gl355_ctx* h, const uint64_t* g, const uint64_t* coeffs, 
         ProfScope ps(ctx, "kzg_divide", n * 64);
         uint64_t z_h[4];
         if (ptr_is_device(z)) { GL355_HIP(ctx, hipMemcpy(z_h, z, 32, hipMemcpyDeviceToHost)); } else memcpy(z_h, z, 32);
-        GL355_TRY(kzg_divide(ctx, sp.as<uint64_t>(), n, h_from_words(z_h), 0, d_q, 1, d_e));
+        GL355_TRY(kzg_divide(ctx, sp.as<uint64_t>(), n, Fr::from_words(z_h), 0, d_q, 1, d_e));
         hipLaunchKernelGGL(kzg_from_mont1_kernel, dim3(1), dim3(64), 0, ctx->stream, (const uint64_t*)d_e, d_e + 4);
         GL355_HIP(ctx, hipGetLastError());
     }

@@ -4,28 +4,13 @@
 // (chip/native_chip/poseidon_bn254_chip.rs:203-233).
 #include "gl355_internal.h"
 #include "halo2_tape.h"
-#include "host_fr.h"
-
-#define BN254_TABLE_QUAL static const
-#include "bn254_tables.h"
+#include "host_mont.h"
 
 namespace gl355 {
+void host_bn254_poseidon_round(Fr s[5], int rnd);      // host_bn254.cpp
 namespace {
 
-Fr table_fr(const uint32_t* p) {
-    uint64_t w[4];
-    for (int i = 0; i < 4; i++) w[i] = (uint64_t)p[2 * i] | ((uint64_t)p[2 * i + 1] << 32);
-    return Fr::from_mont_words(w);
-}
-
 void permute_rows(const H2Cols& c, const uint64_t* e) {
-    static const struct Tables {
-        Fr rc[340], mds[25];
-        Tables() {
-            for (int i = 0; i < 340; i++) rc[i] = table_fr(BN254_RC[i]);
-            for (int i = 0; i < 25; i++) mds[i] = table_fr(BN254_MDS[i]);
-        }
-    } T;
     const uint64_t row = e[1];
     Fr s[5];
     for (int i = 0; i < 5; i++) s[i] = Fr::from_words(h2_operand(c, e[2 + i]).w);
@@ -35,19 +20,7 @@ void permute_rows(const H2Cols& c, const uint64_t* e) {
             s[i].to_words(v.w);
             h2_store(c, H2_COL_STATE + i, row + rnd, v);
         }
-        if (rnd == 68) break;
-        const bool full = rnd < 4 || rnd >= 64;
-        for (int i = 0; i < 5; i++) {
-            s[i] = s[i] + T.rc[5 * rnd + i];
-            if (full || i == 0) { const Fr x2 = s[i] * s[i]; s[i] = x2 * x2 * s[i]; }
-        }
-        Fr nx[5];
-        for (int i = 0; i < 5; i++) {
-            Fr acc = s[0] * T.mds[5 * i];
-            for (int j = 1; j < 5; j++) acc = acc + s[j] * T.mds[5 * i + j];
-            nx[i] = acc;
-        }
-        for (int i = 0; i < 5; i++) s[i] = nx[i];
+        if (rnd < 68) host_bn254_poseidon_round(s, rnd);
     }
 }
 

@@ -3,7 +3,7 @@
 //     result = sum_w 2^(c w) W_w          (Horner from the top window: 254 dependent doublings)
 // and the conversion to an affine point.  It is strictly sequential -- 270 group operations of ~10 k VALU instructions each are
 // ~4 ms on one GPU lane (what the first version did) and ~0.1 ms here on one host core with 64-bit limbs.
-// Fq arithmetic: 4 x 64-bit limbs, Montgomery form with R = 2^256 (the representation the kernels store), CIOS on unsigned __int128.
+// Fq arithmetic: host_mont.h (the representation the kernels store); the point formulas: host_fq.h.
 #include <stdint.h>
 #include <string.h>
 
@@ -17,54 +17,28 @@ namespace gl355 {
 using namespace hostfq;
 namespace {
 Fq load_fq(const uint32_t* p) {
-    Fq r;
-    for (int i = 0; i < 4; i++) r.l[i] = (uint64_t)p[2 * i] | ((uint64_t)p[2 * i + 1] << 32);
-    return fq_canon(r);
+    uint64_t w[4];
+    for (int i = 0; i < 4; i++) w[i] = (uint64_t)p[2 * i] | ((uint64_t)p[2 * i + 1] << 32);
+    return Fq::from_mont_words(w);
 }
+Jac load_jac(const uint32_t* p) { return {load_fq(p), load_fq(p + 8), load_fq(p + 16)}; }
 }  // namespace
 
 // s, wt: n_windows Jacobian points each as the kernels store them (x | y | z, 8 x 32-bit limbs each, Montgomery form, < 2q); the sum
 // of window w is s[w] + wt[w] (bucket j weighs j + 1); wt may be null (a window of one bucket)
 void bn254_g1_horner_host(const uint32_t* s, const uint32_t* wt, uint32_t n_windows, uint32_t c, uint64_t result[8]) {
-    Jac r; r.x = fq_one(); r.y = r.x; memset(r.z.l, 0, 32);
+    Jac r = j_identity();
     for (uint32_t w = n_windows; w-- > 0;) {
         for (uint32_t k = 0; k < c; k++) r = j_double(r);
-        Jac t;
-        t.x = load_fq(s + 24 * w); t.y = load_fq(s + 24 * w + 8); t.z = load_fq(s + 24 * w + 16);
-        r = j_add(r, t);
-        if (wt) {
-            t.x = load_fq(wt + 24 * w); t.y = load_fq(wt + 24 * w + 8); t.z = load_fq(wt + 24 * w + 16);
-            r = j_add(r, t);
-        }
+        r = j_add(r, load_jac(s + 24 * w));
+        if (wt) r = j_add(r, load_jac(wt + 24 * w));
     }
-    if (j_is_identity(r)) { memset(result, 0, 64); return; }
-    const Fq zi = fq_inv(r.z), zi2 = fq_mul(zi, zi);
-    Fq one_int; memset(one_int.l, 0, 32); one_int.l[0] = 1;                 // x R * 1 * R^-1 = x: out of Montgomery form
-    const Fq x = fq_mul(fq_mul(r.x, zi2), one_int), y = fq_mul(fq_mul(r.y, fq_mul(zi2, zi)), one_int);
-    memcpy(result, x.l, 32);
-    memcpy(result + 4, y.l, 32);
+    g1_store(r, result);
 }
 
-// out = a + b for affine points as canonical integers (x | y, zeros = the identity): the host end of a commitment made in two parts
-void bn254_g1_add_host(const uint64_t a[8], const uint64_t b[8], uint64_t out[8]) {
-    auto lift = [](const uint64_t p[8]) {
-        Jac r;
-        bool ident = true;
-        for (int i = 0; i < 8; i++) ident = ident && p[i] == 0;
-        if (ident) { r.x = fq_one(); r.y = r.x; memset(r.z.l, 0, 32); return r; }
-        Fq x, y, r2;
-        memcpy(x.l, p, 32); memcpy(y.l, p + 4, 32); memcpy(r2.l, BN254C_FQ_R2_64, 32);
-        r.x = fq_mul(fq_canon(x), r2); r.y = fq_mul(fq_canon(y), r2); r.z = fq_one();
-        return r;
-    };
-    const Jac r = j_add(lift(a), lift(b));
-    if (j_is_identity(r)) { memset(out, 0, 64); return; }
-    const Fq zi = fq_inv(r.z), zi2 = fq_mul(zi, zi);
-    Fq one_int; memset(one_int.l, 0, 32); one_int.l[0] = 1;
-    const Fq x = fq_mul(fq_mul(r.x, zi2), one_int), y = fq_mul(fq_mul(r.y, fq_mul(zi2, zi)), one_int);
-    memcpy(out, x.l, 32);
-    memcpy(out + 4, y.l, 32);
-}
+// out = a + b for affine points as integers (x | y, zeros = the identity; g1_load reduces a coordinate at or above q): the host end of a
+// commitment made in two parts
+void bn254_g1_add_host(const uint64_t a[8], const uint64_t b[8], uint64_t out[8]) { g1_store(j_add(g1_load(a), g1_load(b)), out); }
 
 // sum_i scalars[i] points[i] on one core: the verifier's MSM over a proof's ~150 commitments, and the batch verifier's below the size
 // where a device launch pays.  Pippenger buckets over unsigned c-bit digits; windows above the longest scalar are never built (the batch
@@ -100,11 +74,9 @@ void bn254_g1_msm_host(const uint64_t* points, const uint64_t* scalars, uint64_t
 }
 
 void bn254_g1_neg_host(const uint64_t p[8], uint64_t out[8]) {
-    bool ident = true;
-    for (int i = 0; i < 8; i++) ident = ident && p[i] == 0;
-    if (ident) { memset(out, 0, 64); return; }
+    if (g1_words_are_identity(p)) { memset(out, 0, 64); return; }
     memcpy(out, p, 32);
-    fq_to_int(fq_neg(fq_from_int(p + 4)), out + 4);
+    Fq::from_words(p + 4).neg().to_words(out + 4);
 }
 
 bool bn254_g1_valid_host(const uint64_t p[8]) { return g1_valid(p); }

@@ -3,7 +3,7 @@
 // computes.  One proof, or one batch of any size, needs two Miller loops and one final exponentiation -- milliseconds on one core, with
 // nothing to run in parallel -- so there is no device code here.
 //
-// Tower over host_fq.h's Montgomery Fq:  Fq2 = Fq[u] / (u^2 + 1),  Fq6 = Fq2[v] / (v^3 - xi),  Fq12 = Fq6[w] / (w^2 - v),  xi = 9 + u, so w^6 = xi.
+// Tower over host_mont.h's Montgomery Fq:  Fq2 = Fq[u] / (u^2 + 1),  Fq6 = Fq2[v] / (v^3 - xi),  Fq12 = Fq6[w] / (w^2 - v),  xi = 9 + u, so w^6 = xi.
 // G2 is the order-r subgroup of the twist E': y^2 = x^3 + 3 / xi over Fq2; (x', y') -> (x' w^2, y' w^3) maps it into E(Fq12).
 // Miller loop: f_{6x+2,Q}(P), x = 4965661367192848881, with T kept affine (one Fq2 inversion per step), then the two lines through
 // pi(Q) and -pi^2(Q); a line through twist points T, T2 with twist slope l, evaluated at P = (xP, yP) in E(Fq):
@@ -34,32 +34,31 @@ namespace {
 
 // ---- Fq2 ---------------------------------------------------------------------------------------------------------------------------
 struct Fq2 { Fq c0, c1; };
-Fq fq_zero() { Fq z; memset(z.l, 0, 32); return z; }
-Fq2 operator+(const Fq2& a, const Fq2& b) { return {fq_add(a.c0, b.c0), fq_add(a.c1, b.c1)}; }
-Fq2 operator-(const Fq2& a, const Fq2& b) { return {fq_sub(a.c0, b.c0), fq_sub(a.c1, b.c1)}; }
-Fq2 operator-(const Fq2& a) { return {fq_neg(a.c0), fq_neg(a.c1)}; }
+Fq2 operator+(const Fq2& a, const Fq2& b) { return {a.c0 + b.c0, a.c1 + b.c1}; }
+Fq2 operator-(const Fq2& a, const Fq2& b) { return {a.c0 - b.c0, a.c1 - b.c1}; }
+Fq2 operator-(const Fq2& a) { return {a.c0.neg(), a.c1.neg()}; }
 Fq2 operator*(const Fq2& a, const Fq2& b) {            // Karatsuba over u^2 = -1
-    const Fq t0 = fq_mul(a.c0, b.c0), t1 = fq_mul(a.c1, b.c1);
-    return {fq_sub(t0, t1), fq_sub(fq_sub(fq_mul(fq_add(a.c0, a.c1), fq_add(b.c0, b.c1)), t0), t1)};
+    const Fq t0 = a.c0 * b.c0, t1 = a.c1 * b.c1;
+    return {t0 - t1, (a.c0 + a.c1) * (b.c0 + b.c1) - t0 - t1};
 }
 Fq2 sqr(const Fq2& a) {
-    const Fq t = fq_mul(a.c0, a.c1);
-    return {fq_mul(fq_add(a.c0, a.c1), fq_sub(a.c0, a.c1)), fq_add(t, t)};
+    const Fq t = a.c0 * a.c1;
+    return {(a.c0 + a.c1) * (a.c0 - a.c1), t + t};
 }
-Fq2 scale(const Fq2& a, const Fq& s) { return {fq_mul(a.c0, s), fq_mul(a.c1, s)}; }
-Fq2 conj(const Fq2& a) { return {a.c0, fq_neg(a.c1)}; }
+Fq2 scale(const Fq2& a, const Fq& s) { return {a.c0 * s, a.c1 * s}; }
+Fq2 conj(const Fq2& a) { return {a.c0, a.c1.neg()}; }
 Fq2 dbl(const Fq2& a) { return a + a; }
-bool is_zero(const Fq2& a) { return fq_is_zero(a.c0) && fq_is_zero(a.c1); }
-bool operator==(const Fq2& a, const Fq2& b) { return fq_eq(a.c0, b.c0) && fq_eq(a.c1, b.c1); }
-Fq2 fq2_zero() { return {fq_zero(), fq_zero()}; }
-Fq2 fq2_one() { return {fq_one(), fq_zero()}; }
+bool is_zero(const Fq2& a) { return a.c0.is_zero() && a.c1.is_zero(); }
+bool operator==(const Fq2& a, const Fq2& b) { return a.c0 == b.c0 && a.c1 == b.c1; }
+Fq2 fq2_zero() { return {Fq::zero(), Fq::zero()}; }
+Fq2 fq2_one() { return {Fq::one(), Fq::zero()}; }
 Fq2 inv(const Fq2& a) {                                 // conj(a) / (c0^2 + c1^2); inv(0) = 0
-    const Fq n = fq_inv(fq_add(fq_mul(a.c0, a.c0), fq_mul(a.c1, a.c1)));
-    return {fq_mul(a.c0, n), fq_neg(fq_mul(a.c1, n))};
+    const Fq n = (a.c0 * a.c0 + a.c1 * a.c1).inv();
+    return {a.c0 * n, (a.c1 * n).neg()};
 }
 Fq2 mul_xi(const Fq2& a) {                              // (c0 + c1 u)(9 + u) = (9 c0 - c1) + (9 c1 + c0) u
-    auto x9 = [](const Fq& v) { Fq t = fq_add(v, v); t = fq_add(t, t); t = fq_add(t, t); return fq_add(t, v); };
-    return {fq_sub(x9(a.c0), a.c1), fq_add(x9(a.c1), a.c0)};
+    auto x9 = [](const Fq& v) { Fq t = v + v; t = t + t; t = t + t; return t + v; };
+    return {x9(a.c0) - a.c1, x9(a.c1) + a.c0};
 }
 Fq2 pow(const Fq2& a, const uint64_t e[4]) {
     Fq2 r = fq2_one();
@@ -111,9 +110,9 @@ struct Consts {
     Fq g22;                 // xi^((q^2-1)/3): the q^2-Frobenius on the twist's x (its y changes sign)
     Fq z[6];                // zeta^i, zeta = xi^((q^2-1)/6): the q^2-Frobenius multiplies the coefficient of w^i by zeta^i
     Consts() {
-        const uint64_t nine[4] = {9, 0, 0, 0}, three[4] = {3, 0, 0, 0};
-        const Fq2 xi = {fq_from_int(nine), fq_one()};
-        b_twist = scale(inv(xi), fq_from_int(three));
+        const uint64_t* Q = Fq::M();
+        const Fq2 xi = {Fq::from_u64(9), Fq::one()};
+        b_twist = scale(inv(xi), Fq::from_u64(3));
         uint64_t e[4];                                  // (q - 1) / 6
         unsigned __int128 rem = 0;
         for (int i = 3; i >= 0; i--) {
@@ -125,9 +124,9 @@ struct Consts {
         g12 = sqr(g11);
         g13 = g12 * g11;
         g22 = (g12 * conj(g12)).c0;                     // the norm: x^(q+1)
-        z[0] = fq_one();
+        z[0] = Fq::one();
         z[1] = (g11 * conj(g11)).c0;
-        for (int i = 2; i < 6; i++) z[i] = fq_mul(z[i - 1], z[1]);
+        for (int i = 2; i < 6; i++) z[i] = z[i - 1] * z[1];
     }
 };
 const Consts& K() { static const Consts k; return k; }
@@ -195,11 +194,11 @@ bool g2_is_identity_words(const uint64_t p[16]) {
     for (int i = 0; i < 16; i++) o |= p[i];
     return o == 0;
 }
-G2Aff g2_load(const uint64_t p[16]) { return {{fq_from_int(p), fq_from_int(p + 4)}, {fq_from_int(p + 8), fq_from_int(p + 12)}}; }
+G2Aff g2_load(const uint64_t p[16]) { return {{Fq::from_words(p), Fq::from_words(p + 4)}, {Fq::from_words(p + 8), Fq::from_words(p + 12)}}; }
 void g2_store(const G2Jac& r, uint64_t out[16]) {
     if (is_zero(r.z)) { memset(out, 0, 128); return; }
     const Fq2 zi = inv(r.z), zi2 = sqr(zi), x = r.x * zi2, y = r.y * zi2 * zi;
-    fq_to_int(x.c0, out); fq_to_int(x.c1, out + 4); fq_to_int(y.c0, out + 8); fq_to_int(y.c1, out + 12);
+    x.c0.to_words(out); x.c1.to_words(out + 4); y.c0.to_words(out + 8); y.c1.to_words(out + 12);
 }
 bool g2_on_twist(const G2Aff& p) { return sqr(p.y) == sqr(p.x) * p.x + K().b_twist; }
 
@@ -207,7 +206,7 @@ bool g2_on_twist(const G2Aff& p) { return sqr(p.y) == sqr(p.x) * p.x + K().b_twi
 struct Pair { Fq xp, yp; G2Aff q, t; };
 Fq12 line(const Pair& pr, const Fq2& slope) {
     Fq12 l;
-    l.c0 = {{pr.yp, fq_zero()}, fq2_zero(), fq2_zero()};
+    l.c0 = {{pr.yp, Fq::zero()}, fq2_zero(), fq2_zero()};
     l.c1 = {-scale(slope, pr.xp), slope * pr.t.x - pr.t.y, fq2_zero()};
     return l;
 }
@@ -255,7 +254,7 @@ bool bn254_pairing_product_is_one(const uint64_t* g1, const uint64_t* g2, uint32
         for (int j = 0; j < 8; j++) ident1 = ident1 && g1[8 * i + j] == 0;
         if (ident1 || g2_is_identity_words(g2 + 16 * i)) continue;
         Pair pr;
-        pr.xp = fq_from_int(g1 + 8 * i); pr.yp = fq_from_int(g1 + 8 * i + 4);
+        pr.xp = Fq::from_words(g1 + 8 * i); pr.yp = Fq::from_words(g1 + 8 * i + 4);
         pr.q = g2_load(g2 + 16 * i); pr.t = pr.q;
         pairs.push_back(pr);
     }

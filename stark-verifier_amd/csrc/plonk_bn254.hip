@@ -826,9 +826,7 @@ struct Proving {
             GL355_TRY(lincomb(pk, ps, cs, low, nullptr, bufa));
             uint64_t *src_ = bufa, *dst_ = bufb;
             for (auto& p : set_pts) {
-                uint64_t pw[4];
-                p.to_words(pw);
-                GL355_TRY(kzg_divide(ctx, src_, n, h_from_words(pw), 1, dst_, 0, nullptr));
+                GL355_TRY(kzg_divide(ctx, src_, n, p, 1, dst_, 0, nullptr));
                 std::swap(src_, dst_);
             }
             GL355_TRY(lincomb(pk, {src_}, {vi}, {}, sh_h, sh_h));
@@ -861,9 +859,7 @@ struct Proving {
         ps.push_back(sh_h);
         cs.push_back((zt * z0inv).neg());
         GL355_TRY(lincomb(pk, ps, cs, {cterm}, nullptr, bufa));
-        uint64_t uw[4];
-        su.to_words(uw);
-        GL355_TRY(kzg_divide(ctx, bufa, n, h_from_words(uw), 1, bufb, 0, nullptr));
+        GL355_TRY(kzg_divide(ctx, bufa, n, su, 1, bufb, 0, nullptr));
         return commit(pk->g, bufb, 1);
     }
 };

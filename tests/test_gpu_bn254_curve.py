@@ -308,10 +308,11 @@ def test_g1_msm_prepared_errors(ctx, orc):
     assert ctx.lib.gl355_bn254_g1_msm_bases_free(ctx.h, None) == 0
 
 
-@pytest.mark.parametrize("log_small,log_n", [(3, 3), (6, 9), (9, 11), (10, 13), (12, 14)])
+@pytest.mark.parametrize("log_small,log_n", [(2, 3), (3, 3), (6, 9), (9, 11), (10, 13), (12, 14)])
 def test_fr_coset_ntt_vs_oracle(ctx, orc, log_small, log_n):
     """coeff_to_extended / extended_to_coeff of halo2's EvaluationDomain: c_i shift^i zero-padded, transformed -- against the oracle's FFT of
-    the shifted coefficients (Python integers for the powers); the inverse form gives the coefficients back"""
+    the shifted coefficients (Python integers for the powers); the inverse form gives the coefficients back.  The case (2, 3) hands the shift
+    over unreduced, as shift + r (still below 2^256): the library reduces it, so everything below holds unchanged"""
     cv = Bn254Curve(orc)
     rng = np.random.default_rng(0x4E8 + log_n)
     ns, n = 1 << log_small, 1 << log_n
@@ -320,7 +321,8 @@ def test_fr_coset_ntt_vs_oracle(ctx, orc, log_small, log_n):
     ci = [v % pm.R for v in cv.ints(c)]
     padded = cv.scalars([ci[i] * pow(shift, i, pm.R) % pm.R if i < ns else 0 for i in range(n)])
     want = cv.ntt_array(padded)
-    sh = cv.scalars([shift])[0]
+    passed = shift + pm.R if (log_small, log_n) == (2, 3) else shift
+    sh = cv.scalars([passed])[0]
     out = np.full((n, 4), 0xAA, dtype=np.uint64)
     ctx.check(ctx.lib.gl355_bn254_fr_coset_ntt(ctx.h, np.ascontiguousarray(c).ctypes.data, log_small, log_n, sh.ctypes.data, 0, out.ctypes.data))
     assert np.array_equal(out, want)
@@ -335,3 +337,6 @@ def test_fr_coset_ntt_vs_oracle(ctx, orc, log_small, log_n):
     assert cv.ints(back) == [inv[i] * pow(sinv, i, pm.R) % pm.R for i in range(ns)]
     zero = np.zeros(4, dtype=np.uint64)
     assert ctx.lib.gl355_bn254_fr_coset_ntt(ctx.h, ev.ctypes.data, log_small, log_n, zero.ctypes.data, 0, out.ctypes.data) == -1
+    r_words = cv.scalars([pm.R])[0]                      # exactly r: zero after reduction
+    for inverse in (0, 1):
+        assert ctx.lib.gl355_bn254_fr_coset_ntt(ctx.h, ev.ctypes.data, log_small, log_n, r_words.ctypes.data, inverse, out.ctypes.data) == -1

@@ -128,6 +128,26 @@ def test_kzg_commit_and_open_vs_model(ctx, orc, log_n):
     assert ctx.lib.gl355_kzg_commit(ctx.h, g.ctypes.data, c.ctypes.data, 27, 0, c.ctypes.data) == -5
 
 
+def test_kzg_tau_and_z_above_r_are_reduced(ctx, orc):
+    """gl355_kzg_setup and gl355_kzg_open take any 256-bit tau / z and reduce it: tau + r and z + r (both below 2^256) give what tau and z give"""
+    cv = Bn254Curve(orc)
+    log_n, n = 3, 8
+    g, gl = setup(ctx, cv, log_n)
+    g2, gl2 = np.full_like(g, 0xAA), np.full_like(gl, 0xAA)
+    ctx.check(ctx.lib.gl355_kzg_setup(ctx.h, cv.scalars([TAU + R])[0].ctypes.data, log_n, g2.ctypes.data, gl2.ctypes.data))
+    assert np.array_equal(g2, g) and np.array_equal(gl2, gl)
+    # a tau in the domain stays refused when it arrives as omega + r
+    t = cv.scalars([pm.omega(log_n) + R])[0]
+    assert ctx.lib.gl355_kzg_setup(ctx.h, t.ctypes.data, log_n, g2.ctypes.data, gl2.ctypes.data) == -1
+    c = rand_scalars(np.random.default_rng(0x4F5), n)
+    z = 0x1234567
+    y, wit, q = kzg_open(ctx, cv, g, c, z)
+    assert y == horner(to_ints(c), z)
+    ev, wit2, q2 = np.zeros(4, dtype=np.uint64), np.zeros(8, dtype=np.uint64), np.full((n, 4), 0xAA, dtype=np.uint64)
+    ctx.check(ctx.lib.gl355_kzg_open(ctx.h, g.ctypes.data, c.ctypes.data, log_n, cv.scalars([z + R])[0].ctypes.data, ev.ctypes.data, wit2.ctypes.data, q2.ctypes.data))
+    assert cv.ints(ev)[0] == y and np.array_equal(wit2, wit) and np.array_equal(q2, q)
+
+
 def test_fr_ntt_k23_and_extended_k25(ctx, orc):
     """the reference's circuit size: FFT over 2^23 points (round trip, spectrum of an impulse, a sampled output against the definition) and
     coeff_to_extended onto the 2^25 coset domain and back"""
