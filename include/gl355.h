@@ -43,6 +43,7 @@ extern "C" {
 #define GL355_P UINT64_C(0xFFFFFFFF00000001) /* chip/native_chip/arithmetic_chip.rs:19 */
 #define GL355_COSET_SHIFT UINT64_C(7)        /* chip/plonk/plonk_verifier_chip.rs:225-227 */
 #define GL355_SALT_SIZE 4                    /* types/assigned.rs:67-71 */
+#define GL355_MAX_FRI_ARITY_BITS 4           /* a FRI layer folds by 2, 4, 8 or 16 (plonky2's standard_recursion_config: ConstantArityBits(4, 5)) */
 #define GL355_MAX_UNITS 16                   /* independent proofs of one circuit a prover context proves in lock-step (gl355_*_units) */
 
 typedef struct gl355_ctx gl355_ctx;
@@ -292,10 +293,17 @@ int32_t gl355_lde_ext(gl355_ctx* ctx, const uint64_t* coeffs, uint32_t log_n, ui
                       uint64_t shift, uint64_t* out);
 
 /* ---- a12: fri_committed_trees (fri_chip.rs:168-226,275-316) ---------------------------------- */
-/* arity-2 fold of n extension coefficients: out[k] = c[2k] + beta*c[2k+1] */
+/* fold of n extension coefficients by A = 2^arity_bits (1..GL355_MAX_FRI_ARITY_BITS): out[k] = sum_{j<A} beta^j c[A k + j], n / A
+ * elements (plonky2 fri_committed_trees' reduce_with_powers over chunks of A) = arity_bits arity-2 folds with beta, beta^2, beta^4, ..
+ * gl355_fri_fold is arity_bits = 1: out[k] = c[2k] + beta*c[2k+1] */
+int32_t gl355_fri_fold_arity(gl355_ctx* ctx, const uint64_t* coeffs, uint64_t n, uint32_t arity_bits, const uint64_t beta[2], uint64_t* out);
 int32_t gl355_fri_fold(gl355_ctx* ctx, const uint64_t* coeffs, uint64_t n, const uint64_t beta[2], uint64_t* out);
-/* commit-phase layer tree from natural-order extension values (n ext): leaves = pairs in
- * bit-reversed order, flattened to 4 u64 (no leaf hash); outputs as gl355_merkle_build */
+/* commit-phase layer tree from natural-order extension values (n ext): leaf i = the A = 2^arity_bits values [A i, A i + A) of the
+ * bit-reversed sequence, flattened to 2A u64 (`leaves`: n ext, the whole bit-reversed sequence).  hash_or_noop: the 4-word leaf of
+ * arity 2 is its own digest, the 8, 16 and 32-word leaves of the larger arities are hashed (hash_no_pad of `hasher`); digests and
+ * cap as gl355_merkle_build of n / A leaves.  gl355_fri_layer_commit_h is arity_bits = 1. */
+int32_t gl355_fri_layer_commit_arity_h(gl355_ctx* ctx, int32_t hasher, const uint64_t* values, uint64_t n, uint32_t arity_bits,
+                                       uint32_t cap_height, uint64_t* leaves, uint64_t* digests, uint64_t* cap);
 int32_t gl355_fri_layer_commit_h(gl355_ctx* ctx, int32_t hasher, const uint64_t* values, uint64_t n, uint32_t cap_height,
                                  uint64_t* leaves, uint64_t* digests, uint64_t* cap);
 int32_t gl355_fri_layer_commit(gl355_ctx* ctx, const uint64_t* values, uint64_t n, uint32_t cap_height,
@@ -335,11 +343,16 @@ int32_t gl355_poseidon_gate_witness(const uint64_t inputs[12], uint64_t swap, ui
 
 /* ---- a12 + a13 + a14 in one call: fri_proof (fri_chip.rs:168-226,275-327,364-376) ------------------
  * final_coeffs: n = 2^log_n extension coefficients of the DEEP polynomial (host or device).  Runs the
- * commit phase (n_layers arity-2 folds), observes the final polynomial, grinds the PoW, squeezes the
- * query indices and opens every layer tree at every query; `ch` is advanced exactly as
- * plonk_verifier_chip.rs:120-140 replays it.  Host outputs:
- *   caps[n_layers][2^cap_height][4], final_poly[(n >> n_layers) ext], pow_witness, query_indices[num_queries],
- *   step_evals[num_queries][n_layers][4], step_siblings[num_queries][sum_l (log_n+rate_bits-1-l-cap_height)][4]. */
+ * commit phase, observes the final polynomial, grinds the PoW, squeezes the query indices and opens every
+ * layer tree at every query; `ch` is advanced exactly as plonk_verifier_chip.rs:120-140 replays it.
+ * Layer l folds by A_l = 2^arity_bits[l] (plonky2 FriReductionStrategy; the reference pins ConstantArityBits(1, 5) for what its
+ * Halo2 FriChip checks, fri_chip.rs:211, and uses (3, 5) natively, access_set.rs:124).  With s_l = arity_bits[0] + .. + arity_bits[l]
+ * and lde_bits = log_n + rate_bits: layer l's tree has 2^(lde_bits - s_l) leaves of A_l extension values each (bit-reversed
+ * order; 2 A_l words, hashed when longer than a digest), a query opens leaf x_index >> s_l.  Host outputs:
+ *   caps[n_layers][2^cap_height][4], final_poly[(n >> s_last) ext], pow_witness, query_indices[num_queries],
+ *   step_evals[num_queries][sum_l 2 A_l] (layer after layer), step_siblings[num_queries][sum_l (lde_bits - s_l - cap_height)][4].
+ * GL355_E_INVALID_ARG: an arity of 0 bits, s_last > log_n, or a layer with fewer leaves than the cap has entries;
+ * GL355_E_UNSUPPORTED: more than GL355_MAX_FRI_ARITY_BITS bits in one layer. */
 int32_t gl355_fri_prove(gl355_ctx* ctx, const uint64_t* final_coeffs, uint32_t log_n, uint32_t rate_bits,
                         uint32_t cap_height, const uint32_t* arity_bits, uint32_t n_layers, uint32_t pow_bits,
                         uint32_t num_queries, gl355_challenger* ch, uint64_t* caps, uint64_t* final_poly,
@@ -360,6 +373,7 @@ typedef struct {
     int32_t hasher;              /* GL355_HASH_*: GenericConfig::Hasher = Merkle trees, transcript and PoW of this proof
                                     (constants_sigmas must have been committed with it, gl355_commit_h).  Public inputs are
                                     always hashed with Poseidon (GenericConfig::InnerHasher). */
+    const uint32_t* fri_arity_bits; /* [n_fri_layers]; NULL = every layer folds by 2 */
 } gl355_prover_data;
 /* u64 words of the flat proof gl355_prove writes */
 uint64_t gl355_proof_words(const gl355_prover_data* pd);
@@ -383,9 +397,11 @@ int32_t gl355_blinding_elements(gl355_ctx* ctx, const uint8_t key[32], uint32_t 
  *   header[8] = {total_words, degree_bits, n_fri_layers, num_queries, n_public_inputs, zero_knowledge, cap_height, num_challenges}
  *   wires_cap[C]H  zs_partial_products_cap[C]H  quotient_polys_cap[C]H
  *   openings at zeta: constants | sigmas | wires | zs | partial_products | quotient_polys (E each), then zs at g*zeta
- *   fri caps[n_fri_layers][C]H   final_poly[n >> n_fri_layers]E   pow_witness
+ *   fri caps[n_fri_layers][C]H   final_poly[n >> s_last]E   pow_witness
  *   per query: x_index; for oracle 0..3: leaf[leaf_len], siblings[log2 N - cap_height]H;
- *              for layer l: evals[2]E, siblings[log2 N - 1 - l - cap_height]H */
+ *              for layer l: evals[2^a_l]E, siblings[log2 N - s_l - cap_height]H
+ * a_l = fri_arity_bits[l] of the prover / verifier data (1 when that is NULL), s_l = a_0 + .. + a_l: the header carries the layer
+ * count only, a proof is read with the arities of the data it is checked against. */
 int32_t gl355_prove(gl355_ctx* ctx, const gl355_prover_data* pd, const uint64_t* wires, const uint64_t* public_inputs,
                     uint32_t n_public_inputs, const uint8_t* blinding_key, uint64_t* proof, uint64_t proof_capacity_words);
 
@@ -420,6 +436,7 @@ typedef struct {
     uint64_t circuit_digest[4];
     uint32_t cap_height, pow_bits, num_queries, n_fri_layers;
     int32_t zero_knowledge, hasher;
+    const uint32_t* fri_arity_bits; /* [n_fri_layers]; NULL = every layer folds by 2 */
 } gl355_verifier_data;
 int32_t gl355_verify(const gl355_verifier_data* vd, const uint64_t* proof, uint64_t proof_words, const uint64_t* public_inputs,
                      uint32_t n_public_inputs);
@@ -465,7 +482,7 @@ int32_t gl355_witness_replay_segmented(const uint64_t* tape, uint64_t n_ops, uin
  * host-side builder stark-verifier_amd/plonk.py) and serialised with CircuitData.export_blob(): u64 words
  *   [0] magic "GL355CIR" [1] version 2 (3: the digest at [106..109] was computed elsewhere, e.g. by plonky2's CircuitBuilder::build,
  *   and the artifact ends with the expected constants_sigmas cap [2^cap_height][4], which is checked instead of the digest) [2..11] the gl355_circuit scalars [12..91] 16 gates x {type, param, selector_index,
- *   group_start, group_end} [92] cap_height [93] pow_bits [94] num_queries [95] n_fri_layers [96] zero_knowledge [97] hasher
+ *   group_start, group_end} [92] cap_height [93] pow_bits [94] num_queries [95] n_fri_layers (every layer folds by 2: an artifact's circuit is proven and verified with fri_arity_bits = NULL) [96] zero_knowledge [97] hasher
  *   [98] blind_start [99] n_blind [100] z_start [101] n_z_pairs [102] n_rows [103] n_tape_ops [104] n_inputs [105] n_public_inputs
  *   [106..109] circuit digest [110] sequential tape entries [111] independent tape segments, then constants[num_selectors + num_constants][n] | sigmas[routed][n] | k_is[routed] |
  *   row_idx[n_rows] | public-input positions[n_pi] | tape[n_tape_ops][5] (gl355_witness_replay format) | segment lengths.

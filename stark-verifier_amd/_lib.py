@@ -28,13 +28,13 @@ class Challenger(C.Structure):
 class VerifierData(C.Structure):
     _fields_ = [("circuit", vp), ("constants_sigmas_cap", vp), ("k_is", vp), ("circuit_digest", C.c_uint64 * 4),
                 ("cap_height", C.c_uint32), ("pow_bits", C.c_uint32), ("num_queries", C.c_uint32), ("n_fri_layers", C.c_uint32),
-                ("zero_knowledge", C.c_int32), ("hasher", C.c_int32)]
+                ("zero_knowledge", C.c_int32), ("hasher", C.c_int32), ("fri_arity_bits", vp)]
 
 
 class ProverData(C.Structure):
     _fields_ = [("circuit", vp), ("constants_sigmas", vp), ("sigmas", vp), ("k_is", vp), ("circuit_digest", C.c_uint64 * 4),
                 ("cap_height", C.c_uint32), ("pow_bits", C.c_uint32), ("num_queries", C.c_uint32), ("n_fri_layers", C.c_uint32),
-                ("zero_knowledge", C.c_int32), ("hasher", C.c_int32)]
+                ("zero_knowledge", C.c_int32), ("hasher", C.c_int32), ("fri_arity_bits", vp)]
 
 
 MAX_GATES = 16
@@ -185,6 +185,8 @@ SIGNATURES = {
     "gl355_eval_polys": (C.c_int32, [vp, C.POINTER(PolyRef), C.c_uint32, vp, vp]),
     "gl355_lde_ext": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp]),
     "gl355_fri_fold": (C.c_int32, [vp, vp, C.c_uint64, vp, vp]),
+    "gl355_fri_fold_arity": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+    "gl355_fri_layer_commit_arity_h": (C.c_int32, [vp, C.c_int32, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp]),
     "gl355_fri_layer_commit_h": (C.c_int32, [vp, C.c_int32, vp, C.c_uint64, C.c_uint32, vp, vp, vp]),
     "gl355_fri_layer_commit": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp]),
     "gl355_pow_grind_h": (C.c_int32, [vp, C.c_int32, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -540,24 +540,37 @@ int32_t gl355_lde_ext(gl355_ctx* h, const uint64_t* coeffs, uint32_t log_n, uint
 
 // ---- a12 / a13 -------------------------------------------------------------------------------
 int32_t gl355_fri_fold(gl355_ctx* h, const uint64_t* coeffs, uint64_t n, const uint64_t beta[2], uint64_t* out) {
+    return gl355_fri_fold_arity(h, coeffs, n, 1, beta, out);
+}
+int32_t gl355_fri_fold_arity(gl355_ctx* h, const uint64_t* coeffs, uint64_t n, uint32_t arity_bits, const uint64_t beta[2], uint64_t* out) {
     CTX_OR_FAIL(h);
+    if (arity_bits == 0) return ctx->fail(GL355_E_INVALID_ARG, "fri_fold: an arity of 0 bits");
+    if (arity_bits > GL355_MAX_FRI_ARITY_BITS) return ctx->fail(GL355_E_UNSUPPORTED, "fri_fold: at most GL355_MAX_FRI_ARITY_BITS arity bits");
     if (n < 2 || (n & (n - 1))) return ctx->fail(GL355_E_INVALID_ARG, "fri_fold: n must be a power of two >= 2");
+    if ((n >> arity_bits) == 0) return ctx->fail(GL355_E_INVALID_ARG, "fri_fold: fewer coefficients than the arity");
     Staged si(ctx), so(ctx);
     GL355_TRY(si.open(coeffs, n * 16, 1));
-    GL355_TRY(so.open(out, n * 8, 2));
-    GL355_TRY(fri_fold_dev(ctx, si.as<uint64_t>(), n, beta, so.as<uint64_t>()));
+    GL355_TRY(so.open(out, (n >> arity_bits) * 16, 2));
+    GL355_TRY(fri_fold_dev(ctx, si.as<uint64_t>(), n, arity_bits, beta, so.as<uint64_t>()));
     return so.finish();
 }
 int32_t gl355_fri_layer_commit(gl355_ctx* h, const uint64_t* values, uint64_t n, uint32_t cap_height, uint64_t* leaves,
                                uint64_t* digests, uint64_t* cap) {
-    return gl355_fri_layer_commit_h(h, GL355_HASH_POSEIDON, values, n, cap_height, leaves, digests, cap);
+    return gl355_fri_layer_commit_arity_h(h, GL355_HASH_POSEIDON, values, n, 1, cap_height, leaves, digests, cap);
 }
 int32_t gl355_fri_layer_commit_h(gl355_ctx* h, int32_t hasher, const uint64_t* values, uint64_t n, uint32_t cap_height, uint64_t* leaves,
                                  uint64_t* digests, uint64_t* cap) {
+    return gl355_fri_layer_commit_arity_h(h, hasher, values, n, 1, cap_height, leaves, digests, cap);
+}
+int32_t gl355_fri_layer_commit_arity_h(gl355_ctx* h, int32_t hasher, const uint64_t* values, uint64_t n, uint32_t arity_bits, uint32_t cap_height,
+                                       uint64_t* leaves, uint64_t* digests, uint64_t* cap) {
     CTX_OR_FAIL(h);
     HASHER_OR_FAIL(hasher);
+    if (arity_bits == 0) return ctx->fail(GL355_E_INVALID_ARG, "fri_layer_commit: an arity of 0 bits");
+    if (arity_bits > GL355_MAX_FRI_ARITY_BITS) return ctx->fail(GL355_E_UNSUPPORTED, "fri_layer_commit: at most GL355_MAX_FRI_ARITY_BITS arity bits");
     if (n < 2 || (n & (n - 1))) return ctx->fail(GL355_E_INVALID_ARG, "fri_layer_commit: n must be a power of two >= 2");
-    const uint64_t n_leaves = n / 2;
+    const uint64_t n_leaves = n >> arity_bits;
+    if (n_leaves == 0) return ctx->fail(GL355_E_INVALID_ARG, "fri_layer_commit: fewer values than the arity");
     const uint32_t lg = log2_u64(n_leaves);
     if (cap_height > lg) return ctx->fail(GL355_E_INVALID_ARG, "fri_layer_commit: cap_height too large");
     const uint64_t n_cap = 1ull << cap_height, n_dig = 2 * (n_leaves - n_cap);
@@ -567,7 +580,7 @@ int32_t gl355_fri_layer_commit_h(gl355_ctx* h, int32_t hasher, const uint64_t* v
     GL355_TRY(sd.open(digests, n_dig * 32, 2));
     GL355_TRY(sc.open(cap, n_cap * 32, 2));
     GL355_TRY(fri_layer_leaves_dev(ctx, sv.as<uint64_t>(), n, sl.as<uint64_t>()));
-    GL355_TRY(merkle_build_any(ctx, hasher, sl.as<uint64_t>(), n_leaves, 4, false, 0, cap_height, sd.as<uint64_t>(), sc.as<uint64_t>()));
+    GL355_TRY(merkle_build_any(ctx, hasher, sl.as<uint64_t>(), n_leaves, 2u << arity_bits, false, 0, cap_height, sd.as<uint64_t>(), sc.as<uint64_t>()));
     GL355_TRY(sl.finish());
     GL355_TRY(sd.finish());
     return sc.finish();

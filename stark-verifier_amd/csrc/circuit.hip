@@ -176,6 +176,7 @@ int32_t gl355_circuit_load(gl355_ctx* h, const uint64_t* blob, uint64_t words, g
     memcpy(ch->pd.circuit_digest, blob + 106, 32);
     ch->pd.cap_height = (uint32_t)blob[92]; ch->pd.pow_bits = (uint32_t)blob[93]; ch->pd.num_queries = (uint32_t)blob[94];
     ch->pd.n_fri_layers = (uint32_t)blob[95]; ch->pd.zero_knowledge = (int32_t)blob[96]; ch->pd.hasher = hasher;
+    ch->pd.fri_arity_bits = nullptr;      // the artifact carries a layer count only: its flow is the reference's, every layer folds by 2
     *out = ch;
     return GL355_OK;
 }
@@ -212,6 +213,7 @@ int32_t gl355_circuit_verify(const gl355_circuit_handle* ch, const uint64_t* pro
     memcpy(vd.circuit_digest, ch->pd.circuit_digest, 32);
     vd.cap_height = ch->pd.cap_height; vd.pow_bits = ch->pd.pow_bits; vd.num_queries = ch->pd.num_queries; vd.n_fri_layers = ch->pd.n_fri_layers;
     vd.zero_knowledge = ch->pd.zero_knowledge; vd.hasher = ch->pd.hasher;
+    vd.fri_arity_bits = nullptr;
     return gl355_verify(&vd, proof, proof_words, public_inputs, n_public_inputs);
 }
 

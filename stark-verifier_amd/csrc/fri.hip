@@ -202,20 +202,36 @@ int32_t eval_polys_ext_dev(Ctx* ctx, const uint64_t* const* poly_ptrs_host, uint
 }
 
 // ---- a12: FRI ---------------------------------------------------------------------------------
-__global__ void fri_fold_kernel(const uint64_t* c, uint64_t half, uint64_t b0, uint64_t b1, uint64_t* out) {
+// fold by A = 2^AB: out[k] = sum_{j<A} beta^j c[A k + j], one lane per output.  The lane's A interleaved coefficients are 16 A
+// contiguous bytes (16-byte loads); Horner from the top in the lazy gl2 forms, canonical on the way out.  <1> is c[2k] + beta c[2k+1].
+template <int AB>
+__global__ void fri_fold_kernel(const uint64_t* c, uint64_t n_out, uint64_t b0, uint64_t b1, uint64_t* out) {
+    constexpr int A = 1 << AB;
     const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (k >= half) return;
-    const ulonglong2 e = *reinterpret_cast<const ulonglong2*>(c + 4 * k);
-    const ulonglong2 o = *reinterpret_cast<const ulonglong2*>(c + 4 * k + 2);
-    const gl2 r = gl2_canon(gl2_add(gl2_make(e.x, e.y), gl2_mul(gl2_make(o.x, o.y), gl2_make(b0, b1))));
+    if (k >= n_out) return;
+    ulonglong2 v[A];
+#pragma unroll
+    for (int j = 0; j < A; j++) v[j] = *reinterpret_cast<const ulonglong2*>(c + 2 * (A * k + j));
+    const gl2 beta = gl2_make(b0, b1);
+    gl2 acc = gl2_make(v[A - 1].x, v[A - 1].y);
+#pragma unroll
+    for (int j = A - 2; j >= 0; j--) acc = gl2_add(gl2_make(v[j].x, v[j].y), gl2_mul(acc, beta));
+    const gl2 r = gl2_canon(acc);
     *reinterpret_cast<ulonglong2*>(out + 2 * k) = make_ulonglong2(r.c0, r.c1);
 }
-int32_t fri_fold_dev(Ctx* ctx, const uint64_t* coeffs, uint64_t n, const uint64_t beta[2], uint64_t* out) {
-    const uint64_t half = n / 2;
-    if (half == 0) return GL355_OK;
-    ProfScope ps(ctx, "fri_fold", n * 16 + half * 16);
-    hipLaunchKernelGGL(fri_fold_kernel, dim3((uint32_t)((half + 255) / 256)), dim3(256), 0, ctx->stream, coeffs, half,
-                       gl_canon(beta[0]), gl_canon(beta[1]), out);
+int32_t fri_fold_dev(Ctx* ctx, const uint64_t* coeffs, uint64_t n, uint32_t arity_bits, const uint64_t beta[2], uint64_t* out) {
+    const uint64_t n_out = n >> arity_bits;
+    if (n_out == 0) return GL355_OK;
+    ProfScope ps(ctx, "fri_fold", n * 16 + n_out * 16);
+    const dim3 grid((uint32_t)((n_out + 255) / 256)), block(256);
+    const uint64_t b0 = gl_canon(beta[0]), b1 = gl_canon(beta[1]);
+    switch (arity_bits) {
+        case 1: hipLaunchKernelGGL(fri_fold_kernel<1>, grid, block, 0, ctx->stream, coeffs, n_out, b0, b1, out); break;
+        case 2: hipLaunchKernelGGL(fri_fold_kernel<2>, grid, block, 0, ctx->stream, coeffs, n_out, b0, b1, out); break;
+        case 3: hipLaunchKernelGGL(fri_fold_kernel<3>, grid, block, 0, ctx->stream, coeffs, n_out, b0, b1, out); break;
+        case 4: hipLaunchKernelGGL(fri_fold_kernel<4>, grid, block, 0, ctx->stream, coeffs, n_out, b0, b1, out); break;
+        default: return ctx->fail(GL355_E_UNSUPPORTED, "fri_fold: 1..4 arity bits");
+    }
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }

@@ -240,7 +240,7 @@ int32_t deep_batch_dev(Ctx* ctx, const uint64_t* const* poly_ptrs_host, uint32_t
                        const uint64_t alpha[2], const uint64_t z[2], uint64_t* acc /* n ext */);
 int32_t eval_polys_ext_dev(Ctx* ctx, const uint64_t* const* poly_ptrs_host, uint32_t n_polys, uint32_t log_n,
                            const uint64_t z[2], uint64_t* out_host_or_dev);
-int32_t fri_fold_dev(Ctx* ctx, const uint64_t* coeffs, uint64_t n, const uint64_t beta[2], uint64_t* out);
+int32_t fri_fold_dev(Ctx* ctx, const uint64_t* coeffs, uint64_t n, uint32_t arity_bits, const uint64_t beta[2], uint64_t* out);
 int32_t fri_layer_leaves_dev(Ctx* ctx, const uint64_t* values, uint64_t n, uint64_t* leaves);
 int32_t lde_ext_dev(Ctx* ctx, const uint64_t* coeffs, uint32_t log_n, uint32_t rate_bits, uint64_t shift, uint64_t* out,
                     bool out_bitrev);
@@ -284,23 +284,43 @@ int32_t circuit_replay_units(const gl355_circuit_handle* ch, uint32_t threads, u
                              uint64_t* failed_unit, uint64_t* failed_op);
 int32_t resolve_blinding_key_words(Ctx* ctx, const uint8_t* key, uint32_t out[8]);
 
+// The commit-phase layers of one FRI proof as numbers: the ONE description of "which leaf does layer l open and how long is its
+// path" that gl355_fri_prove, the lock-step prover's buffers and assembly loop, gl355_proof_words and gl355_verify all read.
+// Layer l folds by A_l = 2^a[l]; s[l] = a[0] + .. + a[l]; its tree has N >> s[l] leaves of A_l extension values (2 A_l words), a query
+// opens leaf x_index >> s[l] with a path of depth[l] = lde_bits - s[l] - cap_height digests.
+struct FriLayers {
+    uint32_t n = 0, total_bits = 0;          // layers; s[n - 1] (0 without layers)
+    uint32_t a[32], s[32], depth[32];
+    uint64_t ev_off[32], ev_total = 0;       // words: where layer l's 2 A_l words start inside one query's layer evaluations; their sum
+    uint64_t sib_off[32], sib_total = 0;     // words: the same for the layer paths
+    // arity_bits == NULL: every layer folds by 2.  GL355_OK, or the code of the first layer that cannot be built (no message: the caller names itself)
+    int32_t init(uint32_t lde_bits, uint32_t cap_height, uint32_t n_layers, const uint32_t* arity_bits) {
+        n = 0; total_bits = 0; ev_total = 0; sib_total = 0;
+        if (n_layers > 32) return GL355_E_UNSUPPORTED;
+        for (uint32_t l = 0; l < n_layers; l++) {
+            const uint32_t al = arity_bits ? arity_bits[l] : 1;
+            if (al == 0) return GL355_E_INVALID_ARG;
+            if (al > GL355_MAX_FRI_ARITY_BITS) return GL355_E_UNSUPPORTED;
+            total_bits += al;
+            if (total_bits > lde_bits || lde_bits - total_bits < cap_height) return GL355_E_INVALID_ARG;   // a layer narrower than the cap
+            a[l] = al; s[l] = total_bits; depth[l] = lde_bits - total_bits - cap_height;
+            ev_off[l] = ev_total; ev_total += 2ull << al;
+            sib_off[l] = sib_total; sib_total += (uint64_t)depth[l] * 4;
+        }
+        n = n_layers;
+        return GL355_OK;
+    }
+};
+
 // The flat proof (layout in include/gl355.h) as numbers, computed once from the prover data: gl355_proof_words, the prover's
 // staging and device open buffers and its assembly loop all read this.
-// FRI layer l's Merkle path starts at off[l] words inside a query's layer siblings; returns their total
-static inline uint64_t fri_sibling_offsets(uint32_t lde_bits, uint32_t cap_height, uint32_t n_layers, uint64_t off[32]) {
-    uint64_t total = 0;
-    for (uint32_t l = 0; l < n_layers; l++) {
-        if (l < 32) off[l] = total;
-        total += (uint64_t)(lde_bits - 1 - l - cap_height) * 4;
-    }
-    return total;
-}
 struct ProofLayout {
     uint32_t leaf_len[4];              // constants_sigmas | wires | Z and partial products | quotient chunks (salt included)
     uint32_t depth0;                   // digests of a path in one of those four trees
-    uint64_t sib_off[32], sib_total;   // fri_sibling_offsets
+    FriLayers fri;                     // the commit-phase layers; fri_rc != GL355_OK: the arities cannot be built (words = 0)
+    int32_t fri_rc;
     uint64_t n_open;                   // polynomials opened at zeta (the num_challenges Z polynomials also at g * zeta)
-    uint64_t query_words;              // index | 4 x (leaf, path) | n_fri_layers x (pair, path)
+    uint64_t query_words;              // index | 4 x (leaf, path) | n_fri_layers x (2^a_l evaluations, path)
     uint64_t words;                    // the whole proof, header included
     explicit ProofLayout(const gl355_prover_data& pd) {
         const gl355_circuit& c = *pd.circuit;
@@ -308,9 +328,9 @@ struct ProofLayout {
         const uint64_t n_cap = 1ull << pd.cap_height;
         const uint32_t widths[4] = {c.num_selectors + c.num_constants + c.num_routed_wires, c.num_wires, nch * (1 + c.num_partial_products), nch * c.max_degree};
         depth0 = lde_bits - pd.cap_height;
-        sib_total = fri_sibling_offsets(lde_bits, pd.cap_height, L, sib_off);
+        fri_rc = fri.init(lde_bits, pd.cap_height, L, pd.fri_arity_bits);
         n_open = 0;
-        query_words = 1 + (uint64_t)L * 4 + sib_total;
+        query_words = 1 + fri.ev_total + fri.sib_total;
         for (int o = 0; o < 4; o++) {
             n_open += widths[o];
             leaf_len[o] = widths[o] + ((pd.zero_knowledge && o > 0) ? GL355_SALT_SIZE : 0);
@@ -319,22 +339,23 @@ struct ProofLayout {
         words = 8 + 3 * n_cap * 4                              // header; wires / zs / quotient caps
                 + 2 * (n_open + nch)                           // openings (ext)
                 + (uint64_t)L * n_cap * 4                      // commit-phase caps
-                + 2 * ((1ull << c.degree_bits) >> L) + 1       // final polynomial (ext), PoW witness
+                + 2 * ((1ull << c.degree_bits) >> fri.total_bits) + 1   // final polynomial (ext), PoW witness
                 + query_words * pd.num_queries;
+        if (fri_rc != GL355_OK) words = 0;
     }
 };
 
 // ---- the FRI tail of a proof (prover_batch.hip): commit phase, final polynomial, proof of work, query indices, layer openings ----
-struct FriShape { uint32_t log_n, rate_bits, cap_height, n_layers, pow_bits, n_queries; int32_t hasher; };
-struct FriUnitOut { uint64_t* caps /* [n_layers][2^cap_height][4] */; uint64_t* final_poly /* [n >> n_layers] ext */; uint64_t* pow_witness; };
+struct FriShape { uint32_t log_n, rate_bits, cap_height, pow_bits, n_queries; int32_t hasher; FriLayers layers; };
+struct FriUnitOut { uint64_t* caps /* [n_layers][2^cap_height][4] */; uint64_t* final_poly /* [n >> total_bits] ext */; uint64_t* pow_witness; };
 // words of host staging fri_tail_units needs
 static inline uint64_t fri_tail_stage_words(const FriShape& s, uint32_t B) {
-    return (uint64_t)B * std::max<uint64_t>({4ull << s.cap_height, 2 * ((1ull << s.log_n) >> s.n_layers), 1});
+    return (uint64_t)B * std::max<uint64_t>({4ull << s.cap_height, 2 * ((1ull << s.log_n) >> s.layers.total_bits), 1});
 }
 // B units, each a polynomial of n = 2^log_n F_p^2 coefficients held as two base columns: cols [B][2][n] (consumed), cols2 [B][n] and
 // vals [B][2][n << rate_bits] are work space.  ch[u] is advanced as the verifier replays it; caps, final polynomial and PoW witness go
 // to out[u], the query indices to q_idx [B][n_queries] (host, must outlive the stream's work) and d_idx (device); the layer openings
-// stay on the device: d_evals [B][n_queries][n_layers][4], d_sibs [B][n_queries][sum of fri_sibling_offsets].  `stage`: pinned host.
+// stay on the device: d_evals [B][n_queries][layers.ev_total], d_sibs [B][n_queries][layers.sib_total].  `stage`: pinned host.
 int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, uint64_t* cols2, uint64_t* vals, uint64_t* stage,
                        gl355_challenger* ch, const FriUnitOut* out, uint64_t* q_idx, uint64_t* d_idx, uint64_t* d_evals, uint64_t* d_sibs);
 int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const uint64_t* cs_lde, const uint64_t* wires_lde, uint64_t wires_us,

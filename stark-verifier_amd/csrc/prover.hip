@@ -4,10 +4,10 @@
 //
 // Replaces plonky2::fri::prover::{fri_proof, fri_committed_trees, fri_proof_of_work,
 // fri_prover_query_rounds} (reached through CircuitData::prove, src/plonky2_semaphore/access_set.rs:94).
-// Per layer: bit-reverse the evaluations into leaves of two extension elements (no leaf hash), Merkle
-// tree with cap, observe cap, squeeze beta, fold the coefficients, coset-NTT on shift^2
-// (src/plonky2_verifier/chip/fri_chip.rs:168-226,275-316; transcript order
-// chip/plonk/plonk_verifier_chip.rs:120-140).  Only the cap (<= 16 digests) crosses PCIe per layer.
+// Per layer, with A = 2^arity_bits[l]: bit-reverse the evaluations into leaves of A extension elements (hash_or_noop: the two
+// elements of arity 2 are their own digest, longer leaves are hashed), Merkle tree with cap, observe cap, squeeze beta, fold the
+// coefficients by A, coset-NTT on shift^A (src/plonky2_verifier/chip/fri_chip.rs:168-226,275-316 states the arity-2 case; transcript
+// order chip/plonk/plonk_verifier_chip.rs:120-140).  Only the cap (<= 16 digests) crosses PCIe per layer.
 #include "gl355_internal.h"
 #include "blinding.cuh"
 
@@ -28,33 +28,37 @@ extern "C" int32_t gl355_fri_prove(gl355_ctx* h, const uint64_t* final_coeffs, u
     if (!final_coeffs || !ch || !caps_out || !final_poly_out || !pow_witness || !query_indices || !step_evals || !step_siblings)
         return ctx->fail(GL355_E_INVALID_ARG, "fri_prove: null argument");
     const uint32_t lde_bits = log_n + rate_bits;
-    if (log_n == 0 || lde_bits > 27 || n_layers > 32 || n_layers > log_n) return ctx->fail(GL355_E_UNSUPPORTED, "fri_prove: unsupported size");
-    for (uint32_t l = 0; l < n_layers; l++)
-        if (arity_bits[l] != 1) return ctx->fail(GL355_E_UNSUPPORTED, "fri_prove: arity-2 folding only (fri_chip.rs:211)");
-    if (lde_bits - n_layers < cap_height + 0u) return ctx->fail(GL355_E_INVALID_ARG, "fri_prove: too many layers for the cap height");
-    const uint64_t n = 1ull << log_n, N = 1ull << lde_bits;
-
+    if (log_n == 0 || lde_bits > 27 || n_layers > 32) return ctx->fail(GL355_E_UNSUPPORTED, "fri_prove: unsupported size");
+    if (n_layers && !arity_bits) return ctx->fail(GL355_E_INVALID_ARG, "fri_prove: null argument");
+    for (uint32_t l = 0; l < n_layers; l++) {
+        if (arity_bits[l] == 0) return ctx->fail(GL355_E_INVALID_ARG, "fri_prove: an arity of 0 bits");
+        if (arity_bits[l] > GL355_MAX_FRI_ARITY_BITS) return ctx->fail(GL355_E_UNSUPPORTED, "fri_prove: a layer folds by 2, 4, 8 or 16");
+    }
     // the interleaved coefficients as the two base columns the shared FRI tail folds, then that tail for one unit
-    const FriShape shape{log_n, rate_bits, cap_height, n_layers, pow_bits, num_queries, ch->hasher};
-    uint64_t sib_off[32];
-    const uint64_t sib_total = fri_sibling_offsets(lde_bits, cap_height, n_layers, sib_off);
+    FriShape shape{log_n, rate_bits, cap_height, pow_bits, num_queries, ch->hasher, FriLayers()};
+    const FriLayers& fl = shape.layers;
+    if (shape.layers.init(lde_bits, cap_height, n_layers, arity_bits) != GL355_OK)
+        return ctx->fail(GL355_E_INVALID_ARG, "fri_prove: too many layers for the cap height");
+    if (fl.total_bits > log_n) return ctx->fail(GL355_E_INVALID_ARG, "fri_prove: the layers fold more than the polynomial has coefficients");
+    const uint64_t n = 1ull << log_n, N = 1ull << lde_bits;
+    const uint64_t sib_total = fl.sib_total;
     Staged sc(ctx);
     GL355_TRY(sc.open(final_coeffs, n * 16, 1));
     Scratch work(ctx), outb(ctx);
     GL355_TRY(work.get((2 * n + n + 8 + 2 * N) * 8));
-    GL355_TRY(outb.get(((uint64_t)num_queries * (1 + n_layers * 4 + sib_total) + 16) * 8));
+    GL355_TRY(outb.get(((uint64_t)num_queries * (1 + fl.ev_total + sib_total) + 16) * 8));
     uint64_t* cols = work.as<uint64_t>();
     uint64_t* cols2 = cols + 2 * n;
     uint64_t* vals = cols2 + n + 8;
     uint64_t* d_idx = outb.as<uint64_t>();
     uint64_t* d_ev = d_idx + num_queries;
-    uint64_t* d_sib = d_ev + (uint64_t)num_queries * n_layers * 4;
+    uint64_t* d_sib = d_ev + (uint64_t)num_queries * fl.ev_total;
     uint64_t* stage = nullptr;
     GL355_TRY(ctx->pinned(fri_tail_stage_words(shape, 1) * 8, reinterpret_cast<void**>(&stage)));
     GL355_TRY(ext_split_dev(ctx, sc.as<uint64_t>(), n, cols, cols + n));
     const FriUnitOut out{caps_out, final_poly_out, pow_witness};
     GL355_TRY(fri_tail_units(ctx, shape, 1, cols, cols2, vals, stage, ch, &out, query_indices, d_idx, d_ev, d_sib));
-    if (n_layers) GL355_HIP(ctx, ctx->d2h(step_evals, d_ev, (uint64_t)num_queries * n_layers * 32));
+    if (n_layers) GL355_HIP(ctx, ctx->d2h(step_evals, d_ev, (uint64_t)num_queries * fl.ev_total * 8));
     if (sib_total) GL355_HIP(ctx, ctx->d2h(step_siblings, d_sib, (uint64_t)num_queries * sib_total * 8));
     GL355_HIP(ctx, ctx->wait());
     return GL355_OK;

@@ -371,8 +371,9 @@ __global__ void __launch_bounds__(DEEP_BLK) deep_finish_units_kernel(DeepArgs a)
 }
 
 // ---- a12: FRI commit phase -----------------------------------------------------------------------------------------------------
-// layer leaves from the bit-reversed F_p^2 evaluations held as two base columns per unit: leaf i = ext values 2i, 2i+1 of the
-// bit-reversed sequence (fri_chip.rs:275-316) = (c0[2i], c1[2i], c0[2i+1], c1[2i+1])
+// layer leaves from the bit-reversed F_p^2 evaluations held as two base columns per unit: the interleaved sequence (c0[e], c1[e]),
+// written a pair of values at a time.  A layer that folds by A takes A consecutive values as one leaf (fri_chip.rs:275-316 for
+// A = 2: leaf i = (c0[2i], c1[2i], c0[2i+1], c1[2i+1])), so this one buffer is the row-major leaf array [len / A][2A] of every arity
 __global__ void fri_leaves_units_kernel(const uint64_t* cols /* [B][2][len] */, uint64_t len, uint64_t* leaves /* [B][len/2][4] */) {
     const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (i >= len / 2) return;
@@ -385,19 +386,35 @@ __global__ void fri_leaves_units_kernel(const uint64_t* cols /* [B][2][len] */, 
     *reinterpret_cast<ulonglong2*>(dst) = make_ulonglong2(a.x, b.x);
     *reinterpret_cast<ulonglong2*>(dst + 2) = make_ulonglong2(a.y, b.y);
 }
-// arity-2 fold of the coefficient columns: out[k] = c[2k] + beta_u * c[2k+1]
-__global__ void fri_fold_units_kernel(const uint64_t* cols /* [B][2][len] */, uint64_t len, UnitVals beta, uint64_t* out /* [B][2][len/2] */) {
+// fold of the coefficient columns by A = 2^AB: out[k] = sum_{j<A} beta_u^j c[A k + j], one lane per output.  The lane's A coefficients
+// of each base column are 8 A contiguous bytes (16-byte loads); Horner from the top in the lazy gl2 forms, canonical on the way out.
+// <1> is c[2k] + beta_u * c[2k+1]
+template <int AB>
+__global__ void fri_fold_units_kernel(const uint64_t* cols /* [B][2][len] */, uint64_t len, UnitVals beta, uint64_t* out /* [B][2][len >> AB] */) {
+    constexpr int H = 1 << (AB - 1);      // pairs of coefficients per column
     const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    const uint64_t half = len / 2;
-    if (k >= half) return;
+    const uint64_t n_out = len >> AB;
+    if (k >= n_out) return;
     const uint32_t u = blockIdx.y;
     const uint64_t* c0 = cols + (uint64_t)u * 2 * len;
     const uint64_t* c1 = c0 + len;
-    const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(c0 + 2 * k);
-    const ulonglong2 b = *reinterpret_cast<const ulonglong2*>(c1 + 2 * k);
-    const gl2 r = gl2_canon(gl2_add(gl2_make(a.x, b.x), gl2_mul(gl2_make(a.y, b.y), gl2_make(beta.v[u * 4], beta.v[u * 4 + 1]))));
-    uint64_t* o0 = out + (uint64_t)u * 2 * half;
-    o0[k] = r.c0; o0[half + k] = r.c1;
+    ulonglong2 a[H], b[H];
+#pragma unroll
+    for (int j = 0; j < H; j++) {
+        a[j] = *reinterpret_cast<const ulonglong2*>(c0 + 2 * (H * k + j));
+        b[j] = *reinterpret_cast<const ulonglong2*>(c1 + 2 * (H * k + j));
+    }
+    const gl2 bt = gl2_make(beta.v[u * 4], beta.v[u * 4 + 1]);
+    gl2 acc = gl2_make(a[H - 1].y, b[H - 1].y);
+    acc = gl2_add(gl2_make(a[H - 1].x, b[H - 1].x), gl2_mul(acc, bt));
+#pragma unroll
+    for (int j = H - 2; j >= 0; j--) {
+        acc = gl2_add(gl2_make(a[j].y, b[j].y), gl2_mul(acc, bt));
+        acc = gl2_add(gl2_make(a[j].x, b[j].x), gl2_mul(acc, bt));
+    }
+    const gl2 r = gl2_canon(acc);
+    uint64_t* o0 = out + (uint64_t)u * 2 * n_out;
+    o0[k] = r.c0; o0[n_out + k] = r.c1;
 }
 
 // ---- a14: query openings ---------------------------------------------------------------------------------------------------------
@@ -422,26 +439,26 @@ __global__ void open_units_kernel(OpenArgs a) {
         so[e] = tree[digest_slot(layer, k) * 4 + (e & 3)];
     }
 }
-// block (q, u, l): the pair of layer l at index idx[u][q] >> (l + 1) and its path
+// block (q, u, l): the leaf of layer l at index idx[u][q] >> s_l (its 2^a_l evaluations) and its path
 struct OpenFriArgs {
-    const uint64_t* trees; uint64_t leaf_off[32], dig_off[32];     // layer l: leaves [B][nl][4] at leaf_off, digests [B][2(nl - cap)][4] at dig_off
-    uint64_t sib_off[32], sib_total;
-    uint32_t lde_bits, cap_height, n_idx, n_layers;
-    const uint64_t* idx; uint64_t* evals /* [B][n_idx][n_layers][4] */; uint64_t* sibs /* [B][n_idx][sib_total] */;
+    const uint64_t* trees; uint64_t leaf_off[32], dig_off[32];     // layer l: leaves [B][nl][2 A_l] at leaf_off, digests [B][2(nl - cap)][4] at dig_off
+    FriLayers lay;
+    uint32_t lde_bits, cap_height, n_idx;
+    const uint64_t* idx; uint64_t* evals /* [B][n_idx][lay.ev_total] */; uint64_t* sibs /* [B][n_idx][lay.sib_total] */;
 };
 __global__ void open_fri_units_kernel(OpenFriArgs a) {
     const uint32_t q = blockIdx.x, u = blockIdx.y, l = blockIdx.z;
-    const uint64_t index = a.idx[(uint64_t)u * a.n_idx + q] >> (l + 1);
-    const uint32_t log_nl = a.lde_bits - 1 - l, layers = log_nl - a.cap_height;
+    const uint64_t index = a.idx[(uint64_t)u * a.n_idx + q] >> a.lay.s[l];
+    const uint32_t log_nl = a.lde_bits - a.lay.s[l], layers = a.lay.depth[l], lw = 2u << a.lay.a[l];
     const uint64_t nl = 1ull << log_nl, n_cap = 1ull << a.cap_height;
-    const uint64_t* leaves = a.trees + a.leaf_off[l] + (uint64_t)u * nl * 4;
+    const uint64_t* leaves = a.trees + a.leaf_off[l] + (uint64_t)u * nl * lw;
     const uint64_t* digs = a.trees + a.dig_off[l] + (uint64_t)u * 2 * (nl - n_cap) * 4;
-    uint64_t* ev = a.evals + (((uint64_t)u * a.n_idx + q) * a.n_layers + l) * 4;
-    if (threadIdx.x < 4) ev[threadIdx.x] = leaves[index * 4 + threadIdx.x];
+    uint64_t* ev = a.evals + ((uint64_t)u * a.n_idx + q) * a.lay.ev_total + a.lay.ev_off[l];
+    if (threadIdx.x < lw) ev[threadIdx.x] = leaves[index * lw + threadIdx.x];      // lw <= 32 < blockDim.x
     const uint64_t sub_leaves = 1ull << layers;
     const uint64_t* tree = digs + (index >> layers) * 2 * (sub_leaves - 1) * 4;
     const uint64_t k0 = index & (sub_leaves - 1);
-    uint64_t* so = a.sibs + ((uint64_t)u * a.n_idx + q) * a.sib_total + a.sib_off[l];
+    uint64_t* so = a.sibs + ((uint64_t)u * a.n_idx + q) * a.lay.sib_total + a.lay.sib_off[l];
     for (uint32_t e = threadIdx.x; e < layers * 4; e += blockDim.x) {
         const uint32_t layer = e >> 2;
         const uint64_t k = (k0 >> layer) ^ 1;
@@ -534,15 +551,17 @@ int32_t zs_partial_products_dev(Ctx* ctx, const uint64_t* wires, const uint64_t*
 // ---- the FRI tail (fri_committed_trees, final polynomial, fri_proof_of_work, query indices, layer openings): gl355_internal.h ----------
 int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, uint64_t* cols2, uint64_t* vals, uint64_t* stage,
                        gl355_challenger* ch, const FriUnitOut* out, uint64_t* q_idx, uint64_t* d_idx, uint64_t* d_evals, uint64_t* d_sibs) {
-    const uint32_t L = s.n_layers, lde_bits = s.log_n + s.rate_bits;
+    const FriLayers& fl = s.layers;
+    const uint32_t L = fl.n, lde_bits = s.log_n + s.rate_bits;
     const uint64_t N = 1ull << lde_bits, n_cap = 1ull << s.cap_height;
-    OpenFriArgs fa;         // the layer trees: leaves [B][nl][4] and digests [B][2(nl - n_cap)][4] of layer l, one after the other
+    if (fl.total_bits > s.log_n) return ctx->fail(GL355_E_INVALID_ARG, "fri: the layers fold more than the polynomial has coefficients");
+    OpenFriArgs fa;         // the layer trees: leaves [B][nl][2 A_l] and digests [B][2(nl - n_cap)][4] of layer l, one after the other
     memset(&fa, 0, sizeof fa);
     uint64_t tree_words = 0;
     for (uint32_t l = 0; l < L; l++) {
-        const uint64_t nl = N >> (l + 1);
+        const uint64_t nl = N >> fl.s[l];
         if (nl < n_cap) return ctx->fail(GL355_E_INVALID_ARG, "fri: layer smaller than the cap");
-        fa.leaf_off[l] = tree_words; tree_words += (uint64_t)B * nl * 4;
+        fa.leaf_off[l] = tree_words; tree_words += (uint64_t)B * (N >> (fl.s[l] - fl.a[l])) * 2;
         fa.dig_off[l] = tree_words; tree_words += (uint64_t)B * 2 * (nl - n_cap) * 4;
     }
     Scratch trees(ctx);
@@ -551,17 +570,18 @@ int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, 
     uint64_t* d_cap = tree_buf + tree_words;
     uint64_t shift = GL355_COSET_SHIFT, len_c = 1ull << s.log_n;
     for (uint32_t l = 0; l < L; l++) {
-        const uint64_t len_v = len_c << s.rate_bits, nl = len_v / 2;
+        const uint32_t ab = fl.a[l];
+        const uint64_t len_v = len_c << s.rate_bits, nl = len_v >> ab;
         GL355_TRY(lde_dev(ctx, cols, len_c, log2_u64(len_c), s.rate_bits, gl_canon(shift), 2 * B, vals, len_v, true));
         uint64_t* lv = tree_buf + fa.leaf_off[l];
         {
             ProfScope ps(ctx, "fri_layer_leaves", (uint64_t)B * len_v * 32);
-            hipLaunchKernelGGL(fri_leaves_units_kernel, dim3((uint32_t)((nl + 255) / 256), B), dim3(256), 0, ctx->stream, vals, len_v, lv);
+            hipLaunchKernelGGL(fri_leaves_units_kernel, dim3((uint32_t)((len_v / 2 + 255) / 256), B), dim3(256), 0, ctx->stream, vals, len_v, lv);
             LAUNCH_CHECK(ctx);
         }
         LeafArgs la;
         memset(&la, 0, sizeof la);
-        la.leaves = lv; la.n_leaves = (uint64_t)B * nl; la.leaf_len = 4; la.col_major = 0; la.stride = 4;
+        la.leaves = lv; la.n_leaves = (uint64_t)B * nl; la.leaf_len = 2u << ab; la.col_major = 0; la.stride = 2u << ab;
         GL355_TRY(merkle_build_args_any(ctx, s.hasher, la, log2_u64(nl) - s.cap_height, tree_buf + fa.dig_off[l], d_cap));
         uint64_t* cap_dst[MAXB];
         for (uint32_t u = 0; u < B; u++) cap_dst[u] = out[u].caps + (uint64_t)l * n_cap * 4;
@@ -571,14 +591,20 @@ int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, 
         for (uint32_t u = 0; u < B; u++) squeeze_ext(&ch[u], &beta.v[u * 4]);
         {
             ProfScope ps(ctx, "fri_fold", (uint64_t)B * (len_c * 16 + len_c * 8));
-            hipLaunchKernelGGL(fri_fold_units_kernel, dim3((uint32_t)((len_c / 2 + 255) / 256), B), dim3(256), 0, ctx->stream, cols, len_c, beta, cols2);
+            const dim3 grid((uint32_t)(((len_c >> ab) + 255) / 256), B), block(256);
+            switch (ab) {
+                case 1: hipLaunchKernelGGL(fri_fold_units_kernel<1>, grid, block, 0, ctx->stream, cols, len_c, beta, cols2); break;
+                case 2: hipLaunchKernelGGL(fri_fold_units_kernel<2>, grid, block, 0, ctx->stream, cols, len_c, beta, cols2); break;
+                case 3: hipLaunchKernelGGL(fri_fold_units_kernel<3>, grid, block, 0, ctx->stream, cols, len_c, beta, cols2); break;
+                default: hipLaunchKernelGGL(fri_fold_units_kernel<4>, grid, block, 0, ctx->stream, cols, len_c, beta, cols2); break;
+            }
             LAUNCH_CHECK(ctx);
         }
         std::swap(cols, cols2);
-        len_c >>= 1;
-        shift = gl_mul(shift, shift);
+        len_c >>= ab;
+        for (uint32_t j = 0; j < ab; j++) shift = gl_mul(shift, shift);
     }
-    // final polynomial: len_c = n >> L extension coefficients per unit, two columns each
+    // final polynomial: len_c = n >> total_bits extension coefficients per unit, two columns each
     GL355_HIP(ctx, ctx->d2h(stage, cols, (uint64_t)B * 2 * len_c * 8));
     GL355_HIP(ctx, ctx->wait());
     uint64_t pow_state[MAXB * 12];
@@ -596,7 +622,7 @@ int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, 
     // proof of work: the smallest witness of every unit
     if (s.hasher == GL355_HASH_POSEIDON) GL355_TRY(pow_grind_units_dev(ctx, B, pow_state, pow_pos, s.pow_bits, 0, stage, p_pow));
     else for (uint32_t u = 0; u < B; u++) GL355_TRY(pow_grind_any(ctx, s.hasher, &pow_state[u * 12], pow_pos[u], s.pow_bits, 0, p_pow[u]));
-    // queries: x_index = challenge mod N; layer l opens the pair at x_index >> (l + 1) and its path
+    // queries: x_index = challenge mod N; layer l opens the leaf at x_index >> s_l and its path
     for (uint32_t u = 0; u < B; u++) {
         gl355_challenger_observe(&ch[u], p_pow[u], 1);
         uint64_t resp;
@@ -609,10 +635,10 @@ int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, 
     GL355_HIP(ctx, hipMemcpyAsync(d_idx, q_idx, (uint64_t)B * s.n_queries * 8, hipMemcpyHostToDevice, ctx->stream));
     if (L) {
         fa.trees = tree_buf;
-        fa.sib_total = fri_sibling_offsets(lde_bits, s.cap_height, L, fa.sib_off);
-        fa.lde_bits = lde_bits; fa.cap_height = s.cap_height; fa.n_idx = s.n_queries; fa.n_layers = L; fa.idx = d_idx;
+        fa.lay = fl;
+        fa.lde_bits = lde_bits; fa.cap_height = s.cap_height; fa.n_idx = s.n_queries; fa.idx = d_idx;
         fa.evals = d_evals; fa.sibs = d_sibs;
-        ProfScope ps(ctx, "open_batch", (uint64_t)B * s.n_queries * (L * 64 + fa.sib_total * 16));
+        ProfScope ps(ctx, "open_batch", (uint64_t)B * s.n_queries * (fl.ev_total * 16 + fl.sib_total * 16));
         hipLaunchKernelGGL(open_fri_units_kernel, dim3(s.n_queries, B, L), dim3(64), 0, ctx->stream, fa);
         LAUNCH_CHECK(ctx);
     }
@@ -677,7 +703,7 @@ static int32_t begin_units(ProveRun& r) {
         gl355_challenger_observe(&r.ch[u], &r.pi_hashes.v[u * 4], 4);
         memcpy(r.keys.k[u].w, r.io[u].key, 32);
     }
-    const uint64_t stage_words = (uint64_t)r.B * std::max<uint64_t>({r.n_cap * 4, 2 * (r.lay.n_open + r.nch), 2 * (r.n >> r.L) + 8,
+    const uint64_t stage_words = (uint64_t)r.B * std::max<uint64_t>({r.n_cap * 4, 2 * (r.lay.n_open + r.nch), 2 * (r.n >> r.lay.fri.total_bits) + 8,
                                                                      (r.lay.query_words - 1) * r.nq_idx, 16});
     return r.ctx->pinned(stage_words * 8, reinterpret_cast<void**>(&r.stage));
 }
@@ -845,20 +871,20 @@ static int32_t stage_fri(ProveRun& r) {
         r.off_leaf[o] = woff; woff += per_oracle * r.lay.leaf_len[o];
         r.off_sib[o] = woff; woff += per_oracle * r.lay.depth0 * 4;
     }
-    r.off_ev = woff; woff += per_oracle * r.L * 4;
-    r.off_fsib = woff; woff += per_oracle * r.lay.sib_total;
+    r.off_ev = woff; woff += per_oracle * r.lay.fri.ev_total;
+    r.off_fsib = woff; woff += per_oracle * r.lay.fri.sib_total;
     r.open_words = woff;
     GL355_TRY(r.ob.get((per_oracle + r.open_words + 16) * 8));
     r.d_idx = r.ob.as<uint64_t>();
     r.d_open = r.d_idx + per_oracle;
-    const uint64_t final_words = 2 * (r.n >> r.L);
+    const uint64_t final_words = 2 * (r.n >> r.lay.fri.total_bits);
     FriUnitOut fo[MAXB];
     for (uint32_t u = 0; u < r.B; u++) {
         fo[u].caps = r.out[u]; r.out[u] += (uint64_t)r.L * r.n_cap * 4;
         fo[u].final_poly = r.out[u]; r.out[u] += final_words;
         fo[u].pow_witness = r.out[u]; r.out[u] += 1;
     }
-    const FriShape shape{r.c.degree_bits, r.c.rate_bits, r.cap_h, r.L, r.pd->pow_bits, r.nq_idx, r.hasher};
+    const FriShape shape{r.c.degree_bits, r.c.rate_bits, r.cap_h, r.pd->pow_bits, r.nq_idx, r.hasher, r.lay.fri};
     return fri_tail_units(r.ctx, shape, r.B, r.colsA.as<uint64_t>(), r.colsB.as<uint64_t>(), r.fri_vals.as<uint64_t>(), r.stage, r.ch.data(), fo, r.q_idx.data(),
                           r.d_idx, r.d_open + r.off_ev, r.d_open + r.off_fsib);
 }
@@ -889,10 +915,11 @@ static int32_t stage_queries(ProveRun& r) {
                 memcpy(o_, st + r.off_leaf[o] + uq * ll, (uint64_t)ll * 8); o_ += ll;
                 memcpy(o_, st + r.off_sib[o] + uq * depth0 * 4, (uint64_t)depth0 * 32); o_ += (uint64_t)depth0 * 4;
             }
+            const FriLayers& fl = r.lay.fri;
             for (uint32_t l = 0; l < r.L; l++) {
-                memcpy(o_, st + r.off_ev + (uq * r.L + l) * 4, 32); o_ += 4;
-                const uint64_t d = (uint64_t)(r.lde_bits - 1 - l - r.cap_h) * 4;
-                memcpy(o_, st + r.off_fsib + uq * r.lay.sib_total + r.lay.sib_off[l], d * 8); o_ += d;
+                const uint64_t w = 2ull << fl.a[l], d = (uint64_t)fl.depth[l] * 4;
+                memcpy(o_, st + r.off_ev + uq * fl.ev_total + fl.ev_off[l], w * 8); o_ += w;
+                memcpy(o_, st + r.off_fsib + uq * fl.sib_total + fl.sib_off[l], d * 8); o_ += d;
             }
         }
         if ((uint64_t)(o_ - r.io[u].proof) != r.lay.words) return ctx->fail(GL355_E_HIP, "prove: internal proof-size mismatch");
@@ -914,8 +941,12 @@ int32_t prove_units(Ctx* ctx, const gl355_prover_data* pd, uint32_t B, const uin
     const gl355_oracle* cs = pd->constants_sigmas;
     const uint32_t nch = c.num_challenges, lde_bits = c.degree_bits + c.rate_bits, cap_h = pd->cap_height, L = pd->n_fri_layers;
     if (nch == 0 || nch > 4 || L > 32 || lde_bits > 27) return ctx->fail(GL355_E_UNSUPPORTED, "prove: unsupported shape");
-    if (L >= c.degree_bits) return ctx->fail(GL355_E_UNSUPPORTED, "prove: the final polynomial must keep at least two coefficients");
-    if (lde_bits - L < cap_h + 1u) return ctx->fail(GL355_E_INVALID_ARG, "prove: too many FRI layers for the cap height");
+    FriLayers fl;
+    const int32_t fl_rc = fl.init(lde_bits, cap_h, L, pd->fri_arity_bits);
+    if (fl_rc == GL355_E_UNSUPPORTED) return ctx->fail(fl_rc, "prove: a FRI layer folds by 2, 4, 8 or 16");
+    if (fl_rc != GL355_OK) return ctx->fail(fl_rc, "prove: a FRI arity of 0 bits, or too many FRI layers for the cap height");
+    if (fl.total_bits >= c.degree_bits) return ctx->fail(GL355_E_UNSUPPORTED, "prove: the final polynomial must keep at least two coefficients");
+    if (lde_bits - fl.total_bits < cap_h + 1u) return ctx->fail(GL355_E_INVALID_ARG, "prove: too many FRI layers for the cap height");
     const uint32_t n_chunks = (c.num_routed_wires + c.max_degree - 1) / c.max_degree;
     if (n_chunks > ZS_MAX_CHUNKS || c.num_partial_products + 1 != n_chunks) return ctx->fail(GL355_E_UNSUPPORTED, "prove: at most 16 partial-product chunks");
     if (cs->log_n != c.degree_bits || cs->rate_bits != c.rate_bits || cs->cap_height != cap_h)

@@ -206,6 +206,23 @@ bool merkle_verify(int32_t hasher, const uint64_t* leaf, uint32_t leaf_len, uint
     return true;
 }
 
+// compute_evaluation's interpolation: the value at beta of the polynomial of degree < A through (pts[j], v[j]), pts distinct base-field
+// points (Lagrange form; A <= 16)
+E interpolate(const uint64_t* pts, const E* v, uint32_t A, E beta) {
+    E acc = gl2_make(0, 0);
+    for (uint32_t j = 0; j < A; j++) {
+        E num = v[j];
+        uint64_t den = 1;
+        for (uint32_t k = 0; k < A; k++) {
+            if (k == j) continue;
+            num = gl2_mul(num, gl2_sub(beta, e_base(pts[k])));
+            den = gl_mul(den, gl_sub(pts[j], pts[k]));
+        }
+        acc = gl2_add(acc, gl2_mul_base(num, gl_inv(den)));
+    }
+    return acc;
+}
+
 int32_t fail(const char* why) { g_verify_error = why; return GL355_E_VERIFY; }
 
 }  // namespace
@@ -233,8 +250,9 @@ static int32_t verify_impl(const gl355_verifier_data* vd, const uint64_t* proof,
     const uint32_t nch = c.num_challenges, qdf = c.max_degree, npp = c.num_partial_products, routed = c.num_routed_wires;
     const uint32_t cap_h = vd->cap_height, L = vd->n_fri_layers, nq = vd->num_queries, lde_bits = c.degree_bits + c.rate_bits;
     const int32_t hasher = vd->hasher;
+    FriLayers fl;
     if (nch == 0 || nch > 4 || L > 32 || lde_bits > 40 || c.num_gates > GL355_MAX_GATES || qdf == 0 || c.num_selectors == 0 ||
-        L > lde_bits || cap_h > lde_bits - L ||        // every FRI layer tree (2^(lde_bits - l) leaves... the last has lde_bits - L path bits) must reach its cap
+        fl.init(lde_bits, cap_h, L, vd->fri_arity_bits) != GL355_OK ||     // every FRI layer tree (2^(lde_bits - s_l) leaves) must reach its cap; 1..4 arity bits
         (hasher != GL355_HASH_POSEIDON && hasher != GL355_HASH_BN254_POSEIDON)) { g_verify_error = "verify: unsupported verifier data"; return GL355_E_INVALID_ARG; }
     const bool zk = vd->zero_knowledge != 0;
     const uint64_t n_cap = 1ull << cap_h;
@@ -243,6 +261,7 @@ static int32_t verify_impl(const gl355_verifier_data* vd, const uint64_t* proof,
     gl355_prover_data pd;
     memset(&pd, 0, sizeof pd);
     pd.circuit = vd->circuit; pd.cap_height = cap_h; pd.num_queries = nq; pd.n_fri_layers = L; pd.zero_knowledge = vd->zero_knowledge;
+    pd.fri_arity_bits = vd->fri_arity_bits;
     const uint64_t need = gl355_proof_words(&pd);
     if (proof_words != need || proof[0] != need) return fail("proof length does not match the circuit");
     if (proof[1] != c.degree_bits || proof[2] != L || proof[3] != nq || proof[4] != n_public_inputs || proof[5] != (uint64_t)zk || proof[6] != cap_h || proof[7] != nch)
@@ -255,7 +274,7 @@ static int32_t verify_impl(const gl355_verifier_data* vd, const uint64_t* proof,
     for (int o = 0; o < 4; o++) n_open += widths[o];
     const uint64_t* open_words = p; p += 2ull * (n_open + nch);
     const uint64_t* fri_caps = p; p += (uint64_t)L * n_cap * 4;
-    const uint64_t final_len = (1ull << c.degree_bits) >> L;
+    const uint64_t final_len = (1ull << c.degree_bits) >> fl.total_bits;
     const uint64_t* final_poly = p; p += 2 * final_len;
     const uint64_t pow_witness = *p++;
     const uint64_t* queries = p;
@@ -409,21 +428,26 @@ static int32_t verify_impl(const gl355_verifier_data* vd, const uint64_t* proof,
         E prev = total;
         uint64_t idx = x_index;
         for (uint32_t l = 0; l < L; l++) {
-            for (int i = 0; i < 4; i++) if (q[i] >= GL_P) return fail("non-canonical field element in a FRI layer opening");
-            const E ev[2] = {gl2_make(q[0], q[1]), gl2_make(q[2], q[3])};
+            const uint32_t ab = fl.a[l], A = 1u << ab;
+            for (uint32_t i = 0; i < 2 * A; i++) if (q[i] >= GL_P) return fail("non-canonical field element in a FRI layer opening");
+            E ev[16];
+            for (uint32_t i = 0; i < A; i++) ev[i] = gl2_make(q[2 * i], q[2 * i + 1]);
             const uint64_t* ev_words = q;
-            q += 4;
-            const uint64_t within = idx & 1, coset_index = idx >> 1;
+            q += 2 * A;
+            const uint64_t within = idx & (A - 1), coset_index = idx >> ab;
             if (!e_eq(ev[within], prev)) return fail("FRI fold consistency");
-            // next_eval (fri_chip.rs:168-226), arity 2: the two points are (x0, -x0)
-            const uint64_t start = within == 0 ? xx : gl_canon(gl_neg(xx));
-            const E a0 = e_base(start), b0 = e_base(gl_canon(gl_neg(start)));
-            const E numer = gl2_mul(gl2_sub(fri_betas[l], a0), gl2_sub(ev[1], ev[0]));
-            prev = gl2_add(ev[0], gl2_mul(numer, gl2_inv(gl2_sub(b0, a0))));
-            const uint32_t layers = lde_bits - 1 - l - cap_h;
-            if (!merkle_verify(hasher, ev_words, 4, coset_index, q, layers, fri_caps + (uint64_t)l * n_cap * 4, cap_h)) return fail("FRI layer opening does not verify");
-            q += (uint64_t)layers * 4;
-            xx = gl_canon(gl_mul(xx, xx));
+            // compute_evaluation (fri_chip.rs:168-226 for arity 2, where the two points are (x0, -x0)): the opened values, in the bit-reversed order
+            // of the leaf, lie on the coset start * <g>, g of order A, start = x * g^-rev(within); their interpolant at beta is the next value
+            const uint64_t gA = gl_root_of_unity(ab);
+            const uint64_t start = gl_canon(gl_mul(xx, gl_pow(gA, A - host_brev((uint32_t)within, ab))));
+            uint64_t pts[16];
+            E vals[16];
+            uint64_t pt = start;
+            for (uint32_t j = 0; j < A; j++) { pts[j] = pt; vals[j] = ev[host_brev(j, ab)]; pt = gl_canon(gl_mul(pt, gA)); }
+            prev = interpolate(pts, vals, A, fri_betas[l]);
+            if (!merkle_verify(hasher, ev_words, 2 * A, coset_index, q, fl.depth[l], fri_caps + (uint64_t)l * n_cap * 4, cap_h)) return fail("FRI layer opening does not verify");
+            q += (uint64_t)fl.depth[l] * 4;
+            for (uint32_t j = 0; j < ab; j++) xx = gl_canon(gl_mul(xx, xx));
             idx = coset_index;
         }
         if (!e_eq(reduce_with_powers(fpoly.data(), fpoly.size(), e_base(xx)), prev)) return fail("final polynomial");

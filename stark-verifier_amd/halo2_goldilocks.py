@@ -989,6 +989,8 @@ class FriVerifierChip:
 
     def __init__(self, ctx, offset, lde_bits, cap_height, reduction_arity_bits, hiding, proof_of_work_bits):      # construct, :35-46
         self.ctx, self.offset = ctx, offset
+        if any(int(a) != 1 for a in reduction_arity_bits):      # next_eval is the reference's: two points per layer (:211)
+            raise ValueError("FriVerifierChip supports arity-2 FRI only (reduction_arity_bits = 1), not %r" % (list(reduction_arity_bits),))
         self.lde_bits, self.cap_height, self.reduction_arity_bits = lde_bits, cap_height, list(reduction_arity_bits)
         self.hiding, self.proof_of_work_bits = hiding, proof_of_work_bits
         self.goldilocks_chip = GoldilocksChip(ctx)

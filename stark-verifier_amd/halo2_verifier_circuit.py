@@ -44,7 +44,8 @@ class FriOpeningsCircuit:
         self.cd = cd
         assert cd["hasher"] == 1, "the circuit hashes with Bn254PoseidonHash"
         self.arity_bits = [int(a) for a in cd["arity_bits"]]
-        assert all(a == 1 for a in self.arity_bits), "the flat proof holds one evaluation pair per layer (arity 2)"
+        if any(a != 1 for a in self.arity_bits):      # as the reference's FriChip (fri_chip.rs:211)
+            raise ValueError("the Halo2 verifier circuit supports arity-2 FRI only (reduction_arity_bits = 1), not %r" % (self.arity_bits,))
         self.cap_height, self.n_cap = cd["cap_height"], 1 << cd["cap_height"]
         self.lde_bits = cd["degree_bits"] + cd["rate_bits"]
         self.n_queries, self.n_layers = cd["num_query_rounds"], len(self.arity_bits)

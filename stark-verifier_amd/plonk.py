@@ -25,6 +25,23 @@ from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CON
 from .api import COSET_SHIFT, P, SALT_SIZE, MerkleTree, PolynomialBatch, _ptr, _u64, deep_batch, eval_polys
 
 UNUSED_SELECTOR = 0xFFFFFFFF
+MAX_FRI_ARITY_BITS = 4      # GL355_MAX_FRI_ARITY_BITS
+
+
+def fri_layer_shape(lde_bits, cap_height, arity_bits):
+    """per FRI layer (words of an opened leaf, digests of its path): layer l opens the 2^a_l extension values of leaf x_index >> s_l,
+    s_l = a_0 + .. + a_l, in a tree of 2^(lde_bits - s_l) leaves (the flat proof's layout, include/gl355.h)"""
+    out, s = [], 0
+    for a in arity_bits:
+        s += a
+        out.append((2 << a, lde_bits - s - cap_height))
+    return out
+
+
+def require_arity_2(arity_bits, who):
+    """the consumers that only speak the reference's arity-2 FRI refuse every other reduction by name"""
+    if any(int(a) != 1 for a in arity_bits):
+        raise ValueError("%s supports arity-2 FRI only (reduction_arity_bits = 1), not %r" % (who, list(arity_bits)))
 
 
 class CircuitConfig:
@@ -41,18 +58,28 @@ class CircuitConfig:
         self.cap_height = 4
         self.proof_of_work_bits = 16
         self.num_query_rounds = 28
-        self.reduction_arity_bits = 1      # FriReductionStrategy::ConstantArityBits(1, 5)
+        self.reduction_arity_bits = 1      # FriReductionStrategy: an int a = ConstantArityBits(a, final_poly_bits), a list = Fixed(list)
         self.final_poly_bits = 5
         self.hasher = 0                    # GenericConfig::Hasher: 0 PoseidonHash, 1 the reference's Bn254PoseidonHash (OuterC)
         self.__dict__.update(kw)
 
     def fri_reduction_arity_bits(self, degree_bits):
-        """ConstantArityBits(a, f): push a while degree_bits > f and degree_bits + rate_bits - a >= cap_height."""
-        out, d = [], degree_bits
-        a, f = self.reduction_arity_bits, self.final_poly_bits
-        while d > f and d + self.rate_bits - a >= self.cap_height:
-            out.append(a)
-            d -= a
+        """ConstantArityBits(a, f): push a while degree_bits > f and degree_bits + rate_bits - a >= cap_height.  Fixed(list): the list.
+        Every layer folds by 2^1 .. 2^MAX_FRI_ARITY_BITS, and a Fixed list must leave the layers of this degree their cap."""
+        if isinstance(self.reduction_arity_bits, (list, tuple)):
+            out = [int(a) for a in self.reduction_arity_bits]
+            if sum(out) > degree_bits or degree_bits + self.rate_bits - sum(out) < self.cap_height:
+                raise ValueError("reduction_arity_bits %r folds a degree-2^%d polynomial below its final polynomial or its Merkle cap" % (out, degree_bits))
+        else:
+            out, d = [], degree_bits
+            a, f = int(self.reduction_arity_bits), self.final_poly_bits
+            if a < 1:
+                raise ValueError("reduction_arity_bits must be at least 1")
+            while d > f and d + self.rate_bits - a >= self.cap_height:
+                out.append(a)
+                d -= a
+        if any(a < 1 or a > MAX_FRI_ARITY_BITS for a in out):
+            raise ValueError("a FRI layer folds by 2, 4, 8 or 16: reduction_arity_bits %r" % (self.reduction_arity_bits,))
         return out
 
 
@@ -375,8 +402,17 @@ class CircuitData:
             pd.cap_height, pd.pow_bits, pd.num_queries = cfg.cap_height, cfg.proof_of_work_bits, cfg.num_query_rounds
             pd.n_fri_layers, pd.zero_knowledge = len(self.fri_arity_bits), int(cfg.zero_knowledge)
             pd.hasher = cfg.hasher
+            pd.fri_arity_bits = self._c_arity_bits()
             cache[key] = pd
         return cache[key]
+
+    def _c_arity_bits(self):
+        """the `const uint32_t* fri_arity_bits` of the prover / verifier data: one array per CircuitData, alive as long as it is"""
+        if not self.fri_arity_bits:
+            return None
+        if "_arity_arr" not in self.__dict__:
+            self._arity_arr = np.array(self.fri_arity_bits, dtype=np.uint32)
+        return self._arity_arr.ctypes.data
 
     def export_blob(self, row_idx, tape=None, pi_pos=None, n_inputs=0, tape_layout=None, external_digest=None):
         """Serialise the built circuit (+ the sparse witness-row map and optionally a witness tape) as the u64 artifact
@@ -384,6 +420,7 @@ class CircuitData:
         by plonky2's own CircuitBuilder::build, whose digest also covers its domain separator): the artifact is then version 3 and
         carries the expected constants_sigmas cap, which the loader checks against its own commitment of the tables instead of
         re-deriving this framework's digest."""
+        require_arity_2(self.fri_arity_bits, "the circuit artifact (its header holds a layer count only)")
         cfg = self.config
         cc = self.c_circuit
         hdr = np.zeros(112, dtype=np.uint64)
@@ -424,6 +461,7 @@ class CircuitData:
             vd.circuit_digest[i] = int(self.circuit_digest[i])
         vd.cap_height, vd.pow_bits, vd.num_queries = cfg.cap_height, cfg.proof_of_work_bits, cfg.num_query_rounds
         vd.n_fri_layers, vd.zero_knowledge, vd.hasher = len(self.fri_arity_bits), int(cfg.zero_knowledge), int(getattr(cfg, "hasher", 0))
+        vd.fri_arity_bits = self._c_arity_bits()
         flat, pi = _u64(flat_proof), _u64(public_inputs)
         rc = lib.gl355_verify(C.byref(vd), _ptr(flat), flat.size, _ptr(pi), pi.size)
         if rc != 0:
@@ -501,6 +539,7 @@ def parse_proof_tagged(data, flat, public_inputs, offset=0):
 def parse_proof(data, flat):
     """Flat u64 proof of gl355_prove (layout in include/gl355.h) -> the dict the verifier restatement reads.
     data: CircuitData, or its common() dict."""
+    arity_bits = data["arity_bits"] if isinstance(data, dict) else data.fri_arity_bits
     if isinstance(data, dict):
         rate_bits, n_const, n_routed, n_wires = data["rate_bits"], data["num_selectors"] + data["num_constants"], data["num_routed_wires"], data["num_wires"]
         n_pp, qdf = data["num_partial_products"], data["quotient_degree_factor"]
@@ -523,7 +562,9 @@ def parse_proof(data, flat):
               ("partial_products", nch * n_pp), ("quotient_polys", nch * qdf), ("plonk_zs_next", nch)]
     openings = {name: take(2 * k, (k, 2)) for name, k in counts}
     caps = take(n_layers * n_cap * 4, (n_layers, n_cap, 4))
-    final_poly = take(2 * (n >> n_layers), (-1, 2))
+    if n_layers != len(arity_bits):
+        raise ValueError("the proof has %d FRI layers, the circuit data %d" % (n_layers, len(arity_bits)))
+    final_poly = take(2 * (n >> sum(arity_bits)), (-1, 2))
     pow_witness = int(take(1)[0])
     widths = [n_const + n_routed, n_wires, nch * (1 + n_pp), nch * qdf]
     depth0 = lde_bits - cap_h
@@ -535,9 +576,8 @@ def parse_proof(data, flat):
             ll = widths[o] + (SALT_SIZE if (zk and o > 0) else 0)
             initial.append((take(ll), take(depth0 * 4, (depth0, 4))))
         steps = []
-        for l in range(n_layers):
-            d = lde_bits - 1 - l - cap_h
-            steps.append((take(4), take(d * 4, (d, 4))))
+        for w, d in fri_layer_shape(lde_bits, cap_h, arity_bits):
+            steps.append((take(w), take(d * 4, (d, 4))))
         queries.append(dict(index=x_index, initial_trees=initial, steps=steps))
     assert pos[0] == total == flat.size
     return dict(wires_cap=wires_cap, plonk_zs_partial_products_cap=zs_cap, quotient_polys_cap=q_cap, openings=openings,
@@ -779,12 +819,13 @@ def prove_staged(ctx, data, wires, public_inputs, rng, timings=None):
     lde_bits = data.degree_bits + cfg.rate_bits
     n_cap = 1 << cfg.cap_height
     nq = cfg.num_query_rounds
-    depths = [lde_bits - 1 - l - cfg.cap_height for l in range(n_layers)]
+    shape = fri_layer_shape(lde_bits, cfg.cap_height, data.fri_arity_bits)
+    widths, depths = [w for w, _ in shape], [d for _, d in shape]
     caps = np.empty((n_layers, n_cap, 4), dtype=np.uint64)
-    final_poly = np.empty((n >> n_layers, 2), dtype=np.uint64)
+    final_poly = np.empty((n >> int(arity.sum()), 2), dtype=np.uint64)
     pow_witness = C.c_uint64()
     x_indices = np.empty(nq, dtype=np.uint64)
-    step_evals = np.empty((nq, n_layers, 4), dtype=np.uint64)
+    step_evals = np.empty((nq, max(1, sum(widths))), dtype=np.uint64)
     step_sibs = np.empty((nq, max(1, sum(depths)), 4), dtype=np.uint64)
     ctx.check(lib.gl355_fri_prove(ctx.h, _ptr(acc), data.degree_bits, cfg.rate_bits, cfg.cap_height,
                                   arity.ctypes.data_as(C.c_void_p), n_layers, cfg.proof_of_work_bits, nq, C.byref(ch.c),
@@ -795,8 +836,9 @@ def prove_staged(ctx, data, wires, public_inputs, rng, timings=None):
     opened = [o.open_batch(x_indices) for o in oracles]
     queries = []
     offs = np.concatenate([[0], np.cumsum(depths)]).astype(int)
+    ev_offs = np.concatenate([[0], np.cumsum(widths)]).astype(int)
     for qi in range(nq):
-        steps = [(step_evals[qi, l], step_sibs[qi, offs[l]:offs[l + 1]]) for l in range(n_layers)]
+        steps = [(step_evals[qi, ev_offs[l]:ev_offs[l + 1]], step_sibs[qi, offs[l]:offs[l + 1]]) for l in range(n_layers)]
         queries.append(dict(index=int(x_indices[qi]), initial_trees=[opened[o][qi] for o in range(len(oracles))], steps=steps))
     lap("initial-tree openings")
     trees_caps = [caps[l] for l in range(n_layers)]

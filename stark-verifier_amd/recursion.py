@@ -15,7 +15,7 @@ import numpy as np
 from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_NOOP, GATE_POSEIDON,
                    GATE_POSEIDON_MDS, GATE_PUBLIC_INPUT, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT)
 from .gadgets import CIRC, GadgetBuilder, T
-from .plonk import CircuitConfig, P, _ptr, _u64, derive_key, parse_proof_tagged, prove_sparse
+from .plonk import CircuitConfig, P, _ptr, _u64, derive_key, parse_proof_tagged, prove_sparse, require_arity_2
 
 UNUSED_SELECTOR = 0xFFFFFFFF
 _RC = None
@@ -274,6 +274,8 @@ def verify_proof(b, cd, proof, register_pis=True):
     """builder.verify_proof: proof (dict as produced by plonk.parse_proof) becomes virtual targets; the inner
     circuit's verifier data (constants_sigmas cap, circuit digest) are constants.  Returns the inner public-input
     targets."""
+    # the step of a larger arity interpolates through 4, 8 or 16 points: an interpolation gate, which is not among the 12 gates here
+    require_arity_2(cd["arity_bits"], "the in-circuit verifier")
     assert cd.get("hasher", 0) == 0, "the in-circuit verifier hashes with Poseidon-Goldilocks: the inner proof must use PoseidonHash"
     nch = cd["num_challenges"]
     tv = b.add_virtual_target
