@@ -242,13 +242,22 @@ int32_t gl355_oracle_open_batch(const gl355_oracle* o, const uint64_t* indices, 
 enum { GL355_GATE_NOOP = 0, GL355_GATE_CONSTANT = 1, GL355_GATE_PUBLIC_INPUT = 2, GL355_GATE_BASE_SUM = 3,
        GL355_GATE_POSEIDON = 4, GL355_GATE_ARITHMETIC = 5, GL355_GATE_ARITHMETIC_EXT = 6, GL355_GATE_MUL_EXT = 7,
        GL355_GATE_POSEIDON_MDS = 8, GL355_GATE_RANDOM_ACCESS = 9, GL355_GATE_REDUCING = 10,
-       GL355_GATE_REDUCING_EXT = 11 };   /* the gate set of gates/mod.rs:141-196 */
-#define GL355_GATE_TYPE_MAX GL355_GATE_REDUCING_EXT
-/* RANDOM_ACCESS param = bits | num_copies << 8 | num_extra_constants << 16 */
+       GL355_GATE_REDUCING_EXT = 11,     /* 0..11: the gate set of gates/mod.rs:141-196 */
+       GL355_GATE_COSET_INTERPOLATION = 12 };   /* plonky2 gates/coset_interpolation.rs (not in the reference's verifier): FRI arities above 2 in-circuit */
+#define GL355_GATE_TYPE_MAX GL355_GATE_COSET_INTERPOLATION
+/* RANDOM_ACCESS param = bits | num_copies << 8 | num_extra_constants << 16
+ * COSET_INTERPOLATION param = subgroup_bits | degree << 8 (D = 2): the interpolant through N = 2^subgroup_bits extension values on the
+ * coset shift * <g>, g = primitive_root_of_unity(subgroup_bits), evaluated at an extension point.  subgroup_bits 2..4, 2 <= degree <= N,
+ * n_int = (N - 2) / (degree - 1) intermediate (eval, prod) pairs.  Wires: shift 0 | value i at 1 + 2i | evaluation_point 1 + 2N |
+ * evaluation_value 3 + 2N | intermediate_eval_i at 5 + 2N + 2i | intermediate_prod_i at 5 + 2N + 2(n_int + i) | shifted_evaluation_point
+ * at 5 + 2N + 4 n_int (the wires from 5 + 2N on are not routed); 2 (2 + 2 n_int) constraints of degree `degree`:
+ *   evaluation_point - shifted * shift; with (eval, prod) <- (eval (x - x_i) + v_i w_i prod, prod (x - x_i)), x = shifted, x_i = g^i,
+ *   w_i = x_i / N, from (0, 1) over the points [0, degree), then per intermediate i: intermediate_eval_i - eval, intermediate_prod_i - prod,
+ *   continue from the intermediate wires over the next degree - 1 points; evaluation_value - eval. */
 typedef struct {
     uint32_t type;            /* GL355_GATE_* */
     uint32_t param;           /* CONSTANT: num_consts; BASE_SUM: num_limbs (base 2); ARITHMETIC(_EXT) and MUL_EXT: num_ops;
-                                 REDUCING*: num_coeffs; RANDOM_ACCESS: packed (above) */
+                                 REDUCING*: num_coeffs; RANDOM_ACCESS, COSET_INTERPOLATION: packed (above) */
     uint32_t selector_index;  /* which constants column is this gate's selector */
     uint32_t group_start, group_end;
 } gl355_gate;
@@ -340,6 +349,10 @@ int32_t gl355_host_permute_h(int32_t hasher, uint64_t state[12]);
 int32_t gl355_host_hash_no_pad_h(int32_t hasher, const uint64_t* in, uint64_t len, uint64_t out[4]);
 /* witness generation of one PoseidonGate row (wire layout gates/poseidon.rs:329-380) */
 int32_t gl355_poseidon_gate_witness(const uint64_t inputs[12], uint64_t swap, uint64_t wires[135]);
+/* witness generation of one CosetInterpolationGate row (layout at GL355_GATE_COSET_INTERPOLATION): shift, the values and the evaluation
+ * point are set in `wires` (5 + 2N + 4 n_int + 2 of them); fills shifted = point / shift, the intermediates and evaluation_value.
+ * GL355_E_INVALID_ARG: bits outside 2..4 or degree outside 2..N; GL355_E_WITNESS: shift is zero (nothing is divided) */
+int32_t gl355_coset_interpolation_witness(uint32_t bits, uint32_t degree, uint64_t* wires);
 
 /* ---- a12 + a13 + a14 in one call: fri_proof (fri_chip.rs:168-226,275-327,364-376) ------------------
  * final_coeffs: n = 2^log_n extension coefficients of the DEEP polynomial (host or device).  Runs the
@@ -462,12 +475,13 @@ int32_t gl355_semaphore_witness(const uint64_t private_key[4], const uint64_t to
  *   RANDOM_ACCESS row a, copy b: claimed element + index bits              (gates/random_access.rs)
  *   REDUCING row a: b coefficients, c = 1 for the extension variant        (gates/reducing.rs, reducing_extension.rs)
  *   LO32 / HI32 a <- halves of [b] | EXT_INV (a, b) <- ([c], [d])^-1
+ *   COSET_INTERP row a: b subgroup bits, c degree; shift, values, point set  (gl355_coset_interpolation_witness; a zero shift fails the entry)
  * rows is zeroed first.  Returns GL355_E_WITNESS (and the entry index in *failed_op) when an ASSERT_EQ or a
  * range condition fails, i.e. the inputs do not satisfy the circuit. */
 enum { GL355_TAPE_CONST = 0, GL355_TAPE_INPUT = 1, GL355_TAPE_COPY = 2, GL355_TAPE_ASSERT_EQ = 3, GL355_TAPE_ARITH = 4,
        GL355_TAPE_ARITH_EXT = 5, GL355_TAPE_POSEIDON = 6, GL355_TAPE_MDS_EXT = 7, GL355_TAPE_BASE_SUM = 8,
        GL355_TAPE_RANDOM_ACCESS = 9, GL355_TAPE_REDUCING = 10, GL355_TAPE_LO32 = 11, GL355_TAPE_HI32 = 12,
-       GL355_TAPE_EXT_INV = 13 };
+       GL355_TAPE_EXT_INV = 13, GL355_TAPE_COSET_INTERP = 14 };
 int32_t gl355_witness_replay(const uint64_t* tape, uint64_t n_ops, const uint64_t* inputs, uint64_t n_inputs,
                              uint64_t* rows, uint64_t n_words, uint32_t num_wires, uint64_t* failed_op);
 /* A segmented tape = [n_seq sequential entries | segment 0 | segment 1 | ...] where the builder has checked that a segment reads

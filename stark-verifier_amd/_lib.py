@@ -39,7 +39,7 @@ class ProverData(C.Structure):
 
 MAX_GATES = 16
 (GATE_NOOP, GATE_CONSTANT, GATE_PUBLIC_INPUT, GATE_BASE_SUM, GATE_POSEIDON, GATE_ARITHMETIC, GATE_ARITHMETIC_EXT,
- GATE_MUL_EXT, GATE_POSEIDON_MDS, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT) = range(12)
+ GATE_MUL_EXT, GATE_POSEIDON_MDS, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT, GATE_COSET_INTERPOLATION) = range(13)
 
 
 class Gate(C.Structure):
@@ -181,6 +181,7 @@ SIGNATURES = {
     "gl355_host_hash_no_pad_h": (C.c_int32, [C.c_int32, vp, C.c_uint64, vp]),
     "gl355_host_permute_h": (C.c_int32, [C.c_int32, vp]),
     "gl355_poseidon_gate_witness": (C.c_int32, [vp, C.c_uint64, vp]),
+    "gl355_coset_interpolation_witness": (C.c_int32, [C.c_uint32, C.c_uint32, vp]),
     "gl355_deep_batch": (C.c_int32, [vp, C.POINTER(PolyRef), C.c_uint32, vp, vp, vp]),
     "gl355_eval_polys": (C.c_int32, [vp, C.POINTER(PolyRef), C.c_uint32, vp, vp]),
     "gl355_lde_ext": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint64, vp]),

@@ -13,6 +13,7 @@
 #include "../../include/gl355.h"
 #include "gl_field.cuh"
 #include "merkle_common.cuh"
+#include "coset_interp.h"
 
 namespace gl355 { struct Ctx; }
 

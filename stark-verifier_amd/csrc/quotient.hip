@@ -6,7 +6,8 @@
 // recursion.rs:168, wrapper.rs:55).  The formula is the one the reference's verifier re-evaluates at
 // zeta: src/plonky2_verifier/chip/plonk/vanishing_poly.rs:18-153 (term order :110-123), gate filter
 // chip/plonk/gates/mod.rs:87-132, quotient identity chip/plonk/plonk_verifier_chip.rs:174-210, and
-// the gate evaluators chip/plonk/gates/*.rs (all 12 gate kinds of the dispatch table gates/mod.rs:141-196).
+// the gate evaluators chip/plonk/gates/*.rs (all 12 gate kinds of the dispatch table gates/mod.rs:141-196), and plonky2's
+// CosetInterpolationGate as a thirteenth kind in kernel instances of its own (gate_coset_interpolation).
 //
 // One lane = one point x = 7*omega^i of the quotient coset (size n * 2^qdb).  The three committed
 // oracles are column-major in bit-reversed row order, and lane t works on storage row t, so every
@@ -452,9 +453,70 @@ GL_DEV void gate_reducing(const QuotArgs& a, const WireSrc& w, uint64_t t, GateA
     }
 }
 
+// CosetInterpolationGate{subgroup_bits b, degree d} (plonky2 gates/coset_interpolation.rs; layout and formula in coset_interp.h):
+// 2 (2 + 2 n_int) constraints.  The domain x_i = g^i of the three subgroup sizes is one table (the 16th roots of unity, strided) and
+// the barycentric weights w_i = x_i / N one table per size; the gate type and its parameter are wave-uniform, so the entries come
+// through the scalar cache.  The value wires arrive in groups of eight (four extension values), requested one group ahead; x, eval and
+// prod stay gl2 values in the lazy form (any u64) until they are pushed.  Every register index is a compile-time one.
+__device__ __constant__ const uint64_t CI_X16[16] = {
+    0x0000000000000001ull, 0xefffffff00000001ull, 0xfffffffeff000001ull, 0x000ffffffff00000ull, 0x0001000000000000ull, 0x0000000000001000ull,
+    0xfffffeff00000101ull, 0xffffffef00000001ull, 0xffffffff00000000ull, 0x1000000000000000ull, 0x0000000001000000ull, 0xffefffff00100001ull,
+    0xfffeffff00000001ull, 0xfffffffefffff001ull, 0x000000ffffffff00ull, 0x0000001000000000ull};      // (7^((p-1)/16))^i
+__device__ __constant__ const uint64_t CI_W[3][16] = {                                                // x_i / N for N = 4, 8, 16
+    {0xbfffffff40000001ull, 0x0000400000000000ull, 0x3fffffffc0000000ull, 0xffffbfff00000001ull},
+    {0xdfffffff20000001ull, 0xfffffffeffe00001ull, 0x0000200000000000ull, 0xffffffdf00000021ull, 0x1fffffffe0000000ull, 0x0000000000200000ull,
+     0xffffdfff00000001ull, 0x0000001fffffffe0ull},
+    {0xefffffff10000001ull, 0xfeffffff00000001ull, 0xfffffffefff00001ull, 0x0000ffffffff0000ull, 0x0000100000000000ull, 0x0000000000000100ull,
+     0xffffffef00000011ull, 0xfffffffe00000001ull, 0x0ffffffff0000000ull, 0x0100000000000000ull, 0x0000000000100000ull, 0xfffeffff00010001ull,
+     0xffffefff00000001ull, 0xfffffffeffffff01ull, 0x0000000ffffffff0ull, 0x0000000100000000ull}};
+template <class GateAcc>
+GL_DEV void gate_coset_interpolation(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g, uint32_t param) {
+    CosetInterpShape s;
+    coset_interp_shape(param, s);                            // checked at launch
+    typedef const __attribute__((address_space(4))) uint64_t* Tab;
+    const Tab xs = (Tab)CI_X16, ws = (Tab)CI_W[s.bits - 2];
+    const uint32_t stride = 16u >> s.bits, last = 2 * s.n;   // the last value wire
+    const uint64_t shift = WIRE(0);
+    uint64_t pv[4], sh[2], nx[8];
+    wire_group<4>(w, s.point, s.point + 3, pv);              // evaluation point, evaluation value
+    wire_group<2>(w, s.shifted, s.shifted + 1, sh);
+    wire_group<8>(w, 1, last, nx);
+    const gl2 x = gl2_make(sh[0], sh[1]);
+    push2(g, gl2_sub(gl2_make(pv[0], pv[1]), gl2_mul_base(x, shift)));
+    gl2 eval = gl2_make(0, 0), prod = gl2_make(1, 0);
+    uint32_t brk = s.degree, ni = 0;
+    for (uint32_t i0 = 0; i0 < s.n; i0 += 4) {
+        uint64_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) v[k] = nx[k];
+        wire_group<8>(w, 1 + 2 * (i0 + 4), last, nx);        // clamped behind the last group
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t i = i0 + k;
+            if (i == brk) {                                  // wave-uniform: the fold continues from intermediate pair ni
+                uint64_t ie[2], ip[2];
+                wire_group<2>(w, s.start_int + 2 * ni, s.start_int + 2 * ni + 1, ie);
+                wire_group<2>(w, s.start_int + 2 * (s.n_int + ni), s.start_int + 2 * (s.n_int + ni) + 1, ip);
+                push2(g, gl2_sub(gl2_make(ie[0], ie[1]), eval));
+                push2(g, gl2_sub(gl2_make(ip[0], ip[1]), prod));
+                eval = gl2_make(ie[0], ie[1]); prod = gl2_make(ip[0], ip[1]);
+                ni++; brk += s.degree - 1;
+            }
+            const gl2 xm = gl2_make(gl_sub(x.c0, xs[i * stride]), x.c1);
+            const gl2 vw = gl2_mul_base(gl2_make(v[2 * k], v[2 * k + 1]), ws[i]);
+            eval = gl2_add(gl2_mul(eval, xm), gl2_mul(vw, prod));
+            prod = gl2_mul(prod, xm);
+        }
+    }
+    push2(g, gl2_sub(gl2_make(pv[2], pv[3]), eval));
+}
+
 // STAGE (experiment of round 2, not instantiated any more: profiles/r02_quotient_ab.txt): the wave first copies its 64 points' wire rows (num_wires x 64 x 8 B = 69 KB) into LDS and
 // every evaluator reads them from there -- each wire column crosses the fabric once instead of ~4 times, at 2 waves per CU.
-template <int NCH, bool STAGE = false>
+// INTERP: the instances that also know CosetInterpolationGate.  The kernel is tuned to three waves per SIMD and its register
+// allocation follows every evaluator in the gate loop, so the thirteenth evaluator lives in instances of its own, launched when (and
+// only when) the circuit has that gate; the INTERP = false instances are the code every circuit without it has always run.
+template <int NCH, bool STAGE = false, bool INTERP = false>
 __global__ void __launch_bounds__(STAGE ? 64 : 128) __attribute__((amdgpu_waves_per_eu(STAGE ? 1 : 3, 3))) quotient_kernel(QuotArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t wire_lds[];
     const uint64_t nq = 1ull << a.qbits;
@@ -556,7 +618,11 @@ __global__ void __launch_bounds__(STAGE ? 64 : 128) __attribute__((amdgpu_waves_
         asm volatile("" : "+s"(wg.stride), "+s"(wg.cs_stride), "+v"(tg));
         wg.idx = STAGE ? w.idx : tg;
         g.init(a, unit, total.idx);
-        switch (gt.type) {
+        bool interp = false;
+        if constexpr (INTERP) {
+            if (gt.type == GL355_GATE_COSET_INTERPOLATION) { gate_coset_interpolation(a, wg, tg, g, gt.param); interp = true; }
+        }
+        if (!interp) switch (gt.type) {
             case GL355_GATE_POSEIDON: gate_poseidon(a, wg, tg, g); break;
             case GL355_GATE_BASE_SUM: gate_base_sum(a, wg, tg, g, gt.param); break;
             case GL355_GATE_CONSTANT: gate_constant(a, wg, tg, g, gt.param); break;
@@ -633,12 +699,23 @@ int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const u
     // length of the constraint stream = the permutation-argument prefix + the longest gate (constraint counts as in
     // gates/*.rs num_constraints; the gate evaluators below push exactly that many terms)
     uint32_t longest = 0;
+    bool has_interp = false;
     for (uint32_t g = 0; g < c->num_gates; g++) {
         const uint32_t p = c->gates[g].param;
         // the evaluator keeps a copy's bit wires in four registers and its list in sixteen
         if (c->gates[g].type == GL355_GATE_RANDOM_ACCESS && ((p & 0xFF) < 1 || (p & 0xFF) > 4))
             return ctx->fail(GL355_E_UNSUPPORTED, "quotient: RandomAccessGate with 1..4 bits");
         uint32_t k = 0;
+        if (c->gates[g].type == GL355_GATE_COSET_INTERPOLATION) {
+            // the evaluator's domain and weight tables are those of 4, 8 and 16 points; every wire it reads is checked here
+            CosetInterpShape s;
+            if ((p & 0xFF) < 2 || (p & 0xFF) > 4) return ctx->fail(GL355_E_UNSUPPORTED, "quotient: CosetInterpolationGate with 2..4 subgroup bits");
+            if (!coset_interp_shape(p, s)) return ctx->fail(GL355_E_INVALID_ARG, "quotient: CosetInterpolationGate degree outside 2..2^subgroup_bits");
+            if (s.num_wires > c->num_wires || s.start_int > c->num_routed_wires)
+                return ctx->fail(GL355_E_INVALID_ARG, "quotient: CosetInterpolationGate does not fit the wires / routed wires");
+            k = s.num_constraints;
+            has_interp = true;
+        }
         switch (c->gates[g].type) {
             case GL355_GATE_CONSTANT: k = p; break;
             case GL355_GATE_PUBLIC_INPUT: k = 4; break;
@@ -668,7 +745,14 @@ int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const u
     // three and four challenges: no circuit of the project has them; those instantiations do not fit 168 registers with the grouped
     // reads and spill (156 / 372 bytes of scratch per lane) -- correct, slower than they could be
     const dim3 grid((uint32_t)((nq + 127) / 128), B);
-    switch (c->num_challenges) {
+    if (has_interp) {        // a circuit with CosetInterpolationGate: the instances that know it (see quotient_kernel)
+        switch (c->num_challenges) {
+            case 1: hipLaunchKernelGGL((quotient_kernel<1, false, true>), grid, dim3(128), 0, ctx->stream, a); break;
+            case 2: hipLaunchKernelGGL((quotient_kernel<2, false, true>), grid, dim3(128), 0, ctx->stream, a); break;
+            case 3: hipLaunchKernelGGL((quotient_kernel<3, false, true>), grid, dim3(128), 0, ctx->stream, a); break;
+            default: hipLaunchKernelGGL((quotient_kernel<4, false, true>), grid, dim3(128), 0, ctx->stream, a); break;
+        }
+    } else switch (c->num_challenges) {
         case 1: hipLaunchKernelGGL(quotient_kernel<1>, grid, dim3(128), 0, ctx->stream, a); break;
         case 2: hipLaunchKernelGGL(quotient_kernel<2>, grid, dim3(128), 0, ctx->stream, a); break;
         case 3: hipLaunchKernelGGL(quotient_kernel<3>, grid, dim3(128), 0, ctx->stream, a); break;

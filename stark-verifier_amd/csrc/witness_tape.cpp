@@ -9,7 +9,7 @@
 //
 // Wire layouts of the gate rows follow the reference's chip/plonk/gates/*.rs (arithmetic.rs,
 // arithmetic_extension.rs, poseidon.rs:329-380, poseidon_mds.rs, base_sum.rs, random_access.rs,
-// reducing.rs, reducing_extension.rs).
+// reducing.rs, reducing_extension.rs); CosetInterpolationGate's is in coset_interp.h.
 #include "gl355_internal.h"
 
 #include <atomic>
@@ -135,6 +135,13 @@ static int32_t run_entries(const uint64_t* tape, uint64_t begin, uint64_t end, c
             W[b] = r.c1;
             break;
         }
+        case GL355_TAPE_COSET_INTERP: {   // b = subgroup bits, c = degree: shift, values and point are set, the rest is filled
+            ROWCHK(a)
+            CosetInterpShape s;
+            if (b > 0xFF || c > 0xFF || !coset_interp_shape((uint32_t)(b | c << 8), s) || s.num_wires > num_wires) { if (failed_op) *failed_op = t; return GL355_E_INVALID_ARG; }
+            if (coset_interp_fill(s, W + a)) { if (failed_op) *failed_op = t; return GL355_E_WITNESS; }
+            break;
+        }
         default:
             if (failed_op) *failed_op = t;
             return GL355_E_INVALID_ARG;
@@ -167,6 +174,11 @@ uint64_t tape_validate(const uint64_t* tape, uint64_t n_ops, uint64_t n_inputs, 
         case GL355_TAPE_RANDOM_ACCESS: good = row(a) && b < 4; break;
         case GL355_TAPE_REDUCING: good = row(a) && b != 0 && b <= num_wires && 6 + (c ? 2 * b : b) + 2 * (b - 1) <= num_wires; break;
         case GL355_TAPE_EXT_INV: good = ok(a, 1) && ok(b, 1) && ok(c, 1) && ok(d, 1); break;
+        case GL355_TAPE_COSET_INTERP: {
+            CosetInterpShape s;
+            good = row(a) && b <= 0xFF && c <= 0xFF && coset_interp_shape((uint32_t)(b | c << 8), s) && s.num_wires <= num_wires;
+            break;
+        }
         default: good = false;
         }
         if (!good) return t;
@@ -174,6 +186,13 @@ uint64_t tape_validate(const uint64_t* tape, uint64_t n_ops, uint64_t n_inputs, 
     return ~0ull;
 }
 }  // namespace gl355
+
+extern "C" int32_t gl355_coset_interpolation_witness(uint32_t bits, uint32_t degree, uint64_t* wires) {
+    CosetInterpShape s;
+    if (!wires || bits > 0xFF || degree > 0xFF || !coset_interp_shape(bits | degree << 8, s)) return GL355_E_INVALID_ARG;
+    for (uint32_t i = 0; i < s.start_int; i++) wires[i] = gl_canon(wires[i]);
+    return coset_interp_fill(s, wires) ? GL355_E_WITNESS : GL355_OK;
+}
 
 extern "C" int32_t gl355_witness_replay(const uint64_t* tape, uint64_t n_ops, const uint64_t* inputs, uint64_t n_inputs,
                                         uint64_t* rows, uint64_t n_words, uint32_t num_wires, uint64_t* failed_op) {

@@ -162,6 +162,12 @@ __global__ void __launch_bounds__(64) tape_replay_kernel(TapeDevArgs a, uint32_t
                 W[x] = r.c0; W[b] = r.c1;
                 break;
             }
+            case GL355_TAPE_COSET_INTERP: {      // shape validated at load; the inverse of the shift as in EXT_INV: zero fails the entry
+                CosetInterpShape s;
+                coset_interp_shape((uint32_t)(b | c << 8), s);
+                if (coset_interp_fill(s, W + x)) fail = 1;
+                break;
+            }
             default: fail = 1; break;
             }
         }

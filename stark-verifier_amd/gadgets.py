@@ -12,15 +12,17 @@ inputs reproduces the same layout and only yields a new witness (checked by a st
 Gates emitted (all evaluated by csrc/quotient.hip and restated in tests/plonk_verifier.py; wire
 layouts from the reference's chip/plonk/gates/*.rs): Constant{2}, PublicInput, Noop (free inputs),
 Arithmetic{20}, ArithmeticExtension{10}, Poseidon, PoseidonMds, BaseSum{32}, RandomAccess{4,4,2},
-Reducing{43}, ReducingExtension{32}.
+Reducing{43}, ReducingExtension{32}; with CircuitConfig.use_interpolation_gate also plonky2's
+CosetInterpolationGate{2,4}, {3,8}, {4,6} (interpolate_coset).
 """
 import hashlib
 
 import numpy as np
 
-from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_NOOP, GATE_POSEIDON,
+from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_COSET_INTERPOLATION, GATE_NOOP, GATE_POSEIDON,
                    GATE_POSEIDON_MDS, GATE_PUBLIC_INPUT, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT)
-from .plonk import CircuitBuilder, CircuitConfig, P, host_hash_no_pad, poseidon_gate_witness
+from .plonk import (CircuitBuilder, CircuitConfig, P, coset_interpolation_param, coset_interpolation_shape, coset_interpolation_witness,
+                    host_hash_no_pad, poseidon_gate_witness)
 
 RA_PARAM = 4 | 4 << 8 | 2 << 16
 CIRC = [17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20]
@@ -29,11 +31,11 @@ CIRC = [17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20]
 # primitive appends the entries that recompute its wires from earlier wires, so a circuit built once can be
 # re-witnessed for new inputs by gl355_witness_replay without running the Python gadgets again.
 (TAPE_CONST, TAPE_INPUT, TAPE_COPY, TAPE_ASSERT_EQ, TAPE_ARITH, TAPE_ARITH_EXT, TAPE_POSEIDON, TAPE_MDS_EXT,
- TAPE_BASE_SUM, TAPE_RANDOM_ACCESS, TAPE_REDUCING, TAPE_LO32, TAPE_HI32, TAPE_EXT_INV) = range(14)
+ TAPE_BASE_SUM, TAPE_RANDOM_ACCESS, TAPE_REDUCING, TAPE_LO32, TAPE_HI32, TAPE_EXT_INV, TAPE_COSET_INTERP) = range(15)
 # which of the four operand fields of an entry are wire references (bit i = operand i)
 TAPE_WIRE_FIELDS = {TAPE_CONST: 1, TAPE_INPUT: 1, TAPE_COPY: 3, TAPE_ASSERT_EQ: 3, TAPE_ARITH: 1, TAPE_ARITH_EXT: 1,
                     TAPE_POSEIDON: 1, TAPE_MDS_EXT: 1, TAPE_BASE_SUM: 1, TAPE_RANDOM_ACCESS: 1, TAPE_REDUCING: 1,
-                    TAPE_LO32: 3, TAPE_HI32: 3, TAPE_EXT_INV: 15}
+                    TAPE_LO32: 3, TAPE_HI32: 3, TAPE_EXT_INV: 15, TAPE_COSET_INTERP: 1}
 
 
 class T:
@@ -384,6 +386,32 @@ class GadgetBuilder:
         self._rec(TAPE_RANDOM_ACCESS, self._w(row, 0), c)
         return self._set(row, 18 * c + 1, items[idx.v].v)
 
+    # ---- CosetInterpolationGate{bits, degree} (plonky2 gates/coset_interpolation.rs; layout in include/gl355.h) -----------------
+    def interpolate_coset(self, bits, shift, values, point):
+        """the interpolant through the 2^bits extension targets `values` on the coset shift * <g> (g = primitive_root_of_unity(bits),
+        natural order; shift a base-field target), evaluated at the extension target `point` -> an extension target; one gate row"""
+        cfg = self.cb.config
+        if not getattr(cfg, "use_interpolation_gate", False):
+            raise ValueError("interpolate_coset emits CosetInterpolationGate, which is not among the 12 gates of the reference's verifier: "
+                             "set CircuitConfig.use_interpolation_gate")
+        param = coset_interpolation_param(bits, cfg.max_quotient_degree_factor)
+        sh = coset_interpolation_shape(param)
+        assert len(values) == sh["n"]
+        assert sh["num_wires"] <= self.nw and sh["start_int"] <= self.routed, "CosetInterpolationGate does not fit the wires"
+        vals = [shift.v] + [c.v for e in values for c in e] + [point[0].v, point[1].v]
+        w = coset_interpolation_witness(param, np.array(vals, dtype=np.uint64))      # before the row exists: a zero shift raises
+        row = self._new_row(GATE_COSET_INTERPOLATION, param)
+        self._link(shift, row, 0)
+        for i, e in enumerate(values):
+            self._link(e[0], row, 1 + 2 * i)
+            self._link(e[1], row, 2 + 2 * i)
+        self._link(point[0], row, sh["point"])
+        self._link(point[1], row, sh["point"] + 1)
+        for c in range(sh["value"], sh["num_wires"]):
+            self.rows[row][c] = int(w[c])
+        self._rec(TAPE_COSET_INTERP, self._w(row, 0), sh["bits"], sh["degree"])
+        return (T(row, sh["value"], int(w[sh["value"]])), T(row, sh["value"] + 1, int(w[sh["value"] + 1])))
+
     # ---- ReducingGate{43} / ReducingExtensionGate{32} (gates/reducing.rs, reducing_extension.rs) ---------------------
     def _reducing(self, ext, alpha, coeffs, old_acc):
         n = 32 if ext else 43
@@ -474,7 +502,7 @@ class GadgetBuilder:
         ops = tape[:, 0].astype(np.int64)
         out = np.zeros(tape.shape, dtype=np.uint64)
         out[:, 0] = ops.astype(np.uint64)
-        masks = np.array([TAPE_WIRE_FIELDS[o] for o in range(14)], dtype=np.int64)[ops]
+        masks = np.array([TAPE_WIRE_FIELDS[o] for o in range(len(TAPE_WIRE_FIELDS))], dtype=np.int64)[ops]
         for f in range(4):
             col = np.array([int(x) for x in tape[:, 1 + f]], dtype=np.uint64)
             is_wire = (masks >> f) & 1 == 1
@@ -527,6 +555,9 @@ class GadgetBuilder:
                 return tuple(range(a + 2, a + 6 + n_c)), (a, a + 1) + tuple(range(a + 6 + n_c, a + 6 + n_c + 2 * (b - 1)))
             if op == TAPE_EXT_INV:
                 return (c, d), (a, b)
+            if op == TAPE_COSET_INTERP:
+                sh = coset_interpolation_shape(b | c << 8)
+                return tuple(range(a, a + sh["value"])), tuple(range(a + sh["value"], a + sh["num_wires"]))
             raise ValueError(op)
         for k in range(tape.shape[0]):
             sk = int(seg[k])

@@ -13,7 +13,7 @@ A gate is identified as common()["gates"] identifies it: (type, parameter).  An 
 extension algebra a list of two extension elements."""
 from . import halo2_goldilocks as hg
 from . import poseidon_spec as ps
-from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_MUL_EXT, GATE_NOOP, GATE_POSEIDON, GATE_POSEIDON_MDS,
+from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_COSET_INTERPOLATION, GATE_MUL_EXT, GATE_NOOP, GATE_POSEIDON, GATE_POSEIDON_MDS,
                    GATE_PUBLIC_INPUT, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT)
 
 P = hg.P
@@ -74,6 +74,9 @@ class GateConstrainer:
 
     def __init__(self, ctx, gate):
         self.ctx, (self.type, self.param) = ctx, gate
+        if self.type == GATE_COSET_INTERPOLATION:
+            raise ValueError("CosetInterpolationGate (gate type %d) has no constrainer: the reference's verifier circuit knows the 12 gates of "
+                             "gates/mod.rs:141-196; build the inner circuit without CircuitConfig.use_interpolation_gate" % self.type)
         self.goldilocks_extension_chip = hg.GoldilocksExtensionChip(ctx)
         self.goldilocks_extension_algebra_chip = GoldilocksExtensionAlgebraChip(ctx)
         self.eval_unfiltered_constraint = {

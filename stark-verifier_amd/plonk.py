@@ -19,8 +19,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_MUL_EXT, GATE_NOOP, GATE_POSEIDON,
-                   GATE_POSEIDON_MDS, GATE_PUBLIC_INPUT, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT,
+from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_COSET_INTERPOLATION, GATE_MUL_EXT, GATE_NOOP,
+                   GATE_POSEIDON, GATE_POSEIDON_MDS, GATE_PUBLIC_INPUT, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT,
                    Challenger as _CChallenger, Circuit as _CCircuit)
 from .api import COSET_SHIFT, P, SALT_SIZE, MerkleTree, PolynomialBatch, _ptr, _u64, deep_batch, eval_polys
 
@@ -61,6 +61,10 @@ class CircuitConfig:
         self.reduction_arity_bits = 1      # FriReductionStrategy: an int a = ConstantArityBits(a, final_poly_bits), a list = Fixed(list)
         self.final_poly_bits = 5
         self.hasher = 0                    # GenericConfig::Hasher: 0 PoseidonHash, 1 the reference's Bn254PoseidonHash (OuterC)
+        # plonky2's CosetInterpolationGate is not among the reference verifier's 12 gates (chip/plonk/gates/mod.rs:141-196): a builder emits
+        # it -- and the in-circuit verifier folds FRI layers by more than 2 -- only when asked, so that a default circuit stays verifiable
+        # by the Halo2 verifier circuit
+        self.use_interpolation_gate = False
         self.__dict__.update(kw)
 
     def fri_reduction_arity_bits(self, degree_bits):
@@ -125,6 +129,45 @@ def poseidon_gate_witness(inputs, swap):
     w = np.empty(135, dtype=np.uint64)
     rc = lib.gl355_poseidon_gate_witness(_ptr(_u64(inputs)), int(swap), _ptr(w))
     assert rc == 0
+    return w
+
+
+def coset_interpolation_param(bits, max_degree=8):
+    """CosetInterpolationGate::with_max_degree(bits, max_degree), max_degree = the configuration's max_quotient_degree_factor, as the
+    packed gate parameter bits | degree << 8: (2, 4), (3, 8), (4, 6) at 8"""
+    n = 1 << bits
+    n_int = (n - 2) // (max_degree - 1)
+    return bits | ((n - 2) // (n_int + 1) + 2) << 8
+
+
+def coset_interpolation_shape(param):
+    """wire layout of CosetInterpolationGate{param} (include/gl355.h): dict of bits, degree, n, n_int, point, value, start_int (= its
+    routed wires), shifted, num_wires, num_constraints"""
+    bits, degree = param & 0xFF, (param >> 8) & 0xFF
+    n = 1 << bits
+    if param >> 16 or not 2 <= bits <= 4 or not 2 <= degree <= n:
+        raise ValueError("CosetInterpolationGate has 2..4 subgroup bits and a degree in 2..2^bits, not %r" % ((bits, degree),))
+    n_int = (n - 2) // (degree - 1)
+    start_int = 1 + 2 * n + 4
+    return dict(bits=bits, degree=degree, n=n, n_int=n_int, point=1 + 2 * n, value=3 + 2 * n, start_int=start_int,
+                shifted=start_int + 4 * n_int, num_wires=start_int + 4 * n_int + 2, num_constraints=2 * (2 + 2 * n_int))
+
+
+def coset_interpolation_weights(bits):
+    """barycentric weights of the subgroup <g>, g = primitive_root_of_unity(bits): 1 / prod_{j != i}(g^i - g^j) = g^i / 2^bits"""
+    g, n_inv = pow(7, (P - 1) >> bits, P), pow(1 << bits, P - 2, P)
+    return [pow(g, i, P) * n_inv % P for i in range(1 << bits)]
+
+
+def coset_interpolation_witness(param, wires):
+    """gl355_coset_interpolation_witness: wires (shift, values, point set) -> the whole row; ValueError on a zero shift"""
+    sh = coset_interpolation_shape(param)
+    w = np.zeros(sh["num_wires"], dtype=np.uint64)
+    w[:sh["start_int"] - 2] = _u64(wires)[:sh["start_int"] - 2]
+    rc = _lib.load().gl355_coset_interpolation_witness(sh["bits"], sh["degree"], _ptr(w))
+    if rc == -6:                                # GL355_E_WITNESS
+        raise ValueError("CosetInterpolationGate: the coset shift is zero")
+    assert rc == 0, rc
     return w
 
 
@@ -326,6 +369,9 @@ def gate_id_string(gtype, param):
         return "ArithmeticExtensionGate { num_ops: %d }" % param
     if gtype == GATE_MUL_EXT:
         return "MulExtensionGate { num_ops: %d }" % param
+    if gtype == GATE_COSET_INTERPOLATION:      # restated from upstream's derived Debug output; not checkable against the reference
+        return "CosetInterpolationGate { subgroup_bits: %d, degree: %d, barycentric_weights: [%s], _phantom: PhantomData<%s> }<D=2>" % (
+            param & 0xFF, (param >> 8) & 0xFF, ", ".join(str(w) for w in coset_interpolation_weights(param & 0xFF)), f)
     raise ValueError("unknown gate type %r" % (gtype,))
 
 
@@ -333,7 +379,7 @@ _GATE_DEGREE = {
     GATE_NOOP: lambda p: 0, GATE_CONSTANT: lambda p: 1, GATE_PUBLIC_INPUT: lambda p: 1, GATE_BASE_SUM: lambda p: 2,
     GATE_POSEIDON: lambda p: 7, GATE_ARITHMETIC: lambda p: 3, GATE_ARITHMETIC_EXT: lambda p: 3, GATE_MUL_EXT: lambda p: 3,
     GATE_POSEIDON_MDS: lambda p: 1, GATE_RANDOM_ACCESS: lambda p: (p & 0xFF) + 1, GATE_REDUCING: lambda p: 2,
-    GATE_REDUCING_EXT: lambda p: 2,
+    GATE_REDUCING_EXT: lambda p: 2, GATE_COSET_INTERPOLATION: lambda p: (p >> 8) & 0xFF,
 }
 _GATE_CONSTRAINTS = {
     GATE_NOOP: lambda p: 0, GATE_CONSTANT: lambda p: p, GATE_PUBLIC_INPUT: lambda p: 4,
@@ -341,6 +387,7 @@ _GATE_CONSTRAINTS = {
     GATE_ARITHMETIC_EXT: lambda p: 2 * p, GATE_MUL_EXT: lambda p: 2 * p, GATE_POSEIDON_MDS: lambda p: 24,
     GATE_RANDOM_ACCESS: lambda p: ((p >> 8) & 0xFF) * ((p & 0xFF) + 2) + ((p >> 16) & 0xFF),
     GATE_REDUCING: lambda p: 2 * p, GATE_REDUCING_EXT: lambda p: 2 * p,
+    GATE_COSET_INTERPOLATION: lambda p: coset_interpolation_shape(p)["num_constraints"],
 }
 
 

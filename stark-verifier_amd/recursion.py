@@ -12,10 +12,11 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_NOOP, GATE_POSEIDON,
+from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_COSET_INTERPOLATION, GATE_NOOP, GATE_POSEIDON,
                    GATE_POSEIDON_MDS, GATE_PUBLIC_INPUT, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT)
 from .gadgets import CIRC, GadgetBuilder, T
-from .plonk import CircuitConfig, P, _ptr, _u64, derive_key, parse_proof_tagged, prove_sparse, require_arity_2
+from .plonk import (CircuitConfig, P, _ptr, _u64, coset_interpolation_shape, coset_interpolation_weights, derive_key, parse_proof_tagged,
+                    prove_sparse, require_arity_2)
 
 UNUSED_SELECTOR = 0xFFFFFFFF
 _RC = None
@@ -211,6 +212,30 @@ def eval_gate(b, gate, consts, w, pi_hash):
             out += list(asub(aadd(_alg_mul(b, acc, alpha), coeff), acc_i))
             acc = acc_i
         return out
+    if t == GATE_COSET_INTERPOLATION:
+        # plonky2 gates/coset_interpolation.rs (layout and fold in include/gl355.h): `shift` is an extension scalar, the value, point and
+        # accumulator pairs are algebra elements, the domain and the barycentric weights constants.  The first point's step from
+        # (eval, prod) = (0, 1) is written out: (v_0 w_0, x - x_0)
+        sh = coset_interpolation_shape(p)
+        g_n = pow(7, (P - 1) >> sh["bits"], P)
+        weights = coset_interpolation_weights(sh["bits"])
+        x = alg(sh["shifted"])
+        out = list(asub(alg(sh["point"]), ascal(w[0], x)))
+        ev = prod = None
+        ni, brk = 0, sh["degree"]
+        for i in range(sh["n"]):
+            if i == brk and ni < sh["n_int"]:
+                ie, ip = alg(sh["start_int"] + 2 * ni), alg(sh["start_int"] + 2 * (sh["n_int"] + ni))
+                out += list(asub(ie, ev)) + list(asub(ip, prod))
+                ev, prod = ie, ip
+                ni, brk = ni + 1, brk + sh["degree"] - 1
+            xm = (b.ext_sub(x[0], b.constant_ext((pow(g_n, i, P), 0))), x[1])
+            vw = ascal(b.constant_ext((weights[i], 0)), alg(1 + 2 * i))
+            if ev is None:
+                ev, prod = vw, xm
+            else:
+                ev, prod = aadd(_alg_mul(b, ev, xm), _alg_mul(b, vw, prod)), _alg_mul(b, prod, xm)
+        return out + list(asub(alg(sh["value"]), ev))
     raise NotImplementedError("gate %r has no in-circuit evaluator" % (gate,))
 
 
@@ -274,8 +299,12 @@ def verify_proof(b, cd, proof, register_pis=True):
     """builder.verify_proof: proof (dict as produced by plonk.parse_proof) becomes virtual targets; the inner
     circuit's verifier data (constants_sigmas cap, circuit digest) are constants.  Returns the inner public-input
     targets."""
-    # the step of a larger arity interpolates through 4, 8 or 16 points: an interpolation gate, which is not among the 12 gates here
-    require_arity_2(cd["arity_bits"], "the in-circuit verifier")
+    # the step of a larger arity interpolates through 4, 8 or 16 points: plonky2's CosetInterpolationGate, which is not among the
+    # reference's 12 gates -- a builder emits it only with CircuitConfig.use_interpolation_gate
+    if not getattr(b.cb.config, "use_interpolation_gate", False):
+        require_arity_2(cd["arity_bits"], "the in-circuit verifier")
+    if any(not 1 <= int(a) <= 4 for a in cd["arity_bits"]):
+        raise ValueError("the in-circuit verifier folds a FRI layer by 2, 4, 8 or 16, not %r" % (list(cd["arity_bits"]),))
     assert cd.get("hasher", 0) == 0, "the in-circuit verifier hashes with Poseidon-Goldilocks: the inner proof must use PoseidonHash"
     nch = cd["num_challenges"]
     tv = b.add_virtual_target
@@ -375,6 +404,29 @@ def verify_proof(b, cd, proof, register_pis=True):
         for l, arity_bits in enumerate(cd["arity_bits"]):
             ev_flat, sib_vals = rnd["steps"][l]
             ev = [tv(v) for v in ev_flat]
+            if arity_bits > 1:
+                # compute_evaluation of an arity A = 2^a > 2: within = the low a bits of the index; the leaf's A values, reordered by
+                # reverse_index_bits, lie on coset_start * <g>, coset_start = x * (g^-1)^rev(within); the next value is their
+                # interpolant at beta (CosetInterpolationGate); then x <- x^A
+                A = 1 << arity_bits
+                evals = [(ev[2 * j], ev[2 * j + 1]) for j in range(A)]
+                within_bits, coset_bits = idx_bits[:arity_bits], idx_bits[arity_bits:]
+                within = b.le_sum(within_bits)
+                picked = tuple(b.random_access(within, [e[k] for e in evals] + [zero] * (16 - A)) for k in range(2))
+                b.connect_ext(picked, prev)
+                sib = [[tv(v) for v in s] for s in sib_vals]
+                verify_merkle_proof(b, ev, coset_bits[:len(coset_bits) - cap_h], cap_index, fri_caps[l], sib)
+                g_inv = pow(7, (P - 1) - ((P - 1) >> arity_bits), P)
+                start = x
+                for k, bit in enumerate(within_bits):      # bit k of within is bit a - 1 - k of rev(within)
+                    f = pow(g_inv, 1 << (arity_bits - 1 - k), P)
+                    start = b.mul(start, b.arithmetic(f - 1, bit, one, 1, one))       # bit ? f : 1
+                rev = [int(format(j, "0%db" % arity_bits)[::-1], 2) for j in range(A)]
+                prev = b.interpolate_coset(arity_bits, start, [evals[rev[j]] for j in range(A)], fri_betas[l])
+                for _ in range(arity_bits):
+                    x = b.mul(x, x)
+                idx_bits = coset_bits
+                continue
             e0, e1 = (ev[0], ev[1]), (ev[2], ev[3])
             within = idx_bits[0]
             coset_bits = idx_bits[1:]
