@@ -78,8 +78,11 @@ enum { GL355_OPT_MERKLE_LANES_LOG = 1,
                                            in two passes (a streaming 2- / 4-row column pass, then 4096-point limb rows, 3 tiles per
                                            CU) instead of one pass whose 64- / 128-KB tile owns a whole CU */
        GL355_OPT_BATCH_UNITS = 5,       /* 1..GL355_MAX_UNITS (default 8): units gl355_semaphore_units proves in lock-step per context */
-       GL355_OPT_DEVICE_REPLAY = 6 };   /* != 0 (default): gl355_semaphore_units generates the recursive circuit's witness rows on the
+       GL355_OPT_DEVICE_REPLAY = 6,     /* != 0 (default): gl355_semaphore_units generates the recursive circuit's witness rows on the
                                            device (tape interpreter kernel) instead of on host threads; same rows, same failures */
+       GL355_OPT_LEAF_LANES_LOG = 7 };  /* 0..31 (default 16): a FRI layer that folds by 4, 8 or 16 (leaves of 8, 16 or 32 words, Poseidon hasher) and has
+                                           fewer than 2^value leaves over all units of the launch hashes them 16 lanes per leaf, straight from the value
+                                           columns; at or above, and with 0 always, one lane per leaf from the copied leaf array */
 int32_t gl355_ctx_set_option(gl355_ctx* ctx, int32_t option, int64_t value);
 const char* gl355_last_error(gl355_ctx* ctx);
 const char* gl355_version(void);
@@ -496,10 +499,14 @@ int32_t gl355_witness_replay_segmented(const uint64_t* tape, uint64_t n_ops, uin
  * host-side builder stark-verifier_amd/plonk.py) and serialised with CircuitData.export_blob(): u64 words
  *   [0] magic "GL355CIR" [1] version 2 (3: the digest at [106..109] was computed elsewhere, e.g. by plonky2's CircuitBuilder::build,
  *   and the artifact ends with the expected constants_sigmas cap [2^cap_height][4], which is checked instead of the digest) [2..11] the gl355_circuit scalars [12..91] 16 gates x {type, param, selector_index,
- *   group_start, group_end} [92] cap_height [93] pow_bits [94] num_queries [95] n_fri_layers (every layer folds by 2: an artifact's circuit is proven and verified with fri_arity_bits = NULL) [96] zero_knowledge [97] hasher
+ *   group_start, group_end} [92] cap_height [93] pow_bits [94] num_queries [95] n_fri_layers (at most 32; versions 2 and 3: every layer folds by 2, the circuit is proven and verified with fri_arity_bits = NULL) [96] zero_knowledge [97] hasher
  *   [98] blind_start [99] n_blind [100] z_start [101] n_z_pairs [102] n_rows [103] n_tape_ops [104] n_inputs [105] n_public_inputs
  *   [106..109] circuit digest [110] sequential tape entries [111] independent tape segments, then constants[num_selectors + num_constants][n] | sigmas[routed][n] | k_is[routed] |
  *   row_idx[n_rows] | public-input positions[n_pi] | tape[n_tape_ops][5] (gl355_witness_replay format) | segment lengths.
+ *   Versions 4 and 5 (export_blob(..., wide_arity=True)) are versions 2 and 3 with the arity table [112 .. 112 + n_fri_layers): one word of arity
+ *   bits per FRI layer (1..GL355_MAX_FRI_ARITY_BITS), directly after the 112 header words and before the constants; everything else, the trailing cap of
+ *   version 5 included, is laid out as in version 2 / 3.  The loader refuses a table FriLayers could not build: a word of 0 or above 32 bits, a sum above
+ *   degree_bits, a layer narrower than the cap (GL355_E_INVALID_ARG), a word above GL355_MAX_FRI_ARITY_BITS (GL355_E_UNSUPPORTED).
  * gl355_circuit_load commits constants_sigmas on `ctx`, re-derives the circuit digest and refuses an artifact whose digest
  * does not match its tables.  The handle is read-only afterwards: any context of the same device may prove with it, concurrently.
  *   gl355_semaphore_prove    = fill_semaphore_targets + data.prove (access_set.rs:61-104): witness rows from the member's
@@ -513,6 +520,10 @@ int32_t gl355_circuit_destroy(gl355_circuit_handle* c);
 int32_t gl355_circuit_info(const gl355_circuit_handle* c, uint64_t* proof_words, uint32_t* n_public_inputs, uint32_t* n_rows,
                            uint64_t* n_inputs, uint32_t* degree_bits);
 const uint64_t* gl355_circuit_digest(const gl355_circuit_handle* c);
+/* the FRI reduction strategy of a loaded circuit: *n_layers = n_fri_layers, out (n_fri_layers words, or NULL) = the arity bits per layer --
+ * the artifact's table, all ones for a version-2/3 artifact.  There is no capacity argument: `out` must hold *n_layers words as a first
+ * call with out = NULL reports them (at most 32) */
+int32_t gl355_circuit_fri_arity_bits(const gl355_circuit_handle* c, uint32_t* out /* n_fri_layers, or NULL */, uint32_t* n_layers);
 /* the witness rows [n_units][n_rows][num_wires] and public inputs [n_units][n_public_inputs] the circuit's tape generates from
  * `inputs` [n_units][n_inputs] -- on host threads (on_device = 0) or by the device interpreter (on_device = 1); both must agree
  * (parity surface of SURVEY 8(f) N3).  GL355_E_WITNESS + *failed_entry when the inputs do not satisfy the circuit. */

@@ -154,6 +154,7 @@ SIGNATURES = {
     "gl355_circuit_info": (C.c_int32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint32)]),
     "gl355_circuit_digest": (C.POINTER(C.c_uint64), [vp]),
+    "gl355_circuit_fri_arity_bits": (C.c_int32, [vp, vp, C.POINTER(C.c_uint32)]),
     "gl355_verify": (C.c_int32, [C.POINTER(VerifierData), vp, C.c_uint64, vp, C.c_uint32]),
     "gl355_verify_last_error": (C.c_char_p, []),
     "gl355_circuit_verify": (C.c_int32, [vp, vp, C.c_uint64, vp, C.c_uint32]),

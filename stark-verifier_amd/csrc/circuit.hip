@@ -28,6 +28,7 @@ struct gl355_circuit_handle {
     std::vector<uint32_t> row_idx;
     std::vector<uint64_t> pi_pos, tape, seg_lens;
     std::vector<uint64_t> cs_cap, k_is_host;     // verifier data (gl355_circuit_verify)
+    std::vector<uint32_t> fri_arity_bits;        // [n_fri_layers]: the artifact's table (versions 4 / 5), all ones for versions 2 / 3; pd.fri_arity_bits points here
     uint64_t n_seq = 0;
     uint32_t blind_start = 0, n_blind = 0, z_start = 0, n_z_pairs = 0, n_pi = 0;
     uint64_t n_inputs = 0;
@@ -46,8 +47,9 @@ int32_t gl355_circuit_load(gl355_ctx* h, const uint64_t* blob, uint64_t words, g
     if (hipSetDevice(ctx->device) != hipSuccess) return ctx->fail(GL355_E_HIP, "hipSetDevice failed");
     if (!blob || !out || words < HDR) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: null or truncated artifact");
     *out = nullptr;
-    if (blob[0] != MAGIC || (blob[1] != 2 && blob[1] != 3)) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: not a version-2/3 gl355 circuit artifact");
-    const bool external_digest = blob[1] == 3;      // the digest was computed elsewhere; the artifact carries the expected cap instead
+    if (blob[0] != MAGIC || blob[1] < 2 || blob[1] > 5) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: not a version-2..5 gl355 circuit artifact");
+    const bool external_digest = blob[1] == 3 || blob[1] == 5;      // the digest was computed elsewhere; the artifact carries the expected cap instead
+    const bool arity_table = blob[1] >= 4;          // versions 4 / 5 = 2 / 3 plus the arity bits of the FRI layers, n_fri_layers words after the header
     gl355_circuit c;
     memset(&c, 0, sizeof c);
     c.degree_bits = (uint32_t)blob[2]; c.rate_bits = (uint32_t)blob[3]; c.num_wires = (uint32_t)blob[4];
@@ -81,10 +83,28 @@ int32_t gl355_circuit_load(gl355_ctx* h, const uint64_t* blob, uint64_t words, g
     const uint64_t n_seq = blob[110], n_segs = blob[111];
     if (n_seq > n_ops || n_segs > n_ops) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: implausible tape segmentation");
     if (blob[92] > 20) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: implausible cap height");
-    const uint64_t need = HDR + (n_sc + routed) * n + routed + n_rows + n_pi + 5 * n_ops + n_segs + (external_digest ? (4ull << blob[92]) : 0);
+    const uint64_t n_layers = blob[95];
+    if (n_layers > 32) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: implausible number of FRI layers");
+    const uint64_t n_arity = arity_table ? n_layers : 0;
+    const uint64_t need = HDR + n_arity + (n_sc + routed) * n + routed + n_rows + n_pi + 5 * n_ops + n_segs + (external_digest ? (4ull << blob[92]) : 0);
     if (words != need) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: artifact length does not match its header");
     const int32_t hasher = (int32_t)blob[97];
     if (hasher != GL355_HASH_POSEIDON && hasher != GL355_HASH_BN254_POSEIDON) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: unknown hasher");
+    // the arity table: what FriLayers::init refuses is refused here, by name, before anything is allocated
+    std::vector<uint32_t> arity(n_layers, 1);
+    if (arity_table) {
+        const uint64_t lde_bits = (uint64_t)c.degree_bits + c.rate_bits;
+        uint64_t sum = 0;
+        for (uint64_t l = 0; l < n_layers; l++) {
+            const uint64_t a = blob[HDR + l];
+            if (a == 0 || a > 0xFFFFFFFFull) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: a FRI layer's arity bits are zero or no 32-bit value");
+            if (a > GL355_MAX_FRI_ARITY_BITS) return ctx->fail(GL355_E_UNSUPPORTED, "circuit_load: a FRI layer folds by 2, 4, 8 or 16");
+            sum += a;
+            if (sum > c.degree_bits) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: the FRI layers fold below one coefficient");
+            if (lde_bits - sum < blob[92]) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: a FRI layer is narrower than the cap");
+            arity[l] = (uint32_t)a;
+        }
+    }
 
     gl355_circuit_handle* ch = new (std::nothrow) gl355_circuit_handle();
     if (!ch) return GL355_E_OOM;
@@ -92,7 +112,8 @@ int32_t gl355_circuit_load(gl355_ctx* h, const uint64_t* blob, uint64_t words, g
     ch->c = c;
     ch->blind_start = (uint32_t)blob[98]; ch->n_blind = (uint32_t)blob[99]; ch->z_start = (uint32_t)blob[100];
     ch->n_z_pairs = (uint32_t)blob[101]; ch->n_inputs = n_inputs; ch->n_pi = (uint32_t)n_pi;
-    const uint64_t* p = blob + HDR;
+    ch->fri_arity_bits.swap(arity);
+    const uint64_t* p = blob + HDR + n_arity;
     const uint64_t* cs_values = p; p += (n_sc + routed) * n;
     const uint64_t* sigmas = cs_values + n_sc * n;
     const uint64_t* k_is = p; p += routed;
@@ -180,7 +201,7 @@ int32_t gl355_circuit_load(gl355_ctx* h, const uint64_t* blob, uint64_t words, g
     memcpy(ch->pd.circuit_digest, blob + 106, 32);
     ch->pd.cap_height = (uint32_t)blob[92]; ch->pd.pow_bits = (uint32_t)blob[93]; ch->pd.num_queries = (uint32_t)blob[94];
     ch->pd.n_fri_layers = (uint32_t)blob[95]; ch->pd.zero_knowledge = (int32_t)blob[96]; ch->pd.hasher = hasher;
-    ch->pd.fri_arity_bits = nullptr;      // the artifact carries a layer count only: its flow is the reference's, every layer folds by 2
+    ch->pd.fri_arity_bits = arity_table ? ch->fri_arity_bits.data() : nullptr;      // versions 2 / 3 carry a layer count only: the reference's flow, every layer folds by 2
     *out = ch;
     return GL355_OK;
 }
@@ -207,6 +228,12 @@ int32_t gl355_circuit_info(const gl355_circuit_handle* ch, uint64_t* proof_words
     return GL355_OK;
 }
 const uint64_t* gl355_circuit_digest(const gl355_circuit_handle* ch) { return ch ? ch->pd.circuit_digest : nullptr; }
+int32_t gl355_circuit_fri_arity_bits(const gl355_circuit_handle* ch, uint32_t* out, uint32_t* n_layers) {
+    if (!ch) return GL355_E_INVALID_ARG;
+    if (n_layers) *n_layers = ch->pd.n_fri_layers;
+    if (out) memcpy(out, ch->fri_arity_bits.data(), ch->fri_arity_bits.size() * sizeof(uint32_t));
+    return GL355_OK;
+}
 
 int32_t gl355_circuit_verify(const gl355_circuit_handle* ch, const uint64_t* proof, uint64_t proof_words, const uint64_t* public_inputs,
                              uint32_t n_public_inputs) {
@@ -217,7 +244,7 @@ int32_t gl355_circuit_verify(const gl355_circuit_handle* ch, const uint64_t* pro
     memcpy(vd.circuit_digest, ch->pd.circuit_digest, 32);
     vd.cap_height = ch->pd.cap_height; vd.pow_bits = ch->pd.pow_bits; vd.num_queries = ch->pd.num_queries; vd.n_fri_layers = ch->pd.n_fri_layers;
     vd.zero_knowledge = ch->pd.zero_knowledge; vd.hasher = ch->pd.hasher;
-    vd.fri_arity_bits = nullptr;
+    vd.fri_arity_bits = ch->pd.fri_arity_bits;
     return gl355_verify(&vd, proof, proof_words, public_inputs, n_public_inputs);
 }
 

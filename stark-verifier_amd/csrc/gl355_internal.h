@@ -88,6 +88,7 @@ struct Ctx {
     uint64_t wait_ns = 0, wait_calls = 0;   // accumulated by wait() while prof_on
     uint64_t wait_cpu_ns = 0, prove_cpu_ns = 0, prove_calls = 0;   // thread CPU time inside wait() / inside prove_units (waits included)
     uint32_t merkle_lanes_log = 14;   // Merkle levels with <= 2^this nodes use the 16-lanes-per-node kernel (GL355_OPT_MERKLE_LANES_LOG)
+    uint32_t leaf_lanes_log = 16;     // FRI layers of 8- to 32-word leaves with < 2^this leaves over all units hash them 16 lanes per leaf; 0 = never (GL355_OPT_LEAF_LANES_LOG)
     bool prof_on = false;
     std::vector<ProfRec> prof;
     std::vector<hipEvent_t> ev_pool;
@@ -206,6 +207,12 @@ int32_t hash_leaves_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uin
 int32_t merkle_build_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
                          uint64_t col_stride, uint32_t cap_height, uint64_t* digests, uint64_t* cap);
 int32_t merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
+// the levels above the leaf digests of merkle_build_args, for a caller that has written digest_slot(0, k) of every cap subtree itself
+int32_t merkle_build_above_leaves(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
+// FRI layer leaves of 2 << ab words (ab = 2..4), hashed 16 lanes per leaf straight from the value columns vals [B][2][len_v]: writes the row-major
+// leaf array leaves [B][len_v >> ab][2 << ab] and the leaf digests (or the cap entries when sub_bits == 0), then builds the levels above
+int32_t fri_wide_leaves_tree_dev(Ctx* ctx, uint32_t ab, uint32_t B, const uint64_t* vals, uint64_t len_v, uint64_t* leaves, uint32_t sub_bits,
+                                 uint64_t* digests, uint64_t* cap);
 int32_t bn254_merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
 int32_t merkle_build_args_any(Ctx* ctx, int32_t hasher, const LeafArgs& a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
 int32_t hash_no_pad_dev(Ctx* ctx, const uint64_t* inputs, uint64_t n, uint32_t len, uint64_t* digests);

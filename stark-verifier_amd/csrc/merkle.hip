@@ -210,6 +210,46 @@ __global__ void __launch_bounds__(64) merkle_level_lanes_kernel(uint64_t* digest
     }
 }
 
+// FRI layer leaves of 2A = 2 << AB words (A = 4, 8, 16), one 16-lane group per leaf, four leaves per wave.  Word w of leaf i is column w & 1,
+// element A i + (w >> 1) of the unit's two value columns, so for chunk c of the overwrite sponge lane li < 8 loads word li of the chunk from
+// column li & 1, element A i + 4 c + (li >> 1): 32 contiguous bytes per column and group.  The same lanes write the chunk into the row-major
+// leaf array [B][nl][2A] the layer openings read (64 contiguous bytes per group), so these layers need no copy launch.  1 / 2 / 4
+// permutations for AB = 2 / 3 / 4.  g = leaf over all units; a group past the end clamps to leaf 0 and skips its stores only: the ring
+// exchange needs the whole wave.  Digest where hash_leaves_kernel puts it.
+template <int AB, int FORM>
+__global__ void __launch_bounds__(64) fri_wide_leaves_units_kernel(const uint64_t* vals /* [B][2][len_v] */, uint64_t len_v, uint32_t log_nl,
+                                                                  uint64_t* leaves /* [B][nl][2A] */, uint64_t n_groups /* B nl */,
+                                                                  uint64_t* digests, uint64_t* cap, uint32_t sub_bits) {
+    __shared__ uint64_t rings[4][24];
+    constexpr int CHUNKS = 1 << (AB - 2);
+    const int li = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    uint64_t g = blockIdx.x * 4ull + grp;
+    const bool valid = g < n_groups;
+    if (!valid) g = 0;
+    const uint64_t u = g >> log_nl, i = g & ((1ull << log_nl) - 1);
+    const uint64_t* src = vals + (u * 2 + (li & 1)) * len_v + (i << AB) + (li >> 1);
+    uint64_t* row = leaves + (g << (AB + 1)) + li;
+    uint64_t s = 0;
+#pragma unroll
+    for (int c = 0; c < CHUNKS; c++) {
+        if (li < 8) {
+            s = src[4 * c];
+            if (valid) row[8 * c] = s;
+        }
+        s = psd_permute_lanes<FORM>(s, li, rings[grp]);
+    }
+    if (valid && li < 4) {
+        uint64_t* dst;
+        if (sub_bits == 0) dst = cap + g * 4;
+        else {
+            const uint64_t sub_leaves = 1ull << sub_bits;
+            const uint64_t t = g >> sub_bits, k = g & (sub_leaves - 1);
+            dst = digests + (t * 2 * (sub_leaves - 1) + digest_slot(0, k)) * 4;
+        }
+        dst[li] = gl_canon(s);
+    }
+}
+
 // The top of every cap subtree in ONE launch: one 1024-thread block per subtree takes its 2^(n_levels - 1) nodes of layer `layer0` (at most
 // 128) and climbs n_levels levels to the cap entry, the digests of a level staying in LDS for the next one (and going to the plonky2
 // layout in HBM).  Each of those levels is one lane-parallel permutation deep (two for the 128-node level: 64 groups of 16 lanes); as
@@ -370,6 +410,36 @@ int32_t merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_t* dig
     if (n_leaves == 0 || (n_leaves & ((1ull << sub_bits) - 1))) return ctx->fail(GL355_E_INVALID_ARG, "merkle: leaves do not fill whole cap subtrees");
     a.out = digests; a.cap = cap; a.sub_bits = sub_bits; a.linear = 0;
     { ProfScope ps(ctx, "hash_leaves_kernel", n_leaves * ((uint64_t)a.leaf_len * 8 + 32)); GL355_TRY(launch_leaves(ctx, a)); }
+    return merkle_build_above_leaves(ctx, n_leaves, sub_bits, digests, cap);
+}
+
+int32_t fri_wide_leaves_tree_dev(Ctx* ctx, uint32_t ab, uint32_t B, const uint64_t* vals, uint64_t len_v, uint64_t* leaves, uint32_t sub_bits,
+                                 uint64_t* digests, uint64_t* cap) {
+    const uint64_t nl = len_v >> ab, n_groups = (uint64_t)B * nl;
+    if (ab < 2 || ab > 4 || nl == 0 || (nl & (nl - 1)) || (nl << ab) != len_v || (nl & ((1ull << sub_bits) - 1)) || (n_groups + 3) / 4 > 0x7FFFFFFFull)
+        return ctx->fail(GL355_E_INVALID_ARG, "fri: wide leaves need 4, 8 or 16 values per leaf and whole cap subtrees");
+    const uint32_t log_nl = log2_u64(nl);
+    const dim3 grid((uint32_t)((n_groups + 3) / 4)), block(64);
+    const bool fast_lanes = (n_groups >> sub_bits) < 64;      // as merkle_build_above_leaves: form 3 for a lone unit's few subtrees, form 0 for lock-step batches
+    {
+        ProfScope ps(ctx, "fri_wide_leaves_units_kernel", n_groups * ((32ull << ab) + 32));
+#define GL355_WIDE_LEAVES(AB)                                                                                                                         \
+        if (fast_lanes) hipLaunchKernelGGL((fri_wide_leaves_units_kernel<AB, 3>), grid, block, 0, ctx->stream, vals, len_v, log_nl, leaves, n_groups, \
+                                           digests, cap, sub_bits);                                                                                   \
+        else hipLaunchKernelGGL((fri_wide_leaves_units_kernel<AB, 0>), grid, block, 0, ctx->stream, vals, len_v, log_nl, leaves, n_groups, digests,   \
+                                cap, sub_bits)
+        switch (ab) {
+            case 2: GL355_WIDE_LEAVES(2); break;
+            case 3: GL355_WIDE_LEAVES(3); break;
+            default: GL355_WIDE_LEAVES(4); break;
+        }
+#undef GL355_WIDE_LEAVES
+        GL355_HIP(ctx, hipGetLastError());
+    }
+    return merkle_build_above_leaves(ctx, n_groups, sub_bits, digests, cap);
+}
+
+int32_t merkle_build_above_leaves(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits, uint64_t* digests, uint64_t* cap) {
     const uint64_t lanes_max = 1ull << ctx->merkle_lanes_log;
     // the last MERKLE_TOP_LEVELS levels of every cap subtree go to merkle_top_kernel (when they are lane-parallel levels anyway: at most
     // lanes_max nodes enter it over the whole forest)

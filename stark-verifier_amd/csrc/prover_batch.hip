@@ -574,15 +574,21 @@ int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, 
         const uint64_t len_v = len_c << s.rate_bits, nl = len_v >> ab;
         GL355_TRY(lde_dev(ctx, cols, len_c, log2_u64(len_c), s.rate_bits, gl_canon(shift), 2 * B, vals, len_v, true));
         uint64_t* lv = tree_buf + fa.leaf_off[l];
-        {
-            ProfScope ps(ctx, "fri_layer_leaves", (uint64_t)B * len_v * 32);
-            hipLaunchKernelGGL(fri_leaves_units_kernel, dim3((uint32_t)((len_v / 2 + 255) / 256), B), dim3(256), 0, ctx->stream, vals, len_v, lv);
-            LAUNCH_CHECK(ctx);
+        // leaves of 8, 16 or 32 words, few enough to leave the chip short of waves at one lane per leaf (1, 2 or 4 dependent permutations per
+        // lane): 16 lanes per leaf, read from the value columns, the leaf array written on the way (merkle.hip); GL355_OPT_LEAF_LANES_LOG
+        if (ab >= 2 && s.hasher == GL355_HASH_POSEIDON && ctx->leaf_lanes_log && (uint64_t)B * nl < (1ull << ctx->leaf_lanes_log)) {
+            GL355_TRY(fri_wide_leaves_tree_dev(ctx, ab, B, vals, len_v, lv, log2_u64(nl) - s.cap_height, tree_buf + fa.dig_off[l], d_cap));
+        } else {
+            {
+                ProfScope ps(ctx, "fri_layer_leaves", (uint64_t)B * len_v * 32);
+                hipLaunchKernelGGL(fri_leaves_units_kernel, dim3((uint32_t)((len_v / 2 + 255) / 256), B), dim3(256), 0, ctx->stream, vals, len_v, lv);
+                LAUNCH_CHECK(ctx);
+            }
+            LeafArgs la;
+            memset(&la, 0, sizeof la);
+            la.leaves = lv; la.n_leaves = (uint64_t)B * nl; la.leaf_len = 2u << ab; la.col_major = 0; la.stride = 2u << ab;
+            GL355_TRY(merkle_build_args_any(ctx, s.hasher, la, log2_u64(nl) - s.cap_height, tree_buf + fa.dig_off[l], d_cap));
         }
-        LeafArgs la;
-        memset(&la, 0, sizeof la);
-        la.leaves = lv; la.n_leaves = (uint64_t)B * nl; la.leaf_len = 2u << ab; la.col_major = 0; la.stride = 2u << ab;
-        GL355_TRY(merkle_build_args_any(ctx, s.hasher, la, log2_u64(nl) - s.cap_height, tree_buf + fa.dig_off[l], d_cap));
         uint64_t* cap_dst[MAXB];
         for (uint32_t u = 0; u < B; u++) cap_dst[u] = out[u].caps + (uint64_t)l * n_cap * 4;
         GL355_TRY(observe_caps_units(ctx, B, n_cap, d_cap, stage, ch, cap_dst));

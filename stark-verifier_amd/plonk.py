@@ -461,13 +461,16 @@ class CircuitData:
             self._arity_arr = np.array(self.fri_arity_bits, dtype=np.uint32)
         return self._arity_arr.ctypes.data
 
-    def export_blob(self, row_idx, tape=None, pi_pos=None, n_inputs=0, tape_layout=None, external_digest=None):
+    def export_blob(self, row_idx, tape=None, pi_pos=None, n_inputs=0, tape_layout=None, external_digest=None, wide_arity=False):
         """Serialise the built circuit (+ the sparse witness-row map and optionally a witness tape) as the u64 artifact
         gl355_circuit_load reads (layout in include/gl355.h).  external_digest: 4 words of a circuit digest computed elsewhere (e.g.
         by plonky2's own CircuitBuilder::build, whose digest also covers its domain separator): the artifact is then version 3 and
         carries the expected constants_sigmas cap, which the loader checks against its own commitment of the tables instead of
-        re-deriving this framework's digest."""
-        require_arity_2(self.fri_arity_bits, "the circuit artifact (its header holds a layer count only)")
+        re-deriving this framework's digest.  wide_arity: the artifact is version 4 (5 with external_digest) and carries the arity
+        bits of its FRI layers, one word per layer, directly after the 112 header words; versions 2 and 3 have no such table and
+        every layer of theirs folds by 2."""
+        if not wide_arity:
+            require_arity_2(self.fri_arity_bits, "the circuit artifact without wide_arity=True (versions 2 and 3 hold a layer count only)")
         cfg = self.config
         cc = self.c_circuit
         hdr = np.zeros(112, dtype=np.uint64)
@@ -491,7 +494,11 @@ class CircuitData:
         if external_digest is not None:
             hdr[1] = 3
             tail = [_u64(self.constants_sigmas_cap).reshape(-1)]
-        return np.concatenate([hdr, _u64(self.constants).reshape(-1), _u64(self.sigmas).reshape(-1), _u64(self.k_is), row_idx,
+        arity_table = np.zeros(0, dtype=np.uint64)
+        if wide_arity:
+            hdr[1] += 2
+            arity_table = np.array(self.fri_arity_bits, dtype=np.uint64)
+        return np.concatenate([hdr, arity_table, _u64(self.constants).reshape(-1), _u64(self.sigmas).reshape(-1), _u64(self.k_is), row_idx,
                                pi_pos, tape.reshape(-1), np.asarray(seg_lens, dtype=np.uint64)] + tail)
 
     def verify(self, flat_proof, public_inputs):
@@ -644,6 +651,11 @@ class NativeCircuit:
         pw, npi, nrows, nin, db = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint32()
         ctx.lib.gl355_circuit_info(self.h, C.byref(pw), C.byref(npi), C.byref(nrows), C.byref(nin), C.byref(db))
         self.proof_words, self.n_public_inputs, self.n_rows, self.n_inputs, self.degree_bits = pw.value, npi.value, nrows.value, nin.value, db.value
+        n_layers = C.c_uint32()
+        ctx.check(ctx.lib.gl355_circuit_fri_arity_bits(self.h, None, C.byref(n_layers)))
+        arity = np.zeros(n_layers.value, dtype=np.uint32)
+        ctx.check(ctx.lib.gl355_circuit_fri_arity_bits(self.h, arity.ctypes.data, C.byref(n_layers)))
+        self.fri_arity_bits = [int(a) for a in arity]      # the artifact's arity table; all ones for versions 2 and 3
 
     def prove_rows(self, ctx, rows, public_inputs, seed):
         rows, pi = _u64(rows), _u64(public_inputs)

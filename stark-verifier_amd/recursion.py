@@ -514,7 +514,10 @@ class RecursiveCircuit:
         gl355_circuit_prove_tape(inner proofs' flat words | public inputs)"""
         if getattr(self, "_native", None) is None:
             from .plonk import NativeCircuit
-            self._native = NativeCircuit(self.ctx, self.data.export_blob(self.row_idx, self.tape, self.pi_pos, self.n_inputs, self.tape_layout))
+            # a circuit whose own FRI folds by more than 2 needs the artifact versions with the arity table; an arity-2 circuit keeps version 2
+            wide = any(int(a) != 1 for a in self.data.fri_arity_bits)
+            self._native = NativeCircuit(self.ctx, self.data.export_blob(self.row_idx, self.tape, self.pi_pos, self.n_inputs, self.tape_layout,
+                                                                         wide_arity=wide))
         return self._native
 
     def witness(self, flat_proofs):
