@@ -98,7 +98,14 @@ int32_t oracle_open_batch_on(Ctx* ctx, const gl355_oracle* o, const uint64_t* in
     uint64_t* d_leaf = d_idx + n_idx;
     uint64_t* d_sib = d_leaf + n_leaf;
     GL355_HIP(ctx, hipMemcpyAsync(d_idx, indices, (uint64_t)n_idx * 8, hipMemcpyHostToDevice, ctx->stream));
-    GL355_TRY(open_batch_dev(ctx, o->lde, N, o->leaf_len, o->digests, bits, o->cap_height, d_idx, n_idx, d_leaf, d_sib));
+    if (n_idx) {      // a grid of no blocks is a launch error
+        // one unit whose leaf is leaf_len columns of lde: a gl355_oracle committed with salt keeps its salt columns there, behind the
+        // polynomials', not in a segment of their own as the lock-step prover's batches do (so this is not prover_batch.hip's view_of)
+        OpenArgs oa;
+        oa.o = OView{o->coeffs, 0, o->lde, 0, nullptr, 0, o->digests, 0, o->leaf_len, o->leaf_len};
+        oa.N = N; oa.lde_bits = bits; oa.cap_height = o->cap_height; oa.n_idx = n_idx; oa.idx = d_idx; oa.leaves = d_leaf; oa.sibs = d_sib;
+        GL355_TRY(open_units_dev(ctx, 1, oa));
+    }
     GL355_HIP(ctx, ctx->d2h(leaves, d_leaf, n_leaf * 8));
     if (n_sib) GL355_HIP(ctx, ctx->d2h(siblings, d_sib, n_sib * 8));
     GL355_HIP(ctx, ctx->wait());

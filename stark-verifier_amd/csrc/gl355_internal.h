@@ -44,6 +44,7 @@ struct Ctx;
         int32_t _rc = (expr);    \
         if (_rc != GL355_OK) return _rc; \
     } while (0)
+#define LAUNCH_CHECK(ctx) GL355_HIP(ctx, hipGetLastError())
 
 struct Ctx {
     int device = 0;
@@ -217,9 +218,6 @@ int32_t bn254_merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_
 int32_t merkle_build_args_any(Ctx* ctx, int32_t hasher, const LeafArgs& a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
 int32_t hash_no_pad_dev(Ctx* ctx, const uint64_t* inputs, uint64_t n, uint32_t len, uint64_t* digests);
 int32_t two_to_one_dev(Ctx* ctx, const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out);
-int32_t open_batch_dev(Ctx* ctx, const uint64_t* lde, uint64_t stride, uint32_t leaf_len, const uint64_t* digests,
-                       uint32_t log_n, uint32_t cap_height, const uint64_t* idx_dev, uint32_t n_idx, uint64_t* leaves_out,
-                       uint64_t* sib_out);
 // second hash back-end (merkle_bn254.hip, host_bn254.cpp)
 void host_bn254_permute(uint64_t state[12]);
 // Merkle tree / PoW with the hasher chosen at run time
@@ -244,15 +242,83 @@ int32_t pow_grind_units_dev(Ctx* ctx, uint32_t B, const uint64_t* states /* [B][
                             uint64_t start, uint64_t* landing, uint64_t* const* witness_host /* [B] */);
 
 // ---- fri.hip -------------------------------------------------------------------------------
+// Openings, DEEP quotient, FRI fold and query openings exist once, with a unit dimension B: the lock-step prover's stages call the
+// *_units_dev routines below, the staged C entry points are their B = 1 calls.
+constexpr uint32_t MAXB = GL355_MAX_UNITS;
+struct UnitVals { uint64_t v[MAXB * 4]; };      // up to 4 words per unit (challenges, pi hash, extension elements)
+
+// Where a kernel finds polynomial i of unit u (n = 2^log_n coefficients): the template parameter `Polys` of the kernels that read polynomials.
+// PolySet: the lock-step prover's, by index, without a pointer table: block o contributes count[o] columns, unit u's at base[o] + u * us[o].
+// It lives in the kernel arguments, so the hot path never waits for a pointer load.
+struct PolySet {
+    const uint64_t* base[4]; uint64_t us[4]; uint32_t count[4];
+    uint32_t n_sets, log_n;
+    GL_DEV const uint64_t* ptr(uint32_t u, uint32_t i) const {
+        uint32_t o = 0;
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            if ((uint32_t)k + 1 < n_sets && i >= count[o]) { i -= count[o]; o++; }
+        return base[o] + (uint64_t)u * us[o] + ((uint64_t)i << log_n);
+    }
+};
+// PolyTable: the staged entry points', which take any list of (oracle, column): a pointer table on the device, one unit
+struct PolyTable {
+    const uint64_t* const* p; uint32_t log_n;
+    GL_DEV const uint64_t* ptr(uint32_t, uint32_t i) const { return p[i]; }
+};
+
+// OpeningSet::new: polynomial i < n_all of `all` at zeta_u, polynomial i - n_all of `zs` at g * zeta_u; out[u][i] (extension)
+template <class Polys>
+struct EvalArgs { Polys all, zs; uint32_t n_all; UnitVals zeta /* [u*4+0..1] = zeta, [u*4+2..3] = g * zeta */; uint64_t* out; uint32_t out_us; };
+template <class Polys> int32_t eval_polys_units_dev(Ctx* ctx, uint32_t B, uint32_t n_zs, const EvalArgs<Polys>& a);
+
+constexpr int DEEP_BLK = 256;  // coefficients per workgroup in the division scan
+// per-unit tables of the two opening batches (point A = zeta, point B = g * zeta), ext elements:
+//   [0, n_alpha]            alpha^i, i <= n_alpha (n_alpha = number of polynomials of the larger batch)
+//   then for A and for B:   z^(2^s), s < 8 | z^e, e <= DEEP_BLK
+GL_HD uint32_t deep_tab_len(uint32_t n_alpha) { return (n_alpha + 1) + 2 * (8 + DEEP_BLK + 1); }
+struct DeepTabArgs { uint64_t* tab; uint32_t n_alpha; UnitVals alpha /* [u*4+0..1] */, zeta /* as EvalArgs */; };
+int32_t deep_tables_dev(Ctx* ctx, uint32_t B, const DeepTabArgs& a);
+struct DeepArgs {
+    uint32_t n_polys, n_alpha, point;   // point 0 = zeta tables, 1 = g * zeta tables
+    const uint64_t* tab;
+    uint64_t n, n_blocks;
+    uint64_t* v;        // [B][n] ext scratch
+    uint64_t* totals;   // [B][n_blocks] ext
+    uint64_t* carry;    // [B][n_blocks] ext
+    uint64_t* acc;      // [B][2][n]: the accumulated quotient as two base-field columns (what the F_p^2 LDE takes)
+};
+template <class Polys> struct DeepScanArgs { Polys polys; DeepArgs a; };      // what the one DEEP kernel that reads polynomials takes
+// acc = acc * alpha^n_polys + (sum_i alpha^i polys_i) / (X - z_point), for every unit
+template <class Polys> int32_t deep_units_dev(Ctx* ctx, uint32_t B, const Polys& polys, const DeepArgs& a);
+
+// fold of B units' coefficient columns cols [B][2][len] by 2^arity_bits with beta_u = betas[u*4+0..1] (canonical) into out [B][2][len >> arity_bits]
+int32_t fri_fold_units_dev(Ctx* ctx, uint32_t arity_bits, uint32_t B, const uint64_t* cols, uint64_t len, const UnitVals& betas, uint64_t* out);
+
+// one oracle as the kernels see it: unit u's data at base + u * stride (stride 0 = shared by all units).  Columns c < batch of a leaf
+// are in lde, the other leaf_len - batch in salt
+struct OView {
+    const uint64_t* coeffs; uint64_t coeffs_us;
+    const uint64_t* lde; uint64_t lde_us;
+    const uint64_t* salt; uint64_t salt_us;
+    const uint64_t* digests; uint64_t dig_us;
+    uint32_t batch, leaf_len;
+};
+// row idx[u][q] of unit u's column-major LDE (+ salt segment) and its Merkle path, dense per-unit outputs
+struct OpenArgs { OView o; uint64_t N; uint32_t lde_bits, cap_height, n_idx; const uint64_t* idx /* [B][n_idx] */; uint64_t* leaves; uint64_t* sibs; };
+int32_t open_units_dev(Ctx* ctx, uint32_t B, const OpenArgs& a);
+
+// the staged forms: interleaved F_p^2 in and out, any (oracle, column) list, challenges in any representation
 int32_t deep_batch_dev(Ctx* ctx, const uint64_t* const* poly_ptrs_host, uint32_t n_polys, uint32_t log_n,
                        const uint64_t alpha[2], const uint64_t z[2], uint64_t* acc /* n ext */);
 int32_t eval_polys_ext_dev(Ctx* ctx, const uint64_t* const* poly_ptrs_host, uint32_t n_polys, uint32_t log_n,
-                           const uint64_t z[2], uint64_t* out_host_or_dev);
+                           const uint64_t z[2], uint64_t* out_dev);
 int32_t fri_fold_dev(Ctx* ctx, const uint64_t* coeffs, uint64_t n, uint32_t arity_bits, const uint64_t beta[2], uint64_t* out);
 int32_t fri_layer_leaves_dev(Ctx* ctx, const uint64_t* values, uint64_t n, uint64_t* leaves);
 int32_t lde_ext_dev(Ctx* ctx, const uint64_t* coeffs, uint32_t log_n, uint32_t rate_bits, uint64_t shift, uint64_t* out,
                     bool out_bitrev);
 int32_t ext_split_dev(Ctx* ctx, const uint64_t* ext, uint64_t n, uint64_t* c0, uint64_t* c1);
+int32_t ext_join_dev(Ctx* ctx, const uint64_t* c0, const uint64_t* c1, uint64_t n, uint64_t* ext);
 int32_t field_batch_dev(Ctx* ctx, int32_t op, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n);
 int32_t zs_partial_products_dev(Ctx* ctx, const uint64_t* wires, const uint64_t* sigmas, const uint64_t* k_is,
                                 uint32_t log_n, uint32_t n_routed, uint32_t max_degree, uint64_t beta, uint64_t gamma,
@@ -353,7 +419,7 @@ struct ProofLayout {
     }
 };
 
-// ---- the FRI tail of a proof (prover_batch.hip): commit phase, final polynomial, proof of work, query indices, layer openings ----
+// ---- the FRI tail of a proof (fri.hip): commit phase, final polynomial, proof of work, query indices, layer openings ----
 struct FriShape { uint32_t log_n, rate_bits, cap_height, pow_bits, n_queries; int32_t hasher; FriLayers layers; };
 struct FriUnitOut { uint64_t* caps /* [n_layers][2^cap_height][4] */; uint64_t* final_poly /* [n >> total_bits] ext */; uint64_t* pow_witness; };
 // words of host staging fri_tail_units needs
@@ -366,6 +432,13 @@ static inline uint64_t fri_tail_stage_words(const FriShape& s, uint32_t B) {
 // stay on the device: d_evals [B][n_queries][layers.ev_total], d_sibs [B][n_queries][layers.sib_total].  `stage`: pinned host.
 int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, uint64_t* cols2, uint64_t* vals, uint64_t* stage,
                        gl355_challenger* ch, const FriUnitOut* out, uint64_t* q_idx, uint64_t* d_idx, uint64_t* d_evals, uint64_t* d_sibs);
+// caps [B][n_cap][4] on the device -> dst[u] on the host, each absorbed by its unit's transcript (prover_batch.hip)
+int32_t observe_caps_units(Ctx* ctx, uint32_t B, uint64_t n_cap, const uint64_t* d_caps, uint64_t* stage, gl355_challenger* ch, uint64_t* const* dst);
+// two canonical words of a transcript's next extension challenge
+static inline void squeeze_ext(gl355_challenger* ch, uint64_t* v) {
+    gl355_challenger_squeeze(ch, v, 2);
+    v[0] = gl_canon(v[0]); v[1] = gl_canon(v[1]);
+}
 int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const uint64_t* cs_lde, const uint64_t* wires_lde, uint64_t wires_us,
                            const uint64_t* zs_lde, uint64_t zs_us, uint64_t lde_stride, const uint64_t* k_is_dev, const uint64_t* betas /* [B][4] */,
                            const uint64_t* gammas, const uint64_t* alphas, const uint64_t* pi_hashes /* [B][4] */, uint64_t* out_values /* [B][nch][nq] */);

@@ -1,6 +1,6 @@
 // FRI prover loop in one call (a12 + a13 + a14 of SURVEY.md 8): commit phase, proof of work and the
 // layer openings of every query, with the polynomial resident on the device throughout: one unit
-// through fri_tail_units (prover_batch.hip), the routine the lock-step prover runs.
+// through fri_tail_units (fri.hip), the routine the lock-step prover runs.
 //
 // Replaces plonky2::fri::prover::{fri_proof, fri_committed_trees, fri_proof_of_work,
 // fri_prover_query_rounds} (reached through CircuitData::prove, src/plonky2_semaphore/access_set.rs:94).

@@ -19,6 +19,10 @@
 // B * batch columns; the leaf hash and the query openings read the salt segment for the last four leaf elements), digests
 // [B][..] in plonky2's layout, caps [B][2^cap_height][4].  B trees of 2^cap_height cap subtrees are, to the Merkle kernels,
 // one forest of B * 2^cap_height subtrees.
+//
+// This file: witness, salt and permutation-argument kernels, the commitment of a batch of units, and prove_units as eight stage
+// routines over one ProveRun.  The kernels of the opening, DEEP, FRI and query stages and fri_tail_units are in fri.hip (shared
+// with the staged C entry points, which call them with B = 1), the quotient in quotient.hip, Merkle trees and the grinder in merkle.hip.
 #include "gl355_internal.h"
 #include "blinding.cuh"
 #include "poseidon.cuh"
@@ -26,8 +30,6 @@
 using namespace gl355;
 
 namespace gl355 {
-
-constexpr uint32_t MAXB = GL355_MAX_UNITS;
 
 // ---- committed batches of B units ------------------------------------------------------------------------------------------
 struct BOracle {
@@ -54,24 +56,17 @@ struct BOracle {
     }
 };
 
-// one oracle as the kernels see it: unit u's data at base + u * stride (stride 0 = shared by all units: constants_sigmas)
-struct OView {
-    const uint64_t* coeffs; uint64_t coeffs_us;
-    const uint64_t* lde; uint64_t lde_us;
-    const uint64_t* salt; uint64_t salt_us;
-    const uint64_t* digests; uint64_t dig_us;
-    uint32_t batch, leaf_len;
-};
 static OView view_of(const BOracle& o) {
     const uint64_t n = 1ull << o.log_n, N = n << o.rate_bits;
     return OView{o.coeffs, (uint64_t)o.batch * n, o.lde, (uint64_t)o.batch * N, o.salt, (uint64_t)GL355_SALT_SIZE * N, o.digests, o.n_dig * 4, o.batch, o.leaf_len};
 }
+// constants_sigmas, shared by all units.  Only for a batch committed without salt (prove_units checks batch == leaf_len): a salted
+// gl355_oracle keeps its salt columns inside lde, which is the view oracle_open_batch_on builds (capi.hip)
 static OView view_of(const gl355_oracle* o) {
     return OView{o->coeffs, 0, o->lde, 0, nullptr, 0, o->digests, 0, o->batch, o->leaf_len};
 }
 
 struct UnitKeys { BlindKey k[MAXB]; };
-struct UnitVals { uint64_t v[MAXB * 4]; };      // up to 4 words per unit (challenges, pi hash, extension elements)
 
 // ---- witness ---------------------------------------------------------------------------------------------------------------
 // scatter the sparse witness rows of every unit into its column-major wire matrix (rows: [B][n_rows][num_wires])
@@ -225,250 +220,6 @@ __global__ void zs_partials_units_kernel(ZsArgs a) {
     }
 }
 
-// ---- openings and DEEP quotient ----------------------------------------------------------------------------------------------
-// the polynomials of an opening batch, by index, without a pointer table: oracle o contributes count[o] columns of n coefficients
-struct PolySet {
-    const uint64_t* base[4]; uint64_t us[4]; uint32_t count[4];
-    uint32_t n_sets, log_n;
-};
-GL_DEV const uint64_t* poly_ptr(const PolySet& s, uint32_t u, uint32_t i) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-        if ((uint32_t)k + 1 < s.n_sets && i >= s.count[o]) { i -= s.count[o]; o++; }
-    return s.base[o] + (uint64_t)u * s.us[o] + ((uint64_t)i << s.log_n);
-}
-
-// OpeningSet::new: block (i, u) evaluates polynomial i of unit u at zeta_u (i < n_all) or Z polynomial i - n_all at g * zeta_u;
-// lane t Horner-evaluates the coefficients k = t (mod 256) in z^256 (coalesced loads) and scales by z^t; the partials are summed in LDS.  out[u][i] (extension)
-struct EvalArgs { PolySet all, zs; uint32_t n_all; UnitVals zeta /* [u*4+0..1] = zeta, [u*4+2..3] = g * zeta */; uint64_t* out; uint32_t out_us; };
-__global__ void __launch_bounds__(256) eval_polys_units_kernel(EvalArgs a) {
-    __shared__ uint64_t sh[512];
-    const int tid = threadIdx.x;
-    const uint32_t u = blockIdx.y, i = blockIdx.x;
-    const bool at_next = i >= a.n_all;
-    const uint64_t* p = at_next ? poly_ptr(a.zs, u, i - a.n_all) : poly_ptr(a.all, u, i);
-    const gl2 zz = at_next ? gl2_make(a.zeta.v[u * 4 + 2], a.zeta.v[u * 4 + 3]) : gl2_make(a.zeta.v[u * 4], a.zeta.v[u * 4 + 1]);
-    const uint64_t n = 1ull << a.all.log_n;
-    const gl2 acc = gl2_horner_strided256(p, n, zz, (uint32_t)tid);
-    sh[2 * tid] = acc.c0; sh[2 * tid + 1] = acc.c1;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            sh[2 * tid] = gl_add(sh[2 * tid], sh[2 * (tid + s)]);
-            sh[2 * tid + 1] = gl_add(sh[2 * tid + 1], sh[2 * (tid + s) + 1]);
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        uint64_t* o = a.out + (uint64_t)u * a.out_us + 2ull * i;
-        o[0] = gl_canon(sh[0]); o[1] = gl_canon(sh[1]);
-    }
-}
-
-constexpr int DEEP_BLK = 256;  // coefficients per workgroup in the division scan
-// per-unit tables of the two opening batches (point A = zeta, point B = g * zeta), ext elements:
-//   [0, n_alpha]            alpha^i, i <= n_alpha (n_alpha = number of polynomials of the larger batch)
-//   then for A and for B:   z^(2^s), s < 8 | z^e, e <= DEEP_BLK
-GL_HD uint32_t deep_tab_len(uint32_t n_alpha) { return (n_alpha + 1) + 2 * (8 + DEEP_BLK + 1); }
-struct DeepTabArgs { uint64_t* tab; uint32_t n_alpha; UnitVals alpha /* [u*4+0..1] */, zeta /* as EvalArgs */; };
-__global__ void __launch_bounds__(256) deep_tables_kernel(DeepTabArgs a) {
-    const uint32_t u = blockIdx.x;
-    uint64_t* t = a.tab + (uint64_t)u * deep_tab_len(a.n_alpha) * 2;
-    const gl2 al = gl2_make(a.alpha.v[u * 4], a.alpha.v[u * 4 + 1]);
-    for (uint32_t i = threadIdx.x; i <= a.n_alpha; i += blockDim.x) {
-        const gl2 c = gl2_canon(gl2_pow(al, i));
-        t[2 * i] = c.c0; t[2 * i + 1] = c.c1;
-    }
-    for (int pt = 0; pt < 2; pt++) {
-        const gl2 z = gl2_make(a.zeta.v[u * 4 + 2 * pt], a.zeta.v[u * 4 + 2 * pt + 1]);
-        uint64_t* tz = t + 2 * ((uint64_t)(a.n_alpha + 1) + (uint64_t)pt * (8 + DEEP_BLK + 1));
-        for (uint32_t i = threadIdx.x; i < 8 + DEEP_BLK + 1; i += blockDim.x) {
-            const gl2 c = gl2_canon(i < 8 ? gl2_pow(z, 1ull << i) : gl2_pow(z, i - 8));
-            tz[2 * i] = c.c0; tz[2 * i + 1] = c.c1;
-        }
-    }
-}
-struct DeepArgs {
-    PolySet polys; uint32_t n_polys, n_alpha, point;   // point 0 = zeta tables, 1 = g * zeta tables
-    const uint64_t* tab;
-    uint64_t n, n_blocks;
-    uint64_t* v;        // [B][n] ext scratch
-    uint64_t* totals;   // [B][n_blocks] ext
-    uint64_t* carry;    // [B][n_blocks] ext
-    uint64_t* acc;      // [B][2][n]: the accumulated quotient as two base-field columns (what the F_p^2 LDE takes)
-};
-GL_DEV const uint64_t* deep_tab_u(const DeepArgs& a, uint32_t u) { return a.tab + (uint64_t)u * deep_tab_len(a.n_alpha) * 2; }
-// phase 1: comp[k] = sum_i alpha^i p_i[k]; in-block suffix Horner sums v[k] = sum_{j>=k, j in block} comp[j] z^(j-k)
-__global__ void __launch_bounds__(DEEP_BLK) deep_reduce_scan_units_kernel(DeepArgs a) {
-    __shared__ uint64_t sh[2 * DEEP_BLK];
-    const int tid = threadIdx.x;
-    const uint32_t u = blockIdx.y;
-    const uint64_t k = blockIdx.x * (uint64_t)DEEP_BLK + tid;
-    const uint64_t* tab = deep_tab_u(a, u);
-    const uint64_t* z_pow2 = tab + 2 * ((uint64_t)(a.n_alpha + 1) + (uint64_t)a.point * (8 + DEEP_BLK + 1));
-    gl2 c = gl2_make(0, 0);
-    if (k < a.n) {
-        for (uint32_t i = 0; i < a.n_polys; i++) {
-            const uint64_t coef = poly_ptr(a.polys, u, i)[k];
-            c.c0 = gl_add(c.c0, gl_mul(tab[2 * i], coef));
-            c.c1 = gl_add(c.c1, gl_mul(tab[2 * i + 1], coef));
-        }
-    }
-    sh[2 * tid] = c.c0; sh[2 * tid + 1] = c.c1;
-    __syncthreads();
-#pragma unroll 1
-    for (int s = 0; s < 8; s++) {
-        const int other = tid + (1 << s);
-        gl2 add = gl2_make(0, 0);
-        if (other < DEEP_BLK) add = gl2_mul(gl2_make(sh[2 * other], sh[2 * other + 1]), gl2_make(z_pow2[2 * s], z_pow2[2 * s + 1]));
-        __syncthreads();
-        c = gl2_add(c, add);
-        sh[2 * tid] = c.c0; sh[2 * tid + 1] = c.c1;
-        __syncthreads();
-    }
-    uint64_t* v = a.v + (uint64_t)u * a.n * 2;
-    if (k < a.n) { v[2 * k] = c.c0; v[2 * k + 1] = c.c1; }
-    if (tid == 0) { uint64_t* t = a.totals + ((uint64_t)u * a.n_blocks + blockIdx.x) * 2; t[0] = c.c0; t[1] = c.c1; }
-}
-// phase 2 (one lane per unit): carry[blk] = T_{blk+1} + z^B carry[blk+1]
-__global__ void deep_carry_units_kernel(DeepArgs a) {
-    const uint32_t u = blockIdx.x;
-    if (threadIdx.x != 0) return;
-    const uint64_t* tab = deep_tab_u(a, u);
-    const uint64_t* z_pows = tab + 2 * ((uint64_t)(a.n_alpha + 1) + (uint64_t)a.point * (8 + DEEP_BLK + 1) + 8);
-    const gl2 zb = gl2_make(z_pows[2 * DEEP_BLK], z_pows[2 * DEEP_BLK + 1]);
-    const uint64_t* totals = a.totals + (uint64_t)u * a.n_blocks * 2;
-    uint64_t* carry = a.carry + (uint64_t)u * a.n_blocks * 2;
-    gl2 c = gl2_make(0, 0);
-    for (uint64_t blk = a.n_blocks; blk-- > 0;) {
-        carry[2 * blk] = c.c0; carry[2 * blk + 1] = c.c1;
-        c = gl2_add(gl2_make(totals[2 * blk], totals[2 * blk + 1]), gl2_mul(zb, c));
-    }
-}
-// phase 3: quotient q_k = b_{k+1}, b_j = v[j] + z^(B - j%B) carry[blk(j)]; acc = acc * alpha^n_polys + q
-__global__ void __launch_bounds__(DEEP_BLK) deep_finish_units_kernel(DeepArgs a) {
-    const uint64_t k = blockIdx.x * (uint64_t)DEEP_BLK + threadIdx.x;
-    if (k >= a.n) return;
-    const uint32_t u = blockIdx.y;
-    const uint64_t* tab = deep_tab_u(a, u);
-    const uint64_t* z_pows = tab + 2 * ((uint64_t)(a.n_alpha + 1) + (uint64_t)a.point * (8 + DEEP_BLK + 1) + 8);
-    const uint64_t* v = a.v + (uint64_t)u * a.n * 2;
-    const uint64_t* carry = a.carry + (uint64_t)u * a.n_blocks * 2;
-    gl2 q = gl2_make(0, 0);
-    const uint64_t j = k + 1;
-    if (j < a.n) {
-        const uint64_t blk = j / DEEP_BLK, off = j % DEEP_BLK;
-        const gl2 cr = gl2_make(carry[2 * blk], carry[2 * blk + 1]);
-        const uint64_t e = DEEP_BLK - off;
-        q = gl2_add(gl2_make(v[2 * j], v[2 * j + 1]), gl2_mul(gl2_make(z_pows[2 * e], z_pows[2 * e + 1]), cr));
-    }
-    uint64_t* acc0 = a.acc + (uint64_t)u * 2 * a.n;
-    uint64_t* acc1 = acc0 + a.n;
-    const gl2 shift = gl2_make(tab[2 * a.n_polys], tab[2 * a.n_polys + 1]);
-    const gl2 r = gl2_canon(gl2_add(gl2_mul(gl2_make(acc0[k], acc1[k]), shift), q));
-    acc0[k] = r.c0; acc1[k] = r.c1;
-}
-
-// ---- a12: FRI commit phase -----------------------------------------------------------------------------------------------------
-// layer leaves from the bit-reversed F_p^2 evaluations held as two base columns per unit: the interleaved sequence (c0[e], c1[e]),
-// written a pair of values at a time.  A layer that folds by A takes A consecutive values as one leaf (fri_chip.rs:275-316 for
-// A = 2: leaf i = (c0[2i], c1[2i], c0[2i+1], c1[2i+1])), so this one buffer is the row-major leaf array [len / A][2A] of every arity
-__global__ void fri_leaves_units_kernel(const uint64_t* cols /* [B][2][len] */, uint64_t len, uint64_t* leaves /* [B][len/2][4] */) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= len / 2) return;
-    const uint32_t u = blockIdx.y;
-    const uint64_t* c0 = cols + (uint64_t)u * 2 * len;
-    const uint64_t* c1 = c0 + len;
-    const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(c0 + 2 * i);
-    const ulonglong2 b = *reinterpret_cast<const ulonglong2*>(c1 + 2 * i);
-    uint64_t* dst = leaves + ((uint64_t)u * (len / 2) + i) * 4;
-    *reinterpret_cast<ulonglong2*>(dst) = make_ulonglong2(a.x, b.x);
-    *reinterpret_cast<ulonglong2*>(dst + 2) = make_ulonglong2(a.y, b.y);
-}
-// fold of the coefficient columns by A = 2^AB: out[k] = sum_{j<A} beta_u^j c[A k + j], one lane per output.  The lane's A coefficients
-// of each base column are 8 A contiguous bytes (16-byte loads); Horner from the top in the lazy gl2 forms, canonical on the way out.
-// <1> is c[2k] + beta_u * c[2k+1]
-template <int AB>
-__global__ void fri_fold_units_kernel(const uint64_t* cols /* [B][2][len] */, uint64_t len, UnitVals beta, uint64_t* out /* [B][2][len >> AB] */) {
-    constexpr int H = 1 << (AB - 1);      // pairs of coefficients per column
-    const uint64_t k = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    const uint64_t n_out = len >> AB;
-    if (k >= n_out) return;
-    const uint32_t u = blockIdx.y;
-    const uint64_t* c0 = cols + (uint64_t)u * 2 * len;
-    const uint64_t* c1 = c0 + len;
-    ulonglong2 a[H], b[H];
-#pragma unroll
-    for (int j = 0; j < H; j++) {
-        a[j] = *reinterpret_cast<const ulonglong2*>(c0 + 2 * (H * k + j));
-        b[j] = *reinterpret_cast<const ulonglong2*>(c1 + 2 * (H * k + j));
-    }
-    const gl2 bt = gl2_make(beta.v[u * 4], beta.v[u * 4 + 1]);
-    gl2 acc = gl2_make(a[H - 1].y, b[H - 1].y);
-    acc = gl2_add(gl2_make(a[H - 1].x, b[H - 1].x), gl2_mul(acc, bt));
-#pragma unroll
-    for (int j = H - 2; j >= 0; j--) {
-        acc = gl2_add(gl2_make(a[j].y, b[j].y), gl2_mul(acc, bt));
-        acc = gl2_add(gl2_make(a[j].x, b[j].x), gl2_mul(acc, bt));
-    }
-    const gl2 r = gl2_canon(acc);
-    uint64_t* o0 = out + (uint64_t)u * 2 * n_out;
-    o0[k] = r.c0; o0[n_out + k] = r.c1;
-}
-
-// ---- a14: query openings ---------------------------------------------------------------------------------------------------------
-// block (q, u): row idx[u][q] of unit u's column-major LDE (+ salt segment) and its Merkle path, dense per-unit outputs
-struct OpenArgs { OView o; uint64_t N; uint32_t lde_bits, cap_height, n_idx; const uint64_t* idx /* [B][n_idx] */; uint64_t* leaves; uint64_t* sibs; };
-__global__ void open_units_kernel(OpenArgs a) {
-    const uint32_t q = blockIdx.x, u = blockIdx.y;
-    const uint64_t index = a.idx[(uint64_t)u * a.n_idx + q];
-    const uint32_t layers = a.lde_bits - a.cap_height;
-    const uint64_t* lde = a.o.lde + (uint64_t)u * a.o.lde_us;
-    const uint64_t* salt = a.o.salt ? a.o.salt + (uint64_t)u * a.o.salt_us : nullptr;
-    uint64_t* lo = a.leaves + ((uint64_t)u * a.n_idx + q) * a.o.leaf_len;
-    for (uint32_t c = threadIdx.x; c < a.o.leaf_len; c += blockDim.x)
-        lo[c] = c < a.o.batch ? lde[(uint64_t)c * a.N + index] : salt[(uint64_t)(c - a.o.batch) * a.N + index];
-    const uint64_t sub_leaves = 1ull << layers;
-    const uint64_t* tree = a.o.digests + (uint64_t)u * a.o.dig_us + (index >> layers) * 2 * (sub_leaves - 1) * 4;
-    const uint64_t k0 = index & (sub_leaves - 1);
-    uint64_t* so = a.sibs + ((uint64_t)u * a.n_idx + q) * layers * 4;
-    for (uint32_t e = threadIdx.x; e < layers * 4; e += blockDim.x) {
-        const uint32_t layer = e >> 2;
-        const uint64_t k = (k0 >> layer) ^ 1;
-        so[e] = tree[digest_slot(layer, k) * 4 + (e & 3)];
-    }
-}
-// block (q, u, l): the leaf of layer l at index idx[u][q] >> s_l (its 2^a_l evaluations) and its path
-struct OpenFriArgs {
-    const uint64_t* trees; uint64_t leaf_off[32], dig_off[32];     // layer l: leaves [B][nl][2 A_l] at leaf_off, digests [B][2(nl - cap)][4] at dig_off
-    FriLayers lay;
-    uint32_t lde_bits, cap_height, n_idx;
-    const uint64_t* idx; uint64_t* evals /* [B][n_idx][lay.ev_total] */; uint64_t* sibs /* [B][n_idx][lay.sib_total] */;
-};
-__global__ void open_fri_units_kernel(OpenFriArgs a) {
-    const uint32_t q = blockIdx.x, u = blockIdx.y, l = blockIdx.z;
-    const uint64_t index = a.idx[(uint64_t)u * a.n_idx + q] >> a.lay.s[l];
-    const uint32_t log_nl = a.lde_bits - a.lay.s[l], layers = a.lay.depth[l], lw = 2u << a.lay.a[l];
-    const uint64_t nl = 1ull << log_nl, n_cap = 1ull << a.cap_height;
-    const uint64_t* leaves = a.trees + a.leaf_off[l] + (uint64_t)u * nl * lw;
-    const uint64_t* digs = a.trees + a.dig_off[l] + (uint64_t)u * 2 * (nl - n_cap) * 4;
-    uint64_t* ev = a.evals + ((uint64_t)u * a.n_idx + q) * a.lay.ev_total + a.lay.ev_off[l];
-    if (threadIdx.x < lw) ev[threadIdx.x] = leaves[index * lw + threadIdx.x];      // lw <= 32 < blockDim.x
-    const uint64_t sub_leaves = 1ull << layers;
-    const uint64_t* tree = digs + (index >> layers) * 2 * (sub_leaves - 1) * 4;
-    const uint64_t k0 = index & (sub_leaves - 1);
-    uint64_t* so = a.sibs + ((uint64_t)u * a.n_idx + q) * a.lay.sib_total + a.lay.sib_off[l];
-    for (uint32_t e = threadIdx.x; e < layers * 4; e += blockDim.x) {
-        const uint32_t layer = e >> 2;
-        const uint64_t k = (k0 >> layer) ^ 1;
-        so[e] = tree[digest_slot(layer, k) * 4 + (e & 3)];
-    }
-}
-
-// ---- host side -----------------------------------------------------------------------------------------------------------------
-#define LAUNCH_CHECK(ctx) GL355_HIP(ctx, hipGetLastError())
-
 // PolynomialBatch::from_values / from_coeffs for B units: o.coeffs already holds the values (or coefficients) [B * batch][n]
 static int32_t commit_units(Ctx* ctx, int32_t hasher, BOracle& o, bool is_coeffs, bool canonical, const UnitKeys* keys, uint32_t stream_id) {
     const uint64_t n = 1ull << o.log_n, N = n << o.rate_bits;
@@ -489,9 +240,8 @@ static int32_t commit_units(Ctx* ctx, int32_t hasher, BOracle& o, bool is_coeffs
     return merkle_build_args_any(ctx, hasher, a, lde_bits - o.cap_height, o.digests, o.cap);
 }
 
-
 // caps [B][n_cap][4] on the device -> dst[u] on the host, each absorbed by its unit's transcript
-static int32_t observe_caps_units(Ctx* ctx, uint32_t B, uint64_t n_cap, const uint64_t* d_caps, uint64_t* stage, gl355_challenger* ch, uint64_t* const* dst) {
+int32_t observe_caps_units(Ctx* ctx, uint32_t B, uint64_t n_cap, const uint64_t* d_caps, uint64_t* stage, gl355_challenger* ch, uint64_t* const* dst) {
     GL355_HIP(ctx, ctx->d2h(stage, d_caps, (uint64_t)B * n_cap * 32));
     GL355_HIP(ctx, ctx->wait());
     for (uint32_t u = 0; u < B; u++) {
@@ -499,11 +249,6 @@ static int32_t observe_caps_units(Ctx* ctx, uint32_t B, uint64_t n_cap, const ui
         gl355_challenger_observe(&ch[u], dst[u], n_cap * 4);
     }
     return GL355_OK;
-}
-// two canonical words of unit u's next extension challenge
-static void squeeze_ext(gl355_challenger* ch, uint64_t* v) {
-    gl355_challenger_squeeze(ch, v, 2);
-    v[0] = gl_canon(v[0]); v[1] = gl_canon(v[1]);
 }
 
 // the permutation argument of n_inst = B * nch instances: unit u's Z_0..Z_{nch-1} and then its partial products go to zbuf + u * z_us
@@ -545,109 +290,6 @@ int32_t zs_partial_products_dev(Ctx* ctx, const uint64_t* wires, const uint64_t*
     GL355_TRY(zs_units_dev(ctx, 1, 1, wires, 0, sigmas, k_is, log_n, n_routed, max_degree, betas, gammas, zb.as<uint64_t>(), (uint64_t)n_chunks * n));
     GL355_HIP(ctx, hipMemcpyAsync(z_out, zb.p, n * 8, hipMemcpyDeviceToDevice, ctx->stream));
     if (n_chunks > 1) GL355_HIP(ctx, hipMemcpyAsync(pp_out, zb.as<uint64_t>() + n, (uint64_t)(n_chunks - 1) * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    return GL355_OK;
-}
-
-// ---- the FRI tail (fri_committed_trees, final polynomial, fri_proof_of_work, query indices, layer openings): gl355_internal.h ----------
-int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, uint64_t* cols2, uint64_t* vals, uint64_t* stage,
-                       gl355_challenger* ch, const FriUnitOut* out, uint64_t* q_idx, uint64_t* d_idx, uint64_t* d_evals, uint64_t* d_sibs) {
-    const FriLayers& fl = s.layers;
-    const uint32_t L = fl.n, lde_bits = s.log_n + s.rate_bits;
-    const uint64_t N = 1ull << lde_bits, n_cap = 1ull << s.cap_height;
-    if (fl.total_bits > s.log_n) return ctx->fail(GL355_E_INVALID_ARG, "fri: the layers fold more than the polynomial has coefficients");
-    OpenFriArgs fa;         // the layer trees: leaves [B][nl][2 A_l] and digests [B][2(nl - n_cap)][4] of layer l, one after the other
-    memset(&fa, 0, sizeof fa);
-    uint64_t tree_words = 0;
-    for (uint32_t l = 0; l < L; l++) {
-        const uint64_t nl = N >> fl.s[l];
-        if (nl < n_cap) return ctx->fail(GL355_E_INVALID_ARG, "fri: layer smaller than the cap");
-        fa.leaf_off[l] = tree_words; tree_words += (uint64_t)B * (N >> (fl.s[l] - fl.a[l])) * 2;
-        fa.dig_off[l] = tree_words; tree_words += (uint64_t)B * 2 * (nl - n_cap) * 4;
-    }
-    Scratch trees(ctx);
-    GL355_TRY(trees.get((tree_words + (uint64_t)B * n_cap * 4 + 16) * 8));
-    uint64_t* tree_buf = trees.as<uint64_t>();
-    uint64_t* d_cap = tree_buf + tree_words;
-    uint64_t shift = GL355_COSET_SHIFT, len_c = 1ull << s.log_n;
-    for (uint32_t l = 0; l < L; l++) {
-        const uint32_t ab = fl.a[l];
-        const uint64_t len_v = len_c << s.rate_bits, nl = len_v >> ab;
-        GL355_TRY(lde_dev(ctx, cols, len_c, log2_u64(len_c), s.rate_bits, gl_canon(shift), 2 * B, vals, len_v, true));
-        uint64_t* lv = tree_buf + fa.leaf_off[l];
-        // leaves of 8, 16 or 32 words, few enough to leave the chip short of waves at one lane per leaf (1, 2 or 4 dependent permutations per
-        // lane): 16 lanes per leaf, read from the value columns, the leaf array written on the way (merkle.hip); GL355_OPT_LEAF_LANES_LOG
-        if (ab >= 2 && s.hasher == GL355_HASH_POSEIDON && ctx->leaf_lanes_log && (uint64_t)B * nl < (1ull << ctx->leaf_lanes_log)) {
-            GL355_TRY(fri_wide_leaves_tree_dev(ctx, ab, B, vals, len_v, lv, log2_u64(nl) - s.cap_height, tree_buf + fa.dig_off[l], d_cap));
-        } else {
-            {
-                ProfScope ps(ctx, "fri_layer_leaves", (uint64_t)B * len_v * 32);
-                hipLaunchKernelGGL(fri_leaves_units_kernel, dim3((uint32_t)((len_v / 2 + 255) / 256), B), dim3(256), 0, ctx->stream, vals, len_v, lv);
-                LAUNCH_CHECK(ctx);
-            }
-            LeafArgs la;
-            memset(&la, 0, sizeof la);
-            la.leaves = lv; la.n_leaves = (uint64_t)B * nl; la.leaf_len = 2u << ab; la.col_major = 0; la.stride = 2u << ab;
-            GL355_TRY(merkle_build_args_any(ctx, s.hasher, la, log2_u64(nl) - s.cap_height, tree_buf + fa.dig_off[l], d_cap));
-        }
-        uint64_t* cap_dst[MAXB];
-        for (uint32_t u = 0; u < B; u++) cap_dst[u] = out[u].caps + (uint64_t)l * n_cap * 4;
-        GL355_TRY(observe_caps_units(ctx, B, n_cap, d_cap, stage, ch, cap_dst));
-        UnitVals beta;
-        memset(&beta, 0, sizeof beta);
-        for (uint32_t u = 0; u < B; u++) squeeze_ext(&ch[u], &beta.v[u * 4]);
-        {
-            ProfScope ps(ctx, "fri_fold", (uint64_t)B * (len_c * 16 + len_c * 8));
-            const dim3 grid((uint32_t)(((len_c >> ab) + 255) / 256), B), block(256);
-            switch (ab) {
-                case 1: hipLaunchKernelGGL(fri_fold_units_kernel<1>, grid, block, 0, ctx->stream, cols, len_c, beta, cols2); break;
-                case 2: hipLaunchKernelGGL(fri_fold_units_kernel<2>, grid, block, 0, ctx->stream, cols, len_c, beta, cols2); break;
-                case 3: hipLaunchKernelGGL(fri_fold_units_kernel<3>, grid, block, 0, ctx->stream, cols, len_c, beta, cols2); break;
-                default: hipLaunchKernelGGL(fri_fold_units_kernel<4>, grid, block, 0, ctx->stream, cols, len_c, beta, cols2); break;
-            }
-            LAUNCH_CHECK(ctx);
-        }
-        std::swap(cols, cols2);
-        len_c >>= ab;
-        for (uint32_t j = 0; j < ab; j++) shift = gl_mul(shift, shift);
-    }
-    // final polynomial: len_c = n >> total_bits extension coefficients per unit, two columns each
-    GL355_HIP(ctx, ctx->d2h(stage, cols, (uint64_t)B * 2 * len_c * 8));
-    GL355_HIP(ctx, ctx->wait());
-    uint64_t pow_state[MAXB * 12];
-    uint32_t pow_pos[MAXB];
-    uint64_t* p_pow[MAXB];
-    for (uint32_t u = 0; u < B; u++) {
-        const uint64_t* c0 = stage + (uint64_t)u * 2 * len_c;
-        uint64_t* fp = out[u].final_poly;
-        for (uint64_t k = 0; k < len_c; k++) { fp[2 * k] = c0[k]; fp[2 * k + 1] = c0[len_c + k]; }
-        gl355_challenger_observe(&ch[u], fp, 2 * len_c);
-        if (gl355_challenger_pow_state(&ch[u], &pow_state[u * 12], &pow_pos[u]) != GL355_OK) return ctx->fail(GL355_E_INVALID_ARG, "fri: challenger state");
-        for (int k = 0; k < 12; k++) pow_state[u * 12 + k] = gl_canon(pow_state[u * 12 + k]);
-        p_pow[u] = out[u].pow_witness;
-    }
-    // proof of work: the smallest witness of every unit
-    if (s.hasher == GL355_HASH_POSEIDON) GL355_TRY(pow_grind_units_dev(ctx, B, pow_state, pow_pos, s.pow_bits, 0, stage, p_pow));
-    else for (uint32_t u = 0; u < B; u++) GL355_TRY(pow_grind_any(ctx, s.hasher, &pow_state[u * 12], pow_pos[u], s.pow_bits, 0, p_pow[u]));
-    // queries: x_index = challenge mod N; layer l opens the leaf at x_index >> s_l and its path
-    for (uint32_t u = 0; u < B; u++) {
-        gl355_challenger_observe(&ch[u], p_pow[u], 1);
-        uint64_t resp;
-        gl355_challenger_squeeze(&ch[u], &resp, 1);
-        if (s.pow_bits && (resp >> (64 - s.pow_bits)) != 0) return ctx->fail(GL355_E_HIP, "fri: proof-of-work response check failed");
-        uint64_t* qi = q_idx + (uint64_t)u * s.n_queries;
-        gl355_challenger_squeeze(&ch[u], qi, s.n_queries);
-        for (uint32_t q = 0; q < s.n_queries; q++) qi[q] &= (N - 1);
-    }
-    GL355_HIP(ctx, hipMemcpyAsync(d_idx, q_idx, (uint64_t)B * s.n_queries * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (L) {
-        fa.trees = tree_buf;
-        fa.lay = fl;
-        fa.lde_bits = lde_bits; fa.cap_height = s.cap_height; fa.n_idx = s.n_queries; fa.idx = d_idx;
-        fa.evals = d_evals; fa.sibs = d_sibs;
-        ProfScope ps(ctx, "open_batch", (uint64_t)B * s.n_queries * (fl.ev_total * 16 + fl.sib_total * 16));
-        hipLaunchKernelGGL(open_fri_units_kernel, dim3(s.n_queries, B, L), dim3(64), 0, ctx->stream, fa);
-        LAUNCH_CHECK(ctx);
-    }
     return GL355_OK;
 }
 
@@ -814,13 +456,9 @@ static int32_t stage_openings(ProveRun& r) {
     r.all.n_sets = 4; r.all.log_n = r.c.degree_bits;
     r.zsset.base[0] = r.views[2].coeffs; r.zsset.us[0] = r.views[2].coeffs_us; r.zsset.count[0] = nch; r.zsset.n_sets = 1; r.zsset.log_n = r.c.degree_bits;
     GL355_TRY(r.evb.get((uint64_t)B * (n_open + nch) * 16));
-    {
-        EvalArgs ea;
-        ea.all = r.all; ea.zs = r.zsset; ea.n_all = n_open; ea.zeta = r.zetas; ea.out = r.evb.as<uint64_t>(); ea.out_us = 2 * (n_open + nch);
-        ProfScope ps(ctx, "eval_polys", (uint64_t)B * ((uint64_t)(n_open + nch) << r.c.degree_bits) * 8);
-        hipLaunchKernelGGL(eval_polys_units_kernel, dim3(n_open + nch, B), dim3(256), 0, ctx->stream, ea);
-        LAUNCH_CHECK(ctx);
-    }
+    EvalArgs<PolySet> ea;
+    ea.all = r.all; ea.zs = r.zsset; ea.n_all = n_open; ea.zeta = r.zetas; ea.out = r.evb.as<uint64_t>(); ea.out_us = 2 * (n_open + nch);
+    GL355_TRY(eval_polys_units_dev(ctx, B, nch, ea));
     GL355_HIP(ctx, ctx->d2h(r.stage, r.evb.as<uint64_t>(), (uint64_t)B * (n_open + nch) * 16));
     GL355_HIP(ctx, ctx->wait());
     for (uint32_t u = 0; u < B; u++) {
@@ -847,8 +485,7 @@ static int32_t stage_deep(ProveRun& r) {
     GL355_TRY(vbuf.get((uint64_t)B * (2 * n + 4 * n_blocks + 8) * 8));
     DeepTabArgs ta;
     ta.tab = tab.as<uint64_t>(); ta.n_alpha = n_open; ta.alpha = r.fri_alpha; ta.zeta = r.zetas;
-    hipLaunchKernelGGL(deep_tables_kernel, dim3(B), dim3(256), 0, ctx->stream, ta);
-    LAUNCH_CHECK(ctx);
+    GL355_TRY(deep_tables_dev(ctx, B, ta));
     GL355_HIP(ctx, hipMemsetAsync(r.colsA.p, 0, (uint64_t)B * 2 * n * 8, ctx->stream));
     DeepArgs da;
     memset(&da, 0, sizeof da);
@@ -856,14 +493,8 @@ static int32_t stage_deep(ProveRun& r) {
     da.v = vbuf.as<uint64_t>(); da.totals = da.v + (uint64_t)B * 2 * n; da.carry = da.totals + (uint64_t)B * 2 * n_blocks;
     da.acc = r.colsA.as<uint64_t>();
     for (int pass = 0; pass < 2; pass++) {
-        da.polys = pass ? r.zsset : r.all; da.n_polys = pass ? r.nch : n_open; da.point = pass;
-        ProfScope ps(ctx, "deep_batch", (uint64_t)B * ((uint64_t)da.n_polys * n * 8 + n * 32));
-        hipLaunchKernelGGL(deep_reduce_scan_units_kernel, dim3((uint32_t)n_blocks, B), dim3(DEEP_BLK), 0, ctx->stream, da);
-        LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(deep_carry_units_kernel, dim3(B), dim3(64), 0, ctx->stream, da);
-        LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(deep_finish_units_kernel, dim3((uint32_t)n_blocks, B), dim3(DEEP_BLK), 0, ctx->stream, da);
-        LAUNCH_CHECK(ctx);
+        da.n_polys = pass ? r.nch : n_open; da.point = pass;
+        GL355_TRY(deep_units_dev(ctx, B, pass ? r.zsset : r.all, da));
     }
     return GL355_OK;
 }
@@ -904,9 +535,7 @@ static int32_t stage_queries(ProveRun& r) {
         oa.o = r.views[o]; oa.N = r.N; oa.lde_bits = r.lde_bits; oa.cap_height = r.cap_h; oa.n_idx = nq_idx; oa.idx = r.d_idx;
         oa.leaves = r.d_open + r.off_leaf[o]; oa.sibs = r.d_open + r.off_sib[o];
         if (oa.o.leaf_len != r.lay.leaf_len[o]) return ctx->fail(GL355_E_HIP, "prove: internal leaf-length mismatch");
-        ProfScope ps(ctx, "open_batch", (uint64_t)B * nq_idx * (r.lay.leaf_len[o] * 16 + depth0 * 64));
-        hipLaunchKernelGGL(open_units_kernel, dim3(nq_idx, B), dim3(64), 0, ctx->stream, oa);
-        LAUNCH_CHECK(ctx);
+        GL355_TRY(open_units_dev(ctx, B, oa));
     }
     GL355_HIP(ctx, ctx->d2h(r.stage, r.d_open, r.open_words * 8));
     GL355_HIP(ctx, ctx->wait());
