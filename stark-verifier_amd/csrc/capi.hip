@@ -210,8 +210,7 @@ int32_t gl355_permute_h(gl355_ctx* h, int32_t hasher, uint64_t* states, uint64_t
     if (count == 0) return GL355_OK;
     Staged s(ctx);
     GL355_TRY(s.open(states, count * 96, 3));
-    if (hasher == GL355_HASH_BN254_POSEIDON) GL355_TRY(bn254_permute_dev(ctx, s.as<uint64_t>(), count));
-    else GL355_TRY(poseidon_permute_dev(ctx, s.as<uint64_t>(), count));
+    GL355_TRY(permute_dev(ctx, hasher, s.as<uint64_t>(), count));
     return s.finish();
 }
 int32_t gl355_poseidon_permute(gl355_ctx* h, uint64_t* states, uint64_t count) { return gl355_permute_h(h, GL355_HASH_POSEIDON, states, count); }
@@ -223,8 +222,7 @@ int32_t gl355_hash_no_pad_h(gl355_ctx* h, int32_t hasher, const uint64_t* inputs
     Staged si(ctx), so(ctx);
     GL355_TRY(si.open(inputs, n * len * 8, 1));
     GL355_TRY(so.open(digests, n * 32, 2));
-    if (hasher == GL355_HASH_BN254_POSEIDON) GL355_TRY(bn254_hash_leaves_dev(ctx, si.as<uint64_t>(), n, len, false, 0, so.as<uint64_t>(), true));
-    else GL355_TRY(hash_no_pad_dev(ctx, si.as<uint64_t>(), n, len, so.as<uint64_t>()));
+    GL355_TRY(hash_leaves_dev(ctx, hasher, si.as<uint64_t>(), n, len, false, 0, so.as<uint64_t>(), true));
     return so.finish();
 }
 int32_t gl355_hash_no_pad(gl355_ctx* h, const uint64_t* inputs, uint64_t n, uint32_t len, uint64_t* digests) {
@@ -237,8 +235,7 @@ int32_t gl355_hash_leaves_h(gl355_ctx* h, int32_t hasher, const uint64_t* leaves
     Staged si(ctx), so(ctx);
     GL355_TRY(si.open(leaves, n_leaves * leaf_len * 8, 1));
     GL355_TRY(so.open(digests, n_leaves * 32, 2));
-    if (hasher == GL355_HASH_BN254_POSEIDON) GL355_TRY(bn254_hash_leaves_dev(ctx, si.as<uint64_t>(), n_leaves, leaf_len, false, 0, so.as<uint64_t>(), false));
-    else GL355_TRY(hash_leaves_dev(ctx, si.as<uint64_t>(), n_leaves, leaf_len, false, 0, so.as<uint64_t>()));
+    GL355_TRY(hash_leaves_dev(ctx, hasher, si.as<uint64_t>(), n_leaves, leaf_len, false, 0, so.as<uint64_t>(), false));
     return so.finish();
 }
 int32_t gl355_hash_leaves(gl355_ctx* h, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, uint64_t* digests) {
@@ -252,8 +249,7 @@ int32_t gl355_two_to_one_h(gl355_ctx* h, int32_t hasher, const uint64_t* left, c
     GL355_TRY(sl.open(left, n * 32, 1));
     GL355_TRY(sr.open(right, n * 32, 1));
     GL355_TRY(so.open(out, n * 32, 2));
-    if (hasher == GL355_HASH_BN254_POSEIDON) GL355_TRY(bn254_two_to_one_dev(ctx, sl.as<uint64_t>(), sr.as<uint64_t>(), n, so.as<uint64_t>()));
-    else GL355_TRY(two_to_one_dev(ctx, sl.as<uint64_t>(), sr.as<uint64_t>(), n, so.as<uint64_t>()));
+    GL355_TRY(two_to_one_dev(ctx, hasher, sl.as<uint64_t>(), sr.as<uint64_t>(), n, so.as<uint64_t>()));
     return so.finish();
 }
 int32_t gl355_two_to_one(gl355_ctx* h, const uint64_t* left, const uint64_t* right, uint64_t n, uint64_t* out) {
@@ -277,10 +273,7 @@ int32_t gl355_merkle_build_h(gl355_ctx* h, int32_t hasher, const uint64_t* leave
     GL355_TRY(sl.open(leaves, n_leaves * leaf_len * 8, 1));
     GL355_TRY(sd.open(digests, n_dig * 32, 2));
     GL355_TRY(sc.open(cap, n_cap * 32, 2));
-    if (hasher == GL355_HASH_BN254_POSEIDON)
-        GL355_TRY(bn254_merkle_build_dev(ctx, sl.as<uint64_t>(), n_leaves, leaf_len, false, 0, cap_height, sd.as<uint64_t>(), sc.as<uint64_t>()));
-    else
-        GL355_TRY(merkle_build_dev(ctx, sl.as<uint64_t>(), n_leaves, leaf_len, false, 0, cap_height, sd.as<uint64_t>(), sc.as<uint64_t>()));
+    GL355_TRY(merkle_build_dev(ctx, hasher, sl.as<uint64_t>(), n_leaves, leaf_len, false, 0, cap_height, sd.as<uint64_t>(), sc.as<uint64_t>()));
     GL355_TRY(sd.finish());
     return sc.finish();
 }
@@ -376,7 +369,7 @@ int32_t gl355_commit_h(gl355_ctx* h, int32_t hasher, const uint64_t* values, uin
             rc = bitrev_permute(ctx, ss.as<uint64_t>(), dst, log_n + rate_bits, 1, N, N, GL355_SALT_SIZE); if (rc) break;
             rc = ss.finish(); if (rc) break;
         }
-        rc = merkle_build_any(ctx, hasher, o->lde, N, leaf_len, true, N, cap_height, o->digests, o->cap);
+        rc = merkle_build_dev(ctx, hasher, o->lde, N, leaf_len, true, N, cap_height, o->digests, o->cap);
         if (rc) break;
         e = ctx->wait();
         if (e != hipSuccess) { rc = ctx->fail_hip(e, "hipStreamSynchronize(commit)", __FILE__, __LINE__); break; }
@@ -587,7 +580,7 @@ int32_t gl355_fri_layer_commit_arity_h(gl355_ctx* h, int32_t hasher, const uint6
     GL355_TRY(sd.open(digests, n_dig * 32, 2));
     GL355_TRY(sc.open(cap, n_cap * 32, 2));
     GL355_TRY(fri_layer_leaves_dev(ctx, sv.as<uint64_t>(), n, sl.as<uint64_t>()));
-    GL355_TRY(merkle_build_any(ctx, hasher, sl.as<uint64_t>(), n_leaves, 2u << arity_bits, false, 0, cap_height, sd.as<uint64_t>(), sc.as<uint64_t>()));
+    GL355_TRY(merkle_build_dev(ctx, hasher, sl.as<uint64_t>(), n_leaves, 2u << arity_bits, false, 0, cap_height, sd.as<uint64_t>(), sc.as<uint64_t>()));
     GL355_TRY(sl.finish());
     GL355_TRY(sd.finish());
     return sc.finish();
@@ -600,7 +593,7 @@ int32_t gl355_pow_grind_h(gl355_ctx* h, int32_t hasher, const uint64_t state[12]
     CTX_OR_FAIL(h);
     HASHER_OR_FAIL(hasher);
     if (!state || !witness || pos >= 8) return ctx->fail(GL355_E_INVALID_ARG, "pow_grind: bad argument");
-    return pow_grind_any(ctx, hasher, state, pos, bits, start, witness);
+    return pow_grind_dev(ctx, hasher, state, pos, bits, start, witness);
 }
 
 // ---- a9 --------------------------------------------------------------------------------------

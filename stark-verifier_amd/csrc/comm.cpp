@@ -406,7 +406,7 @@ int32_t gl355_aggregation_root(gl355_ctx* h, const uint64_t* leaves, uint64_t n_
     uint64_t* d_cap = d_dig + 2 * (m - 1) * 4;
     GL355_HIP(ctx, hipMemsetAsync(d_leaves, 0, m * leaf_len * 8, ctx->stream));
     GL355_HIP(ctx, hipMemcpyAsync(d_leaves, leaves, n_leaves * leaf_len * 8, ptr_is_device(leaves) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    GL355_TRY(merkle_build_dev(ctx, d_leaves, m, leaf_len, false, 0, 0, d_dig, d_cap));
+    GL355_TRY(merkle_build_dev(ctx, GL355_HASH_POSEIDON, d_leaves, m, leaf_len, false, 0, 0, d_dig, d_cap));
     if (ptr_is_device(root)) GL355_HIP(ctx, hipMemcpyAsync(root, d_cap, 32, hipMemcpyDeviceToDevice, ctx->stream));
     else GL355_HIP(ctx, ctx->d2h(root, d_cap, 32));
     GL355_HIP(ctx, ctx->wait());

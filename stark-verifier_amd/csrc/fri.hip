@@ -390,7 +390,7 @@ int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, 
             LeafArgs la;
             memset(&la, 0, sizeof la);
             la.leaves = lv; la.n_leaves = (uint64_t)B * nl; la.leaf_len = 2u << ab; la.col_major = 0; la.stride = 2u << ab;
-            GL355_TRY(merkle_build_args_any(ctx, s.hasher, la, log2_u64(nl) - s.cap_height, tree_buf + fa.dig_off[l], d_cap));
+            GL355_TRY(merkle_build_args(ctx, s.hasher, la, log2_u64(nl) - s.cap_height, tree_buf + fa.dig_off[l], d_cap));
         }
         uint64_t* cap_dst[MAXB];
         for (uint32_t u = 0; u < B; u++) cap_dst[u] = out[u].caps + (uint64_t)l * n_cap * 4;
@@ -419,8 +419,7 @@ int32_t fri_tail_units(Ctx* ctx, const FriShape& s, uint32_t B, uint64_t* cols, 
         p_pow[u] = out[u].pow_witness;
     }
     // proof of work: the smallest witness of every unit
-    if (s.hasher == GL355_HASH_POSEIDON) GL355_TRY(pow_grind_units_dev(ctx, B, pow_state, pow_pos, s.pow_bits, 0, stage, p_pow));
-    else for (uint32_t u = 0; u < B; u++) GL355_TRY(pow_grind_any(ctx, s.hasher, &pow_state[u * 12], pow_pos[u], s.pow_bits, 0, p_pow[u]));
+    GL355_TRY(pow_grind_units_dev(ctx, s.hasher, B, pow_state, pow_pos, s.pow_bits, 0, stage, p_pow));
     // queries: x_index = challenge mod N; layer l opens the leaf at x_index >> s_l and its path
     for (uint32_t u = 0; u < B; u++) {
         gl355_challenger_observe(&ch[u], p_pow[u], 1);

@@ -199,47 +199,44 @@ int32_t ntt_dev(Ctx* ctx, uint64_t* data, uint32_t log_n, uint32_t batch, uint64
 int32_t lde_dev(Ctx* ctx, const uint64_t* coeffs, uint64_t in_stride, uint32_t log_n, uint32_t rate_bits,
                 uint64_t shift, uint32_t batch, uint64_t* out, uint64_t out_stride, bool out_bitrev);
 
-// ---- merkle.hip ----------------------------------------------------------------------------
-int32_t poseidon_permute_dev(Ctx* ctx, uint64_t* states, uint64_t count);
+// ---- merkle.hip: the launch code of both hash back-ends (kernels: merkle.hip, merkle_bn254.hip); hasher = GL355_HASH_* ---------------
+// What the launch code (merkle.hip) needs to know of a back-end; each of the two files fills its own.
+struct HasherLaunch {
+    void (*permute)(uint64_t*, uint64_t);
+    void (*leaves)(LeafArgs);
+    void (*two_to_one)(const uint64_t*, const uint64_t*, uint64_t, uint64_t*);
+    void (*grind)(PowArgs);
+    const char *permute_scope, *leaves_scope, *two_to_one_scope, *grind_scope;      // profile scopes of those four launches
+    uint32_t grind_window_log;      // a grinder launch tries at most 2^this candidates per unit
+    // the levels above the leaf digests (digest_slot(0, k) of every cap subtree is written), the hasher's level kernels among them
+    int32_t (*above_leaves)(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
+};
+const HasherLaunch& bn254_hasher_launch();      // merkle_bn254.hip
+int32_t permute_dev(Ctx* ctx, int32_t hasher, uint64_t* states, uint64_t count);
 // leaves: row-major [n][leaf_len] (row_stride = leaf_len) when col_major == false, else
-// column-major: element (leaf i, column c) at leaves[c * col_stride + i].
-int32_t hash_leaves_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
-                        uint64_t col_stride, uint64_t* digests /* n_leaves * 4, linear order */);
-int32_t merkle_build_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
+// column-major: element (leaf i, column c) at leaves[c * col_stride + i].  always_hash: hash_no_pad (no "at most 4 words are their own digest")
+int32_t hash_leaves_dev(Ctx* ctx, int32_t hasher, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
+                        uint64_t col_stride, uint64_t* digests /* n_leaves * 4, linear order */, bool always_hash);
+int32_t two_to_one_dev(Ctx* ctx, int32_t hasher, const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out);
+int32_t merkle_build_dev(Ctx* ctx, int32_t hasher, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
                          uint64_t col_stride, uint32_t cap_height, uint64_t* digests, uint64_t* cap);
-int32_t merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
-// the levels above the leaf digests of merkle_build_args, for a caller that has written digest_slot(0, k) of every cap subtree itself
+int32_t merkle_build_args(Ctx* ctx, int32_t hasher, LeafArgs a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
+// the levels above the leaf digests of a Poseidon tree, for a caller that has written digest_slot(0, k) of every cap subtree itself
 int32_t merkle_build_above_leaves(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
 // FRI layer leaves of 2 << ab words (ab = 2..4), hashed 16 lanes per leaf straight from the value columns vals [B][2][len_v]: writes the row-major
-// leaf array leaves [B][len_v >> ab][2 << ab] and the leaf digests (or the cap entries when sub_bits == 0), then builds the levels above
+// leaf array leaves [B][len_v >> ab][2 << ab] and the leaf digests (or the cap entries when sub_bits == 0), then builds the levels above (Poseidon only)
 int32_t fri_wide_leaves_tree_dev(Ctx* ctx, uint32_t ab, uint32_t B, const uint64_t* vals, uint64_t len_v, uint64_t* leaves, uint32_t sub_bits,
                                  uint64_t* digests, uint64_t* cap);
-int32_t bn254_merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
-int32_t merkle_build_args_any(Ctx* ctx, int32_t hasher, const LeafArgs& a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
-int32_t hash_no_pad_dev(Ctx* ctx, const uint64_t* inputs, uint64_t n, uint32_t len, uint64_t* digests);
-int32_t two_to_one_dev(Ctx* ctx, const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out);
-// second hash back-end (merkle_bn254.hip, host_bn254.cpp)
-void host_bn254_permute(uint64_t state[12]);
-// Merkle tree / PoW with the hasher chosen at run time
-int32_t merkle_build_any(Ctx* ctx, int32_t hasher, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
-                         uint64_t col_stride, uint32_t cap_height, uint64_t* digests, uint64_t* cap);
-int32_t pow_grind_any(Ctx* ctx, int32_t hasher, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start,
+// the grinder for B <= GL355_MAX_UNITS sponge states at once (pow_grind_dev is its B = 1 call): the smallest passing
+// candidate >= start of every unit; `landing` is a host area of B words for the device's answers (pinned: no hidden wait)
+int32_t pow_grind_units_dev(Ctx* ctx, int32_t hasher, uint32_t B, const uint64_t* states /* [B][12] */, const uint32_t* pos /* [B] */, uint32_t bits,
+                            uint64_t start, uint64_t* landing, uint64_t* const* witness_host /* [B] */);
+int32_t pow_grind_dev(Ctx* ctx, int32_t hasher, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start,
                       uint64_t* witness_host);
-int32_t bn254_pow_grind_dev(Ctx* ctx, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start, uint64_t* witness_host);
-int32_t bn254_permute_dev(Ctx* ctx, uint64_t* states, uint64_t count);
-int32_t bn254_hash_leaves_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major, uint64_t col_stride,
-                              uint64_t* digests, bool always_hash);
-int32_t bn254_two_to_one_dev(Ctx* ctx, const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out);
-int32_t bn254_merkle_build_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major, uint64_t col_stride,
-                               uint32_t cap_height, uint64_t* digests, uint64_t* cap);
+// host_bn254.cpp
+void host_bn254_permute(uint64_t state[12]);
 int32_t oracle_open_batch_on(Ctx* ctx, const gl355_oracle* o, const uint64_t* indices, uint32_t n_idx, uint64_t* leaves,
                              uint64_t* siblings);
-int32_t pow_grind_dev(Ctx* ctx, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start,
-                      uint64_t* witness_host);
-// the Poseidon grinder for B <= GL355_MAX_UNITS sponge states at once (pow_grind_dev is its B = 1 call): the smallest passing
-// candidate >= start of every unit; `landing` is a host area of B words for the device's answers (pinned: no hidden wait)
-int32_t pow_grind_units_dev(Ctx* ctx, uint32_t B, const uint64_t* states /* [B][12] */, const uint32_t* pos /* [B] */, uint32_t bits,
-                            uint64_t start, uint64_t* landing, uint64_t* const* witness_host /* [B] */);
 
 // ---- fri.hip -------------------------------------------------------------------------------
 // Openings, DEEP quotient, FRI fold and query openings exist once, with a unit dimension B: the lock-step prover's stages call the

@@ -23,77 +23,22 @@ namespace gl355 {
 // the chip is full of waves either way and the one-lane-per-node kernel wins on instruction count
 // the default of Ctx::merkle_lanes_log (gl355_ctx_set_option) is 14: see the lane-parallel kernel below
 
-__global__ void __launch_bounds__(256) poseidon_permute_kernel(uint64_t* states, uint64_t count) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    uint64_t s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = states[i * 12 + k];
-    psd_permute(s);
-#pragma unroll
-    for (int k = 0; k < 12; k++) states[i * 12 + k] = gl_canon(s[k]);
-}
+// the Poseidon-Goldilocks policy of merkle_common.cuh's kernel bodies
+struct PoseidonHasher {
+    static constexpr bool wide_digests = true;
+    static GL_DEV void permute(uint64_t (&s)[12]) { psd_permute(s); }
+    static GL_DEV uint64_t out(uint64_t x) { return gl_canon(x); }
+    static GL_DEV uint64_t in2(uint64_t x) { return x; }
+};
 
+__global__ void __launch_bounds__(256) poseidon_permute_kernel(uint64_t* states, uint64_t count) { permute_body<PoseidonHasher>(states, count); }
 
-// one lane = one leaf: overwrite-mode sponge over ceil(len/8) chunks
 constexpr int psd_leaf_waves = 4;
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(psd_leaf_waves))) hash_leaves_kernel(LeafArgs a) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= a.n_leaves) return;
-    uint64_t s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = 0;
-    const uint32_t len = a.leaf_len;
-    uint64_t d[4];
-    if (len <= 4 && !a.always_hash) {
-        for (uint32_t k = 0; k < 4; k++) {
-            uint64_t v = 0;
-            if (k < len) v = leaf_elem(a, i, k);
-            d[k] = gl_canon(v);
-        }
-    } else {
-        for (uint32_t off = 0; off < len; off += 8) {
-            const uint32_t m = min(8u, len - off);
-#pragma unroll
-            for (uint32_t k = 0; k < 8; k++) {
-                if (k < m) s[k] = leaf_elem(a, i, off + k);
-            }
-            psd_permute(s);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = gl_canon(s[k]);
-    }
-    uint64_t* dst;
-    if (a.linear) dst = a.out + i * 4;
-    else if (a.sub_bits == 0) dst = a.cap + i * 4;
-    else {
-        const uint64_t sub_leaves = 1ull << a.sub_bits;
-        const uint64_t t = i >> a.sub_bits, k = i & (sub_leaves - 1);
-        dst = a.out + (t * 2 * (sub_leaves - 1) + digest_slot(0, k)) * 4;
-    }
-    *reinterpret_cast<ulonglong2*>(dst) = make_ulonglong2(d[0], d[1]);
-    *reinterpret_cast<ulonglong2*>(dst + 2) = make_ulonglong2(d[2], d[3]);
-}
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(psd_leaf_waves))) hash_leaves_kernel(LeafArgs a) { hash_leaves_body<PoseidonHasher>(a); }
 
-// one lane = one parent node of layer `layer` (>= 1): two_to_one of its children in layer-1
 __global__ void __launch_bounds__(256) merkle_level_kernel(uint64_t* digests, uint64_t* cap, uint32_t sub_bits,
                                                           uint32_t layer, uint64_t n_nodes /* all subtrees */) {
-    const uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (g >= n_nodes) return;
-    const uint64_t sub_leaves = 1ull << sub_bits;
-    const uint64_t per = sub_leaves >> layer;
-    const uint64_t t = g / per, k = g % per;
-    uint64_t* tree = digests + t * 2 * (sub_leaves - 1) * 4;
-    const uint64_t child = digest_slot(layer - 1, 2 * k);  // left child; right child is +1
-    const ulonglong2 l0 = *reinterpret_cast<const ulonglong2*>(tree + child * 4);
-    const ulonglong2 l1 = *reinterpret_cast<const ulonglong2*>(tree + child * 4 + 2);
-    const ulonglong2 r0 = *reinterpret_cast<const ulonglong2*>(tree + child * 4 + 4);
-    const ulonglong2 r1 = *reinterpret_cast<const ulonglong2*>(tree + child * 4 + 6);
-    uint64_t s[12] = {l0.x, l0.y, l1.x, l1.y, r0.x, r0.y, r1.x, r1.y, 0, 0, 0, 0};
-    psd_permute(s);
-    uint64_t* dst = (layer == sub_bits) ? cap + t * 4 : tree + digest_slot(layer, k) * 4;
-    *reinterpret_cast<ulonglong2*>(dst) = make_ulonglong2(gl_canon(s[0]), gl_canon(s[1]));
-    *reinterpret_cast<ulonglong2*>(dst + 2) = make_ulonglong2(gl_canon(s[2]), gl_canon(s[3]));
+    merkle_level_body<PoseidonHasher>(digests, cap, sub_bits, layer, n_nodes);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -108,13 +53,6 @@ __global__ void __launch_bounds__(256) merkle_level_kernel(uint64_t* digests, ui
 // ------------------------------------------------------------------------------------------------
 __device__ __constant__ const uint32_t PSD_CIRC_DEV[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
 
-// the 16 lanes sharing a state sit in ONE wave, and a wave's LDS instructions complete in issue order: the ring
-// exchange only needs the compiler (and the LGKM counter) to keep write -> read -> next write ordered, not s_barrier
-#define GL_WAVE_LDS_SYNC()                                      \
-    do {                                                        \
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  \
-        __builtin_amdgcn_wave_barrier();                        \
-    } while (0)
 // FORM (round 6): the 22 PARTIAL rounds of the 16-lane permutation.
 //   0  as the full rounds: S-box (only lane 0's matters), the state through the ring, the whole MDS row: S-box + LDS round trip + 24 multiply-adds +
 //      recombination, one after the other on the critical path;
@@ -197,17 +135,10 @@ __global__ void __launch_bounds__(64) merkle_level_lanes_kernel(uint64_t* digest
     uint64_t g = blockIdx.x * 4ull + grp;
     const bool valid = g < n_nodes;
     if (!valid) g = 0;  // keep the whole wave in the barriers
-    const uint64_t sub_leaves = 1ull << sub_bits;
-    const uint64_t per = sub_leaves >> layer;
-    const uint64_t t = g / per, k = g % per;
-    uint64_t* tree = digests + t * 2 * (sub_leaves - 1) * 4;
-    const uint64_t child = digest_slot(layer - 1, 2 * k);  // left child; the right one follows it
-    uint64_t s = (li < 8) ? tree[child * 4 + li] : 0;
+    const MerkleNode nd = merkle_node(digests, cap, sub_bits, layer, g);
+    uint64_t s = (li < 8) ? nd.tree[nd.child() * 4 + li] : 0;      // left child, then the right one
     s = psd_permute_lanes<FORM>(s, li, rings[grp]);
-    if (valid && li < 4) {
-        uint64_t* dst = (layer == sub_bits) ? cap + t * 4 : tree + digest_slot(layer, k) * 4;
-        dst[li] = gl_canon(s);
-    }
+    if (valid && li < 4) nd.dst()[li] = gl_canon(s);
 }
 
 // FRI layer leaves of 2A = 2 << AB words (A = 4, 8, 16), one 16-lane group per leaf, four leaves per wave.  Word w of leaf i is column w & 1,
@@ -238,16 +169,7 @@ __global__ void __launch_bounds__(64) fri_wide_leaves_units_kernel(const uint64_
         }
         s = psd_permute_lanes<FORM>(s, li, rings[grp]);
     }
-    if (valid && li < 4) {
-        uint64_t* dst;
-        if (sub_bits == 0) dst = cap + g * 4;
-        else {
-            const uint64_t sub_leaves = 1ull << sub_bits;
-            const uint64_t t = g >> sub_bits, k = g & (sub_leaves - 1);
-            dst = digests + (t * 2 * (sub_leaves - 1) + digest_slot(0, k)) * 4;
-        }
-        dst[li] = gl_canon(s);
-    }
+    if (valid && li < 4) leaf_digest_dst(digests, cap, 0, sub_bits, g)[li] = gl_canon(s);
 }
 
 // The top of every cap subtree in ONE launch: one 1024-thread block per subtree takes its 2^(n_levels - 1) nodes of layer `layer0` (at most
@@ -263,9 +185,7 @@ __global__ void __launch_bounds__(1024) merkle_top_kernel(uint64_t* digests, uin
     __shared__ uint64_t lvl[2][(1 << (MERKLE_TOP_LEVELS - 1)) * 4];
     const int li = threadIdx.x & 15, grp = threadIdx.x >> 4;
     const int wave_first_grp = (threadIdx.x >> 6) << 2;
-    const uint64_t sub_leaves = 1ull << sub_bits;
     const uint64_t t = blockIdx.x;
-    uint64_t* tree = digests + t * 2 * (sub_leaves - 1) * 4;
     int cur = 0;
     for (uint32_t l = 0; l < n_levels; l++) {
         const uint32_t layer = layer0 + l;
@@ -274,14 +194,14 @@ __global__ void __launch_bounds__(1024) merkle_top_kernel(uint64_t* digests, uin
             if (base + wave_first_grp < cnt) {                // wave-uniform: this wave owns at least one node of the round
                 const bool valid = base + grp < cnt;
                 const int j = valid ? base + grp : 0;
+                const MerkleNode nd = merkle_node(digests, cap, sub_bits, layer, t, (uint64_t)j);
                 uint64_t s = 0;
-                if (li < 8) s = (l == 0) ? tree[digest_slot(layer - 1, 2 * (uint64_t)j) * 4 + li] : lvl[cur][(2 * j) * 4 + li];
+                if (li < 8) s = (l == 0) ? nd.tree[nd.child() * 4 + li] : lvl[cur][(2 * j) * 4 + li];
                 s = psd_permute_lanes<FORM>(s, li, rings[grp]);
                 if (valid && li < 4) {
                     const uint64_t v = gl_canon(s);
                     lvl[cur ^ 1][j * 4 + li] = v;
-                    uint64_t* dst = (layer == sub_bits) ? cap + t * 4 : tree + digest_slot(layer, (uint64_t)j) * 4;
-                    dst[li] = v;
+                    nd.dst()[li] = v;
                 }
             }
         }
@@ -290,96 +210,77 @@ __global__ void __launch_bounds__(1024) merkle_top_kernel(uint64_t* digests, uin
     }
 }
 
-__global__ void __launch_bounds__(256) two_to_one_kernel(const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint64_t s[12] = {l[4 * i], l[4 * i + 1], l[4 * i + 2], l[4 * i + 3],
-                      r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3], 0, 0, 0, 0};
-    psd_permute(s);
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[4 * i + k] = gl_canon(s[k]);
-}
+__global__ void __launch_bounds__(256) two_to_one_kernel(const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out) { two_to_one_body<PoseidonHasher>(l, r, n, out); }
 
-// proof of work of every unit that still lacks a witness: candidates start + g, the smallest passing one of the launch wins
-struct PowArgs { uint64_t state[GL355_MAX_UNITS * 12]; uint32_t pos[GL355_MAX_UNITS]; uint32_t todo[GL355_MAX_UNITS]; uint32_t bits; uint64_t start; unsigned long long* best; };
-__global__ void __launch_bounds__(256) pow_grind_units_kernel(PowArgs a) {
-    const uint32_t u = blockIdx.y;
-    if (!a.todo[u]) return;
-    const uint64_t w = a.start + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    // the smallest witness wins, so a candidate above the best one found so far cannot matter: workgroups are dispatched in
-    // roughly increasing order, and once a witness is known the rest of the launch exits here (expected work ~2^bits instead of the
-    // 2^(bits+1) candidates of the launch); candidates below the current best are never skipped, so the result is still the minimum
-    if (w > __hip_atomic_load(a.best + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    uint64_t s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = a.state[u * 12 + k];
-#pragma unroll
-    for (int k = 0; k < 12; k++) if ((uint32_t)k == a.pos[u]) s[k] = w;
-    psd_permute(s);
-    const uint64_t resp = gl_canon(s[7]);
-    if (a.bits == 0 || (resp >> (64 - a.bits)) == 0) atomicMin(a.best + u, (unsigned long long)w);
-}
+__global__ void __launch_bounds__(256) pow_grind_units_kernel(PowArgs a) { pow_grind_units_body<PoseidonHasher>(a); }
 
 // ------------------------------------------------------------------------------------------------
-int32_t poseidon_permute_dev(Ctx* ctx, uint64_t* states, uint64_t count) {
+// The launch code of both back-ends: `hasher` picks the table (GL355_HASH_*, checked at the C ABI).
+static const HasherLaunch& launch_of(int32_t hasher) {
+    static const HasherLaunch poseidon = {
+        poseidon_permute_kernel, hash_leaves_kernel, two_to_one_kernel, pow_grind_units_kernel,
+        "poseidon_permute_kernel", "hash_leaves_kernel", "two_to_one_kernel", "pow_grind", 22, merkle_build_above_leaves};
+    return hasher == GL355_HASH_BN254_POSEIDON ? bn254_hasher_launch() : poseidon;
+}
+
+int32_t permute_dev(Ctx* ctx, int32_t hasher, uint64_t* states, uint64_t count) {
     if (count == 0) return GL355_OK;
-    hipLaunchKernelGGL(poseidon_permute_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, states, count);
+    const HasherLaunch& h = launch_of(hasher);
+    ProfScope ps(ctx, h.permute_scope, count * 192);
+    hipLaunchKernelGGL(h.permute, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, states, count);
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }
 
-static int32_t launch_leaves(Ctx* ctx, const LeafArgs& a) {
+static int32_t launch_leaves(Ctx* ctx, const HasherLaunch& h, const LeafArgs& a) {
     if (a.n_leaves == 0) return GL355_OK;
-    hipLaunchKernelGGL(hash_leaves_kernel, dim3((uint32_t)((a.n_leaves + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    ProfScope ps(ctx, h.leaves_scope, a.n_leaves * ((uint64_t)a.leaf_len * 8 + 32));
+    hipLaunchKernelGGL(h.leaves, dim3((uint32_t)((a.n_leaves + 255) / 256)), dim3(256), 0, ctx->stream, a);
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }
 
-int32_t hash_leaves_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
-                        uint64_t col_stride, uint64_t* digests) {
+static LeafArgs leaf_args(const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major, uint64_t col_stride) {
     LeafArgs a;
     memset(&a, 0, sizeof a);
     a.leaves = leaves; a.n_leaves = n_leaves; a.leaf_len = leaf_len; a.col_major = col_major;
     a.stride = col_major ? col_stride : leaf_len;
-    a.out = digests; a.linear = 1;
-    return launch_leaves(ctx, a);
+    return a;
 }
 
-int32_t hash_no_pad_dev(Ctx* ctx, const uint64_t* inputs, uint64_t n, uint32_t len, uint64_t* digests) {
-    LeafArgs a;
-    memset(&a, 0, sizeof a);
-    a.leaves = inputs; a.n_leaves = n; a.leaf_len = len; a.col_major = 0; a.stride = len;
-    a.out = digests; a.linear = 1; a.always_hash = 1;
-    return launch_leaves(ctx, a);
+int32_t hash_leaves_dev(Ctx* ctx, int32_t hasher, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
+                        uint64_t col_stride, uint64_t* digests, bool always_hash) {
+    LeafArgs a = leaf_args(leaves, n_leaves, leaf_len, col_major, col_stride);
+    a.out = digests; a.linear = 1; a.always_hash = always_hash;
+    return launch_leaves(ctx, launch_of(hasher), a);
 }
 
-int32_t two_to_one_dev(Ctx* ctx, const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out) {
+int32_t two_to_one_dev(Ctx* ctx, int32_t hasher, const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out) {
     if (n == 0) return GL355_OK;
-    hipLaunchKernelGGL(two_to_one_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, l, r, n, out);
+    const HasherLaunch& h = launch_of(hasher);
+    ProfScope ps(ctx, h.two_to_one_scope, n * 96);
+    hipLaunchKernelGGL(h.two_to_one, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, l, r, n, out);
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }
 
-int32_t merkle_build_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
+int32_t merkle_build_dev(Ctx* ctx, int32_t hasher, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
                          uint64_t col_stride, uint32_t cap_height, uint64_t* digests, uint64_t* cap) {
     const uint32_t log_n = log2_u64(n_leaves);
     if ((1ull << log_n) != n_leaves) return ctx->fail(GL355_E_INVALID_ARG, "merkle: n_leaves must be a power of two");
     if (cap_height > log_n) return ctx->fail(GL355_E_INVALID_ARG, "merkle: cap_height > log2(n_leaves)");
-    LeafArgs a;
-    memset(&a, 0, sizeof a);
-    a.leaves = leaves; a.n_leaves = n_leaves; a.leaf_len = leaf_len; a.col_major = col_major;
-    a.stride = col_major ? col_stride : leaf_len;
-    return merkle_build_args(ctx, a, log_n - cap_height, digests, cap);
+    return merkle_build_args(ctx, hasher, leaf_args(leaves, n_leaves, leaf_len, col_major, col_stride), log_n - cap_height, digests, cap);
 }
 
 // a.n_leaves leaves (any multiple of 2^sub_bits: the cap subtrees of one tree, or of several units' trees laid out one after
 // the other) -> per-subtree digests in plonky2's layout + one cap entry per subtree.  `a` describes where the leaves are.
-int32_t merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap) {
+int32_t merkle_build_args(Ctx* ctx, int32_t hasher, LeafArgs a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap) {
     const uint64_t n_leaves = a.n_leaves;
     if (n_leaves == 0 || (n_leaves & ((1ull << sub_bits) - 1))) return ctx->fail(GL355_E_INVALID_ARG, "merkle: leaves do not fill whole cap subtrees");
+    const HasherLaunch& h = launch_of(hasher);
     a.out = digests; a.cap = cap; a.sub_bits = sub_bits; a.linear = 0;
-    { ProfScope ps(ctx, "hash_leaves_kernel", n_leaves * ((uint64_t)a.leaf_len * 8 + 32)); GL355_TRY(launch_leaves(ctx, a)); }
-    return merkle_build_above_leaves(ctx, n_leaves, sub_bits, digests, cap);
+    GL355_TRY(launch_leaves(ctx, h, a));
+    return h.above_leaves(ctx, n_leaves, sub_bits, digests, cap);
 }
 
 int32_t fri_wide_leaves_tree_dev(Ctx* ctx, uint32_t ab, uint32_t B, const uint64_t* vals, uint64_t len_v, uint64_t* leaves, uint32_t sub_bits,
@@ -450,9 +351,10 @@ int32_t merkle_build_above_leaves(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits
     return GL355_OK;
 }
 
-int32_t pow_grind_units_dev(Ctx* ctx, uint32_t B, const uint64_t* states, const uint32_t* pos, uint32_t bits, uint64_t start, uint64_t* landing,
+int32_t pow_grind_units_dev(Ctx* ctx, int32_t hasher, uint32_t B, const uint64_t* states, const uint32_t* pos, uint32_t bits, uint64_t start, uint64_t* landing,
                             uint64_t* const* witness_host) {
     if (bits > 40) return ctx->fail(GL355_E_UNSUPPORTED, "pow: more than 40 bits of grinding refused");
+    const HasherLaunch& h = launch_of(hasher);
     PowArgs pa;
     memset(&pa, 0, sizeof pa);
     for (uint32_t u = 0; u < B; u++) {
@@ -466,29 +368,30 @@ int32_t pow_grind_units_dev(Ctx* ctx, uint32_t B, const uint64_t* states, const 
     GL355_HIP(ctx, hipMemsetAsync(pb.p, 0xFF, GL355_MAX_UNITS * 8, ctx->stream));
     // within a launch the minimum wins, and earlier launches found nothing for that unit, so the result is the global minimum.
     // a launch of 2^(bits+1) candidates holds a solution with probability 1 - e^-2; units without one go again, with a larger window
-    uint64_t per_launch = 1ull << std::min<uint32_t>(std::max<uint32_t>(bits + 1, 12), 22);
+    // (up to the hasher's largest window: 2^22 candidates, 2^20 of the 35x longer BN254 permutation; the window sizes do not change the witness)
+    uint64_t per_launch = 1ull << std::min<uint32_t>(std::max<uint32_t>(bits + 1, 12), h.grind_window_log);
     uint64_t base = start;
     for (uint32_t left = B; left;) {
-        ProfScope ps(ctx, "pow_grind", 0);   // pure compute: one permutation per candidate, no HBM traffic
+        ProfScope ps(ctx, h.grind_scope, 0);   // pure compute: one permutation per candidate, no HBM traffic
         pa.start = base;
-        hipLaunchKernelGGL(pow_grind_units_kernel, dim3((uint32_t)(per_launch / 256), B), dim3(256), 0, ctx->stream, pa);
+        hipLaunchKernelGGL(h.grind, dim3((uint32_t)(per_launch / 256), B), dim3(256), 0, ctx->stream, pa);
         GL355_HIP(ctx, hipGetLastError());
         GL355_HIP(ctx, ctx->d2h(landing, pb.p, (uint64_t)B * 8));
         GL355_HIP(ctx, ctx->wait());
         for (uint32_t u = 0; u < B; u++)
             if (pa.todo[u] && landing[u] != ~0ull) { *witness_host[u] = landing[u]; pa.todo[u] = 0; left--; }
         base += per_launch;
-        if (per_launch < (1ull << 22)) per_launch <<= 1;
+        if (per_launch < (1ull << h.grind_window_log)) per_launch <<= 1;
         if (base - start > (1ull << 44)) return ctx->fail(GL355_E_UNSUPPORTED, "pow: no witness found in 2^44 candidates");
     }
     return GL355_OK;
 }
 
-int32_t pow_grind_dev(Ctx* ctx, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start,
+int32_t pow_grind_dev(Ctx* ctx, int32_t hasher, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start,
                       uint64_t* witness_host) {
     if (pos >= 8) return ctx->fail(GL355_E_INVALID_ARG, "pow: witness position must be in the rate part");
     uint64_t landing;
-    return pow_grind_units_dev(ctx, 1, state, &pos, bits, start, &landing, &witness_host);
+    return pow_grind_units_dev(ctx, hasher, 1, state, &pos, bits, start, &landing, &witness_host);
 }
 
 }  // namespace gl355

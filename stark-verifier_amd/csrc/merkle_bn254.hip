@@ -2,85 +2,31 @@
 // over native.rs:16-77) for permutation batches, leaf hashing, Merkle levels, two_to_one and PoW -- the hasher of the
 // final wrap proof (wrapper.rs:35-56 with OuterC = Bn254PoseidonGoldilocksConfig).  SURVEY 8(f) N1.
 //
-// Same launch shapes and the same plonky2 digest layout as merkle.hip; only the permutation differs (bn254.cuh).  One
-// lane = one sponge state: a permutation is ~2 000 254-bit Montgomery products (~0.9 M VALU instructions, ~35x the
-// Goldilocks Poseidon), so every level is throughput-bound down to a few hundred nodes and no lane-parallel variant is used.
+// The one-lane-per-state kernels are merkle_common.cuh's bodies with this file's policy (the permutation of bn254.cuh: ~2 000 254-bit
+// Montgomery products, ~35x the Goldilocks Poseidon), launched by merkle.hip's launch code through the table at the end of this
+// file; what is this hasher's own are the lane-parallel level kernel and the choice of kernel per level (bn254_above_leaves).
 #include "gl355_internal.h"
 #include "bn254.cuh"
 #include "merkle_common.cuh"
 
 namespace gl355 {
 
-__global__ void __launch_bounds__(256) bn254_permute_kernel(uint64_t* states, uint64_t count) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    uint64_t s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = states[i * 12 + k];
-    bn254_permute(s);
-#pragma unroll
-    for (int k = 0; k < 12; k++) states[i * 12 + k] = s[k];
-}
+// the BN254-Poseidon policy of merkle_common.cuh's kernel bodies
+struct Bn254Hasher {
+    static constexpr bool wide_digests = false;
+    static GL_DEV void permute(uint64_t (&s)[12]) { bn254_permute(s); }
+    static GL_DEV uint64_t out(uint64_t x) { return x; }
+    static GL_DEV uint64_t in2(uint64_t x) { return gl_canon(x); }
+};
 
-__global__ void __launch_bounds__(256) bn254_hash_leaves_kernel(LeafArgs a) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= a.n_leaves) return;
-    uint64_t s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = 0;
-    const uint32_t len = a.leaf_len;
-    uint64_t d[4];
-    if (len <= 4 && !a.always_hash) {
-        for (uint32_t k = 0; k < 4; k++) {
-            uint64_t v = 0;
-            if (k < len) v = leaf_elem(a, i, k);
-            d[k] = gl_canon(v);
-        }
-    } else {
-#pragma unroll 1
-        for (uint32_t off = 0; off < len; off += 8) {
-            const uint32_t m = min(8u, len - off);
-#pragma unroll
-            for (uint32_t k = 0; k < 8; k++) {
-                if (k < m) s[k] = leaf_elem(a, i, off + k);
-            }
-            bn254_permute(s);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = s[k];
-    }
-    uint64_t* dst;
-    if (a.linear) dst = a.out + i * 4;
-    else if (a.sub_bits == 0) dst = a.cap + i * 4;
-    else {
-        const uint64_t sub_leaves = 1ull << a.sub_bits;
-        const uint64_t t = i >> a.sub_bits, k = i & (sub_leaves - 1);
-        dst = a.out + (t * 2 * (sub_leaves - 1) + digest_slot(0, k)) * 4;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) dst[k] = d[k];
-}
+__global__ void __launch_bounds__(256) bn254_permute_kernel(uint64_t* states, uint64_t count) { permute_body<Bn254Hasher>(states, count); }
+
+__global__ void __launch_bounds__(256) bn254_hash_leaves_kernel(LeafArgs a) { hash_leaves_body<Bn254Hasher>(a); }
 
 __global__ void __launch_bounds__(256) bn254_merkle_level_kernel(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer,
                                                                 uint64_t n_nodes) {
-    const uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (g >= n_nodes) return;
-    const uint64_t sub_leaves = 1ull << sub_bits;
-    const uint64_t per = sub_leaves >> layer;
-    const uint64_t t = g / per, k = g % per;
-    uint64_t* tree = digests + t * 2 * (sub_leaves - 1) * 4;
-    const uint64_t child = digest_slot(layer - 1, 2 * k);
-    uint64_t s[12];
-#pragma unroll
-    for (int e = 0; e < 8; e++) s[e] = tree[child * 4 + e];
-#pragma unroll
-    for (int e = 8; e < 12; e++) s[e] = 0;
-    bn254_permute(s);
-    uint64_t* dst = (layer == sub_bits) ? cap + t * 4 : tree + digest_slot(layer, k) * 4;
-#pragma unroll
-    for (int e = 0; e < 4; e++) dst[e] = s[e];
+    merkle_level_body<Bn254Hasher>(digests, cap, sub_bits, layer, n_nodes);
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------
 // Lane-parallel permutation for SMALL levels.  With one lane per node a level costs one full permutation latency
@@ -91,11 +37,6 @@ __global__ void __launch_bounds__(256) bn254_merkle_level_kernel(uint64_t* diges
 // ~7x lower latency at ~4.6x the instruction count, so it is used only below 2^13 nodes (BN254_LANES_MAX_LOG).
 // ------------------------------------------------------------------------------------------------------------------
 #define BN254_LANES_MAX_LOG 13
-#define GL_WAVE_LDS_SYNC()                                      \
-    do {                                                        \
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  \
-        __builtin_amdgcn_wave_barrier();                        \
-    } while (0)
 
 GL_DEV fr8 lds_load_fr(const uint32_t* p) {
     fr8 r;
@@ -114,17 +55,13 @@ __global__ void __launch_bounds__(64) bn254_merkle_level_lanes_kernel(uint64_t* 
     uint64_t g = blockIdx.x * 2ull + grp;
     const bool valid = g < n_nodes;
     if (!valid) g = 0;
-    const uint64_t sub_leaves = 1ull << sub_bits;
-    const uint64_t per = sub_leaves >> layer;
-    const uint64_t t = g / per, k = g % per;
-    uint64_t* tree = digests + t * 2 * (sub_leaves - 1) * 4;
-    const uint64_t child = digest_slot(layer - 1, 2 * k);
+    const MerkleNode nd = merkle_node(digests, cap, sub_bits, layer, g);
     // column j packs sponge elements 3j .. 3j+2 of (left digest | right digest | 0^4)
     uint64_t e[3];
 #pragma unroll
     for (int q = 0; q < 3; q++) {
         const int idx = 3 * j + q;
-        e[q] = idx < 8 ? tree[child * 4 + idx] : 0;
+        e[q] = idx < 8 ? nd.tree[nd.child() * 4 + idx] : 0;
     }
     fr8 s = fr_encode3(e[0], e[1], e[2]);            // column 4 (and the padding of column 2, 3) encodes zeros
     const fr8 m = fr_const(BN254F_MDS[5 * i + j]);
@@ -154,70 +91,22 @@ __global__ void __launch_bounds__(64) bn254_merkle_level_lanes_kernel(uint64_t* 
     fr_decode3(s, d);
     // digest = sponge elements 0..3 = digits 0..2 of column 0 and digit 0 of column 1 (row 0 lanes write)
     if (valid && act && i == 0) {
-        uint64_t* dst = (layer == sub_bits) ? cap + t * 4 : tree + digest_slot(layer, k) * 4;
+        uint64_t* dst = nd.dst();
         if (j == 0) { dst[0] = d[0]; dst[1] = d[1]; dst[2] = d[2]; }
         if (j == 1) dst[3] = d[0];
     }
 }
 
-__global__ void __launch_bounds__(256) bn254_two_to_one_kernel(const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint64_t s[12] = {gl_canon(l[4 * i]), gl_canon(l[4 * i + 1]), gl_canon(l[4 * i + 2]), gl_canon(l[4 * i + 3]),
-                      gl_canon(r[4 * i]), gl_canon(r[4 * i + 1]), gl_canon(r[4 * i + 2]), gl_canon(r[4 * i + 3]), 0, 0, 0, 0};
-    bn254_permute(s);
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[4 * i + k] = s[k];
-}
+__global__ void __launch_bounds__(256) bn254_two_to_one_kernel(const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out) { two_to_one_body<Bn254Hasher>(l, r, n, out); }
 
-int32_t bn254_permute_dev(Ctx* ctx, uint64_t* states, uint64_t count) {
-    if (count == 0) return GL355_OK;
-    ProfScope ps(ctx, "bn254_permute_kernel", count * 192);
-    hipLaunchKernelGGL(bn254_permute_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, states, count);
-    GL355_HIP(ctx, hipGetLastError());
-    return GL355_OK;
-}
-static int32_t launch_leaves(Ctx* ctx, const LeafArgs& a) {
-    if (a.n_leaves == 0) return GL355_OK;
-    ProfScope ps(ctx, "bn254_hash_leaves_kernel", a.n_leaves * ((uint64_t)a.leaf_len * 8 + 32));
-    hipLaunchKernelGGL(bn254_hash_leaves_kernel, dim3((uint32_t)((a.n_leaves + 255) / 256)), dim3(256), 0, ctx->stream, a);
-    GL355_HIP(ctx, hipGetLastError());
-    return GL355_OK;
-}
-int32_t bn254_hash_leaves_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major, uint64_t col_stride,
-                              uint64_t* digests, bool always_hash) {
-    LeafArgs a;
-    memset(&a, 0, sizeof a);
-    a.leaves = leaves; a.n_leaves = n_leaves; a.leaf_len = leaf_len; a.col_major = col_major;
-    a.stride = col_major ? col_stride : leaf_len;
-    a.out = digests; a.linear = 1; a.always_hash = always_hash;
-    return launch_leaves(ctx, a);
-}
-int32_t bn254_two_to_one_dev(Ctx* ctx, const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out) {
-    if (n == 0) return GL355_OK;
-    hipLaunchKernelGGL(bn254_two_to_one_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, l, r, n, out);
-    GL355_HIP(ctx, hipGetLastError());
-    return GL355_OK;
-}
-int32_t bn254_merkle_build_dev(Ctx* ctx, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major, uint64_t col_stride,
-                               uint32_t cap_height, uint64_t* digests, uint64_t* cap) {
-    const uint32_t log_n = log2_u64(n_leaves);
-    if ((1ull << log_n) != n_leaves) return ctx->fail(GL355_E_INVALID_ARG, "merkle: n_leaves must be a power of two");
-    if (cap_height > log_n) return ctx->fail(GL355_E_INVALID_ARG, "merkle: cap_height > log2(n_leaves)");
-    LeafArgs a;
-    memset(&a, 0, sizeof a);
-    a.leaves = leaves; a.n_leaves = n_leaves; a.leaf_len = leaf_len; a.col_major = col_major;
-    a.stride = col_major ? col_stride : leaf_len;
-    return bn254_merkle_build_args(ctx, a, log_n - cap_height, digests, cap);
-}
-int32_t bn254_merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap) {
-    const uint64_t n_leaves = a.n_leaves;
-    if (n_leaves == 0 || (n_leaves & ((1ull << sub_bits) - 1))) return ctx->fail(GL355_E_INVALID_ARG, "merkle: leaves do not fill whole cap subtrees");
-    a.out = digests; a.cap = cap; a.sub_bits = sub_bits; a.linear = 0;
-    GL355_TRY(launch_leaves(ctx, a));
+__global__ void __launch_bounds__(256) bn254_pow_grind_units_kernel(PowArgs a) { pow_grind_units_body<Bn254Hasher>(a); }
+
+// every level one launch: 32 lanes per node up to lanes_max nodes, one lane per node above
+static int32_t bn254_above_leaves(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits, uint64_t* digests, uint64_t* cap) {
+    const uint64_t lanes_max = (1ull << BN254_LANES_MAX_LOG) - 1;
     for (uint32_t layer = 1; layer <= sub_bits; layer++) {
         const uint64_t n_nodes = n_leaves >> layer;
-        const bool lanes = n_nodes < (1ull << BN254_LANES_MAX_LOG);
+        const bool lanes = n_nodes <= lanes_max;
         ProfScope ps(ctx, lanes ? "bn254_merkle_level_lanes_kernel" : "bn254_merkle_level_kernel", n_nodes * 96);
         if (lanes)
             hipLaunchKernelGGL(bn254_merkle_level_lanes_kernel, dim3((uint32_t)((n_nodes + 1) / 2)), dim3(64), 0, ctx->stream, digests, cap,
@@ -230,58 +119,11 @@ int32_t bn254_merkle_build_args(Ctx* ctx, LeafArgs a, uint32_t sub_bits, uint64_
     return GL355_OK;
 }
 
-// proof of work with this hasher: same search as pow_grind_dev (smallest passing candidate of the first launch that holds one)
-__global__ void __launch_bounds__(256) bn254_pow_grind_kernel(const uint64_t* state, uint32_t pos, uint32_t bits, uint64_t start,
-                                                             unsigned long long* best) {
-    const uint64_t w = start + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    uint64_t s[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) s[k] = state[k];
-#pragma unroll
-    for (int k = 0; k < 12; k++) if ((uint32_t)k == pos) s[k] = w;
-    bn254_permute(s);
-    if (bits == 0 || (s[7] >> (64 - bits)) == 0) atomicMin(best, (unsigned long long)w);
-}
-int32_t bn254_pow_grind_dev(Ctx* ctx, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start, uint64_t* witness_host) {
-    Scratch sc(ctx);
-    GL355_TRY(sc.get(13 * sizeof(uint64_t)));
-    uint64_t* d_state = sc.as<uint64_t>();
-    unsigned long long* d_best = reinterpret_cast<unsigned long long*>(d_state + 12);
-    uint64_t host[13];
-    for (int i = 0; i < 12; i++) host[i] = gl_canon(state[i]);
-    host[12] = ~0ull;
-    GL355_HIP(ctx, hipMemcpyAsync(d_state, host, sizeof host, hipMemcpyHostToDevice, ctx->stream));
-    uint64_t per_launch = 1ull << std::min<uint32_t>(std::max<uint32_t>(bits + 1, 12), 20);
-    uint64_t base = start;
-    for (;;) {
-        ProfScope ps(ctx, "bn254_pow_grind", 0);
-        hipLaunchKernelGGL(bn254_pow_grind_kernel, dim3((uint32_t)(per_launch / 256)), dim3(256), 0, ctx->stream, d_state, pos, bits, base,
-                           d_best);
-        GL355_HIP(ctx, hipGetLastError());
-        unsigned long long best;
-        GL355_HIP(ctx, ctx->d2h(&best, d_best, sizeof best));
-        GL355_HIP(ctx, ctx->wait());
-        if (best != ~0ull) { *witness_host = best; return GL355_OK; }
-        base += per_launch;
-        if (per_launch < (1ull << 20)) per_launch <<= 1;
-        if (base - start > (1ull << 40)) return ctx->fail(GL355_E_UNSUPPORTED, "pow: no witness found in 2^40 candidates");
-    }
-}
-
-int32_t merkle_build_any(Ctx* ctx, int32_t hasher, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, bool col_major,
-                         uint64_t col_stride, uint32_t cap_height, uint64_t* digests, uint64_t* cap) {
-    if (hasher == GL355_HASH_BN254_POSEIDON)
-        return bn254_merkle_build_dev(ctx, leaves, n_leaves, leaf_len, col_major, col_stride, cap_height, digests, cap);
-    return merkle_build_dev(ctx, leaves, n_leaves, leaf_len, col_major, col_stride, cap_height, digests, cap);
-}
-int32_t merkle_build_args_any(Ctx* ctx, int32_t hasher, const LeafArgs& a, uint32_t sub_bits, uint64_t* digests, uint64_t* cap) {
-    if (hasher == GL355_HASH_BN254_POSEIDON) return bn254_merkle_build_args(ctx, a, sub_bits, digests, cap);
-    return merkle_build_args(ctx, a, sub_bits, digests, cap);
-}
-int32_t pow_grind_any(Ctx* ctx, int32_t hasher, const uint64_t state[12], uint32_t pos, uint32_t bits, uint64_t start,
-                      uint64_t* witness_host) {
-    if (hasher == GL355_HASH_BN254_POSEIDON) return bn254_pow_grind_dev(ctx, state, pos, bits, start, witness_host);
-    return pow_grind_dev(ctx, state, pos, bits, start, witness_host);
+const HasherLaunch& bn254_hasher_launch() {
+    static const HasherLaunch h = {
+        bn254_permute_kernel, bn254_hash_leaves_kernel, bn254_two_to_one_kernel, bn254_pow_grind_units_kernel,
+        "bn254_permute_kernel", "bn254_hash_leaves_kernel", "bn254_two_to_one_kernel", "bn254_pow_grind_units_kernel", 20, bn254_above_leaves};
+    return h;
 }
 
 // ---- test hook: the hasher's fr_enter / fr_leave on raw 9-word records (gl355_bn254_arith_batch, GL355_BN_HASH_FR_*; device buffers)

@@ -237,7 +237,7 @@ static int32_t commit_units(Ctx* ctx, int32_t hasher, BOracle& o, bool is_coeffs
     memset(&a, 0, sizeof a);
     a.leaves = o.lde; a.n_leaves = (uint64_t)o.B * N; a.leaf_len = o.leaf_len; a.col_major = 1; a.stride = N;
     a.unit_log = lde_bits; a.n_main = o.batch; a.unit_stride = (uint64_t)o.batch * N; a.salt = o.salt; a.salt_unit_stride = (uint64_t)GL355_SALT_SIZE * N;
-    return merkle_build_args_any(ctx, hasher, a, lde_bits - o.cap_height, o.digests, o.cap);
+    return merkle_build_args(ctx, hasher, a, lde_bits - o.cap_height, o.digests, o.cap);
 }
 
 // caps [B][n_cap][4] on the device -> dst[u] on the host, each absorbed by its unit's transcript

@@ -1,5 +1,6 @@
 """GPU: the second hash back-end (GL355_HASH_BN254_POSEIDON = the reference's Bn254PoseidonHash) through the C ABI, bit-exact
 against the CPU restatement (oracle/bn254_oracle.c) and the committed known-answer vectors."""
+import ctypes as C
 import importlib
 import json
 import os
@@ -52,7 +53,8 @@ def test_hash_no_pad_and_leaves(gl, ctx, orc, length):
         assert np.array_equal(leaves, want)
 
 
-@pytest.mark.parametrize("n,leaf_len,cap_h", [(1 << 10, 4, 4), (1 << 9, 20, 0), (1 << 8, 135, 4), (16, 7, 4), (2, 3, 0)])
+# (1 << 14, 4, 0): layer 1 has 2^13 nodes, one lane each (bn254_merkle_level_kernel); from layer 2 (2^12 nodes) on the levels run lane-parallel
+@pytest.mark.parametrize("n,leaf_len,cap_h", [(1 << 10, 4, 4), (1 << 9, 20, 0), (1 << 8, 135, 4), (16, 7, 4), (2, 3, 0), (1 << 14, 4, 0)])
 def test_merkle_tree_equals_oracle(gl, ctx, orc, n, leaf_len, cap_h):
     b = Bn254Oracle(orc)
     rng = np.random.default_rng(n + leaf_len)
@@ -73,6 +75,75 @@ def test_two_to_one_batch_and_errors(gl, ctx, orc):
     assert np.array_equal(h.two_to_one(l, r), np.stack([b.two_to_one(a, c) for a, c in zip(l, r)]))
     st = np.zeros((1, 12), dtype=np.uint64)
     assert ctx.lib.gl355_permute_h(ctx.h, 7, st.ctypes.data, 1) == -1       # unknown hasher
+
+
+def grind_h(ctx, hasher, state, pos, bits, start=0):
+    """gl355_pow_grind_h -> (return code, witness)"""
+    s = np.ascontiguousarray(state, dtype=np.uint64)
+    w = C.c_uint64()
+    rc = ctx.lib.gl355_pow_grind_h(ctx.h, hasher, s.ctypes.data, pos, bits, start, C.byref(w))
+    return rc, w.value
+
+
+def brute_force_grind(b, state, pos, bits, start=0):
+    """the smallest w >= start whose BN254-Poseidon response (word 7 of the permuted state with w at `pos`) has `bits` leading zero bits"""
+    st = np.array(state, dtype=np.uint64)
+    w = start
+    while True:
+        st[pos] = w
+        if bits == 0 or int(b.permute(st)[7]) >> (64 - bits) == 0:
+            return w
+        w += 1
+
+
+def test_pow_grind_equals_brute_force(gl, ctx, orc):
+    b = Bn254Oracle(orc)
+    rng = np.random.default_rng(0x256b)
+    for bits, pos in ((0, 0), (1, 7), (6, 2)):
+        st = rand_field(rng, 12)
+        assert grind_h(ctx, gl.HASH_BN254_POSEIDON, st, pos, bits) == (0, brute_force_grind(b, st, pos, bits)), (bits, pos)
+    later = brute_force_grind(b, st, 2, 6, 1000)
+    assert later >= 1000 and later != brute_force_grind(b, st, 2, 6)
+    assert grind_h(ctx, gl.HASH_BN254_POSEIDON, st, 2, 6, 1000) == (0, later)
+
+
+def test_pow_grind_beyond_the_first_window(gl, ctx, orc):
+    """11 bits: the first launch tries 2^12 candidates and finds none; the witness comes from the second, larger window"""
+    b = Bn254Oracle(orc)
+    st = rand_field(np.random.default_rng(0x256c), 12)
+    assert brute_force_grind(b, st, 2, 11) == 7366 > 4096
+    assert grind_h(ctx, gl.HASH_BN254_POSEIDON, st, 2, 11) == (0, 7366)
+    assert orc.pow_grind(st, 2, 11) == 6584            # the same state under the Goldilocks hasher: also past its first window
+    assert ctx.pow_grind(st, 2, 11) == 6584
+    assert grind_h(ctx, gl.HASH_POSEIDON, st, 2, 11) == (0, 6584)
+
+
+def test_pow_grind_refusals(gl, ctx):
+    st = np.zeros(12, np.uint64)
+    for hasher in (gl.HASH_POSEIDON, gl.HASH_BN254_POSEIDON):
+        assert grind_h(ctx, hasher, st, 8, 4)[0] == -1         # GL355_E_INVALID_ARG: the witness goes into the rate part
+        assert grind_h(ctx, hasher, st, 2, 41)[0] == -5        # GL355_E_UNSUPPORTED: more than 40 bits
+    assert grind_h(ctx, gl.HASH_BN254_POSEIDON, st, 2, 0) == (0, 0)     # the context stays usable
+
+
+def test_two_units_in_lock_step(gl, ctx, orc):
+    """the BN254 trees and grinder with a unit dimension: two witnesses of one small circuit proven by one prove_sparse_units call, each
+    proof byte for byte the CPU prover's of that unit alone.  Degree 2^6: the smallest at which the circuit has a FRI layer tree."""
+    import fri_arity_cases as fc
+    from oracle_lib import CpuProver
+    plonk = importlib.import_module("stark-verifier_amd.plonk")
+    cfg = plonk.CircuitConfig(hasher=gl.HASH_BN254_POSEIDON, cap_height=0, zero_knowledge=False, proof_of_work_bits=6)
+    builders = [fc.small_circuit(cfg, 0x2560 + u) for u in range(2)]
+    data = builders[0][0].cb.build(ctx, np.random.default_rng(0x2569), min_degree_bits=6)
+    assert data.common()["hasher"] == 1 and len(data.fri_arity_bits) == 1
+    wit = [b.sparse_witness() for b, _ in builders]
+    assert np.array_equal(wit[0][0], wit[1][0]) and not np.array_equal(wit[0][1], wit[1][1])
+    rows, pis, seeds = np.stack([w[1] for w in wit]), np.stack([pi for _, pi in builders]), [0x256d, 0x256e]
+    flat = plonk.prove_sparse_units(ctx, data, wit[0][0], rows, pis, seeds)
+    cpu = CpuProver.from_circuit_data(orc, data)
+    for u in range(2):
+        assert np.array_equal(flat[u], cpu.prove_sparse(wit[0][0], rows[u], pis[u], seeds[u])), u
+    assert not np.array_equal(flat[0], flat[1])
 
 
 def test_wrap_proof_with_bn254_hasher(gl, ctx, orc):
