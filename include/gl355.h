@@ -147,7 +147,10 @@ int32_t gl355_field_batch(gl355_ctx* ctx, int32_t op, const uint64_t* a, const u
 
 /* ---- a2: fft_with_options / ifft_with_options (plonky2_field::fft) --------------------------
  * In place, natural order in and out.  batch columns, column c at data + c*stride, n = 2^log_n.
- * forward: out[j] = sum_i in[i] * omega_n^(i j), omega_n = 7^((p-1)/n)  (fri_chip.rs:162-163). */
+ * forward: out[j] = sum_i in[i] * omega_n^(i j), omega_n = 7^((p-1)/n)  (fri_chip.rs:162-163).
+ * Inputs may be any u64 (a word stands for its residue mod p); every output word is canonical (< p), at
+ * every size including n = 1 (log_n = 0), where the transform is the identity on residues.
+ * stride >= n; the stride - n words between two columns keep their values. */
 int32_t gl355_ntt(gl355_ctx* ctx, uint64_t* data, uint32_t log_n, uint32_t batch, uint64_t stride,
                   int32_t inverse);
 /* coset_fft / coset_ifft: forward evaluates on shift*<omega>; inverse interpolates from it. */

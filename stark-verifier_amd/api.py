@@ -115,27 +115,33 @@ class Context:
         return out
 
     # ---- a2 / a3: plonky2_field::fft ---------------------------------------------------------
-    def fft(self, values, inverse=False, shift=None):
-        """fft_with_options / ifft_with_options (+ coset variants) on columns: values[batch][n]."""
+    def fft(self, values, inverse=False, shift=None, stride=None, log_n=None):
+        """fft_with_options / ifft_with_options (+ coset variants) on columns: values[batch][n].
+        With stride: values[batch][stride], the first 2^log_n words of each row are transformed, the rest of the row is kept."""
         v = _u64(values).copy()
         v2 = v.reshape(1, -1) if v.ndim == 1 else v
         batch, n = v2.shape
-        log_n = int(n).bit_length() - 1
-        assert 1 << log_n == n
-        if shift is None:
-            self.check(self.lib.gl355_ntt(self.h, _ptr(v2), log_n, batch, n, int(inverse)))
+        if stride is None:
+            assert log_n is None or 1 << log_n == n
+            log_n = int(n).bit_length() - 1
+            assert 1 << log_n == n
+            stride = n
         else:
-            self.check(self.lib.gl355_coset_ntt(self.h, _ptr(v2), log_n, batch, n, shift, int(inverse)))
+            assert log_n is not None and v2.shape[1] == stride, "strided call: values[batch][stride] and an explicit log_n"
+        if shift is None:
+            self.check(self.lib.gl355_ntt(self.h, _ptr(v2), log_n, batch, stride, int(inverse)))
+        else:
+            self.check(self.lib.gl355_coset_ntt(self.h, _ptr(v2), log_n, batch, stride, shift, int(inverse)))
         return v
 
-    def ifft(self, values):
-        return self.fft(values, inverse=True)
+    def ifft(self, values, stride=None, log_n=None):
+        return self.fft(values, inverse=True, stride=stride, log_n=log_n)
 
-    def coset_fft(self, coeffs, shift=COSET_SHIFT):
-        return self.fft(coeffs, inverse=False, shift=shift)
+    def coset_fft(self, coeffs, shift=COSET_SHIFT, stride=None, log_n=None):
+        return self.fft(coeffs, inverse=False, shift=shift, stride=stride, log_n=log_n)
 
-    def coset_ifft(self, values, shift=COSET_SHIFT):
-        return self.fft(values, inverse=True, shift=shift)
+    def coset_ifft(self, values, shift=COSET_SHIFT, stride=None, log_n=None):
+        return self.fft(values, inverse=True, shift=shift, stride=stride, log_n=log_n)
 
     def lde(self, coeffs, rate_bits, shift=COSET_SHIFT, bitrev=False):
         """PolynomialCoeffs::lde(rate_bits).coset_fft(shift): [batch][n] -> [batch][n << rate_bits]."""

@@ -151,6 +151,13 @@ __global__ void build_nat_step_table_kernel(const uint64_t* lo, const uint64_t* 
     out[g] = gl_canon(gl_mul(lo[e & 4095], hi[e >> 12]));
 }
 
+// n = 1: the transform of a single point is that point, in every direction and on every coset (g^0 = 1, 1/n = 1).  What is left of the
+// contract is the canonical output: one word per column, at the column stride, nothing between the columns touched.
+__global__ void canon_points_kernel(const uint64_t* in, uint64_t* out, uint64_t in_col_stride, uint64_t out_col_stride, uint32_t batch) {
+    const uint64_t col = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (col < batch) out[col * out_col_stride] = gl_canon(in[col * in_col_stride]);
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -250,7 +257,11 @@ static void split_two_pass(uint32_t log_n, bool natural_in, uint32_t* log_n1, ui
 
 int32_t ntt_run(Ctx* ctx, const NttPlan& p) {
     if (p.log_n == 0) {
-        if (p.in != p.out) GL355_HIP(ctx, hipMemcpyAsync(p.out, p.in, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+        if (p.batch == 0) return GL355_OK;
+        ProfScope ps(ctx, "ntt_single_points", (uint64_t)p.batch * 16);
+        hipLaunchKernelGGL(canon_points_kernel, dim3((p.batch + 255) / 256), dim3(256), 0, ctx->stream, p.in, p.out, p.in_col_stride,
+                           p.out_col_stride, p.batch);
+        GL355_HIP(ctx, hipGetLastError());
         return GL355_OK;
     }
     if (p.log_n > 24) return ctx->fail(GL355_E_UNSUPPORTED, "ntt: log_n > 24 unsupported");

@@ -97,6 +97,30 @@ def test_ntt_above_2p20(ctx, orc, log_n):
         eq(ctx.coset_ifft(x[:1]), orc.ntt(x[:1], inverse=True, shift=7))
 
 
+@pytest.mark.parametrize("log_n", [21, 22])
+def test_ntt_above_2p20_strided(ctx, orc, log_n):
+    """stride = n + 8 keeps the forward transform off the big-tile / three-pass forms (they need contiguous output columns): it runs
+    the general column pass with two-level step tables, then rows (4096-point at 2^21, 16384-point over a 2^8 column pass at 2^22) and
+    the in-place bit reversal; the inverse runs bit reversal, rows, columns at both strides.  The 8 words behind each column keep
+    their values.  At 2^22 also the one-column coset pair at stride n."""
+    n, stride = 1 << log_n, (1 << log_n) + 8
+    rng = np.random.default_rng(0x357 + log_n)
+    x = rand_field(rng, (2, n))
+    idx = np.arange(2 * stride, dtype=np.uint64).reshape(2, stride)
+    buf = np.where(idx % np.uint64(3) != 0, np.uint64(0xFFFFFFFFA5A5A5A5), np.uint64(0xA5A5A5A5A5A5A5A5)) ^ idx
+    pad = buf[:, n:].copy()                                 # distinct words, two of three non-canonical
+    buf[:, :n] = x
+    y = ctx.fft(buf, stride=stride, log_n=log_n)
+    eq(y[:, :n], orc.ntt(x))
+    eq(y[:, n:], pad)
+    z = ctx.ifft(y, stride=stride, log_n=log_n)
+    eq(z[:, :n], x)
+    eq(z[:, n:], pad)
+    if log_n == 22:
+        eq(ctx.coset_fft(x[:1]), orc.ntt(x[:1], shift=7))
+        eq(ctx.coset_ifft(x[:1]), orc.ntt(x[:1], inverse=True, shift=7))
+
+
 @pytest.mark.parametrize("log_n", [18, 20])
 def test_lde_to_2p21_2p23(ctx, orc, log_n):
     rng = np.random.default_rng(0x455 + log_n)
