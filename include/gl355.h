@@ -483,7 +483,11 @@ int32_t gl355_semaphore_witness(const uint64_t private_key[4], const uint64_t to
  *   LO32 / HI32 a <- halves of [b] | EXT_INV (a, b) <- ([c], [d])^-1
  *   COSET_INTERP row a: b subgroup bits, c degree; shift, values, point set  (gl355_coset_interpolation_witness; a zero shift fails the entry)
  * rows is zeroed first.  Returns GL355_E_WITNESS (and the entry index in *failed_op) when an ASSERT_EQ or a
- * range condition fails, i.e. the inputs do not satisfy the circuit. */
+ * range condition fails, i.e. the inputs do not satisfy the circuit.  A malformed tape is refused, not run: every
+ * entry is checked before it executes (tape_entry_fits, csrc/witness_tape.h), and the first one with an unknown
+ * opcode or with operands that do not fit inputs[n_inputs] and rows[n_words] -- an offset or an input index out of
+ * range, a row operand that is no multiple of num_wires, a count or parameter outside its gate's layout -- gives
+ * GL355_E_INVALID_ARG with *failed_op set to it.  Nothing outside `rows` is read or written. */
 enum { GL355_TAPE_CONST = 0, GL355_TAPE_INPUT = 1, GL355_TAPE_COPY = 2, GL355_TAPE_ASSERT_EQ = 3, GL355_TAPE_ARITH = 4,
        GL355_TAPE_ARITH_EXT = 5, GL355_TAPE_POSEIDON = 6, GL355_TAPE_MDS_EXT = 7, GL355_TAPE_BASE_SUM = 8,
        GL355_TAPE_RANDOM_ACCESS = 9, GL355_TAPE_REDUCING = 10, GL355_TAPE_LO32 = 11, GL355_TAPE_HI32 = 12,

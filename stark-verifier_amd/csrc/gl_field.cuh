@@ -318,6 +318,11 @@ GL_HD uint64_t gl_mul_small(uint64_t a, uint32_t c) {
     return r;
 }
 
+// Poseidon's MDS matrix over this field (width 12), the one statement of it in csrc/: new[r] = sum_i CIRC[i] old[(i + r) % 12] + DIAG0 old[0] for
+// r = 0 (poseidon.rs:450-486; the other diagonal entries are zero).  Device code that indexes it at run time reads it as a __constant__.
+constexpr uint32_t GL_PSD_MDS_CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
+constexpr uint32_t GL_PSD_MDS_DIAG0 = 8;
+
 // a * 2^S mod p for a compile-time 0 <= S < 96: powers of two are roots of unity in Goldilocks
 // (2^96 = -1), so the radix-16 butterflies' internal twiddles cost shifts instead of a 64x64 multiply.
 template <int S>

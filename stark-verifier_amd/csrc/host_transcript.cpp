@@ -21,13 +21,12 @@ static inline uint64_t h_sbox(uint64_t x) {
 // MDS layer on the 32-bit halves: 12 x 6-bit constants keep both partial sums below 2^42, so the inner loops are plain
 // 64-bit multiply-adds over a doubled array (no modulo indexing, no 128-bit arithmetic) and vectorise
 static void h_mds(uint64_t s[12]) {
-    static const uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
     uint32_t lo[24], hi[24];
     for (int i = 0; i < 12; i++) { lo[i] = lo[i + 12] = (uint32_t)s[i]; hi[i] = hi[i + 12] = (uint32_t)(s[i] >> 32); }
     for (int r = 0; r < 12; r++) {
         uint64_t al = 0, ah = 0;
-        for (int i = 0; i < 12; i++) { al += (uint64_t)lo[i + r] * CIRC[i]; ah += (uint64_t)hi[i + r] * CIRC[i]; }
-        if (r == 0) { al += (uint64_t)lo[0] * 8; ah += (uint64_t)hi[0] * 8; }
+        for (int i = 0; i < 12; i++) { al += (uint64_t)lo[i + r] * GL_PSD_MDS_CIRC[i]; ah += (uint64_t)hi[i + r] * GL_PSD_MDS_CIRC[i]; }
+        if (r == 0) { al += (uint64_t)lo[0] * GL_PSD_MDS_DIAG0; ah += (uint64_t)hi[0] * GL_PSD_MDS_DIAG0; }
         // value = al + ah * 2^32 (< 2^75): ah * 2^32 = (ah >> 32) * 2^64 + (ah << 32)
         const uint64_t mid = ah << 32;
         const unsigned __int128 w0 = (unsigned __int128)al + mid;

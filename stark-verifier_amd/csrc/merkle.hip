@@ -51,6 +51,7 @@ __global__ void __launch_bounds__(256) merkle_level_kernel(uint64_t* digests, ui
 // 30 rounds use the naive form (constants + S-box + full MDS; the S-box result is kept on lane 0
 // only in the 22 partial rounds): with one element per lane the dense MDS is as cheap as the sparse one.
 // ------------------------------------------------------------------------------------------------
+// gl_field.cuh's GL_PSD_MDS_CIRC, in a symbol of this unit's own: reading the shared table lays the unit's code out differently
 __device__ __constant__ const uint32_t PSD_CIRC_DEV[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
 
 // FORM (round 6): the 22 PARTIAL rounds of the 16-lane permutation.

@@ -348,7 +348,6 @@ GL_DEV void gate_mul_ext(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAc
 // that every register index is a compile-time one.  A row's two output wires are read when the row is pushed (a group of them does not fit next to the inputs at three waves).
 template <class GateAcc>
 GL_DEV void gate_poseidon_mds(const QuotArgs& a, const WireSrc& w, uint64_t t, GateAcc& g) {
-    constexpr uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
     uint64_t in[24];
     wire_group<24>(w, 0, 23, in);
 #pragma unroll 1
@@ -359,7 +358,7 @@ GL_DEV void gate_poseidon_mds(const QuotArgs& a, const WireSrc& w, uint64_t t, G
 #pragma unroll
             for (uint32_t i = 0; i < 12; i++) {
                 const gl2 x = gl2_make(in[2 * ((i + r) % 12)], in[2 * ((i + r) % 12) + 1]);
-                acc = gl2_add(acc, gl2_make(gl_mul_small(x.c0, CIRC[i]), gl_mul_small(x.c1, CIRC[i])));
+                acc = gl2_add(acc, gl2_make(gl_mul_small(x.c0, GL_PSD_MDS_CIRC[i]), gl_mul_small(x.c1, GL_PSD_MDS_CIRC[i])));
             }
             if (r0 + r == 0) {
                 const gl2 x = gl2_make(in[0], in[1]);

@@ -23,7 +23,6 @@ using namespace gl355;
 namespace {
 
 thread_local std::string g_verify_error;
-const uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
 
 typedef gl2 E;
 inline E e_base(uint64_t v) { return gl2_make(gl_canon(v), 0); }
@@ -46,8 +45,8 @@ void e_mds(E s[12], const uint64_t* rc) {
     E o[12];
     for (int r = 0; r < 12; r++) {
         E acc = e_base(rc[r]);
-        for (int i = 0; i < 12; i++) acc = gl2_add(acc, e_small(s[(i + r) % 12], CIRC[i]));
-        if (r == 0) acc = gl2_add(acc, e_small(s[0], 8));
+        for (int i = 0; i < 12; i++) acc = gl2_add(acc, e_small(s[(i + r) % 12], GL_PSD_MDS_CIRC[i]));
+        if (r == 0) acc = gl2_add(acc, e_small(s[0], GL_PSD_MDS_DIAG0));
         o[r] = acc;
     }
     for (int r = 0; r < 12; r++) s[r] = o[r];
@@ -141,8 +140,8 @@ bool eval_gate(const gl355_gate& gt, const E* consts, const E* w, const uint64_t
         if (num_wires < 48) return false;
         for (uint32_t r = 0; r < 12; r++) {
             Alg acc{gl2_make(0, 0), gl2_make(0, 0)};
-            for (uint32_t i = 0; i < 12; i++) acc = alg_add(acc, alg_scal(e_base(CIRC[i]), alg(2 * ((i + r) % 12))));
-            if (r == 0) acc = alg_add(acc, alg_scal(e_base(8), alg(0)));
+            for (uint32_t i = 0; i < 12; i++) acc = alg_add(acc, alg_scal(e_base(GL_PSD_MDS_CIRC[i]), alg(2 * ((i + r) % 12))));
+            if (r == 0) acc = alg_add(acc, alg_scal(e_base(GL_PSD_MDS_DIAG0), alg(0)));
             push_alg(alg_sub(alg(2 * (12 + r)), acc));
         }
         return true;

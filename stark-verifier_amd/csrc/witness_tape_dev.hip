@@ -11,15 +11,15 @@
 // bound work on a handful of waves (8 units x 29 waves): tens of milliseconds per batch, but it runs on the context's side stream
 // under the proving of the previous batch and takes ~0.1 % of the chip's issue slots.
 //
-// Offsets are validated once when the artifact is loaded (tape_validate, witness_tape.cpp), so the interpreter does not bounds-
-// check; data-dependent failures (ASSERT_EQ, range conditions = an invalid inner proof) are reported as the smallest failing
-// entry per unit, exactly like the host replay.
+// What an entry does is witness_tape.h's tape_entry_exec, the host replay's own code.  Every entry passed tape_entry_fits when the
+// artifact was loaded (tape_validate, witness_tape.cpp), so the interpreter does not bounds-check; data-dependent failures
+// (ASSERT_EQ, range conditions = an invalid inner proof) are reported as the smallest failing entry per unit, exactly like the
+// host replay.
 #include "gl355_internal.h"
 #include "poseidon.cuh"
+#include "witness_tape.h"
 
 namespace gl355 {
-
-__device__ __constant__ const uint32_t TAPE_CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
 
 // stores of one lane -> loads of another lane of the same wave, through global memory.  The lanes share one CU and therefore
 // one vector L1 (write-through): WORKGROUP scope is enough -- the stores only have to complete (s_waitcnt).  An agent-scope fence
@@ -46,7 +46,7 @@ GL_DEV void tape_poseidon_row(uint64_t* row, int li, uint64_t* ring) {
     const bool active = li < 12;
     const int me = active ? li : 0;
     const uint64_t in = active ? row[li] : 0;
-    const uint64_t swap = row[24];
+    const uint64_t swap = row[TAPE_POSEIDON_SWAP];
     uint64_t s = in;
     if (li < 8) {
         const uint64_t partner = row[li ^ 4];
@@ -77,7 +77,7 @@ GL_DEV void tape_poseidon_row(uint64_t* row, int li, uint64_t* ring) {
 #pragma unroll
         for (int j = 0; j < 12; j++) {
             const uint64_t x = ring[me + j];
-            const uint32_t c = TAPE_CIRC[j] + ((me == 0 && j == 0) ? 8u : 0u);
+            const uint32_t c = GL_PSD_MDS_CIRC[j] + ((me == 0 && j == 0) ? GL_PSD_MDS_DIAG0 : 0u);
             al += (uint64_t)(uint32_t)x * c;
             ah += (uint64_t)(uint32_t)(x >> 32) * c;
         }
@@ -96,80 +96,17 @@ __global__ void __launch_bounds__(64) tape_replay_kernel(TapeDevArgs a, uint32_t
     uint64_t* W = a.rows + (uint64_t)u * a.n_words;
     const uint64_t* in = a.inputs + (uint64_t)u * a.n_inputs;
     for (uint64_t t = begin; t < end; t++) {
-        const uint64_t* e = a.tape + 5 * t;
-        const uint64_t op = e[0], x = e[1], b = e[2], c = e[3], d = e[4];
+        const uint64_t* p = a.tape + 5 * t;
+        const uint64_t e[5] = {p[0], p[1], p[2], p[3], p[4]};      // the whole entry at once: one load latency, not one per operand
         int fail = 0;
-        if (op == GL355_TAPE_POSEIDON) {
+        if (e[0] == GL355_TAPE_POSEIDON) {
+            uint64_t* row = W + e[1];
             TAPE_FENCE();
-            if (W[x + 24] > 1) fail = 1;
-            else tape_poseidon_row(W + x, lane & 15, ring);      // lanes 16..63 mirror lanes 0..15 of their group: same values, same stores
+            if (!tape_poseidon_swap_ok(row)) fail = 1;
+            else tape_poseidon_row(row, lane & 15, ring);      // lanes 16..63 mirror lanes 0..15 of their group: same values, same stores
             TAPE_FENCE();
         } else if (lane == 0) {
-            switch (op) {
-            case GL355_TAPE_CONST: W[x] = gl_canon(b); break;
-            case GL355_TAPE_INPUT: W[x] = gl_canon(in[b]); break;
-            case GL355_TAPE_COPY: W[x] = W[b]; break;
-            case GL355_TAPE_ASSERT_EQ: if (W[x] != W[b]) fail = 1; break;
-            case GL355_TAPE_ARITH:
-                W[x + 3] = gl_canon(gl_add(gl_mul(gl_mul(W[x], W[x + 1]), b), gl_mul(W[x + 2], c)));
-                break;
-            case GL355_TAPE_ARITH_EXT: {
-                const gl2 pr = gl2_mul(gl2_make(W[x], W[x + 1]), gl2_make(W[x + 2], W[x + 3]));
-                const gl2 r = gl2_canon(gl2_add(gl2_mul_base(pr, b), gl2_mul_base(gl2_make(W[x + 4], W[x + 5]), c)));
-                W[x + 6] = r.c0; W[x + 7] = r.c1;
-                break;
-            }
-            case GL355_TAPE_MDS_EXT:
-                for (int r = 0; r < 12; r++)
-                    for (int k = 0; k < 2; k++) {
-                        uint64_t acc = 0;
-                        for (int i = 0; i < 12; i++) acc = gl_add(acc, gl_mul_small(W[x + 2 * ((i + r) % 12) + k], TAPE_CIRC[i]));
-                        if (r == 0) acc = gl_add(acc, gl_mul_small(W[x + k], 8));
-                        W[x + 2 * (12 + r) + k] = gl_canon(acc);
-                    }
-                break;
-            case GL355_TAPE_BASE_SUM: {
-                const uint64_t v = W[x];
-                if (v >> b) { fail = 1; break; }
-                for (uint64_t i = 0; i < b; i++) W[x + 1 + i] = (v >> i) & 1;
-                break;
-            }
-            case GL355_TAPE_RANDOM_ACCESS: {
-                const uint64_t idx = W[x + 18 * b];
-                if (idx >= 16) { fail = 1; break; }
-                W[x + 18 * b + 1] = W[x + 18 * b + 2 + idx];
-                for (int k = 0; k < 4; k++) W[x + 74 + 4 * b + k] = (idx >> k) & 1;
-                break;
-            }
-            case GL355_TAPE_REDUCING: {
-                const uint64_t n = b, ext = c;
-                const uint64_t start_accs = 6 + (ext ? 2 * n : n);
-                const gl2 alpha = gl2_make(W[x + 2], W[x + 3]);
-                gl2 acc = gl2_make(W[x + 4], W[x + 5]);
-                for (uint64_t i = 0; i < n; i++) {
-                    const gl2 cf = ext ? gl2_make(W[x + 6 + 2 * i], W[x + 7 + 2 * i]) : gl2_make(W[x + 6 + i], 0);
-                    acc = gl2_canon(gl2_add(gl2_mul(acc, alpha), cf));
-                    const uint64_t o = i == n - 1 ? 0 : start_accs + 2 * i;
-                    W[x + o] = acc.c0; W[x + o + 1] = acc.c1;
-                }
-                break;
-            }
-            case GL355_TAPE_LO32: W[x] = W[b] & 0xFFFFFFFFull; break;
-            case GL355_TAPE_HI32: W[x] = W[b] >> 32; break;
-            case GL355_TAPE_EXT_INV: {
-                if (W[c] == 0 && W[d] == 0) { fail = 1; break; }
-                const gl2 r = gl2_canon(gl2_inv(gl2_make(W[c], W[d])));
-                W[x] = r.c0; W[b] = r.c1;
-                break;
-            }
-            case GL355_TAPE_COSET_INTERP: {      // shape validated at load; the inverse of the shift as in EXT_INV: zero fails the entry
-                CosetInterpShape s;
-                coset_interp_shape((uint32_t)(b | c << 8), s);
-                if (coset_interp_fill(s, W + x)) fail = 1;
-                break;
-            }
-            default: fail = 1; break;
-            }
+            fail = tape_entry_exec(e, in, W);
         }
         fail = __shfl(fail, 0);      // lane 0 decides (a POSEIDON failure is seen by every lane alike)
         if (fail) {

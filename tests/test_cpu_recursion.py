@@ -74,6 +74,13 @@ def test_witness_tape_replay_and_malformed_tapes():
         broken[e, f] = np.uint64(rng.integers(0, 1 << 63)) if trial % 2 else np.uint64(vals.size + int(rng.integers(0, 200)))
         rc, _, _ = replay(broken, inputs, idx.size)
         assert rc in (0, -1, -6)
+    # a REDUCING count whose wire sums 4 b + 4 or 3 b + 4 wrap in 64 bits is refused at that entry like any other that does not fit
+    e = int(np.flatnonzero(tape[:, 0] == gad.TAPE_REDUCING)[0])
+    for count, ext in ((1 << 62, 1), ((1 << 62) + 32, 1), (((1 << 64) - 4) // 3, 0)):
+        broken = tape.copy()
+        broken[e, 2], broken[e, 3] = np.uint64(count), np.uint64(ext)
+        rc, _, failed = replay(broken, inputs, idx.size)
+        assert rc == -1 and failed == e
     assert replay(tape, inputs[:5], idx.size)[0] == -1              # INPUT index past the input vector
     assert replay(tape, inputs, idx.size - 1)[0] == -1               # rows buffer too small
 
