@@ -278,6 +278,11 @@ typedef struct {
     uint32_t num_gates;
     gl355_gate gates[GL355_MAX_GATES];
 } gl355_circuit;
+/* A descriptor is refused with GL355_E_INVALID_ARG -- by gl355_circuit_load, gl355_quotient / gl355_quotient_values and gl355_verify, before
+ * a kernel or an evaluator sees it -- when a gate has an unknown type, a bad selector group, a parameter that describes no gate, or reads
+ * wires or gate constants the circuit does not have: every gate's highest wire lies below num_wires and it reads at most num_constants
+ * gate constants (ARITHMETIC and ARITHMETIC_EXT two, MUL_EXT one, CONSTANT num_consts, RANDOM_ACCESS num_extra_constants); the provers
+ * also want COSET_INTERPOLATION's 5 + 2N leading wires routed.  The loader's and the provers' message names the gate by its index. */
 /* Evaluates the combined vanishing polynomial / Z_H on the quotient coset for every challenge,
  * interpolates (coset iNTT) and writes the quotient chunks: out[(c*max_degree + j)][n] coefficients.
  * Oracles: constants_sigmas = [selectors | gate constants | sigmas], wires, zs_partial_products =

@@ -63,19 +63,12 @@ int32_t gl355_circuit_load(gl355_ctx* h, const uint64_t* blob, uint64_t words, g
         const uint64_t* p = blob + 12 + 5 * g;
         c.gates[g].type = (uint32_t)p[0]; c.gates[g].param = (uint32_t)p[1]; c.gates[g].selector_index = (uint32_t)p[2];
         c.gates[g].group_start = (uint32_t)p[3]; c.gates[g].group_end = (uint32_t)p[4];
-        if (g < c.num_gates && (c.gates[g].type > GL355_GATE_TYPE_MAX || c.gates[g].selector_index >= c.num_selectors ||
-                                c.gates[g].group_end > c.num_gates || c.gates[g].group_start > c.gates[g].group_end))
-            return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: bad gate table");
-        // gate parameters are counts of per-gate operations (RANDOM_ACCESS, COSET_INTERPOLATION: packed bytes): more of them than wires cannot be laid
-        // out, and a value >= 2^30 would wrap the 32-bit products (4 p, 8 p ...) evaluators form from it
-        const bool packed = c.gates[g].type == GL355_GATE_RANDOM_ACCESS || c.gates[g].type == GL355_GATE_COSET_INTERPOLATION;
-        if (g < c.num_gates && (p[1] > 0xFFFFFFFFull || (!packed && p[1] > c.num_wires) || (packed && p[1] > 0xFFFFFFull)))
-            return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: gate parameter out of range");
-        CosetInterpShape cis;
-        if (g < c.num_gates && c.gates[g].type == GL355_GATE_COSET_INTERPOLATION &&
-            (!coset_interp_shape(c.gates[g].param, cis) || cis.num_wires > c.num_wires || cis.start_int > c.num_routed_wires))
-            return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: CosetInterpolationGate does not fit the circuit");
+        // the artifact's words are 64 bits wide: the parameter the check below sees is the one the artifact states
+        if (g < c.num_gates && p[1] > 0xFFFFFFFFull) return ctx->fail(GL355_E_INVALID_ARG, "circuit_load: gate parameter out of range");
     }
+    // every gate's type, selector group, wires and constants (gate_shape.h): the provers' kernels read the descriptor unchecked
+    char gate_msg[GATE_MSG_LEN];
+    if (gate_table_check(c, "circuit_load", gate_msg) != GL355_OK) return ctx->fail(GL355_E_INVALID_ARG, gate_msg);
     const uint64_t n = 1ull << c.degree_bits;
     const uint64_t n_sc = c.num_selectors + c.num_constants, routed = c.num_routed_wires;
     const uint64_t n_rows = blob[102], n_ops = blob[103], n_inputs = blob[104], n_pi = blob[105];

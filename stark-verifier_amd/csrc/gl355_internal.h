@@ -14,6 +14,7 @@
 #include "gl_field.cuh"
 #include "merkle_common.cuh"
 #include "coset_interp.h"
+#include "gate_shape.h"
 
 namespace gl355 { struct Ctx; }
 
@@ -439,6 +440,10 @@ static inline void squeeze_ext(gl355_challenger* ch, uint64_t* v) {
 int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const uint64_t* cs_lde, const uint64_t* wires_lde, uint64_t wires_us,
                            const uint64_t* zs_lde, uint64_t zs_us, uint64_t lde_stride, const uint64_t* k_is_dev, const uint64_t* betas /* [B][4] */,
                            const uint64_t* gammas, const uint64_t* alphas, const uint64_t* pi_hashes /* [B][4] */, uint64_t* out_values /* [B][nch][nq] */);
+
+// verifier.cpp: the constraints of one gate at an opened point, in the extension field; false = the gate does not fit num_wires / num_constants
+bool verifier_eval_gate(const gl355_gate& gt, const gl2* consts, const gl2* w, const uint64_t pi_hash[4], uint32_t num_wires, uint32_t num_constants,
+                        std::vector<gl2>& c);
 
 static inline uint32_t log2_u64(uint64_t n) { uint32_t l = 0; while ((1ull << l) < n) l++; return l; }
 static inline uint32_t host_brev(uint32_t x, uint32_t bits) {

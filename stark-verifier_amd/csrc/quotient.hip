@@ -666,8 +666,27 @@ int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const u
     while ((1u << qdb) < c->max_degree) qdb++;
     if ((1u << qdb) != c->max_degree || qdb > c->rate_bits || qdb > 4) return ctx->fail(GL355_E_UNSUPPORTED, "quotient: degree factor must be a power of two <= 2^rate_bits");
     if (c->num_challenges == 0 || c->num_challenges > 4) return ctx->fail(GL355_E_UNSUPPORTED, "quotient: 1..4 challenges");
-    if (c->num_gates > GL355_MAX_GATES) return ctx->fail(GL355_E_INVALID_ARG, "quotient: too many gates");
     if (B == 0 || B > GL355_MAX_UNITS) return ctx->fail(GL355_E_INVALID_ARG, "quotient: 1..GL355_MAX_UNITS units");
+    // the evaluators index the wire and constant columns unchecked: every gate's wires and constants exist (gate_shape.h) before
+    // anything is allocated or launched.  The evaluators' own limits follow.
+    char msg[GATE_MSG_LEN];
+    if (gate_table_check(*c, "quotient", msg) != GL355_OK) return ctx->fail(GL355_E_INVALID_ARG, msg);
+    // length of the constraint stream = the permutation-argument prefix + the longest gate (the evaluators push exactly
+    // GateShape::constraints terms)
+    uint32_t longest = 0;
+    bool has_interp = false;
+    for (uint32_t g = 0; g < c->num_gates; g++) {
+        const uint32_t type = c->gates[g].type, bits = c->gates[g].param & 0xFF;
+        // the evaluator keeps a copy's bit wires in four registers and its list in sixteen
+        if (type == GL355_GATE_RANDOM_ACCESS && (bits < 1 || bits > 4)) return ctx->fail(GL355_E_UNSUPPORTED, "quotient: RandomAccessGate with 1..4 bits");
+        // the evaluator's domain and weight tables are those of 4, 8 and 16 points (coset_interp_shape knows no other today)
+        if (type == GL355_GATE_COSET_INTERPOLATION && (bits < 2 || bits > 4))
+            return ctx->fail(GL355_E_UNSUPPORTED, "quotient: CosetInterpolationGate with 2..4 subgroup bits");
+        has_interp |= type == GL355_GATE_COSET_INTERPOLATION;
+        GateShape s;
+        gate_shape(type, c->gates[g].param, s);
+        longest = s.constraints > longest ? s.constraints : longest;
+    }
     QuotArgs a;
     memset(&a, 0, sizeof a);
     a.c = *c;
@@ -695,39 +714,6 @@ int32_t quotient_units_dev(Ctx* ctx, const gl355_circuit* c, uint32_t B, const u
     }
     a.n_inv = gl_canon(gl_inv((1ull << c->degree_bits) % GL_P));
     a.out = out_values;
-    // length of the constraint stream = the permutation-argument prefix + the longest gate (constraint counts as in
-    // gates/*.rs num_constraints; the gate evaluators below push exactly that many terms)
-    uint32_t longest = 0;
-    bool has_interp = false;
-    for (uint32_t g = 0; g < c->num_gates; g++) {
-        const uint32_t p = c->gates[g].param;
-        // the evaluator keeps a copy's bit wires in four registers and its list in sixteen
-        if (c->gates[g].type == GL355_GATE_RANDOM_ACCESS && ((p & 0xFF) < 1 || (p & 0xFF) > 4))
-            return ctx->fail(GL355_E_UNSUPPORTED, "quotient: RandomAccessGate with 1..4 bits");
-        uint32_t k = 0;
-        if (c->gates[g].type == GL355_GATE_COSET_INTERPOLATION) {
-            // the evaluator's domain and weight tables are those of 4, 8 and 16 points; every wire it reads is checked here
-            CosetInterpShape s;
-            if ((p & 0xFF) < 2 || (p & 0xFF) > 4) return ctx->fail(GL355_E_UNSUPPORTED, "quotient: CosetInterpolationGate with 2..4 subgroup bits");
-            if (!coset_interp_shape(p, s)) return ctx->fail(GL355_E_INVALID_ARG, "quotient: CosetInterpolationGate degree outside 2..2^subgroup_bits");
-            if (s.num_wires > c->num_wires || s.start_int > c->num_routed_wires)
-                return ctx->fail(GL355_E_INVALID_ARG, "quotient: CosetInterpolationGate does not fit the wires / routed wires");
-            k = s.num_constraints;
-            has_interp = true;
-        }
-        switch (c->gates[g].type) {
-            case GL355_GATE_CONSTANT: k = p; break;
-            case GL355_GATE_PUBLIC_INPUT: k = 4; break;
-            case GL355_GATE_BASE_SUM: k = 1 + p; break;
-            case GL355_GATE_POSEIDON: k = 123; break;
-            case GL355_GATE_ARITHMETIC: k = p; break;
-            case GL355_GATE_ARITHMETIC_EXT: case GL355_GATE_MUL_EXT: case GL355_GATE_REDUCING: case GL355_GATE_REDUCING_EXT: k = 2 * p; break;
-            case GL355_GATE_POSEIDON_MDS: k = 24; break;
-            case GL355_GATE_RANDOM_ACCESS: k = ((p >> 8) & 0xFF) * ((p & 0xFF) + 2) + ((p >> 16) & 0xFF); break;
-            default: break;
-        }
-        longest = k > longest ? k : longest;
-    }
     const uint32_t n_chunks = (c->num_routed_wires + c->max_degree - 1) / c->max_degree;
     a.pw_stride = ((c->num_challenges * (1 + n_chunks) + longest + 1) + 63) & ~63u;
     Scratch pw(ctx);

@@ -60,42 +60,40 @@ inline Alg alg_add(Alg a, Alg b) { return Alg{gl2_add(a.a0, b.a0), gl2_add(a.a1,
 inline Alg alg_sub(Alg a, Alg b) { return Alg{gl2_sub(a.a0, b.a0), gl2_sub(a.a1, b.a1)}; }
 inline Alg alg_scal(E c, Alg a) { return Alg{gl2_mul(c, a.a0), gl2_mul(c, a.a1)}; }
 
-// constraints of one gate at the opened point: consts = the gate constants (after the selectors), w = the wires
-// (num_constants = gate constants present in the opening; every read of consts[] / w[] is bounded against the verifier data here,
-// which may come from an untrusted artifact)
-bool eval_gate(const gl355_gate& gt, const E* consts, const E* w, const uint64_t pi_hash[4], uint32_t num_wires, uint32_t num_constants,
-               std::vector<E>& c) {
+}  // namespace
+
+// constraints of one gate at the opened point: consts = the gate constants (after the selectors), w = the wires.  The gate data may
+// come from an untrusted artifact: gate_fits (gate_shape.h) bounds every read of consts[num_constants] and w[num_wires] below, the
+// cases check nothing themselves.  false = the gate does not fit
+bool gl355::verifier_eval_gate(const gl355_gate& gt, const E* consts, const E* w, const uint64_t pi_hash[4], uint32_t num_wires,
+                               uint32_t num_constants, std::vector<E>& c) {
     c.clear();
     auto alg = [&](uint32_t j) { return Alg{w[j], w[j + 1]}; };
     auto push_alg = [&](Alg v) { c.push_back(v.a0); c.push_back(v.a1); };
     const uint32_t p = gt.param;
-    // gt.param is untrusted: every bound below is computed in 64 bits (4 * p, 8 * p, 1 + p and 6 + 2 * p wrap in 32), and no gate whose
-    // parameter is a count can have more of them than there are wires (RANDOM_ACCESS packs three byte-sized fields instead)
-    const uint64_t P = p, NW = num_wires;
-    if (gt.type != GL355_GATE_RANDOM_ACCESS && gt.type != GL355_GATE_COSET_INTERPOLATION && P > NW) return false;
+    GateShape shape;
+    if (!gate_fits(gt.type, p, num_wires, num_constants, shape)) return false;
+    // a count above num_wires cannot fit (RANDOM_ACCESS and COSET_INTERPOLATION pack byte-sized fields instead).  The shape implies
+    // this for every gate that has a count; the four gates without a parameter do not read it and have always been refused so
+    if (gt.type != GL355_GATE_RANDOM_ACCESS && gt.type != GL355_GATE_COSET_INTERPOLATION && p > num_wires) return false;
     switch (gt.type) {
     case GL355_GATE_NOOP: return true;
     case GL355_GATE_CONSTANT:
-        if (p > num_constants || p > num_wires) return false;
         for (uint32_t i = 0; i < p; i++) c.push_back(gl2_sub(consts[i], w[i]));
         return true;
     case GL355_GATE_PUBLIC_INPUT:
-        if (num_wires < 4) return false;
         for (int i = 0; i < 4; i++) c.push_back(gl2_sub(w[i], e_base(pi_hash[i])));
         return true;
     case GL355_GATE_BASE_SUM: {
-        if (1 + P > NW) return false;
         c.push_back(gl2_sub(reduce_with_powers(w + 1, p, e_base(2)), w[0]));
         for (uint32_t i = 0; i < p; i++) c.push_back(gl2_sub(gl2_mul(w[1 + i], w[1 + i]), w[1 + i]));
         return true;
     }
     case GL355_GATE_ARITHMETIC:
-        if (4 * P > NW || num_constants < 2) return false;
         for (uint32_t i = 0; i < p; i++)
             c.push_back(gl2_sub(w[4 * i + 3], gl2_add(gl2_mul(gl2_mul(w[4 * i], w[4 * i + 1]), consts[0]), gl2_mul(w[4 * i + 2], consts[1]))));
         return true;
     case GL355_GATE_POSEIDON: {
-        if (num_wires < 135) return false;
         const E swap = w[24];
         c.push_back(gl2_sub(gl2_mul(swap, swap), swap));
         E s[12];
@@ -128,16 +126,13 @@ bool eval_gate(const gl355_gate& gt, const E* consts, const E* w, const uint64_t
         return true;
     }
     case GL355_GATE_ARITHMETIC_EXT:
-        if (8 * P > NW || num_constants < 2) return false;
         for (uint32_t i = 0; i < p; i++)
             push_alg(alg_sub(alg(8 * i + 6), alg_add(alg_scal(consts[0], alg_mul(alg(8 * i), alg(8 * i + 2))), alg_scal(consts[1], alg(8 * i + 4)))));
         return true;
     case GL355_GATE_MUL_EXT:
-        if (6 * P > NW || num_constants < 1) return false;
         for (uint32_t i = 0; i < p; i++) push_alg(alg_sub(alg(6 * i + 4), alg_scal(consts[0], alg_mul(alg(6 * i), alg(6 * i + 2)))));
         return true;
     case GL355_GATE_POSEIDON_MDS:
-        if (num_wires < 48) return false;
         for (uint32_t r = 0; r < 12; r++) {
             Alg acc{gl2_make(0, 0), gl2_make(0, 0)};
             for (uint32_t i = 0; i < 12; i++) acc = alg_add(acc, alg_scal(e_base(GL_PSD_MDS_CIRC[i]), alg(2 * ((i + r) % 12))));
@@ -148,7 +143,6 @@ bool eval_gate(const gl355_gate& gt, const E* consts, const E* w, const uint64_t
     case GL355_GATE_RANDOM_ACCESS: {
         const uint32_t bits = p & 0xFF, copies = (p >> 8) & 0xFF, extra = (p >> 16) & 0xFF;
         const uint32_t vec = 1u << bits, routed = (2 + vec) * copies + extra;
-        if (bits > 8 || (uint64_t)routed + (uint64_t)copies * bits > NW || extra > num_constants) return false;
         for (uint32_t cp = 0; cp < copies; cp++) {
             const uint32_t b0 = (2 + vec) * cp;
             const E* bl = w + routed + cp * bits;
@@ -167,7 +161,6 @@ bool eval_gate(const gl355_gate& gt, const E* consts, const E* w, const uint64_t
     case GL355_GATE_REDUCING:
     case GL355_GATE_REDUCING_EXT: {
         const bool isext = gt.type == GL355_GATE_REDUCING_EXT;
-        if (p == 0 || 6 + (isext ? 2 * P : P) + 2 * (P - 1) > NW) return false;
         const uint32_t start_accs = 6 + (isext ? 2 * p : p);
         const Alg alpha = alg(2);
         Alg acc = alg(4);
@@ -183,7 +176,7 @@ bool eval_gate(const gl355_gate& gt, const E* consts, const E* w, const uint64_t
         // plonky2 gates/coset_interpolation.rs over the extension algebra (coset_interp.h): the wires are extension values, the value /
         // point / accumulator pairs algebra elements, `shift` an extension scalar, the domain and the weights base-field constants
         CosetInterpShape s;
-        if (!coset_interp_shape(p, s) || s.num_wires > num_wires) return false;
+        coset_interp_shape(p, s);
         const uint64_t g = gl_root_of_unity(s.bits), n_inv = gl_inv(s.n);
         const Alg x = alg(s.shifted);
         push_alg(alg_sub(alg(s.point), alg_scal(w[0], x)));
@@ -209,6 +202,8 @@ bool eval_gate(const gl355_gate& gt, const E* consts, const E* w, const uint64_t
     default: return false;
     }
 }
+
+namespace {
 
 struct Hash4 { uint64_t v[4]; };
 Hash4 two_to_one(int32_t hasher, const uint64_t* l, const uint64_t* r) {
@@ -289,7 +284,7 @@ static int32_t verify_impl(const gl355_verifier_data* vd, const uint64_t* proof,
     memset(&pd, 0, sizeof pd);
     pd.circuit = vd->circuit; pd.cap_height = cap_h; pd.num_queries = nq; pd.n_fri_layers = L; pd.zero_knowledge = vd->zero_knowledge;
     pd.fri_arity_bits = vd->fri_arity_bits;
-    const uint64_t need = gl355_proof_words(&pd);
+    const uint64_t need = ProofLayout(pd).words;
     if (proof_words != need || proof[0] != need) return fail("proof length does not match the circuit");
     if (proof[1] != c.degree_bits || proof[2] != L || proof[3] != nq || proof[4] != n_public_inputs || proof[5] != (uint64_t)zk || proof[6] != cap_h || proof[7] != nch)
         return fail("proof header does not match the verifier data");
@@ -364,7 +359,7 @@ static int32_t verify_impl(const gl355_verifier_data* vd, const uint64_t* proof,
             const gl355_gate& gt = c.gates[gi];
             if (gt.type > GL355_GATE_TYPE_MAX || gt.selector_index >= c.num_selectors || gt.group_end > c.num_gates || gt.group_start > gt.group_end)
                 { g_verify_error = "verify: bad gate table"; return GL355_E_INVALID_ARG; }
-            if (!eval_gate(gt, o_consts + c.num_selectors, o_wires, pi_hash, c.num_wires, c.num_constants, gc)) { g_verify_error = "verify: gate does not fit the wire / constant count"; return GL355_E_INVALID_ARG; }
+            if (!verifier_eval_gate(gt, o_consts + c.num_selectors, o_wires, pi_hash, c.num_wires, c.num_constants, gc)) { g_verify_error = "verify: gate does not fit the wire / constant count"; return GL355_E_INVALID_ARG; }
             const E sel = o_consts[gt.selector_index];
             E filt = one;
             for (uint32_t k = gt.group_start; k < gt.group_end; k++)

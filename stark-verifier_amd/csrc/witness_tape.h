@@ -8,6 +8,7 @@
 #pragma once
 #include "../../include/gl355.h"
 #include "coset_interp.h"
+#include "gate_shape.h"
 
 namespace gl355 {
 
@@ -18,11 +19,14 @@ static_assert(TAPE_RA_STRIDE == 18 && TAPE_RA_BIT_WIRES == 74, "random_access.rs
 enum { TAPE_POSEIDON_SWAP = 24 };      // PoseidonGate's swap wire
 
 // Does everything the entry reads and writes lie inside inputs[n_inputs] and W[n_words]?  Rows are num_wires >= 135 wide (the callers'
-// pre-condition: the widest fixed layout here, PoseidonGate, has 135 wires).  No sum of operands is formed, so nothing wraps.
+// pre-condition: the widest fixed layout here, PoseidonGate, has 135 wires).  No sum of operands is formed, so nothing wraps;
+// the spans of BASE_SUM and REDUCING are their gates' (gate_shape.h).
 GL_HD bool tape_entry_fits(const uint64_t* e, uint64_t n_inputs, uint64_t n_words, uint32_t num_wires) {
     const uint64_t a = e[1], b = e[2], c = e[3], d = e[4];
     auto ok = [&](uint64_t i, uint64_t span) { return i < n_words && span <= n_words - i; };
     auto row = [&](uint64_t i) { return ok(i, num_wires) && i % num_wires == 0; };
+    // a gate of `count` limbs or coefficients inside a row: count is compared with num_wires before it is narrowed to the 32 bits of a gate parameter
+    auto gate = [&](uint32_t type, uint64_t count) { GateShape g; return count <= num_wires && gate_fits(type, (uint32_t)count, num_wires, 0, g); };
     switch (e[0]) {
     case GL355_TAPE_CONST: return ok(a, 1);
     case GL355_TAPE_INPUT: return ok(a, 1) && b < n_inputs;
@@ -30,9 +34,9 @@ GL_HD bool tape_entry_fits(const uint64_t* e, uint64_t n_inputs, uint64_t n_word
     case GL355_TAPE_ARITH: return ok(a, 4);
     case GL355_TAPE_ARITH_EXT: return ok(a, 8);
     case GL355_TAPE_POSEIDON: case GL355_TAPE_MDS_EXT: return row(a);
-    case GL355_TAPE_BASE_SUM: return row(a) && b <= 63 && 1 + b <= num_wires;
+    case GL355_TAPE_BASE_SUM: return row(a) && b <= 63 && gate(GL355_GATE_BASE_SUM, b);
     case GL355_TAPE_RANDOM_ACCESS: return row(a) && b < TAPE_RA_COPIES;
-    case GL355_TAPE_REDUCING: return row(a) && b != 0 && b <= num_wires && 6 + (c ? 2 * b : b) + 2 * (b - 1) <= num_wires;
+    case GL355_TAPE_REDUCING: return row(a) && gate(c ? GL355_GATE_REDUCING_EXT : GL355_GATE_REDUCING, b);
     case GL355_TAPE_EXT_INV: return ok(a, 1) && ok(b, 1) && ok(c, 1) && ok(d, 1);
     case GL355_TAPE_COSET_INTERP: {
         CosetInterpShape s;

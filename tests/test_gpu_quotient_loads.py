@@ -65,7 +65,7 @@ def check_every_row(gl, ctx, d, seed):
     assert len(gates) <= 16 and npp == (routed + d["max_degree"] - 1) // d["max_degree"] - 1
     sel_idx = [next(s for s, (lo, hi) in enumerate(groups) if lo <= g < hi) for g in range(len(gates))]
     n, N = 1 << DEGREE_BITS, 1 << (DEGREE_BITS + RATE_BITS)
-    n_sel, n_cst, nw = len(groups), 2, 135
+    n_sel, n_cst, nw = len(groups), d.get("num_constants", 2), d.get("num_wires", 135)
     cs_vals = rand_field(rng, (n_sel + n_cst + routed, n))
     cs_vals[:n_sel] = rng.integers(0, len(gates), size=(n_sel, n)).astype(np.uint64)   # selector-like small values
     cs = gl.PolynomialBatch.from_values(ctx, cs_vals, RATE_BITS, 2)
@@ -132,6 +132,34 @@ def test_every_row_one_wire_last_chunk(gl, ctx, nch):
     """17 routed wires in chunks of 8: three chunks, the last holds one wire, and sigma_16 is the last column of the
     constants_sigmas oracle -- the read-ahead past it is clamped; the values must be equal (quotient_kernel<1> shares the code)"""
     check_every_row(gl, ctx, one_wire_last_chunk(nch), 0x36C + nch)
+
+
+def exact_fit_at_48_wires():
+    lib = _lib()
+    gates = [(lib.GATE_POSEIDON_MDS, 0), (lib.GATE_ARITHMETIC, 12), (lib.GATE_ARITHMETIC_EXT, 6), (lib.GATE_MUL_EXT, 8), (lib.GATE_REDUCING_EXT, 11),
+             (lib.GATE_BASE_SUM, 47), (lib.GATE_RANDOM_ACCESS, 2 | 6 << 8), (lib.GATE_REDUCING, 14), (lib.GATE_CONSTANT, 2),
+             (lib.GATE_PUBLIC_INPUT, 0), (lib.GATE_NOOP, 0)]
+    return dict(gates=gates, groups=[(0, 3), (3, 7), (7, 11)], routed=40, max_degree=8, npp=4, nch=2, num_wires=48)
+
+
+def test_every_row_exact_fit_at_48_wires(gl, ctx):
+    """a wires oracle of exactly 48 columns: PoseidonMds, Arithmetic{12}, ArithmeticExtension{6}, MulExtension{8}, ReducingExtension{11},
+    BaseSum{47} and RandomAccess{bits 2, copies 6} (36 routed wires + 12 bit wires) each read wire 47 and none beyond; Reducing{14}
+    reads 46, Constant{2} both gate constants.  The smallest descriptor at which the launcher's check (csrc/gate_shape.h) and the
+    evaluators meet: every one of the 256 rows"""
+    check_every_row(gl, ctx, exact_fit_at_48_wires(), 0x370)
+
+
+@pytest.mark.parametrize("gate,num_constants", [("CONSTANT", 2), ("ARITHMETIC", 1)], ids=["Constant{3} with two constants", "Arithmetic{1} with one"])
+def test_gates_that_read_more_constants_than_the_circuit_has_are_refused(gl, ctx, gate, num_constants):
+    """unchecked, the evaluator would take a sigma column of the same oracle for a gate constant (in bounds, and wrong); the
+    descriptor check refuses with GL355_E_INVALID_ARG before anything is launched"""
+    lib = _lib()
+    gates = [(lib.GATE_CONSTANT, 3) if gate == "CONSTANT" else (lib.GATE_ARITHMETIC, 1), (lib.GATE_NOOP, 0)]
+    d = dict(gates=gates, groups=[(0, 2)], routed=17, max_degree=8, npp=2, nch=2, num_constants=num_constants)
+    with pytest.raises(gl.Gl355Error, match="does not fit") as ei:
+        check_every_row(gl, ctx, d, 0x371)
+    assert ei.value.code == -1 and "gate 0" in str(ei.value)
 
 
 @pytest.mark.parametrize("bits", [0, 5])
