@@ -915,6 +915,29 @@ int32_t gl355_bn254_arith_batch(gl355_ctx* ctx, int32_t op, const uint32_t* a /*
 int32_t gl355_bn254_g1_chain(gl355_ctx* ctx, int32_t form, const uint32_t* operands /* n_operands x 28 */, uint32_t n_operands,
                              const uint32_t* steps /* n_chains x n_steps */, uint32_t n_chains, uint32_t n_steps, uint32_t* trace /* n_chains x n_steps x 40 */);
 
+/* ---- test hooks: the Goldilocks product forms and the 16-lane Poseidon permutation on raw words (tests/test_gpu_gl_arith.py,
+ * tests/test_gpu_poseidon_lanes.py).  Not a product path.  Buffers may be host or device memory.
+ *   gl355_gl_arith_batch           out[i] = op(a[i], b[i]) for n records of one u64 each.  Nothing is reduced on the way in (operands are ANY u64: inside
+ *                                  an S-box these routines consume each other's unreduced results) and the outputs are stored as the routine returns
+ *                                  them: some u64 congruent to the result mod p.  GL355_GL_MUL = gl_mul, _MUL_MULTI1 .. 4 = gl_mul_multi<N>, _MUL_FILL =
+ *                                  gl_mul_fill, _MUL2_FILL = gl_mul2_fill, _SQR = gl_sqr, _SBOX = psd_sbox, _SBOX4 = psd_sbox4 (x^7; these three read a only,
+ *                                  b may be NULL), _RECOMBINE = psd_recombine and _RECOMBINE_MULTI4 = psd_recombine_multi<4> (a = al, b = ah, whose
+ *                                  contract is (ah >> 32) + 1 < 2^32).  One lane takes N CONSECUTIVE records of an N-wide form (MULTI N; MUL2_FILL 2;
+ *                                  SBOX4 and RECOMBINE_MULTI4 4): n must be a multiple of N.  The two FILL forms get fillers of the shape of the
+ *                                  permutation's own (two multiply-adds each, into two accumulators, between a carry's writer and its reader) and
+ *                                  write the accumulators out too, so `out` holds 3 n words for them: out[n + i] = al and out[2 n + i] = ah of the
+ *                                  lane whose FIRST record is i (0 at a pair's second record), where with x_k = a[i] (k + 1) + b[i] mod 2^64 and the MDS
+ *                                  row c = {17, 15, 41, 16, 2}: al = lo32(b[i]) + sum_k lo32(x_k) c_k, ah = hi32(b[i]) + sum_k hi32(x_k) c_k, k = 0 .. 4.
+ *                                  GL355_E_INVALID_ARG for an unknown op, n not a multiple of N, or a null buffer with n > 0; n = 0 launches nothing.
+ *   gl355_poseidon_permute_lanes   `count` states of 12 words permuted in place by the 16-lane permutation of the Merkle tops and FRI wide leaves
+ *                                  (gates/poseidon.rs:504-589's rounds, one word per lane): form 0 (every round dense) or 3 (the partial rounds' row
+ *                                  inside the S-box), any other form is GL355_E_INVALID_ARG.  Four states per 64-thread block; all 12 words come back
+ *                                  canonical. */
+enum { GL355_GL_MUL = 0, GL355_GL_MUL_MULTI1 = 1, GL355_GL_MUL_MULTI2 = 2, GL355_GL_MUL_MULTI3 = 3, GL355_GL_MUL_MULTI4 = 4, GL355_GL_MUL_FILL = 5,
+       GL355_GL_MUL2_FILL = 6, GL355_GL_SQR = 7, GL355_GL_SBOX = 8, GL355_GL_SBOX4 = 9, GL355_GL_RECOMBINE = 10, GL355_GL_RECOMBINE_MULTI4 = 11 };
+int32_t gl355_gl_arith_batch(gl355_ctx* ctx, int32_t op, const uint64_t* a /* n */, const uint64_t* b /* n or NULL */, uint64_t* out /* n, or 3 n */, uint64_t n);
+int32_t gl355_poseidon_permute_lanes(gl355_ctx* ctx, int32_t form, uint64_t* states /* count x 12 */, uint64_t count);
+
 
 /* ---- test hooks: the MSM under a caller's bit length, and the prover's column commitments (tests/test_gpu_msm_bits.py).  They wrap shipped code
  * only, and no product path calls them.

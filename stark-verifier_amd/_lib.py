@@ -221,6 +221,9 @@ SIGNATURES = {
     # test hooks (include/gl355.h): the BN254 device arithmetic on raw limbs
     "gl355_bn254_arith_batch": (C.c_int32, [vp, C.c_int32, vp, vp, vp, C.c_uint64]),
     "gl355_bn254_g1_chain": (C.c_int32, [vp, C.c_int32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp]),
+    # test hooks: the Goldilocks product forms and the 16-lane Poseidon permutation on raw words
+    "gl355_gl_arith_batch": (C.c_int32, [vp, C.c_int32, vp, vp, vp, C.c_uint64]),
+    "gl355_poseidon_permute_lanes": (C.c_int32, [vp, C.c_int32, vp, C.c_uint64]),
     # test hooks: the MSM under a caller's bit length and the prover's column commitments (tests/test_gpu_msm_bits.py)
     "gl355_bn254_g1_msm_bits": (C.c_int32, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
     "gl355_plonk_pk_commit_columns": (C.c_int32, [vp, C.c_uint32, vp, C.c_uint32, C.c_uint64, vp]),

@@ -181,6 +181,21 @@ class Context:
         self.check(self.lib.gl355_poseidon_permute(self.h, _ptr(s), s.size // 12))
         return s
 
+    def poseidon_permute_lanes(self, form, states):
+        """test hook: the 16-lane permutation of the Merkle tops (form 0 or 3) on states[count][12]"""
+        s = _u64(states).copy()
+        self.check(self.lib.gl355_poseidon_permute_lanes(self.h, int(form), _ptr(s), s.size // 12))
+        return s
+
+    def gl_arith_batch(self, op, a, b=None):
+        """test hook (GL355_GL_*): op on raw u64 words, results as the device routine returns them (not reduced).  The two FILL forms
+        return (products, al, ah)."""
+        a = _u64(a).reshape(-1)
+        fill = op in (5, 6)          # GL355_GL_MUL_FILL, GL355_GL_MUL2_FILL
+        out = np.empty(a.size * (3 if fill else 1), dtype=np.uint64)
+        self.check(self.lib.gl355_gl_arith_batch(self.h, int(op), _ptr(a), _ptr(_u64(b).reshape(-1)) if b is not None else None, _ptr(out), a.size))
+        return (out[:a.size], out[a.size:2 * a.size], out[2 * a.size:]) if fill else out
+
     def hash_no_pad(self, inputs):
         """PoseidonHash::hash_no_pad on each row of inputs[n][len] -> [n][4]."""
         x = _u64(inputs)

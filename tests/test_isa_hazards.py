@@ -15,7 +15,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc (cross-compiles gfx950 without a GPU)")
 
 
-@pytest.mark.parametrize("src", ["merkle.hip", "quotient.hip", "fri.hip"])
+@pytest.mark.parametrize("src", ["merkle.hip", "quotient.hip", "fri.hip", "gl_hook.hip"])
 def test_valu_scalar_hazard_distance(src):
     bad, n = ch.check_listing(ch.listing_of(src), src)
     assert n > 500, "the checker saw almost no carry chains in %s: the ISA parser is out of date" % src
