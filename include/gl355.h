@@ -696,6 +696,12 @@ int32_t gl355_kzg_open(gl355_ctx* ctx, const uint64_t* g, const uint64_t* coeffs
  *   the constant pool (4 words each), the gate program, and per lookup [input instructions, table instructions] + the two programs.
  *   A program instruction is four u32 (op, dst, a, b): op 0 ADD 1 SUB 2 MUL 3 EMIT 4 NEG 5 MOV; operands kind << 24 | index with kind 0 register
  *   (< 12), 1 constant, 2 / 3 / 4 advice / fixed / instance QUERY; EMIT a = "a is the next polynomial / expression" (folded with y / theta).
+ *   Bounds, one parser for every entry that takes the blob (csrc/plonk_desc.h), anything else is GL355_E_INVALID_ARG: 3 <= k <= 24 for
+ *   gl355_plonk_keygen and gl355_plonk_check_witness, <= 28 (the two-adicity of r) for gl355_plonk_vk_create, which allocates nothing of size
+ *   2^k; advice, fixed, permutation columns <= 256 each, instance columns <= 16, lookups <= 64, 3 <= degree <= 10, 3 <= blinding factors <= 64
+ *   and 2^k >= blinding factors + 3; advice / fixed queries <= 1024 each, instance queries <= 64, constants <= 4096, gate instructions and
+ *   gate polynomials <= 2^20, a lookup program <= 2^16 instructions; every permutation and query column exists, |rotation| <= blinding
+ *   factors + 1, every operand of every instruction is in range, and the blob ends where its header says.
  * Scalars are 4 x u64 little-endian integers, points affine x | y (8 x u64, zeros = identity), as in the KZG block above.
  *   gl355_keccak256          Keccak-256 (Ethereum's), the hash of halo2-solidity-verifier's Keccak256Transcript (test_utils.rs:73)
  *   gl355_kzg_commit_columns n_cols commitments over one resident SRS in batched MSMs: columns = [n_cols][2^log_n] scalars that go with the

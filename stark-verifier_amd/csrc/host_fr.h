@@ -16,6 +16,9 @@ struct KeccakTranscript {
     static void be32(const uint64_t w[4], uint8_t out[32]) {
         for (int i = 0; i < 4; i++) for (int b = 0; b < 8; b++) out[31 - (8 * i + b)] = (uint8_t)(w[i] >> (8 * b));
     }
+    static void from_be32(const uint8_t b[32], uint64_t w[4]) {      // be32's inverse: the one place a 256-bit big-endian integer is read
+        for (int i = 0; i < 4; i++) { w[i] = 0; for (int j = 0; j < 8; j++) w[i] |= (uint64_t)b[31 - (8 * i + j)] << (8 * j); }
+    }
     void common_scalar(const Fr& s) { uint64_t w[4]; s.to_words(w); uint8_t b[32]; be32(w, b); buf.insert(buf.end(), b, b + 32); }
     void write_scalar(const Fr& s) { uint64_t w[4]; s.to_words(w); uint8_t b[32]; be32(w, b); buf.insert(buf.end(), b, b + 32); proof.insert(proof.end(), b, b + 32); }
     void write_point(const uint64_t xy[8]) {            // affine, canonical integers; all zero = the identity
@@ -30,10 +33,9 @@ struct KeccakTranscript {
         uint8_t h[32];
         keccak256_host(data.data(), data.size(), h);
         buf.assign(h, h + 32);
-        // 256-bit big-endian integer mod r
         uint64_t w[4];
-        for (int i = 0; i < 4; i++) { w[i] = 0; for (int b = 0; b < 8; b++) w[i] |= (uint64_t)h[31 - (8 * i + b)] << (8 * b); }
-        return Fr::from_words(w);
+        from_be32(h, w);
+        return Fr::from_words(w);                           // 256-bit big-endian integer mod r
     }
 };
 

@@ -45,10 +45,10 @@ inline u256 to_dev(const Fr& a) { u256 r; for (int i = 0; i < 4; i++) { r.l[2 * 
 
 }  // namespace
 
-struct gl355_plonk_pk : PlkDesc {                                         // the parsed descriptor, and what keygen derives from it
+struct gl355_plonk_pk : PlkDesc {                                         // the parsed descriptor and its shape (plonk_desc.h), and what keygen adds
     Ctx* ctx = nullptr;
     gl355_ctx* handle = nullptr;
-    uint32_t ext_k = 0, n_pieces = 0, n_sets = 0, chunk_len = 0, kind_cols[3] = {0, 0, 0} /* advice, fixed, instance */;
+    uint32_t ext_k = 0;                                                   // the extended domain: the least 2^ext_k >= n n_pieces
     std::vector<Fr> coset_base;                                           // zeta ext_omega^c: the cosets of the extended domain that evaluate_h visits
     std::vector<uint64_t> desc;                                           // the descriptor as given (gl355_plonk_vk_from_pk hands it to the verifier)
     std::vector<std::pair<uint32_t, uint32_t>> lk_single;                 // plk_single_query of every lookup's input (2 l) and table (2 l + 1) expressions
@@ -909,7 +909,7 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
     if (!desc || !g || !g_lagrange || !out || words < PLK_HDR) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: null or truncated argument");
     *out = nullptr;
     PlkDesc d;
-    if (const char* what = plk_parse_desc(desc, words, d)) return ctx->fail(GL355_E_INVALID_ARG, (std::string("plonk_keygen: ") + what).c_str());
+    if (const char* what = plk_parse_desc(desc, words, PLK_MAX_K_DEVICE, d)) return ctx->fail(GL355_E_INVALID_ARG, (std::string("plonk_keygen: ") + what).c_str());
     // keygen's temporaries (staged fixed values and mapping, the MSM scratch of 25 commitments, transform scratch: 66 GB at k = 23) are of no use to a
     // proof: back to the device, not into the context's cache -- on every return path (declared first, so it runs after the key's own destructor on
     // a failure), and only the blocks this call created: a context that already serves proofs keeps its warmed cache
@@ -918,14 +918,10 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
     if (!pk) return GL355_E_OOM;
     static_cast<PlkDesc&>(*pk) = std::move(d);
     pk->ctx = ctx; pk->handle = h;
-    pk->n_pieces = pk->degree - 1;
     pk->ext_k = pk->k;
     while ((1ull << pk->ext_k) < pk->n * pk->n_pieces) pk->ext_k++;
-    pk->chunk_len = pk->degree - 2;
-    pk->n_sets = pk->n_perm ? (pk->n_perm + pk->chunk_len - 1) / pk->chunk_len : 0;
     pk->desc.assign(desc, desc + words);
     if ((pk->n_fixed && !fixed_values) || (pk->n_perm && !mapping)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: fixed values / permutation mapping missing");
-    pk->kind_cols[0] = pk->n_advice; pk->kind_cols[1] = pk->n_fixed; pk->kind_cols[2] = pk->n_instance;
     for (auto& lk : pk->lookups) { pk->lk_single.push_back(plk_single_query(pk->queries, lk.in_code)); pk->lk_single.push_back(plk_single_query(pk->queries, lk.tab_code)); }
     {
         const uint64_t zeta[4] = {0xb8ca0b2d36636f23ull, 0xcc37a73fec2bc5e9ull, 0x048b6e193fd84104ull, 0x30644e72e131a029ull};      // Fr::ZETA
@@ -934,10 +930,9 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
         for (uint32_t c = 0; c < pk->n_pieces; c++) { pk->coset_base.push_back(base); base = base * ext_omega; }
     }
     // every permutation column must be queried at rotation 0 (halo2's enable_equality does that): the verifier reads it at x
-    for (auto& pc : pk->perm_cols) {
-        bool ok = false;
-        for (auto& q : pk->queries[pc.first]) ok = ok || (q.first == (int32_t)pc.second && q.second == 0);
-        if (!ok) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: a permutation column is not queried at the current rotation");
+    {
+        std::vector<uint32_t> perm_query;                // the prover reads the columns themselves; only the verifier needs which query it is
+        if (!plk_perm_queries(*pk, perm_query)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: a permutation column is not queried at the current rotation");
     }
     // SHPLONK's linear combination carries at most four low-order correction terms per polynomial (PlkLincombArgs::low): a column queried at
     // five or more distinct rotations is refused HERE, not at the end of every proof.  The arguments' own polynomials are opened
@@ -1020,21 +1015,9 @@ int32_t gl355_plonk_keygen(gl355_ctx* h, const uint64_t* desc, uint64_t words, c
         if (bad) return ctx->fail(GL355_E_INVALID_ARG, "plonk_keygen: permutation mapping out of range");
     }
     GL355_TRY(key_columns(pk.get(), pk->sigma_vals, pk->sigma_polys, pk->n_perm, pk->sigma_commitments, work.as<uint64_t>()));
-    // the transcript's initial scalar (halo2: vk.transcript_repr, a hash of the PINNED verifying key -- shape, fixed commitments, permutation
-    // commitments): a descriptor whose digest field is zero gets Keccak-256 over (the whole descriptor | fixed commitments | sigma
-    // commitments), as a big-endian integer mod r, so two circuits that differ only in fixed values or copy constraints never share a
-    // Fiat-Shamir prefix and a C caller cannot forget the step.  A non-zero field is taken as given (a host that computed
-    // halo2's own transcript_repr); gl355_plonk_pk_set_digest still overrides.
-    if (!(desc[16] | desc[17] | desc[18] | desc[19])) {
-        std::vector<uint64_t> pre(desc, desc + words);
-        pre.insert(pre.end(), pk->fixed_commitments.begin(), pk->fixed_commitments.end());
-        pre.insert(pre.end(), pk->sigma_commitments.begin(), pk->sigma_commitments.end());
-        uint8_t hsh[32];
-        keccak256_host(reinterpret_cast<const uint8_t*>(pre.data()), pre.size() * 8, hsh);
-        uint64_t w[4];
-        for (int i = 0; i < 4; i++) { w[i] = 0; for (int b = 0; b < 8; b++) w[i] |= (uint64_t)hsh[31 - (8 * i + b)] << (8 * b); }
-        pk->digest = Fr::from_words(w);
-    }
+    // the transcript's initial scalar, now that the commitments exist (plonk_desc.h: the header's, else the pinned-key rule);
+    // gl355_plonk_pk_set_digest still overrides
+    pk->digest = plk_pinned_digest(desc, words, pk->fixed_commitments.data(), pk->sigma_commitments.data(), *pk);
     // l_0, l_last, l_active_row
     GL355_TRY(pk->dalloc(3 * n * 32, &pk->l_polys));
     hipLaunchKernelGGL(plk_indicator_kernel, dim3(blocks(n)), dim3(256), 0, ctx->stream, pk->l_polys, pk->l_polys + 4 * n, pk->l_polys + 8 * n, n, pk->usable);

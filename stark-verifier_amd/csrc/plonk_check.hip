@@ -284,11 +284,6 @@ __global__ void __launch_bounds__(256) chk_extract_kernel(ChkExtractArgs a) {
 namespace {
 
 inline uint32_t blocks(uint64_t n, uint32_t per = 256) { return (uint32_t)((n + per - 1) / per); }
-uint32_t count_emits(const std::vector<uint32_t>& code) {
-    uint32_t c = 0;
-    for (size_t i = 0; i < code.size(); i += 4) c += code[i] == PLK_OP_EMIT;
-    return c;
-}
 struct StageTimer {
     Ctx* ctx; double* slot; std::chrono::steady_clock::time_point t0;
     StageTimer(Ctx* c, double* s) : ctx(c), slot(s), t0(std::chrono::steady_clock::now()) {}
@@ -306,13 +301,13 @@ extern "C" int32_t gl355_plonk_check_witness(gl355_ctx* h, const uint64_t* desc,
     if (!desc || !n_failures || (capacity && !failures)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_check_witness: null argument");
     *n_failures = 0;
     PlkDesc d;
-    if (const char* what = plk_parse_desc(desc, desc_words, d)) return ctx->fail(GL355_E_INVALID_ARG, (std::string("plonk_check_witness: ") + what).c_str());
+    if (const char* what = plk_parse_desc(desc, desc_words, PLK_MAX_K_DEVICE, d)) return ctx->fail(GL355_E_INVALID_ARG, (std::string("plonk_check_witness: ") + what).c_str());
     const uint32_t P = d.n_gate_polys, L = d.n_lookups, M = mapping ? d.n_perm : 0;
-    if (count_emits(d.gate_code) != P) return ctx->fail(GL355_E_INVALID_ARG, "plonk_check_witness: the gate program does not emit the header's number of polynomials");
+    if (d.gate_emits != P) return ctx->fail(GL355_E_INVALID_ARG, "plonk_check_witness: the gate program does not emit the header's number of polynomials");
     std::vector<uint32_t> lk_w(L);
     for (uint32_t l = 0; l < L; l++) {
-        lk_w[l] = count_emits(d.lookups[l].in_code);
-        if (!lk_w[l] || lk_w[l] != count_emits(d.lookups[l].tab_code)) return ctx->fail(GL355_E_INVALID_ARG, "plonk_check_witness: a lookup's input and table differ in width");
+        lk_w[l] = d.lookups[l].in_emits;
+        if (!lk_w[l] || lk_w[l] != d.lookups[l].tab_emits) return ctx->fail(GL355_E_INVALID_ARG, "plonk_check_witness: a lookup's input and table differ in width");
     }
     if ((d.n_fixed && !fixed_values) || (d.n_advice && !advice) || (d.n_instance && !instance_lens))
         return ctx->fail(GL355_E_INVALID_ARG, "plonk_check_witness: fixed values, advice or instance lengths missing");
@@ -331,16 +326,15 @@ extern "C" int32_t gl355_plonk_check_witness(gl355_ctx* h, const uint64_t* desc,
         return GL355_OK;
     };
     // ---- the columns as canonical Montgomery values: advice | fixed | instance (padded with zeros)
-    const uint32_t kind_cols[3] = {d.n_advice, d.n_fixed, d.n_instance};
     uint64_t* vals[3] = {nullptr, nullptr, nullptr};
-    for (int kd = 0; kd < 3; kd++) GL355_TRY(D((size_t)std::max(1u, kind_cols[kd]) * n * 32, &vals[kd]));
+    for (int kd = 0; kd < 3; kd++) GL355_TRY(D((size_t)std::max(1u, d.kind_cols[kd]) * n * 32, &vals[kd]));
     {
         const uint64_t* src[2] = {advice, fixed_values};
         for (int kd = 0; kd < 2; kd++) {
-            if (!kind_cols[kd]) continue;
+            if (!d.kind_cols[kd]) continue;
             Staged st(ctx);
-            GL355_TRY(st.open(src[kd], (size_t)kind_cols[kd] * n * 32, 1));
-            hipLaunchKernelGGL(chk_to_mont_kernel, dim3(blocks((uint64_t)kind_cols[kd] * n)), dim3(256), 0, ctx->stream, st.as<uint64_t>(), vals[kd], (uint64_t)kind_cols[kd] * n);
+            GL355_TRY(st.open(src[kd], (size_t)d.kind_cols[kd] * n * 32, 1));
+            hipLaunchKernelGGL(chk_to_mont_kernel, dim3(blocks((uint64_t)d.kind_cols[kd] * n)), dim3(256), 0, ctx->stream, st.as<uint64_t>(), vals[kd], (uint64_t)d.kind_cols[kd] * n);
             GL355_HIP(ctx, hipGetLastError());
             GL355_HIP(ctx, ctx->wait());
         }
@@ -383,7 +377,7 @@ extern "C" int32_t gl355_plonk_check_witness(gl355_ctx* h, const uint64_t* desc,
     GL355_TRY(D((size_t)(n_all + d.n_perm + 1) * 8, &d_ptrs));
     {
         std::vector<const uint64_t*> v;
-        for (uint32_t kd = 0; kd < 3; kd++) for (uint32_t c = 0; c < kind_cols[kd]; c++) v.push_back(col_ptr(kd, c));
+        for (uint32_t kd = 0; kd < 3; kd++) for (uint32_t c = 0; c < d.kind_cols[kd]; c++) v.push_back(col_ptr(kd, c));
         for (auto& pc : d.perm_cols) v.push_back(col_ptr(pc.first, pc.second));
         GL355_TRY(h2d((void*)d_ptrs, v.data(), v.size() * 8));
     }

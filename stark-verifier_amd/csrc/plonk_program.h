@@ -1,5 +1,5 @@
 // The register programs of the PLONK descriptor (include/gl355.h, stark-verifier_amd/halo2.py ProgramBuilder): what the device evaluator
-// (plonk_kernels.cuh) and the host verifier's interpreter (plonk_verifier.cpp) both read.
+// (plonk_kernels.cuh) and the host interpreter (plonk_desc.h, beside the check that licenses both) read.
 #pragma once
 #include <stdint.h>
 

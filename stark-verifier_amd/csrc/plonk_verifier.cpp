@@ -30,8 +30,8 @@
 #include "blinding.cuh"
 #include "host_fr.h"
 #include "host_pairing.h"
+#include "plonk_desc.h"
 #include "plonk_openings.h"
-#include "plonk_program.h"
 
 using namespace gl355;
 
@@ -49,28 +49,16 @@ thread_local double g_stage_ms[3] = {0, 0, 0};          // transcript + expressi
 // constant changes time only.  GL355_PLONK_VERIFY_DEVICE_MSM_MIN in the environment replaces it (include/gl355.h).
 constexpr uint64_t PLONK_VERIFY_DEVICE_MSM_MIN = 83;
 
-constexpr uint64_t PLK_MAGIC = 0x4B4C503535334C47ull;   // "GL355PLK"
-constexpr uint32_t PLK_HDR = 24;
 constexpr uint32_t STREAM_BATCH_WEIGHTS = 0x21, STREAM_PARAMS_POWERS = 0x22, STREAM_PARAMS_LAGRANGE = 0x23;
 
-struct Lookup { std::vector<uint32_t> in_code, tab_code; };
 typedef std::array<uint64_t, 8> G1Words;
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
 
-struct gl355_plonk_vk {
-    uint32_t k = 0, n_advice = 0, n_fixed = 0, n_instance = 0, n_perm = 0, n_lookups = 0, degree = 0, bf = 0, n_gate_polys = 0;
-    uint32_t n_pieces = 0, n_sets = 0, chunk_len = 0;
-    uint64_t n = 0, usable = 0;
-    Fr digest;
-    std::vector<std::pair<uint32_t, uint32_t>> perm_cols;                 // (kind, index)
-    std::vector<uint32_t> perm_query;                                     // the query (of its kind) that reads the column at rotation 0
-    std::vector<std::pair<int32_t, int32_t>> queries[3];                  // (column, rotation)
-    std::vector<Fr> consts;
-    std::vector<uint32_t> gate_code;
-    std::vector<Lookup> lookups;
+struct gl355_plonk_vk : PlkDesc {                                         // the parsed descriptor (plonk_desc.h), and what the verifier adds
+    std::vector<uint32_t> perm_query;                                     // plk_perm_queries: the query (of its kind) that reads the column at rotation 0
     std::vector<uint64_t> key_points;                                     // fixed | sigma commitments | [1] G1, affine
     uint64_t s_g2[16];
 };
@@ -87,12 +75,9 @@ struct Reader {
     uint64_t len, pos = 0;
     KeccakTranscript tr;
     const char* err = nullptr;
-    static void from_be(const uint8_t* b, uint64_t w[4]) {
-        for (int i = 0; i < 4; i++) { w[i] = 0; for (int j = 0; j < 8; j++) w[i] |= (uint64_t)b[31 - (8 * i + j)] << (8 * j); }
-    }
     bool point(G1Words& out) {
         if (len - pos < 64) { err = "proof too short (point)"; return false; }
-        from_be(p + pos, out.data()); from_be(p + pos + 32, out.data() + 4);
+        KeccakTranscript::from_be32(p + pos, out.data()); KeccakTranscript::from_be32(p + pos + 32, out.data() + 4);
         if (!bn254_g1_valid_host(out.data())) { err = "a point of the proof is not canonical or not on the curve"; return false; }
         tr.buf.insert(tr.buf.end(), p + pos, p + pos + 64);
         pos += 64;
@@ -101,7 +86,7 @@ struct Reader {
     bool scalar(Fr& out) {
         if (len - pos < 32) { err = "proof too short (scalar)"; return false; }
         uint64_t w[4];
-        from_be(p + pos, w);
+        KeccakTranscript::from_be32(p + pos, w);
         if (Fr::geq_m(w)) { err = "a scalar of the proof is not below r"; return false; }
         out = Fr::from_words(w);
         tr.buf.insert(tr.buf.end(), p + pos, p + pos + 32);
@@ -121,31 +106,6 @@ void batch_invert(std::vector<Fr>& v) {                 // Montgomery's trick; a
         acc = acc * v[i];
         v[i] = t;
     }
-}
-
-// the descriptor's register programs (include/gl355.h) at one point: ev[kind][query] are the claimed evaluations
-Fr run_program(const gl355_plonk_vk* vk, const std::vector<uint32_t>& code, const std::vector<Fr> ev[3], const Fr& fold) {
-    Fr regs[PLK_MAX_REGS];
-    for (auto& r : regs) r = Fr::zero();
-    Fr acc = Fr::zero();
-    auto operand = [&](uint32_t o) -> Fr {
-        const uint32_t kind = o >> 24, idx = o & 0xFFFFFFu;
-        if (kind == PLK_K_REG) return regs[idx];
-        if (kind == PLK_K_CONST) return vk->consts[idx];
-        return ev[kind - PLK_K_ADVICE][idx];
-    };
-    for (size_t pc = 0; pc < code.size() / 4; pc++) {
-        const uint32_t op = code[4 * pc], dst = code[4 * pc + 1];
-        const Fr x = operand(code[4 * pc + 2]);
-        if (op == PLK_OP_EMIT) { acc = acc * fold + x; continue; }
-        if (op == PLK_OP_NEG) regs[dst] = x.neg();
-        else if (op == PLK_OP_MOV) regs[dst] = x;
-        else {
-            const Fr y = operand(code[4 * pc + 3]);
-            regs[dst] = op == PLK_OP_ADD ? x + y : (op == PLK_OP_SUB ? x - y : x * y);
-        }
-    }
-    return acc;
 }
 
 // What one proof leaves for the group work: L + u h2 = sum_i proof_scalars[i] proof_points[i] + sum_j key_scalars[j] key_points[j], and h2
@@ -241,7 +201,7 @@ bool prepare(const gl355_plonk_vk* vk, const uint64_t* instances, const uint32_t
     }
     const Fr l_active = one - l_last - l_blind;
     // ---- the quotient's evaluation, folded with y in the prover's order
-    Fr acc = run_program(vk, vk->gate_code, ev, y);
+    Fr acc = plk_run_program(*vk, vk->gate_code, ev, y);
     if (vk->n_sets) {
         acc = acc * y + l_0 * (one - perm_ev[0].z);
         const Fr zl = perm_ev[vk->n_sets - 1].z;
@@ -262,7 +222,7 @@ bool prepare(const gl355_plonk_vk* vk, const uint64_t* instances, const uint32_t
     }
     for (uint32_t l = 0; l < vk->n_lookups; l++) {
         const LookupEv& e = lk_ev[l];
-        const Fr a_in = run_program(vk, vk->lookups[l].in_code, ev, theta), s_in = run_program(vk, vk->lookups[l].tab_code, ev, theta);
+        const Fr a_in = plk_run_program(*vk, vk->lookups[l].in_code, ev, theta), s_in = plk_run_program(*vk, vk->lookups[l].tab_code, ev, theta);
         acc = acc * y + l_0 * (one - e.z);
         acc = acc * y + l_last * (e.z * e.z - e.z);
         acc = acc * y + (e.z_next * (e.a + beta) * (e.s + gamma) - e.z * (a_in + beta) * (s_in + gamma)) * l_active;
@@ -462,77 +422,11 @@ int32_t gl355_plonk_vk_create(const uint64_t* desc, uint64_t words, const uint64
                               gl355_plonk_vk** out) {
     if (!desc || !s_g2 || !out || words < PLK_HDR) return bad_arg("plonk_vk_create: null or truncated argument");
     *out = nullptr;
-    if (desc[0] != PLK_MAGIC || desc[1] != 1) return bad_arg("plonk_vk_create: not a version-1 gl355 PLONK descriptor");
     std::unique_ptr<gl355_plonk_vk> vk(new (std::nothrow) gl355_plonk_vk());
     if (!vk) return GL355_E_OOM;
-    vk->k = (uint32_t)desc[2]; vk->n_advice = (uint32_t)desc[3]; vk->n_fixed = (uint32_t)desc[4]; vk->n_instance = (uint32_t)desc[5];
-    vk->n_perm = (uint32_t)desc[6]; vk->n_lookups = (uint32_t)desc[7]; vk->degree = (uint32_t)desc[8]; vk->bf = (uint32_t)desc[9];
-    const uint64_t nq[3] = {desc[10], desc[11], desc[12]}, n_consts = desc[13], gate_len = desc[14];
-    vk->n_gate_polys = (uint32_t)desc[15];
-    for (int i = 2; i < 16; i++) if (desc[i] >> 32) return bad_arg("plonk_vk_create: implausible circuit shape");
-    if (vk->k < 3 || vk->k > 28 || vk->n_advice > 256 || vk->n_fixed > 256 || vk->n_instance > 16 || vk->n_perm > 256 || vk->n_lookups > 64 || vk->degree < 3 ||
-        vk->degree > 10 || vk->bf < 3 || vk->bf > 64 || nq[0] > 1024 || nq[1] > 1024 || nq[2] > 64 || n_consts > 4096 || gate_len > (1u << 20))
-        return bad_arg("plonk_vk_create: implausible circuit shape");
-    vk->n = 1ull << vk->k;
-    if (vk->n < vk->bf + 3ull) return bad_arg("plonk_vk_create: fewer rows than the blinding needs");
-    vk->usable = vk->n - (vk->bf + 1);
-    vk->n_pieces = vk->degree - 1;
-    vk->chunk_len = vk->degree - 2;
-    vk->n_sets = vk->n_perm ? (vk->n_perm + vk->chunk_len - 1) / vk->chunk_len : 0;
+    if (const char* what = plk_parse_desc(desc, words, PLK_MAX_K_VERIFIER, *vk)) { g_error = std::string("plonk_vk_create: ") + what; return GL355_E_INVALID_ARG; }
     if ((vk->n_fixed && !fixed_c) || (vk->n_perm && !sigma_c)) return bad_arg("plonk_vk_create: commitments missing");
-    const uint64_t* p = desc + PLK_HDR;
-    const uint64_t* end = desc + words;
-    auto need = [&](uint64_t w) { return (uint64_t)(end - p) >= w; };
-    if (!need(vk->n_perm)) return bad_arg("plonk_vk_create: truncated descriptor");
-    const uint32_t kind_cols[3] = {vk->n_advice, vk->n_fixed, vk->n_instance};
-    for (uint32_t j = 0; j < vk->n_perm; j++, p++) {
-        const uint32_t kind = (uint32_t)(*p >> 32), idx = (uint32_t)*p;
-        if (kind > 2 || idx >= kind_cols[kind]) return bad_arg("plonk_vk_create: bad permutation column");
-        vk->perm_cols.push_back({kind, idx});
-    }
-    for (int kd = 0; kd < 3; kd++) {
-        if (!need(nq[kd])) return bad_arg("plonk_vk_create: truncated descriptor");
-        for (uint64_t q = 0; q < nq[kd]; q++, p++) {
-            const int32_t col = (int32_t)(*p >> 32), rot = (int32_t)(uint32_t)*p;
-            if (col < 0 || (uint32_t)col >= kind_cols[kd] || rot < -(int32_t)vk->bf - 1 || rot > (int32_t)vk->bf + 1) return bad_arg("plonk_vk_create: bad query");
-            vk->queries[kd].push_back({col, rot});
-        }
-    }
-    if (!need(4 * n_consts)) return bad_arg("plonk_vk_create: truncated descriptor");
-    for (uint64_t c = 0; c < n_consts; c++, p += 4) vk->consts.push_back(Fr::from_words(p));
-    auto read_code = [&](uint64_t len, std::vector<uint32_t>& code) -> bool {
-        if (!need(2 * len)) return false;
-        code.resize(4 * len);
-        if (len) memcpy(code.data(), p, 16 * len);
-        p += 2 * len;
-        for (uint64_t i = 0; i < len; i++) {                  // every operand in range: the interpreter trusts its program
-            const uint32_t op = code[4 * i], dst = code[4 * i + 1];
-            if (op > PLK_OP_MOV || dst >= PLK_MAX_REGS) return false;
-            for (int o = 0; o < (op == PLK_OP_ADD || op == PLK_OP_SUB || op == PLK_OP_MUL ? 2 : 1); o++) {
-                const uint32_t v = code[4 * i + 2 + o], kind = v >> 24, idx = v & 0xFFFFFFu;
-                if (kind == PLK_K_REG ? idx >= PLK_MAX_REGS : (kind == PLK_K_CONST ? idx >= n_consts : (kind > PLK_K_INSTANCE || idx >= nq[kind - PLK_K_ADVICE]))) return false;
-            }
-        }
-        return true;
-    };
-    if (!read_code(gate_len, vk->gate_code)) return bad_arg("plonk_vk_create: bad gate program");
-    for (uint32_t l = 0; l < vk->n_lookups; l++) {
-        if (!need(2)) return bad_arg("plonk_vk_create: truncated descriptor");
-        const uint64_t li = p[0], lt = p[1];
-        p += 2;
-        Lookup lk;
-        if (li > (1u << 16) || lt > (1u << 16) || !read_code(li, lk.in_code) || !read_code(lt, lk.tab_code)) return bad_arg("plonk_vk_create: bad lookup program");
-        vk->lookups.push_back(std::move(lk));
-    }
-    if (p != end) return bad_arg("plonk_vk_create: descriptor length does not match its header");
-    // the permutation argument reads every equality column at x
-    for (auto& pc : vk->perm_cols) {
-        uint32_t found = ~0u;
-        const auto& qs = vk->queries[pc.first];
-        for (uint32_t q = 0; q < qs.size() && found == ~0u; q++) if (qs[q].first == (int32_t)pc.second && qs[q].second == 0) found = q;
-        if (found == ~0u) return bad_arg("plonk_vk_create: a permutation column is not queried at the current rotation");
-        vk->perm_query.push_back(found);
-    }
+    if (!plk_perm_queries(*vk, vk->perm_query)) return bad_arg("plonk_vk_create: a permutation column is not queried at the current rotation");
     // the key's points
     vk->key_points.assign(8ull * (vk->n_fixed + vk->n_perm + 1), 0);
     if (vk->n_fixed) memcpy(vk->key_points.data(), fixed_c, 64ull * vk->n_fixed);
@@ -544,20 +438,8 @@ int32_t gl355_plonk_vk_create(const uint64_t* desc, uint64_t words, const uint64
     if (const char* why = bn254_g2_invalid(s_g2, true)) { g_error = std::string("plonk_vk_create: s_g2: ") + why; return GL355_E_INVALID_ARG; }
     if (all_zero(s_g2, 16)) return bad_arg("plonk_vk_create: s_g2 is the identity");
     memcpy(vk->s_g2, s_g2, 128);
-    // the transcript's initial scalar: as given, the header's, or keygen's pinned-key rule (plonk_bn254.hip)
-    if (digest) vk->digest = Fr::from_words(digest);
-    else if (desc[16] | desc[17] | desc[18] | desc[19]) vk->digest = Fr::from_words(desc + 16);
-    else {
-        const size_t kb = 64ull * (vk->n_fixed + vk->n_perm);
-        std::vector<uint8_t> pre((size_t)words * 8 + kb);
-        memcpy(pre.data(), desc, (size_t)words * 8);
-        memcpy(pre.data() + (size_t)words * 8, vk->key_points.data(), kb);
-        uint8_t hsh[32];
-        keccak256_host(pre.data(), pre.size(), hsh);
-        uint64_t w[4];
-        Reader::from_be(hsh, w);
-        vk->digest = Fr::from_words(w);
-    }
+    // the transcript's initial scalar: as given, or what keygen takes (the header's, else the pinned-key rule)
+    vk->digest = digest ? Fr::from_words(digest) : plk_pinned_digest(desc, words, fixed_c, sigma_c, *vk);
     *out = vk.release();
     return GL355_OK;
 }

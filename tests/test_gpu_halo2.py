@@ -197,7 +197,8 @@ def test_commit_columns_entry(ctx):
 
 def test_malformed_descriptors_are_refused(gl, ctx):
     """gl355_plonk_keygen on untrusted descriptors: wrong magic, truncation, a program operand out of range, a permutation column that is never
-    queried, an implausible shape -- an error code every time, never a crash"""
+    queried, an implausible shape -- an error code every time, never a crash; the host tests' mutation list with the parser's own text for each
+    refusal, and k = 25, which only the verifier takes"""
     import ctypes as C
     k = 7
     cs, cfg, w = ch.synthetic_circuit(k, table_bits=5, n_permutations=1)
@@ -232,6 +233,36 @@ def test_malformed_descriptors_are_refused(gl, ctx):
     assert keygen(bad) == -1
     bad = desc.copy(); bad[24] = (np.uint64(7) << np.uint64(32))     # permutation column of kind 7
     assert keygen(bad) == -1
+
+    # the mutation list the host tests share (tests/plonk_desc_cases.py), over two other circuits' descriptors: every refusal is -1 with the
+    # parser's text (csrc/plonk_desc.h), and comes before any of the other arguments is looked at
+    import plonk_desc_cases as pdc
+
+    def last_error():
+        return (ctx.lib.gl355_last_error(ctx.h) or b"").decode()
+    refused = 0
+    for kk, (cs2, _) in ((6, random_circuit(6, 0)), (7, plonk_with_tuple_lookup(7, 5))):
+        for what, m in pdc.mutations([int(x) for x in h2.export_desc(cs2, kk, 0)], pdc.MAX_K_DEVICE):
+            want = "null or truncated argument" if len(m) < pdc.HDR else pdc.verdict(m, pdc.MAX_K_DEVICE)       # the entry's own pre-check comes first
+            if want is None:
+                continue                                             # well-formed: the key of a circuit this test has no columns for
+            d, h = np.array(m + [0], dtype=np.uint64), C.c_void_p()
+            rc = ctx.lib.gl355_plonk_keygen(ctx.h, d.ctypes.data, len(m), g.ctypes.data, gl_.ctypes.data, fixed.ctypes.data, mapping.ctypes.data, C.byref(h))
+            assert (rc, last_error(), h.value) == (-1, "plonk_keygen: " + want, None), what
+            refused += 1
+    assert refused > 1000
+    # k = 25 is a verifier's circuit only: nothing of 2^25 rows goes to the device
+    bad = desc.copy(); bad[2] = 25
+    assert keygen(bad) == -1 and last_error() == "plonk_keygen: implausible circuit shape"
+    total = C.c_uint64(0)
+    inst, lens = h2.to_limbs(w.instance[0]), np.array([len(w.instance[0]), 0], dtype=np.uint32)
+
+    def check_witness(d):
+        return ctx.lib.gl355_plonk_check_witness(ctx.h, d.ctypes.data, d.size, fixed.ctypes.data, mapping.ctypes.data, w.advice.ctypes.data, inst.ctypes.data, lens.ctypes.data,
+                                                 None, 0, C.byref(total), None)
+    assert check_witness(bad) == -1 and last_error() == "plonk_check_witness: implausible circuit shape"
+    assert check_witness(desc) == 0 and total.value == 0
+
     m2 = mapping.copy(); m2[0, 0, 1] = 1 << 20                       # a sigma pointing outside the domain
     h = C.c_void_p()
     assert ctx.lib.gl355_plonk_keygen(ctx.h, desc.ctypes.data, desc.size, g.ctypes.data, gl_.ctypes.data, fixed.ctypes.data, m2.ctypes.data, C.byref(h)) == -1

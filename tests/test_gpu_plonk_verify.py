@@ -97,6 +97,25 @@ def test_product_proofs_verify(ctx, s_g2, keys, kind, k):
     assert vk.last_error
 
 
+@pytest.mark.parametrize("kind", ["chip", "tuple"])
+def test_keygen_and_vk_create_derive_one_digest(ctx, s_g2, keys, kind):
+    """a zero digest field: gl355_plonk_pk_digest after keygen == vk_digest over the key's own commitments == what gl355_plonk_vk_create
+    derives from the same descriptor and commitments (one rule, csrc/plonk_desc.h).  The verifying key keeps its digest to itself, so the
+    last is read off its verdicts: the proof verifies under the key from the proving key, under the key made with no digest argument and
+    under the one given vk_digest, and not under the one given another digest"""
+    k = 7
+    key = keys(kind, k)
+    cs, w, prover, proof = key.cs, key.w, key.prover, key.proof
+    assert not prover.desc[16:20].any()
+    digest = h2.vk_digest(cs, k, prover.fixed_commitments, prover.sigma_commitments, hv.keccak256)
+    assert prover.digest == digest
+    assert key.vk.verify(w.instance, proof), key.vk.last_error                       # gl355_plonk_vk_from_pk
+    for given, want in ((None, True), (digest, True), ((digest + 1) % R, False)):
+        made = h2.PlonkVerifier(cs, k, prover.fixed_commitments, prover.sigma_commitments, s_g2, digest=given)      # gl355_plonk_vk_create
+        assert made.verify(w.instance, proof) is want, (given, made.last_error)
+        made.close()
+
+
 def test_verdicts_equal_the_restated_verifier(ctx, keys):
     k = 7
     key = keys("random", k)

@@ -150,6 +150,49 @@ def test_malformed_calls_are_error_codes():
     assert not native.verify(w.instance, proof[:100])
 
 
+def test_malformed_descriptors_are_error_codes():
+    """the mutation list of tests/plonk_desc_cases.py through gl355_plonk_vk_create: -1 and the parser's text (csrc/plonk_desc.h) for every
+    refusal, a key for everything else; k = 28 is a verifier's circuit, k = 29 is not; the digest the key derives is vk_digest"""
+    import ctypes as C
+    import plonk_desc_cases as pdc
+    _lib = importlib.import_module("stark-verifier_amd._lib")
+    lib = _lib.load()
+    s_g2 = h2.g2_words(h2.kzg_setup_g2(TAU))
+    for name in ("random0", "tuple_lookup"):
+        k, cs, w, vk, proof, native, pk = case(name)
+        desc = [int(x) for x in h2.export_desc(cs, k, 0)]
+        # a mutated header may claim up to 256 columns of either kind: the identity stands for the ones the key does not have
+        fc, sc = np.zeros((256, 8), dtype=np.uint64), np.zeros((256, 8), dtype=np.uint64)
+        fc[:cs.num_fixed], sc[:len(cs.permutation)] = points_to_words(pk.fixed_commitments), points_to_words(pk.sigma_commitments)
+
+        def create(words, digest=None):
+            a, h = np.array(list(words) + [0], dtype=np.uint64), C.c_void_p()
+            d = None if digest is None else h2.to_limbs([digest])[0]
+            rc = lib.gl355_plonk_vk_create(a.ctypes.data, len(words), fc.ctypes.data, sc.ctypes.data, None if d is None else d.ctypes.data, s_g2.ctypes.data, C.byref(h))
+            assert (rc == 0) == bool(h.value)
+            return rc, (lib.gl355_plonk_verify_last_error() or b"").decode(), h
+        answers = {}
+        for what, m in pdc.mutations(desc, pdc.MAX_K_VERIFIER):
+            want = "null or truncated argument" if len(m) < pdc.HDR else pdc.verdict(m, pdc.MAX_K_VERIFIER)      # the entry's own pre-check comes first
+            rc, msg, h = create(m)
+            if rc == 0:
+                lib.gl355_plonk_vk_destroy(h)
+            assert (rc, msg) == ((-1, "plonk_vk_create: " + want) if want else (0, msg)), what
+            answers[what] = rc
+        assert answers["header word 2 = 28"] == 0 and answers["header word 2 = 29"] == -1
+        assert sum(1 for rc in answers.values() if rc == 0) > 200 and sum(1 for rc in answers.values() if rc) > 300
+        # no digest argument and a zero digest field: the transcript starts from vk_digest -- the proof made under it verifies, as it does
+        # under the key that is given that digest, and no longer under a key that is given another
+        digest = h2.vk_digest(cs, k, fc[:cs.num_fixed], sc[:len(cs.permutation)], hv.keccak256)
+        assert digest == vk["digest"]
+        for given, want in ((None, True), (digest, True), (digest + 1, False)):
+            rc, msg, h = create(desc, given)
+            assert rc == 0, msg
+            key = h2.PlonkVerifier(cs, k, None, None, None, _handle=h)
+            assert key.verify(w.instance, proof) == want, given
+            key.close()
+
+
 def test_no_new_export_takes_the_secret():
     """the verifier's exports see [s] G2 only: no parameter of a new entry is called tau (or secret), and the new sources never name one"""
     hdr = open(os.path.join(ROOT, "include", "gl355.h")).read()
