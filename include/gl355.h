@@ -519,8 +519,20 @@ int32_t gl355_witness_replay_segmented(const uint64_t* tape, uint64_t n_ops, uin
  *   bits per FRI layer (1..GL355_MAX_FRI_ARITY_BITS), directly after the 112 header words and before the constants; everything else, the trailing cap of
  *   version 5 included, is laid out as in version 2 / 3.  The loader refuses a table FriLayers could not build: a word of 0 or above 32 bits, a sum above
  *   degree_bits, a layer narrower than the cap (GL355_E_INVALID_ARG), a word above GL355_MAX_FRI_ARITY_BITS (GL355_E_UNSUPPORTED).
- * gl355_circuit_load commits constants_sigmas on `ctx`, re-derives the circuit digest and refuses an artifact whose digest
- * does not match its tables.  The handle is read-only afterwards: any context of the same device may prove with it, concurrently.
+ * Bounds, all checked on the host before anything is allocated (artifact_parse, csrc/circuit_artifact.h, where the words have names: ART_DEGREE_BITS ..
+ * ART_N_SEGS).  Every word is compared as the 64-bit word it is, never its low 32 bits, and every sum is formed in 64 bits.  GL355_E_INVALID_ARG unless noted,
+ * the message is "circuit_load: " and what is wrong:
+ *   [1] 2..5   [2] 1..24   [3] 0..4 and [2] + [3] <= 28 (GL355_E_UNSUPPORTED)   [4] 1..1024   [5] <= [4]   [6] + [7] <= 64   [8] 1..4 (GL355_E_UNSUPPORTED)
+ *   [9] 1..2^32 - 1   [10] = ceil([5] / [9]) - 1   [11] <= 16; of the first [11] gates every word below 2^32 and the table as gl355_circuit asks (above);
+ *   the slots behind them are ignored   [92] <= 20 and <= [2] + [3]   [93], [94], [96] below 2^32   [95] <= 32   [97] 0 or 1
+ *   [98] + [99] <= n and [100] + 2 [101] <= n (n = 2^[2])   [102] <= n   [103] <= 2^28   [104] any   [105] <= 2^20   [110] <= [103]   [111] <= [103]
+ *   the length is exactly what the header adds up to; row_idx < n; public-input positions < n_rows * num_wires; [110] + the segment lengths = [103];
+ *   every tape entry inside the rows and the inputs (csrc/witness_tape.h tape_entry_fits; a tape needs num_wires >= 135).
+ *   What only the prover asks of a circuit (a final polynomial of at least two coefficients, at most 16 partial-product chunks, an LDE of at most 2^27
+ *   points) is refused by the first proof, not here: a handle may serve gl355_circuit_verify alone.
+ * gl355_circuit_load then commits constants_sigmas on `ctx`, re-derives the circuit digest and refuses an artifact whose digest
+ * does not match its tables (versions 3 / 5: whose trailing cap does not match the commitment).  The handle is read-only afterwards: any context of the
+ * same device may prove with it, concurrently.
  *   gl355_semaphore_prove    = fill_semaphore_targets + data.prove (access_set.rs:61-104): witness rows from the member's
  *                              key / topic / Merkle path, proof, public inputs root | nullifier | topic
  *   gl355_circuit_prove_tape = set_proof_with_pis_target + data.prove (recursion.rs:72-86,167-168, wrapper.rs:49-55): inputs =

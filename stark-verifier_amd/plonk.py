@@ -417,6 +417,19 @@ def derive_key(base, index):
     return out.raw
 
 
+# The header words of the circuit artifact (export_blob below; layout in include/gl355.h), under the names of the enum in
+# csrc/circuit_artifact.h, whose artifact_parse judges what is written here.  ART_GATES: 16 gates x {type, param, selector_index,
+# group_start, group_end}; ART_DIGEST: 4 words.
+ARTIFACT_WORDS = dict(
+    ART_MAGIC=0, ART_VERSION=1, ART_DEGREE_BITS=2, ART_RATE_BITS=3, ART_NUM_WIRES=4, ART_NUM_ROUTED_WIRES=5, ART_NUM_CONSTANTS=6, ART_NUM_SELECTORS=7,
+    ART_NUM_CHALLENGES=8, ART_MAX_DEGREE=9, ART_NUM_PARTIAL_PRODUCTS=10, ART_NUM_GATES=11, ART_GATES=12,
+    ART_CAP_HEIGHT=92, ART_POW_BITS=93, ART_NUM_QUERIES=94, ART_N_FRI_LAYERS=95, ART_ZERO_KNOWLEDGE=96, ART_HASHER=97,
+    ART_BLIND_START=98, ART_N_BLIND=99, ART_Z_START=100, ART_N_Z_PAIRS=101, ART_N_ROWS=102, ART_N_OPS=103, ART_N_INPUTS=104, ART_N_PI=105,
+    ART_DIGEST=106, ART_N_SEQ=110, ART_N_SEGS=111, ART_HDR_WORDS=112)
+ARTIFACT_MAGIC = 0x5249433535334c47          # "GL355CIR" little endian
+ARTIFACT_GATE_WORDS = 5
+
+
 class CircuitData:
     """The prover/verifier data of one built circuit (plonky2 CircuitData / CommonCircuitData)."""
 
@@ -473,31 +486,31 @@ class CircuitData:
             require_arity_2(self.fri_arity_bits, "the circuit artifact without wide_arity=True (versions 2 and 3 hold a layer count only)")
         cfg = self.config
         cc = self.c_circuit
-        hdr = np.zeros(112, dtype=np.uint64)
-        hdr[0], hdr[1] = 0x5249433535334c47, 2
-        hdr[2:12] = [cc.degree_bits, cc.rate_bits, cc.num_wires, cc.num_routed_wires, cc.num_constants, cc.num_selectors,
-                     cc.num_challenges, cc.max_degree, cc.num_partial_products, cc.num_gates]
-        for g in range(_lib.MAX_GATES):
-            gt = cc.gates[g]
-            hdr[12 + 5 * g: 17 + 5 * g] = [gt.type, gt.param, gt.selector_index, gt.group_start, gt.group_end]
         start, n_blind, z_pairs, _ = self.blind_rows
         tape = np.zeros((0, 5), dtype=np.uint64) if tape is None else _u64(tape)
         pi_pos = np.zeros(0, dtype=np.uint64) if pi_pos is None else np.asarray(pi_pos, dtype=np.uint64)
         row_idx = np.asarray(row_idx, dtype=np.uint64)
-        hdr[92:106] = [cfg.cap_height, cfg.proof_of_work_bits, cfg.num_query_rounds, len(self.fri_arity_bits), int(cfg.zero_knowledge),
-                       cfg.hasher, start, n_blind, z_pairs[0][0] if z_pairs else 0, len(z_pairs), row_idx.size, tape.shape[0],
-                       n_inputs, pi_pos.size]
-        hdr[106:110] = self.circuit_digest if external_digest is None else _u64(external_digest)
         n_seq, seg_lens = tape_layout if tape_layout is not None else (tape.shape[0], [])
-        hdr[110], hdr[111] = n_seq, len(seg_lens)
-        tail = []
-        if external_digest is not None:
-            hdr[1] = 3
-            tail = [_u64(self.constants_sigmas_cap).reshape(-1)]
-        arity_table = np.zeros(0, dtype=np.uint64)
-        if wide_arity:
-            hdr[1] += 2
-            arity_table = np.array(self.fri_arity_bits, dtype=np.uint64)
+        A = ARTIFACT_WORDS
+        hdr = np.zeros(A["ART_HDR_WORDS"], dtype=np.uint64)
+        for name, value in dict(
+                ART_MAGIC=ARTIFACT_MAGIC, ART_VERSION=2 + (external_digest is not None) + 2 * bool(wide_arity),
+                ART_DEGREE_BITS=cc.degree_bits, ART_RATE_BITS=cc.rate_bits, ART_NUM_WIRES=cc.num_wires, ART_NUM_ROUTED_WIRES=cc.num_routed_wires,
+                ART_NUM_CONSTANTS=cc.num_constants, ART_NUM_SELECTORS=cc.num_selectors, ART_NUM_CHALLENGES=cc.num_challenges, ART_MAX_DEGREE=cc.max_degree,
+                ART_NUM_PARTIAL_PRODUCTS=cc.num_partial_products, ART_NUM_GATES=cc.num_gates,
+                ART_CAP_HEIGHT=cfg.cap_height, ART_POW_BITS=cfg.proof_of_work_bits, ART_NUM_QUERIES=cfg.num_query_rounds,
+                ART_N_FRI_LAYERS=len(self.fri_arity_bits), ART_ZERO_KNOWLEDGE=int(cfg.zero_knowledge), ART_HASHER=cfg.hasher,
+                ART_BLIND_START=start, ART_N_BLIND=n_blind, ART_Z_START=z_pairs[0][0] if z_pairs else 0, ART_N_Z_PAIRS=len(z_pairs),
+                ART_N_ROWS=row_idx.size, ART_N_OPS=tape.shape[0], ART_N_INPUTS=n_inputs, ART_N_PI=pi_pos.size,
+                ART_N_SEQ=n_seq, ART_N_SEGS=len(seg_lens)).items():
+            hdr[A[name]] = value
+        for g in range(_lib.MAX_GATES):
+            gt = cc.gates[g]
+            at = A["ART_GATES"] + ARTIFACT_GATE_WORDS * g
+            hdr[at:at + ARTIFACT_GATE_WORDS] = [gt.type, gt.param, gt.selector_index, gt.group_start, gt.group_end]
+        hdr[A["ART_DIGEST"]:A["ART_DIGEST"] + 4] = self.circuit_digest if external_digest is None else _u64(external_digest)
+        tail = [_u64(self.constants_sigmas_cap).reshape(-1)] if external_digest is not None else []
+        arity_table = np.array(self.fri_arity_bits if wide_arity else [], dtype=np.uint64)
         return np.concatenate([hdr, arity_table, _u64(self.constants).reshape(-1), _u64(self.sigmas).reshape(-1), _u64(self.k_is), row_idx,
                                pi_pos, tape.reshape(-1), np.asarray(seg_lens, dtype=np.uint64)] + tail)
 
