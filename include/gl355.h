@@ -48,6 +48,7 @@ extern "C" {
 
 typedef struct gl355_ctx gl355_ctx;
 typedef struct gl355_oracle gl355_oracle; /* a committed polynomial batch resident in HBM */
+typedef struct gl355_merkle_tree gl355_merkle_tree; /* MerkleTree { leaves, digests, cap } resident in HBM, bound to its context like a gl355_oracle */
 
 /* ---- context ------------------------------------------------------------------------------ */
 /* Process-level runtime settings for the many-provers-per-GPU regime of the reference's rayon loop (recursion.rs:214-227,
@@ -80,9 +81,12 @@ enum { GL355_OPT_MERKLE_LANES_LOG = 1,
        GL355_OPT_BATCH_UNITS = 5,       /* 1..GL355_MAX_UNITS (default 8): units gl355_semaphore_units proves in lock-step per context */
        GL355_OPT_DEVICE_REPLAY = 6,     /* != 0 (default): gl355_semaphore_units generates the recursive circuit's witness rows on the
                                            device (tape interpreter kernel) instead of on host threads; same rows, same failures */
-       GL355_OPT_LEAF_LANES_LOG = 7 };  /* 0..31 (default 16): a FRI layer that folds by 4, 8 or 16 (leaves of 8, 16 or 32 words, Poseidon hasher) and has
+       GL355_OPT_LEAF_LANES_LOG = 7,    /* 0..31 (default 16): a FRI layer that folds by 4, 8 or 16 (leaves of 8, 16 or 32 words, Poseidon hasher) and has
                                            fewer than 2^value leaves over all units of the launch hashes them 16 lanes per leaf, straight from the value
                                            columns; at or above, and with 0 always, one lane per leaf from the copied leaf array */
+       GL355_OPT_MERKLE_UPDATE_FULL_LOG = 8 }; /* 0..31 (default 4): gl355_merkle_tree_update of at least n_leaves >> value different leaves writes them and
+                                           rebuilds every level of the tree instead of planning and walking the dirty paths (31: always, 0: only when every
+                                           leaf changes); the crossover is measured in profiles/merkle_update.txt */
 int32_t gl355_ctx_set_option(gl355_ctx* ctx, int32_t option, int64_t value);
 const char* gl355_last_error(gl355_ctx* ctx);
 const char* gl355_version(void);
@@ -207,6 +211,33 @@ int32_t gl355_merkle_build_h(gl355_ctx* ctx, int32_t hasher, const uint64_t* lea
 /* siblings leaf -> cap: (log2(n_leaves) - cap_height) x 4 u64 (host buffer) */
 int32_t gl355_merkle_prove(gl355_ctx* ctx, const uint64_t* digests, uint64_t n_leaves, uint32_t cap_height,
                            uint64_t leaf_index, uint64_t* siblings);
+
+/* ---- a resident, updatable tree: the access set of access_set.rs:25,194-205 (2^20 .. 2^25 members) kept in HBM, so that admitting, replacing or
+ * revoking members costs their paths (height permutations each), not MerkleTree::new over every member and a download of every digest.
+ * create     MerkleTree::new::<F, H>(leaves, cap_height) as gl355_merkle_build_h, leaves (host or device, n_leaves x leaf_len row-major, n_leaves a
+ *            power of two) copied into the handle.  The handle belongs to ctx (its stream, its memory pool) and is destroyed before it; one thread at
+ *            a time uses a handle, like its context.
+ * info       any out pointer may be NULL.
+ * cap / digests / leaves / prove_batch   return host data and therefore wait for the stream.  digests: plonky2's layout, as gl355_merkle_build writes it
+ *            (2 (n_leaves - 2^cap_height) x 4); leaves: leaf indices[j] into row j of n_idx x leaf_len, or with indices == NULL all n_leaves rows (n_idx
+ *            is ignored); prove_batch: MerkleTree::prove(indices[j]) (circuit.rs:91) into n_idx x layers x 4, layers = log2(n_leaves) - cap_height,
+ *            one gather kernel and one copy for the whole batch.  Indices may repeat; one >= n_leaves is GL355_E_INVALID_ARG.
+ * update     leaf indices[j] becomes new_leaves row j, for j = 0 .. n_idx - 1 in order: a repeated index keeps its LAST row.  Afterwards leaves,
+ *            digests and cap are byte for byte what gl355_merkle_build_h gives on the updated leaf array.  Only the nodes above a changed leaf are
+ *            hashed again (or, from n_leaves >> GL355_OPT_MERKLE_UPDATE_FULL_LOG different leaves on, every level).  n_idx == 0 is a no-op; an index
+ *            >= n_leaves is GL355_E_INVALID_ARG with the tree untouched: every index is checked before anything is enqueued.  indices and new_leaves
+ *            are host memory; nothing is staged in the handle: the call uploads new_leaves as they are and the planned indices from memory of its
+ *            own, and ENDS WITH A STREAM SYNC, so both outlive the kernels that read them and the caller's arrays are free on return.
+ * NULL pointers are GL355_E_INVALID_ARG; nothing aborts. */
+int32_t gl355_merkle_tree_create(gl355_ctx* ctx, int32_t hasher, const uint64_t* leaves, uint64_t n_leaves, uint32_t leaf_len, uint32_t cap_height,
+                                 gl355_merkle_tree** out);
+int32_t gl355_merkle_tree_destroy(gl355_merkle_tree* tree);
+int32_t gl355_merkle_tree_info(const gl355_merkle_tree* tree, uint64_t* n_leaves, uint32_t* leaf_len, uint32_t* cap_height, int32_t* hasher);
+int32_t gl355_merkle_tree_cap(const gl355_merkle_tree* tree, uint64_t* cap);
+int32_t gl355_merkle_tree_digests(const gl355_merkle_tree* tree, uint64_t* digests);
+int32_t gl355_merkle_tree_leaves(const gl355_merkle_tree* tree, const uint64_t* indices, uint64_t n_idx, uint64_t* leaves);
+int32_t gl355_merkle_tree_update(gl355_merkle_tree* tree, const uint64_t* indices, uint64_t n_idx, const uint64_t* new_leaves);
+int32_t gl355_merkle_tree_prove_batch(const gl355_merkle_tree* tree, const uint64_t* indices, uint64_t n_idx, uint64_t* siblings);
 
 /* ---- a4 (+a14): PolynomialBatch::from_values / from_coeffs (4x per proof) ---------------------
  * values: batch columns of n (column-major), evaluations on <omega_n> (is_coeffs = 0) or
@@ -588,6 +619,13 @@ int32_t gl355_semaphore_units(gl355_ctx* const* ctxs, uint32_t n_ctx, const gl35
                               const uint64_t* private_keys, uint64_t n_members, const uint64_t topic[4], const uint64_t* tree_digests,
                               const uint64_t* member_indices, uint32_t count, const uint8_t* key_base, uint64_t* leaves_out,
                               uint64_t* proofs_out, uint32_t* units_per_ctx);
+/* The same over a resident access set: `tree` (cap height 0, leaves of 4 words, GL355_HASH_POSEIDON: anything else is GL355_E_INVALID_ARG) takes the
+ * place of n_members and tree_digests.  The paths of all `count` units are fetched by one gl355_merkle_tree_prove_batch on the tree's own context before
+ * the worker threads start; the workers are those of gl355_semaphore_units and never touch the tree, so it need not belong to one of ctxs. */
+int32_t gl355_semaphore_units_tree(gl355_ctx* const* ctxs, uint32_t n_ctx, const gl355_circuit_handle* sem, const gl355_circuit_handle* rec,
+                                   const uint64_t* private_keys, const gl355_merkle_tree* tree, const uint64_t topic[4],
+                                   const uint64_t* member_indices, uint32_t count, const uint8_t* key_base, uint64_t* leaves_out,
+                                   uint64_t* proofs_out, uint32_t* units_per_ctx);
 
 /* recursion.rs:187-247 `aggregate` as ONE native call: the binary aggregation tree over n_leaves = 2^n_levels proofs of one circuit (the
  * reference's benchmark flow, README.md:167-177).  levels[l] = the circuit verifying two proofs of tree level l (level 0: the leaves), each

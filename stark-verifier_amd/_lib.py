@@ -122,6 +122,14 @@ SIGNATURES = {
     "gl355_two_to_one": (C.c_int32, [vp, vp, vp, C.c_uint64, vp]),
     "gl355_merkle_build": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
     "gl355_merkle_prove": (C.c_int32, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp]),
+    "gl355_merkle_tree_create": (C.c_int32, [vp, C.c_int32, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "gl355_merkle_tree_destroy": (C.c_int32, [vp]),
+    "gl355_merkle_tree_info": (C.c_int32, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+    "gl355_merkle_tree_cap": (C.c_int32, [vp, vp]),
+    "gl355_merkle_tree_digests": (C.c_int32, [vp, vp]),
+    "gl355_merkle_tree_leaves": (C.c_int32, [vp, vp, C.c_uint64, vp]),
+    "gl355_merkle_tree_update": (C.c_int32, [vp, vp, C.c_uint64, vp]),
+    "gl355_merkle_tree_prove_batch": (C.c_int32, [vp, vp, C.c_uint64, vp]),
     "gl355_commit_h": (C.c_int32, [vp, C.c_int32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, vp, C.c_uint32, C.POINTER(vp)]),
     "gl355_commit": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, vp, C.c_uint32, C.POINTER(vp)]),
     "gl355_oracle_destroy": (C.c_int32, [vp]),
@@ -166,6 +174,7 @@ SIGNATURES = {
     "gl355_circuit_prove_tape_units": (C.c_int32, [vp, vp, C.c_uint32, vp, C.c_uint64, vp, vp, vp]),
     "gl355_semaphore_prove_units": (C.c_int32, [vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, vp, vp]),
     "gl355_semaphore_units": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
+    "gl355_semaphore_units_tree": (C.c_int32, [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp]),
     "gl355_semaphore_witness": (C.c_int32, [vp, vp, C.c_uint64, vp, C.c_uint32, vp, vp]),
     "gl355_witness_replay_segmented": (C.c_int32, [vp, C.c_uint64, C.c_uint64, vp, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32,
                                                    C.POINTER(C.c_uint64)]),

@@ -346,6 +346,79 @@ class MerkleTree:
         return sib
 
 
+class DeviceMerkleTree:
+    """MerkleTree { leaves, digests, cap } resident in HBM (gl355_merkle_tree): leaves are replaced in place at the cost of their
+    paths, paths are read in batches; `cap`, `digests` and `leaves` download what they name."""
+
+    def __init__(self, ctx, leaves, cap_height, hasher=HASH_POSEIDON):
+        lv = _u64(leaves)
+        n, leaf_len = lv.shape
+        self.ctx, self.cap_height, self.n_leaves, self.leaf_len = ctx, cap_height, n, leaf_len
+        self.hasher = getattr(hasher, "ID", hasher)
+        self.layers = (int(n).bit_length() - 1) - cap_height
+        h = C.c_void_p()
+        ctx.check(ctx.lib.gl355_merkle_tree_create(ctx.h, self.hasher, _ptr(lv), n, leaf_len, cap_height, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):      # as PolynomialBatch.close: the memory belongs to the context's pool
+                self.ctx.lib.gl355_merkle_tree_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self, indices, leaves):
+        """leaf indices[j] <- leaves[j], in order (a repeated index keeps its last leaf)"""
+        idx = _u64(indices).reshape(-1)
+        lv = _u64(leaves).reshape(idx.size, self.leaf_len)
+        self.ctx.check(self.ctx.lib.gl355_merkle_tree_update(self.h, _ptr(idx), idx.size, _ptr(lv)))
+
+    @property
+    def cap(self):
+        out = np.empty((1 << self.cap_height, 4), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.gl355_merkle_tree_cap(self.h, _ptr(out)))
+        return out
+
+    @property
+    def digests(self):
+        out = np.empty((2 * (self.n_leaves - (1 << self.cap_height)), 4), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.gl355_merkle_tree_digests(self.h, _ptr(out)))
+        return out
+
+    @property
+    def leaves(self):
+        out = np.empty((self.n_leaves, self.leaf_len), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.gl355_merkle_tree_leaves(self.h, None, 0, _ptr(out)))
+        return out
+
+    def get_batch(self, indices):
+        idx = _u64(indices).reshape(-1)
+        out = np.empty((idx.size, self.leaf_len), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.gl355_merkle_tree_leaves(self.h, _ptr(idx), idx.size, _ptr(out)))
+        return out
+
+    def get(self, i):
+        return self.get_batch([i])[0]
+
+    def prove_batch(self, indices):
+        """MerkleTree::prove of every index: [len(indices)][layers][4], one kernel and one copy"""
+        idx = _u64(indices).reshape(-1)
+        sib = np.empty((idx.size, self.layers, 4), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.gl355_merkle_tree_prove_batch(self.h, _ptr(idx), idx.size, _ptr(sib)))
+        return sib
+
+    def prove(self, leaf_index):
+        return self.prove_batch([leaf_index])[0]
+
+    def to_host(self):
+        return MerkleTree._from_parts(self.ctx, self.leaves, self.digests, self.cap, self.cap_height)
+
+
 class PolynomialBatch:
     """plonky2::fri::oracle::PolynomialBatch, resident in HBM (gl355_oracle)."""
 

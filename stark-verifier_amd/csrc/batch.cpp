@@ -13,15 +13,30 @@
 
 using namespace gl355;
 
-extern "C" int32_t gl355_semaphore_units(gl355_ctx* const* ctxs, uint32_t n_ctx, const gl355_circuit_handle* sem, const gl355_circuit_handle* rec,
-                                         const uint64_t* private_keys, uint64_t n_members, const uint64_t topic[4], const uint64_t* tree_digests,
-                                         const uint64_t* member_indices, uint32_t count, const uint8_t* key_base, uint64_t* leaves_out,
-                                         uint64_t* proofs_out, uint32_t* units_per_ctx) {
-    if (!ctxs || n_ctx == 0 || !sem || !private_keys || !topic || (!tree_digests && n_members > 1) || (!member_indices && count) || !leaves_out)
-        return GL355_E_INVALID_ARG;
-    for (uint32_t t = 0; t < n_ctx; t++)
-        if (!ctxs[t]) return GL355_E_INVALID_ARG;
-    if (n_members == 0 || (n_members & (n_members - 1))) return ctx_of(ctxs[0])->fail(GL355_E_INVALID_ARG, "semaphore_units: the access set must hold a power-of-two number of members");
+namespace {
+
+// Where a unit's Merkle path comes from: the host copy of the access-set tree's digests (gl355_semaphore_units walks it per unit, MerkleTree::prove
+// on the plonky2 layout, cap height 0), or the paths of all units fetched from a resident tree before the workers start (gl355_semaphore_units_tree)
+struct SiblingSource {
+    const uint64_t* digests = nullptr;      // host, plonky2 layout
+    const uint64_t* paths = nullptr;        // host, [count][height][4]: unit j's path
+    void fill(uint64_t* sib, uint32_t j, uint64_t idx, uint32_t height) const {
+        if (paths) { memcpy(sib, paths + (size_t)j * height * 4, (size_t)height * 32); return; }
+        uint64_t pair = idx;
+        for (uint32_t i = 0; i < height; i++) {
+            const uint64_t parity = pair & 1;
+            pair >>= 1;
+            const uint64_t slot = (pair << (i + 1)) + (1ull << i) - 1;
+            memcpy(sib + (size_t)i * 4, digests + (2 * slot + (1 - parity)) * 4, 32);
+        }
+    }
+};
+
+// the batch runtime behind both entry points; the pointers are checked by the callers
+int32_t semaphore_units_run(gl355_ctx* const* ctxs, uint32_t n_ctx, const gl355_circuit_handle* sem, const gl355_circuit_handle* rec,
+                            const uint64_t* private_keys, uint64_t n_members, const uint64_t topic[4], const SiblingSource& siblings,
+                            const uint64_t* member_indices, uint32_t count, const uint8_t* key_base, uint64_t* leaves_out,
+                            uint64_t* proofs_out, uint32_t* units_per_ctx) {
     uint32_t height = 0;
     while ((1ull << height) < n_members) height++;
     uint64_t sem_words = 0, rec_words = 0, rec_inputs = 0;
@@ -127,14 +142,7 @@ extern "C" int32_t gl355_semaphore_units(gl355_ctx* const* ctxs, uint32_t n_ctx,
                     idxs[b] = idx;
                     memcpy(&sks[4 * b], private_keys + 4 * idx, 32);
                     memcpy(&topics[4 * b], topic, 32);
-                    // MerkleTree::prove on the plonky2 digest layout (cap height 0: one tree)
-                    uint64_t pair = idx;
-                    for (uint32_t i = 0; i < height; i++) {
-                        const uint64_t parity = pair & 1;
-                        pair >>= 1;
-                        const uint64_t slot = (pair << (i + 1)) + (1ull << i) - 1;
-                        memcpy(&sib[((size_t)b * height + i) * 4], tree_digests + (2 * slot + (1 - parity)) * 4, 32);
-                    }
+                    siblings.fill(&sib[(size_t)b * height * 4], j, idx, height);
                     // per-proof blinding keys: derived from the batch key (reproducible batches), or NULL = fresh OS randomness per proof
                     if (key_base) { gl355_derive_key(key_base, 2ull * j, &k_sem[32 * b]); gl355_derive_key(key_base, 2ull * j + 1, &s.k_rec[32 * b]); }
                 }
@@ -197,6 +205,44 @@ extern "C" int32_t gl355_semaphore_units(gl355_ctx* const* ctxs, uint32_t n_ctx,
     guarded(0);
     for (auto& th : pool) th.join();
     return first_error.load();
+}
+
+}  // namespace
+
+extern "C" int32_t gl355_semaphore_units(gl355_ctx* const* ctxs, uint32_t n_ctx, const gl355_circuit_handle* sem, const gl355_circuit_handle* rec,
+                                         const uint64_t* private_keys, uint64_t n_members, const uint64_t topic[4], const uint64_t* tree_digests,
+                                         const uint64_t* member_indices, uint32_t count, const uint8_t* key_base, uint64_t* leaves_out,
+                                         uint64_t* proofs_out, uint32_t* units_per_ctx) {
+    if (!ctxs || n_ctx == 0 || !sem || !private_keys || !topic || (!tree_digests && n_members > 1) || (!member_indices && count) || !leaves_out)
+        return GL355_E_INVALID_ARG;
+    for (uint32_t t = 0; t < n_ctx; t++)
+        if (!ctxs[t]) return GL355_E_INVALID_ARG;
+    if (n_members == 0 || (n_members & (n_members - 1))) return ctx_of(ctxs[0])->fail(GL355_E_INVALID_ARG, "semaphore_units: the access set must hold a power-of-two number of members");
+    SiblingSource src;
+    src.digests = tree_digests;
+    return semaphore_units_run(ctxs, n_ctx, sem, rec, private_keys, n_members, topic, src, member_indices, count, key_base, leaves_out, proofs_out, units_per_ctx);
+}
+
+extern "C" int32_t gl355_semaphore_units_tree(gl355_ctx* const* ctxs, uint32_t n_ctx, const gl355_circuit_handle* sem, const gl355_circuit_handle* rec,
+                                              const uint64_t* private_keys, const gl355_merkle_tree* tree, const uint64_t topic[4],
+                                              const uint64_t* member_indices, uint32_t count, const uint8_t* key_base, uint64_t* leaves_out,
+                                              uint64_t* proofs_out, uint32_t* units_per_ctx) {
+    if (!ctxs || n_ctx == 0 || !sem || !private_keys || !topic || !tree || (!member_indices && count) || !leaves_out) return GL355_E_INVALID_ARG;
+    for (uint32_t t = 0; t < n_ctx; t++)
+        if (!ctxs[t]) return GL355_E_INVALID_ARG;
+    if (tree->cap_height != 0 || tree->leaf_len != 4 || tree->hasher != GL355_HASH_POSEIDON)
+        return ctx_of(ctxs[0])->fail(GL355_E_INVALID_ARG, "semaphore_units_tree: the access set is a Poseidon tree of 4-word leaves with cap height 0");
+    // every unit's path in one gather on the tree's own context, before a worker exists (an index out of range is refused there)
+    std::vector<uint64_t> paths;
+    try {
+        paths.resize((size_t)count * tree->sub_bits * 4 + 4);
+    } catch (...) {
+        return GL355_E_OOM;
+    }
+    GL355_TRY(gl355_merkle_tree_prove_batch(tree, member_indices, count, paths.data()));
+    SiblingSource src;
+    src.paths = paths.data();
+    return semaphore_units_run(ctxs, n_ctx, sem, rec, private_keys, tree->n_leaves, topic, src, member_indices, count, key_base, leaves_out, proofs_out, units_per_ctx);
 }
 
 // recursion.rs:187-247 `aggregate` as one native call: the binary aggregation tree over n_leaves = 2^n_levels proofs of one circuit.

@@ -361,6 +361,10 @@ int32_t gl355_ctx_set_option(gl355_ctx* ctx, int32_t option, int64_t value) {
         if (value < 0 || value > 30) return ctx->c.fail(GL355_E_INVALID_ARG, "set_option: MERKLE_LANES_LOG must be in 0..30");
         ctx->c.merkle_lanes_log = (uint32_t)value;
         return GL355_OK;
+    case GL355_OPT_MERKLE_UPDATE_FULL_LOG:
+        if (value < 0 || value > 31) return ctx->c.fail(GL355_E_INVALID_ARG, "set_option: MERKLE_UPDATE_FULL_LOG must be in 0..31");
+        ctx->c.merkle_update_full_log = (uint32_t)value;
+        return GL355_OK;
     case GL355_OPT_LEAF_LANES_LOG:
         if (value < 0 || value > 31) return ctx->c.fail(GL355_E_INVALID_ARG, "set_option: LEAF_LANES_LOG must be in 0..31");
         ctx->c.leaf_lanes_log = (uint32_t)value;

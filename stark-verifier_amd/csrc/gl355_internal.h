@@ -15,6 +15,7 @@
 #include "merkle_common.cuh"
 #include "coset_interp.h"
 #include "gate_shape.h"
+#include "merkle_update_plan.h"
 
 namespace gl355 { struct Ctx; }
 
@@ -28,6 +29,18 @@ struct gl355_oracle {
     uint64_t* cap;
     uint64_t n_digests;
     int32_t hasher;     // GL355_HASH_*: the hash of this batch's Merkle tree
+};
+
+// MerkleTree { leaves, digests, cap } resident in HBM, updated in place (merkle.hip, merkle_tree.hip); one allocation from the context pool
+struct gl355_merkle_tree {
+    struct gl355::Ctx* ctx;
+    int32_t hasher;         // GL355_HASH_*
+    uint64_t n_leaves;
+    uint32_t leaf_len, cap_height, sub_bits;      // sub_bits = log2(n_leaves) - cap_height: the layers of a cap subtree = the digests of a path
+    uint64_t* digests;      // plonky2 layout; the allocation starts here
+    uint64_t* cap;
+    uint64_t* leaves;       // row-major [n_leaves][leaf_len]
+    uint64_t n_digests;
 };
 
 namespace gl355 {
@@ -90,6 +103,7 @@ struct Ctx {
     uint64_t wait_ns = 0, wait_calls = 0;   // accumulated by wait() while prof_on
     uint64_t wait_cpu_ns = 0, prove_cpu_ns = 0, prove_calls = 0;   // thread CPU time inside wait() / inside prove_units (waits included)
     uint32_t merkle_lanes_log = 14;   // Merkle levels with <= 2^this nodes use the 16-lanes-per-node kernel (GL355_OPT_MERKLE_LANES_LOG)
+    uint32_t merkle_update_full_log = 4;   // gl355_merkle_tree_update rebuilds every level from n_leaves >> this changed leaves on (GL355_OPT_MERKLE_UPDATE_FULL_LOG)
     uint32_t leaf_lanes_log = 16;     // FRI layers of 8- to 32-word leaves with < 2^this leaves over all units hash them 16 lanes per leaf; 0 = never (GL355_OPT_LEAF_LANES_LOG)
     bool prof_on = false;
     std::vector<ProfRec> prof;
@@ -211,6 +225,12 @@ struct HasherLaunch {
     uint32_t grind_window_log;      // a grinder launch tries at most 2^this candidates per unit
     // the levels above the leaf digests (digest_slot(0, k) of every cap subtree is written), the hasher's level kernels among them
     int32_t (*above_leaves)(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits, uint64_t* digests, uint64_t* cap);
+    // in-place updates: the leaf kernel, the one-lane kernel over a dirty list, their profile scopes, and whether the dirty path may take the
+    // 16-lane kernels (merkle_update_level_lanes_kernel, merkle_update_climb_kernel: Poseidon only)
+    void (*update_leaves)(UpdateLeafArgs);
+    void (*update_level)(uint64_t*, uint64_t*, uint32_t, uint32_t, const uint64_t*, uint64_t);
+    const char *update_leaves_scope, *update_level_scope;
+    bool lanes16;
 };
 const HasherLaunch& bn254_hasher_launch();      // merkle_bn254.hip
 int32_t permute_dev(Ctx* ctx, int32_t hasher, uint64_t* states, uint64_t count);
@@ -228,6 +248,10 @@ int32_t merkle_build_above_leaves(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits
 // leaf array leaves [B][len_v >> ab][2 << ab] and the leaf digests (or the cap entries when sub_bits == 0), then builds the levels above (Poseidon only)
 int32_t fri_wide_leaves_tree_dev(Ctx* ctx, uint32_t ab, uint32_t B, const uint64_t* vals, uint64_t len_v, uint64_t* leaves, uint32_t sub_bits,
                                  uint64_t* digests, uint64_t* cap);
+// a resident tree's update (p: the sorted unique leaves, the row of rows_host [n_rows][leaf_len] each one takes and, unless `full`, the dirty lists)
+// and its batched reads (what = 0: paths, 1: leaves) into host memory; all three wait for the stream
+int32_t merkle_update_dev(Ctx* ctx, const gl355_merkle_tree* t, const MerkleUpdatePlan& p, const uint64_t* rows_host, uint64_t n_rows, bool full);
+int32_t merkle_tree_gather_dev(Ctx* ctx, const gl355_merkle_tree* t, int what, const uint64_t* indices_host, uint64_t n_idx, uint64_t* out_host);
 // the grinder for B <= GL355_MAX_UNITS sponge states at once (pow_grind_dev is its B = 1 call): the smallest passing
 // candidate >= start of every unit; `landing` is a host area of B words for the device's answers (pinned: no hidden wait)
 int32_t pow_grind_units_dev(Ctx* ctx, int32_t hasher, uint32_t B, const uint64_t* states /* [B][12] */, const uint32_t* pos /* [B] */, uint32_t bits,

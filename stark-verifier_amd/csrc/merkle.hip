@@ -42,6 +42,17 @@ __global__ void __launch_bounds__(256) merkle_level_kernel(uint64_t* digests, ui
     merkle_level_body<PoseidonHasher>(digests, cap, sub_bits, layer, n_nodes);
 }
 
+// one 16-lane group = one parent node g of layer `layer` (counted over all subtrees): lane li < 8 loads word li of the two children, lanes 0 .. 3 store the
+// digest.  A group without a node of its own is given any node and valid = false: it goes through the permutation (the ring exchange and the DPP
+// broadcast need the whole wave) and skips only its store.
+template <int FORM>
+GL_DEV void merkle_node_lanes(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer, uint64_t g, bool valid, int li, uint64_t* ring) {
+    const MerkleNode nd = merkle_node(digests, cap, sub_bits, layer, g);
+    uint64_t s = (li < 8) ? nd.tree[nd.child() * 4 + li] : 0;      // left child, then the right one
+    s = psd_permute_lanes<FORM>(s, li, ring);
+    if (valid && li < 4) nd.dst()[li] = gl_canon(s);
+}
+
 // one 16-lane group = one parent node of layer `layer`; block = 64 threads = 4 nodes
 template <int FORM>
 __global__ void __launch_bounds__(64) merkle_level_lanes_kernel(uint64_t* digests, uint64_t* cap, uint32_t sub_bits,
@@ -51,10 +62,63 @@ __global__ void __launch_bounds__(64) merkle_level_lanes_kernel(uint64_t* digest
     uint64_t g = blockIdx.x * 4ull + grp;
     const bool valid = g < n_nodes;
     if (!valid) g = 0;  // keep the whole wave in the barriers
-    const MerkleNode nd = merkle_node(digests, cap, sub_bits, layer, g);
-    uint64_t s = (li < 8) ? nd.tree[nd.child() * 4 + li] : 0;      // left child, then the right one
-    s = psd_permute_lanes<FORM>(s, li, rings[grp]);
-    if (valid && li < 4) nd.dst()[li] = gl_canon(s);
+    merkle_node_lanes<FORM>(digests, cap, sub_bits, layer, g, valid, li, rings[grp]);
+}
+
+// ---- in-place update of a resident tree (gl355_merkle_tree_update; the dirty lists: merkle_update_plan.h) ----
+__global__ void __launch_bounds__(256) merkle_update_leaves_kernel(UpdateLeafArgs a) { update_leaves_body<PoseidonHasher>(a); }
+
+__global__ void __launch_bounds__(256) merkle_update_level_kernel(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer,
+                                                                 const uint64_t* list, uint64_t n_list) {
+    merkle_update_level_body<PoseidonHasher>(digests, cap, sub_bits, layer, list, n_list);
+}
+
+// merkle_level_lanes_kernel over a dirty list: group e takes node list[e]; a group past the end clamps to entry 0 and skips only its store
+template <int FORM>
+__global__ void __launch_bounds__(64) merkle_update_level_lanes_kernel(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer,
+                                                                      const uint64_t* list, uint64_t n_list) {
+    __shared__ uint64_t rings[4][24];
+    const int li = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    uint64_t e = blockIdx.x * 4ull + grp;
+    const bool valid = e < n_list;
+    if (!valid) e = 0;
+    merkle_node_lanes<FORM>(digests, cap, sub_bits, layer, list[e], valid, li, rings[grp]);
+}
+
+// The top of the dirty path in ONE launch of ONE workgroup: 1024 threads = 64 groups of 16 lanes take the at most 64 dirty nodes of layer layer0, then
+// of every layer above it up to the subtree roots (n_layers layers; their ids follow one another in `list`, counts.n[l] of them in layer layer0 + l).  A
+// dirty child's digest was written to HBM by this workgroup one layer earlier and is read back behind the __syncthreads() between the layers: the
+// workgroup-scope release / barrier / acquire of DESIGN 4.9 "Visibility" -- one workgroup's vector memory operations go through its CU's one L1 in
+// order.  Nothing wider is relied on: the layers below were written by earlier launches on the same stream.  Hang safety: n_layers and the counts are
+// kernel arguments, every thread reaches every barrier, a group without a node clamps to entry 0 of its layer and still arrives, a wave none of whose
+// groups has a node skips the permutation (a wave-uniform branch without a barrier inside) and arrives too, and no thread returns early.
+template <int FORM>
+__global__ void __launch_bounds__(1024) merkle_update_climb_kernel(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer0, uint32_t n_layers,
+                                                                  const uint64_t* list, ClimbCounts counts) {
+    __shared__ uint64_t rings[64][24];
+    const int li = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    const int wave_first_grp = (threadIdx.x >> 6) << 2;
+    uint32_t first = 0;
+    for (uint32_t l = 0; l < n_layers; l++) {
+        const int cnt = counts.n[l];
+        if (wave_first_grp < cnt) {
+            const bool valid = grp < cnt;
+            merkle_node_lanes<FORM>(digests, cap, sub_bits, layer0 + l, list[first + (valid ? grp : 0)], valid, li, rings[grp]);
+        }
+        first += cnt;
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) merkle_paths_kernel(const uint64_t* digests, uint32_t layers, const uint64_t* idx, uint64_t n_idx, uint64_t* out) {
+    merkle_paths_body(digests, layers, idx, n_idx, out);
+}
+
+// leaf idx[q] of the resident row-major leaf array into out [n_idx][leaf_len]: one thread per word
+__global__ void __launch_bounds__(256) merkle_gather_leaves_kernel(const uint64_t* leaves, uint32_t leaf_len, const uint64_t* idx, uint64_t n_idx, uint64_t* out) {
+    const uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (j >= n_idx * leaf_len) return;
+    out[j] = leaves[idx[j / leaf_len] * leaf_len + j % leaf_len];
 }
 
 // FRI layer leaves of 2A = 2 << AB words (A = 4, 8, 16), one 16-lane group per leaf, four leaves per wave.  Word w of leaf i is column w & 1,
@@ -135,7 +199,8 @@ __global__ void __launch_bounds__(256) pow_grind_units_kernel(PowArgs a) { pow_g
 static const HasherLaunch& launch_of(int32_t hasher) {
     static const HasherLaunch poseidon = {
         poseidon_permute_kernel, hash_leaves_kernel, two_to_one_kernel, pow_grind_units_kernel,
-        "poseidon_permute_kernel", "hash_leaves_kernel", "two_to_one_kernel", "pow_grind", 22, merkle_build_above_leaves};
+        "poseidon_permute_kernel", "hash_leaves_kernel", "two_to_one_kernel", "pow_grind", 22, merkle_build_above_leaves,
+        merkle_update_leaves_kernel, merkle_update_level_kernel, "merkle_update_leaves_kernel", "merkle_update_level_kernel", true};
     return hasher == GL355_HASH_BN254_POSEIDON ? bn254_hasher_launch() : poseidon;
 }
 
@@ -264,6 +329,88 @@ int32_t merkle_build_above_leaves(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits
         }
         GL355_HIP(ctx, hipGetLastError());
     }
+    return GL355_OK;
+}
+
+// The resident tree's update.  The caller's n_rows new rows go up as they came; the k = p.leaves.size() leaves to write, the row each one takes
+// (p.src) and, unless `full`, the plan's dirty lists go up in one more copy.  Then leaf words + digests, then layer by layer the kernel
+// merkle_update_kernel_of names -- or, for a full update, the hasher's whole above_leaves.  The 16-lane form is merkle_build_above_leaves' choice:
+// form 3 below 64 cap subtrees, form 0 from there.  Ends with a wait for the stream: the staging is a local of this call.
+int32_t merkle_update_dev(Ctx* ctx, const gl355_merkle_tree* t, const MerkleUpdatePlan& p, const uint64_t* rows_host, uint64_t n_rows, bool full) {
+    const HasherLaunch& h = launch_of(t->hasher);
+    const uint64_t k = p.leaves.size(), row_words = n_rows * t->leaf_len, n_nodes = full ? 0 : p.nodes.size();
+    if (k == 0) return GL355_OK;
+    if ((k + 255) / 256 > 0x7FFFFFFFull || (!full && !merkle_update_grids_fit(p))) return ctx->fail(GL355_E_INVALID_ARG, "merkle_tree_update: too many leaves for one launch");
+    std::vector<uint64_t> stage(2 * k + n_nodes);
+    std::copy(p.leaves.begin(), p.leaves.end(), stage.begin());
+    std::copy(p.src.begin(), p.src.end(), stage.begin() + k);
+    std::copy(p.nodes.begin(), p.nodes.begin() + n_nodes, stage.begin() + 2 * k);
+    Scratch sc(ctx);
+    GL355_TRY(sc.get((stage.size() + row_words) * 8));
+    uint64_t* d_idx = sc.as<uint64_t>();
+    const uint64_t* d_nodes = d_idx + 2 * k;
+    uint64_t* d_rows = d_idx + stage.size();
+    GL355_HIP(ctx, hipMemcpyAsync(d_idx, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    GL355_HIP(ctx, hipMemcpyAsync(d_rows, rows_host, row_words * 8, hipMemcpyHostToDevice, ctx->stream));
+    {
+        ProfScope ps(ctx, h.update_leaves_scope, k * ((uint64_t)t->leaf_len * 16 + 48));
+        const UpdateLeafArgs a{d_idx, d_idx + k, d_rows, k, n_rows, t->leaves, t->leaf_len, t->sub_bits, t->digests, t->cap};
+        hipLaunchKernelGGL(h.update_leaves, dim3((uint32_t)((k + 255) / 256)), dim3(256), 0, ctx->stream, a);
+        GL355_HIP(ctx, hipGetLastError());
+    }
+    if (full) GL355_TRY(h.above_leaves(ctx, t->n_leaves, t->sub_bits, t->digests, t->cap));
+    const bool fast_lanes = (t->n_leaves >> t->sub_bits) < 64;
+    for (uint32_t layer = 1; !full && layer <= t->sub_bits; layer++) {
+        const uint64_t cnt = p.count(layer);
+        const uint64_t* list = d_nodes + p.offset[layer];
+        const MerkleUpdateKernel which = merkle_update_kernel_of(p, layer, ctx->merkle_lanes_log, h.lanes16);
+        if (which == MERKLE_UPDATE_CLIMB) {
+            const uint32_t n_layers = t->sub_bits - layer + 1;
+            ClimbCounts counts;
+            memset(&counts, 0, sizeof counts);
+            for (uint32_t l = 0; l < n_layers; l++) counts.n[l] = (uint8_t)p.count(layer + l);
+            ProfScope ps(ctx, "merkle_update_climb_kernel", (p.nodes.size() - p.offset[layer]) * 104);
+            if (fast_lanes) hipLaunchKernelGGL(merkle_update_climb_kernel<3>, dim3(1), dim3(1024), 0, ctx->stream, t->digests, t->cap, t->sub_bits, layer, n_layers, list, counts);
+            else hipLaunchKernelGGL(merkle_update_climb_kernel<0>, dim3(1), dim3(1024), 0, ctx->stream, t->digests, t->cap, t->sub_bits, layer, n_layers, list, counts);
+            GL355_HIP(ctx, hipGetLastError());
+            break;
+        }
+        // 2 child digests and the node id in, 1 digest out per node
+        ProfScope ps(ctx, which == MERKLE_UPDATE_LANES ? "merkle_update_level_lanes_kernel" : h.update_level_scope, cnt * 104);
+        if (which == MERKLE_UPDATE_LANES) {
+            if (fast_lanes) hipLaunchKernelGGL(merkle_update_level_lanes_kernel<3>, dim3((uint32_t)((cnt + 3) / 4)), dim3(64), 0, ctx->stream, t->digests, t->cap, t->sub_bits, layer, list, cnt);
+            else hipLaunchKernelGGL(merkle_update_level_lanes_kernel<0>, dim3((uint32_t)((cnt + 3) / 4)), dim3(64), 0, ctx->stream, t->digests, t->cap, t->sub_bits, layer, list, cnt);
+        } else {
+            hipLaunchKernelGGL(h.update_level, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, t->digests, t->cap, t->sub_bits, layer, list, cnt);
+        }
+        GL355_HIP(ctx, hipGetLastError());
+    }
+    GL355_HIP(ctx, ctx->wait());
+    return GL355_OK;
+}
+
+// rows of a resident array picked by index, into a host buffer: the indices go up, one kernel gathers, one copy comes back, and the call waits for it.
+// what = 0: the Merkle paths (layers x 4 words per index, any hasher: digests are copied, not hashed); what = 1: the leaves (leaf_len words per index)
+int32_t merkle_tree_gather_dev(Ctx* ctx, const gl355_merkle_tree* t, int what, const uint64_t* indices_host, uint64_t n_idx, uint64_t* out_host) {
+    const uint32_t per = what == 0 ? t->sub_bits * 4 : t->leaf_len;
+    const uint64_t n_out = n_idx * per;
+    if (n_out == 0) return GL355_OK;
+    const uint64_t n_threads = what == 0 ? n_idx * t->sub_bits : n_out;
+    if ((n_threads + 255) / 256 > 0x7FFFFFFFull) return ctx->fail(GL355_E_INVALID_ARG, "merkle_tree: too many indices for one launch");
+    Scratch sc(ctx);
+    GL355_TRY(sc.get((n_out + n_idx) * 8));
+    uint64_t* d_out = sc.as<uint64_t>();      // first: the paths move as 16-byte words
+    uint64_t* d_idx = d_out + n_out;
+    GL355_HIP(ctx, hipMemcpyAsync(d_idx, indices_host, n_idx * 8, hipMemcpyHostToDevice, ctx->stream));
+    {
+        ProfScope ps(ctx, what == 0 ? "merkle_paths_kernel" : "merkle_gather_leaves_kernel", n_out * 16 + n_idx * 8);
+        const dim3 grid((uint32_t)((n_threads + 255) / 256)), block(256);
+        if (what == 0) hipLaunchKernelGGL(merkle_paths_kernel, grid, block, 0, ctx->stream, t->digests, t->sub_bits, d_idx, n_idx, d_out);
+        else hipLaunchKernelGGL(merkle_gather_leaves_kernel, grid, block, 0, ctx->stream, t->leaves, t->leaf_len, d_idx, n_idx, d_out);
+        GL355_HIP(ctx, hipGetLastError());
+    }
+    GL355_HIP(ctx, ctx->d2h(out_host, d_out, n_out * 8));
+    GL355_HIP(ctx, ctx->wait());
     return GL355_OK;
 }
 

@@ -28,6 +28,14 @@ __global__ void __launch_bounds__(256) bn254_merkle_level_kernel(uint64_t* diges
     merkle_level_body<Bn254Hasher>(digests, cap, sub_bits, layer, n_nodes);
 }
 
+// in-place update of a resident tree: this hasher has no 16-lane form, so every dirty layer takes the one-lane kernel
+__global__ void __launch_bounds__(256) bn254_merkle_update_leaves_kernel(UpdateLeafArgs a) { update_leaves_body<Bn254Hasher>(a); }
+
+__global__ void __launch_bounds__(256) bn254_merkle_update_level_kernel(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer,
+                                                                       const uint64_t* list, uint64_t n_list) {
+    merkle_update_level_body<Bn254Hasher>(digests, cap, sub_bits, layer, list, n_list);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Lane-parallel permutation for SMALL levels.  With one lane per node a level costs one full permutation latency
 // (~2.4 ms: 2 000 dependent Montgomery products) however few nodes it has, and a proof walks ~140 such levels.  Here 32
@@ -122,7 +130,8 @@ static int32_t bn254_above_leaves(Ctx* ctx, uint64_t n_leaves, uint32_t sub_bits
 const HasherLaunch& bn254_hasher_launch() {
     static const HasherLaunch h = {
         bn254_permute_kernel, bn254_hash_leaves_kernel, bn254_two_to_one_kernel, bn254_pow_grind_units_kernel,
-        "bn254_permute_kernel", "bn254_hash_leaves_kernel", "bn254_two_to_one_kernel", "bn254_pow_grind_units_kernel", 20, bn254_above_leaves};
+        "bn254_permute_kernel", "bn254_hash_leaves_kernel", "bn254_two_to_one_kernel", "bn254_pow_grind_units_kernel", 20, bn254_above_leaves,
+        bn254_merkle_update_leaves_kernel, bn254_merkle_update_level_kernel, "bn254_merkle_update_leaves_kernel", "bn254_merkle_update_level_kernel", false};
     return h;
 }
 

@@ -83,6 +83,19 @@ __device__ __forceinline__ uint64_t leaf_elem(const LeafArgs& a, uint64_t g, uin
     return a.salt[u * a.salt_unit_stride + (uint64_t)(k - a.n_main) * a.stride + i];     // salt columns are always column-major
 }
 
+// An in-place update of a resident tree (gl355_merkle_tree_update): leaf idx[r] takes the leaf_len words of row src[r] of the caller's new leaves
+// (`rows`, uploaded as they came).  The host has sorted the indices and removed duplicates, keeping each one's last row (merkle_update_plan.h), so no
+// two lanes write one slot.
+struct UpdateLeafArgs {
+    const uint64_t* idx; const uint64_t* src; const uint64_t* rows; uint64_t n_idx, n_rows;
+    uint64_t* leaves;       // the resident row-major leaf array
+    uint32_t leaf_len, sub_bits;
+    uint64_t* digests; uint64_t* cap;
+};
+
+// what merkle_update_climb_kernel walks: the dirty counts (1 .. 64) of its layers, whose node ids follow one another in its list
+struct ClimbCounts { uint8_t n[64]; };
+
 // proof of work of every unit that still lacks a witness: candidates start + g, the smallest passing one of the launch wins
 struct PowArgs { uint64_t state[GL355_MAX_UNITS * 12]; uint32_t pos[GL355_MAX_UNITS]; uint32_t todo[GL355_MAX_UNITS]; uint32_t bits; uint64_t start; unsigned long long* best; };
 
@@ -116,10 +129,9 @@ template <class H> GL_DEV void permute_body(uint64_t* states, uint64_t count) {
     for (int k = 0; k < 12; k++) states[i * 12 + k] = H::out(s[k]);
 }
 
-// one lane = one leaf: overwrite-mode sponge over ceil(len/8) chunks
-template <class H> GL_DEV void hash_leaves_body(const LeafArgs& a) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= a.n_leaves) return;
+// one lane = one leaf: overwrite-mode sponge over ceil(len/8) chunks.  Leaf i of `a` is hashed, its digest goes where leaf `dst` of the tree belongs
+// (the same leaf when a tree is built, another one when an update's new rows are hashed)
+template <class H> GL_DEV void hash_leaf(const LeafArgs& a, uint64_t i, uint64_t dst) {
     uint64_t s[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) s[k] = 0;
@@ -145,13 +157,30 @@ template <class H> GL_DEV void hash_leaves_body(const LeafArgs& a) {
 #pragma unroll
         for (int k = 0; k < 4; k++) d[k] = H::out(s[k]);
     }
-    store_digest<H>(leaf_digest_dst(a.out, a.cap, a.linear, a.sub_bits, i), d);
+    store_digest<H>(leaf_digest_dst(a.out, a.cap, a.linear, a.sub_bits, dst), d);
 }
 
-// one lane = one parent node of layer `layer` (>= 1): two_to_one of its children in layer-1
-template <class H> GL_DEV void merkle_level_body(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer, uint64_t n_nodes /* all subtrees */) {
-    const uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (g >= n_nodes) return;
+template <class H> GL_DEV void hash_leaves_body(const LeafArgs& a) {
+    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (i >= a.n_leaves) return;
+    hash_leaf<H>(a, i, i);
+}
+
+// one lane = one updated leaf: its words into the resident leaf array, its digest where hash_leaves_body puts it
+template <class H> GL_DEV void update_leaves_body(const UpdateLeafArgs& u) {
+    const uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (r >= u.n_idx) return;
+    const uint64_t i = u.idx[r], from = u.src[r];
+    for (uint32_t k = 0; k < u.leaf_len; k++) u.leaves[i * u.leaf_len + k] = u.rows[from * u.leaf_len + k];
+    LeafArgs a;      // the new rows as a row-major leaf array of one unit
+    a.leaves = u.rows; a.n_leaves = u.n_rows; a.leaf_len = u.leaf_len; a.col_major = 0; a.stride = u.leaf_len;
+    a.out = u.digests; a.sub_bits = u.sub_bits; a.linear = 0; a.always_hash = 0; a.cap = u.cap;
+    a.unit_log = 0; a.n_main = 0; a.unit_stride = 0; a.salt = nullptr; a.salt_unit_stride = 0;
+    hash_leaf<H>(a, from, i);
+}
+
+// node g of layer `layer` (>= 1), counted over all subtrees: two_to_one of its children in layer - 1, by one lane
+template <class H> GL_DEV void merkle_node_hash(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer, uint64_t g) {
     const MerkleNode nd = merkle_node(digests, cap, sub_bits, layer, g);
     const uint64_t* in = nd.tree + nd.child() * 4;      // left child; right child is +1
     uint64_t s[12];
@@ -170,6 +199,34 @@ template <class H> GL_DEV void merkle_level_body(uint64_t* digests, uint64_t* ca
     H::permute(s);
     const uint64_t d[4] = {H::out(s[0]), H::out(s[1]), H::out(s[2]), H::out(s[3])};
     store_digest<H>(nd.dst(), d);
+}
+
+// one lane = one parent node of layer `layer`
+template <class H> GL_DEV void merkle_level_body(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer, uint64_t n_nodes /* all subtrees */) {
+    const uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (g >= n_nodes) return;
+    merkle_node_hash<H>(digests, cap, sub_bits, layer, g);
+}
+
+// the same for the dirty nodes of an update: lane e takes node list[e]
+template <class H> GL_DEV void merkle_update_level_body(uint64_t* digests, uint64_t* cap, uint32_t sub_bits, uint32_t layer, const uint64_t* list, uint64_t n_list) {
+    const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (e >= n_list) return;
+    merkle_node_hash<H>(digests, cap, sub_bits, layer, list[e]);
+}
+
+// one thread per (index q, layer i): the sibling MerkleTree::prove reads on the way from leaf idx[q] to its cap entry, 32 bytes into out [n_idx][layers][4]
+__device__ __forceinline__ void merkle_paths_body(const uint64_t* digests, uint32_t layers, const uint64_t* idx, uint64_t n_idx, uint64_t* out) {
+    const uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (j >= n_idx * layers) return;
+    const uint64_t q = j / layers, leaf = idx[q];
+    const uint32_t i = (uint32_t)(j % layers);
+    const uint64_t tree_len = 2 * ((1ull << layers) - 1);
+    const uint64_t pair = (leaf & ((1ull << layers) - 1)) >> i;      // the node of layer i on the path; its sibling is pair ^ 1
+    const uint64_t* src = digests + ((leaf >> layers) * tree_len + digest_slot(i, pair ^ 1)) * 4;
+    const ulonglong2 lo = *reinterpret_cast<const ulonglong2*>(src), hi = *reinterpret_cast<const ulonglong2*>(src + 2);
+    *reinterpret_cast<ulonglong2*>(out + j * 4) = lo;
+    *reinterpret_cast<ulonglong2*>(out + j * 4 + 2) = hi;
 }
 
 template <class H> GL_DEV void two_to_one_body(const uint64_t* l, const uint64_t* r, uint64_t n, uint64_t* out) {

@@ -8,7 +8,7 @@ taken from a base-2 split (circuit.rs:42-51), and nullifier = Poseidon(private_k
 import numpy as np
 
 from ._lib import GATE_BASE_SUM, GATE_CONSTANT, GATE_POSEIDON, GATE_PUBLIC_INPUT
-from .api import MerkleTree
+from .api import DeviceMerkleTree, MerkleTree
 import ctypes as C
 
 from . import _lib
@@ -74,10 +74,33 @@ class Signal:
 class AccessSet:
     """access_set.rs:25 -- AccessSet(pub MerkleTree<F, PoseidonHash>) over the members' public keys."""
 
-    def __init__(self, ctx, public_keys):
+    def __init__(self, ctx, public_keys, resident=False):
+        """resident: the tree stays in HBM (api.DeviceMerkleTree) and update_members costs the changed members' paths; otherwise it is
+        built once into host arrays (api.MerkleTree) and update_members rebuilds it"""
         self.ctx = ctx
-        self.tree = MerkleTree(ctx, np.ascontiguousarray(public_keys, dtype=np.uint64), 0)
+        keys = np.ascontiguousarray(public_keys, dtype=np.uint64)
+        self.n_members = keys.shape[0]
+        self.tree = (DeviceMerkleTree if resident else MerkleTree)(ctx, keys, 0)
         self._circuit = None
+
+    @property
+    def resident(self):
+        return isinstance(self.tree, DeviceMerkleTree)
+
+    def update_members(self, indices, public_keys):
+        """member indices[j] <- public_keys[j], in order (admit into an empty slot, replace, or revoke by writing the empty leaf).  The
+        circuit depends on the height alone and is kept."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        keys = np.ascontiguousarray(public_keys, dtype=np.uint64).reshape(idx.size, 4)
+        if self.resident:
+            self.tree.update(idx, keys)
+            return
+        if idx.size and int(idx.max()) >= self.n_members:
+            raise _lib.Gl355Error(-1, "update_members: member index out of range")
+        leaves = self.tree.leaves.copy()
+        for j in range(idx.size):
+            leaves[int(idx[j])] = keys[j]
+        self.tree = MerkleTree(self.ctx, leaves, 0)
 
     @staticmethod
     def public_key(private_key):
@@ -85,7 +108,7 @@ class AccessSet:
         return host_hash_no_pad(np.concatenate([np.asarray(private_key, dtype=np.uint64), np.zeros(4, np.uint64)]))
 
     def tree_height(self):
-        return int(self.tree.leaves.shape[0]).bit_length() - 1
+        return int(self.n_members).bit_length() - 1
 
     # ---- circuit.rs:25-65 ------------------------------------------------------------------------------
     def semaphore_circuit(self, builder):
