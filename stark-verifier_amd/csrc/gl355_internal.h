@@ -76,6 +76,19 @@ struct Ctx {
     struct PowTab { uint64_t* lo; uint64_t* hi; };
     std::map<std::vector<uint64_t>, PowTab> pow_cache;
     std::map<std::vector<uint64_t>, uint64_t*> full_cache;   // full-size multiplier tables (ntt.hip)
+    // the table of `words` words under `key`: built once by build(device pointer), one kernel launch on the stream, and kept as long as the context
+    template <class Build>
+    int32_t cached_table(const std::vector<uint64_t>& key, uint64_t words, const uint64_t** out, Build build) {
+        auto it = full_cache.find(key);
+        if (it != full_cache.end()) { *out = it->second; return GL355_OK; }
+        uint64_t* d = nullptr;
+        GL355_HIP(this, hipMalloc((void**)&d, words * 8));
+        build(d);
+        GL355_HIP(this, hipGetLastError());
+        full_cache[key] = d;
+        *out = d;
+        return GL355_OK;
+    }
     int32_t full_pow_table(const uint64_t* lo, const uint64_t* hi, uint32_t n_cosets, uint32_t log_n, const uint64_t** out);
     int32_t full_step_table(const uint64_t* lo, const uint64_t* hi, uint32_t l1, uint32_t l2, bool inv, const uint64_t** out);
     int32_t nat_step_table(const uint64_t* lo, const uint64_t* hi, uint32_t l1, uint32_t l2, const uint64_t** out);   // natural -> natural flow

@@ -23,6 +23,11 @@
 //     layers of the zero-padded size-N transform are trivial); coset c's output is the contiguous
 //     block bitrev(c) of the bit-reversed result, and workgroup id % n_cosets selects the coset so
 //     that with 8 cosets each XCD's L2 keeps exactly one coset's power table.
+// Which kernels run for a transform is decided in ONE place, ntt_route (ntt_route.h, pure host code): it turns the shape of a plan into at most
+// four steps -- kernel instance, tables, flags, profile scope -- and ntt_run below only executes them.  The instances that exist are listed once, in
+// that header; this unit compiles the radix-16 forms of the list, ntt_r8.hip the radix-8 forms, ntt_l24.hip the 24-bit-limb forms, each with its own
+// field product.  tests/ntt_route_check.cpp prints the route of every shape the callers in capi.hip can build and tests/test_ntt_route_host.py
+// holds every listed instance to be reached by one of them (docs/history/ntt_route.md has the table).
 // Field products: the compiler-scheduled formulation (gl_field.cuh, GL_MUL_VARIANT 2).  These kernels run 2-4 waves per SIMD
 // between LDS exchanges, so what matters is that the 16 independent butterflies of a thread interleave freely; the
 // inline-asm formulation has fewer instructions but serialises each product (measured: 4-7 % slower single-pass tiles).
@@ -159,280 +164,119 @@ __global__ void canon_points_kernel(const uint64_t* in, uint64_t* out, uint64_t 
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side
+// host side: ntt_run executes the route that ntt_route (ntt_route.h) gives for the plan's shape
 // ------------------------------------------------------------------------------------------------
-template <int LT, int LOG_T>
-static hipError_t launch_rows_lt(const PassArgs& a, bool inv, uint64_t blocks, hipStream_t s) {
-    const size_t shmem = ((1u << LT) + (1u << (LT - 4))) * sizeof(uint64_t);
-    constexpr int NT = 1 << (LT - 4);
-    // (the FAST instantiation and 4 waves per SIMD measured no better for rows: HISTORY rounds 2-3)
-    if (inv) {
-        auto k = ntt_rows_kernel<LT, LOG_T, true>;
-        if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(NT), shmem, s, a);
-    } else {
-        auto k = ntt_rows_kernel<LT, LOG_T, false>;
-        if (shmem > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(NT), shmem, s, a);
+// the radix-16 forms and the single points; (4 waves per SIMD measured no better for rows: HISTORY rounds 2-3)
+static hipError_t launch_step_r16(const NttStep& st, const PassArgs& a, hipStream_t s) {
+    switch (st.form) {
+        case NTT_POINTS: {
+            const NttGrid g = ntt_step_grid(st, a.batch, a.n_cosets);
+            hipLaunchKernelGGL(canon_points_kernel, dim3((uint32_t)g.x), dim3(256), 0, s, a.in, a.out, a.in_col_stride, a.out_col_stride, a.batch);
+            return hipGetLastError();
+        }
+        case NTT_ROWS16:
+#define GL355_X(LT, LOG_T, PRE, INV, PASS) \
+    if (GL355_NTT_STEP_IS(st, LT, LOG_T, PRE, INV, PASS)) return launch_pass(ntt_rows_kernel<LT, LOG_T, INV>, st, 1 << (LT - 4), tile_lds_bytes(LT), a, s);
+            GL355_NTT_ROWS16_INSTANCES(GL355_X)
+#undef GL355_X
+            break;
+        case NTT_COLS16:
+#define GL355_X(LT, LOG_T, PRE, INV, PASS) \
+    if (GL355_NTT_STEP_IS(st, LT, LOG_T, PRE, INV, PASS)) return launch_pass(ntt_cols_kernel<LOG_T, INV>, st, 256, tile_lds_bytes(LT), a, s);
+            GL355_NTT_COLS16_INSTANCES(GL355_X)
+#undef GL355_X
+            break;
+        default: break;
     }
-    return hipGetLastError();
+    return hipErrorInvalidValue;     // not reached: ntt_route lets no step through whose instance is not listed
 }
 
-static hipError_t launch_rows(const PassArgs& a, uint32_t log_t, bool inv, hipStream_t s) {
-    // 4096-point rows of the two-pass LDE / forward transform on 24-bit limbs (a.mid is set by ntt_run for exactly that shape)
-    if (a.mid && !inv && log_t == 12 && a.n_cosets == 1 && !a.pre_full && !a.pre_lo && !a.post_lo && a.scale == 1 && a.canon && !a.in_bitrev &&
-        !a.out_natural)
-        return launch_rows_l24(a, s);
-    // the commit-path shape (forward, whole rows of 2^12..2^14 points in natural order, at most a full pre table) runs the
-    // radix-8 kernel
-    if (!inv && log_t >= 12 && log_t <= 14 && !a.post_lo && a.scale == 1 && a.canon && !a.in_bitrev && !a.out_natural &&
-        (a.pre_full || !a.pre_lo || !a.pre_hi)) {
-        PassArgs b = a;
-        if (!b.pre_full && b.pre_lo) { b.pre_full = b.pre_lo; b.pre_full_stride = 4096; }   // n <= 2^12: the one-level table is the full one
-        return launch_rows_r8(b, log_t, false, s);
-    }
-    // ... and so do the inverse forms without multiplier tables (values -> coefficients: natural order within the row and the 1/n at the store)
-    if (inv && log_t >= 12 && log_t <= 14 && !a.post_lo && !a.pre_lo && !a.pre_full && a.canon && !a.in_bitrev)
-        return launch_rows_r8(a, log_t, true, s);
-    const uint64_t total_rows = ((uint64_t)a.batch) << a.log_rows;
-    const int lt = log_t <= 12 ? 12 : (int)log_t;
-    const uint64_t rpt = 1ull << (lt - log_t);
-    const uint64_t blocks = ((total_rows + rpt - 1) / rpt) * a.n_cosets;
-    switch (log_t) {
-#define GL355_ROW_CASE(L) case L: return launch_rows_lt<12, L>(a, inv, blocks, s);
-        GL355_ROW_CASE(1) GL355_ROW_CASE(2) GL355_ROW_CASE(3) GL355_ROW_CASE(4) GL355_ROW_CASE(5)
-        GL355_ROW_CASE(6) GL355_ROW_CASE(7) GL355_ROW_CASE(8) GL355_ROW_CASE(9) GL355_ROW_CASE(10)
-        GL355_ROW_CASE(11) GL355_ROW_CASE(12)
-#undef GL355_ROW_CASE
-        case 13: return launch_rows_lt<13, 13>(a, inv, blocks, s);
-        case 14: return launch_rows_lt<14, 14>(a, inv, blocks, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <int LOG_T>
-static hipError_t launch_cols_t(const PassArgs& a, bool inv, uint64_t blocks, hipStream_t s) {
-    const size_t shmem = (4096 + 256) * sizeof(uint64_t);
-    const bool fast = !inv && a.pre_full && a.step_full && !a.in_bitrev && !a.out_natural && !a.post_lo && a.scale == 1 && !a.canon;
-    const bool r8 = a.step_full && (inv ? !a.pre_lo && !a.pre_full : (a.pre_full || !a.pre_lo)) && !a.in_bitrev && !a.out_natural && !a.post_lo &&
-                    a.scale == 1 && !a.canon;
-    if (r8 && !inv && a.ratio_full && a.pre_full && LOG_T == 5 && a.log_rows == 12) return launch_cols_l24_cosets(a, s);
-    // column dimension 2, 4 or 8 (n = 2^13 .. 2^15 with 4096-point rows): the streaming kernel, no tile (profiles/r03b_single_pass_ab.txt)
-    if (r8 && !inv && a.ratio_full && a.pre_full && LOG_T <= 3 && a.log_rows == 12 && a.batch <= 65535)
-        return launch_cols_small_cosets(a, LOG_T, s);
-    if (r8 && !inv && a.ratio_full && a.pre_full) return launch_cols_r8_cosets(a, LOG_T, s);
-    if (r8) return launch_cols_r8(a, LOG_T, inv, s);
-    if (fast) hipLaunchKernelGGL((ntt_cols_kernel<LOG_T, false, true>), dim3((uint32_t)blocks), dim3(256), shmem, s, a);
-    else if (inv) hipLaunchKernelGGL((ntt_cols_kernel<LOG_T, true>), dim3((uint32_t)blocks), dim3(256), shmem, s, a);
-    else hipLaunchKernelGGL((ntt_cols_kernel<LOG_T, false>), dim3((uint32_t)blocks), dim3(256), shmem, s, a);
-    return hipGetLastError();
-}
-
-static hipError_t launch_cols(const PassArgs& a, uint32_t log_t, bool inv, hipStream_t s) {
-    const uint64_t n2 = 1ull << a.log_rows;
-    const uint64_t tc = 1ull << (12 - log_t);
-    const uint64_t blocks = (n2 / tc) * a.batch * a.n_cosets;
-    switch (log_t) {
-#define GL355_COL_CASE(L) case L: return launch_cols_t<L>(a, inv, blocks, s);
-        GL355_COL_CASE(1) GL355_COL_CASE(2) GL355_COL_CASE(3) GL355_COL_CASE(4) GL355_COL_CASE(5)
-        GL355_COL_CASE(6) GL355_COL_CASE(7) GL355_COL_CASE(8) GL355_COL_CASE(9) GL355_COL_CASE(10)
-        GL355_COL_CASE(11) GL355_COL_CASE(12)
-#undef GL355_COL_CASE
-        default: return hipErrorInvalidValue;
-    }
-}
-
-// Split of a two-pass transform: N = N1 * N2, first-pass dimension N1 (columns kernel in the
-// natural->bitrev flow, rows kernel in the bitrev->natural flow).
-static void split_two_pass(uint32_t log_n, bool natural_in, uint32_t* log_n1, uint32_t* log_n2) {
-    // the column pass works on tiles of 2^(12 - LOG_T) adjacent columns: with 4096-point rows a 2^22 / 2^23-point transform leaves it
-    // 4 / 2 columns (32- / 16-byte accesses: 570 / 450 GB/s against 860 at 2^21), so from 2^22 on the row dimension is 2^14
-    const uint32_t row = log_n >= 22 ? 14 : 12;
-    if (natural_in) {  // cols over N1 (<= 2^12, prefers >= 16 cols per tile), rows over N2
-        *log_n1 = log_n - row; *log_n2 = row;
-    } else {           // rows over N1 (contiguous), then cols over N2 (<= 2^12)
-        *log_n1 = row; *log_n2 = log_n - row;
+static hipError_t launch_step(const NttStep& st, const PassArgs& a, hipStream_t s) {
+    switch (st.form) {
+        case NTT_POINTS: case NTT_ROWS16: case NTT_COLS16: return launch_step_r16(st, a, s);
+        case NTT_ROWS_L24: case NTT_COLS_L24_COSETS: case NTT_COLS_SMALL_COSETS: return launch_step_l24(st, a, s);
+        default: return launch_step_r8(st, a, s);
     }
 }
 
 int32_t ntt_run(Ctx* ctx, const NttPlan& p) {
-    if (p.log_n == 0) {
-        if (p.batch == 0) return GL355_OK;
-        ProfScope ps(ctx, "ntt_single_points", (uint64_t)p.batch * 16);
-        hipLaunchKernelGGL(canon_points_kernel, dim3((p.batch + 255) / 256), dim3(256), 0, ctx->stream, p.in, p.out, p.in_col_stride,
-                           p.out_col_stride, p.batch);
-        GL355_HIP(ctx, hipGetLastError());
-        return GL355_OK;
-    }
-    if (p.log_n > 24) return ctx->fail(GL355_E_UNSUPPORTED, "ntt: log_n > 24 unsupported");
-    if (p.n_cosets > 16 || p.n_cosets == 0) return ctx->fail(GL355_E_INVALID_ARG, "ntt: bad coset count");
-    const bool inv = p.inverse;
-    PassArgs a;
-    memset(&a, 0, sizeof a);
-    a.batch = p.batch;
-    a.n_cosets = p.n_cosets;
-    a.coset_out_stride = p.coset_out_stride;
-    for (uint32_t c = 0; c < 16; c++) a.coset_slot[c] = c < p.n_cosets ? p.coset_slot[c] : 0;
-    a.log_n = p.log_n;
-    a.tw = ctx->twr(4, inv);
-    a.tw_r8 = ctx->twr(3, inv);
-    a.scale = 1;
+    if (p.log_n == 0 && p.batch == 0) return GL355_OK;
+    const uint64_t n = 1ull << (p.log_n & 63);
+    NttShape sh;
+    sh.log_n = p.log_n; sh.n_cosets = p.n_cosets;
+    sh.inverse = p.inverse; sh.in_bitrev = p.in_bitrev; sh.out_bitrev = p.out_bitrev;
+    sh.pre = p.pre_lo != nullptr; sh.post = p.post_lo != nullptr; sh.scale = p.scale != 1; sh.ratio = p.coset_ratio != 0;
+    sh.out_contig = p.out_col_stride == n; sh.cosets_contig = p.coset_out_stride == n; sh.slot0_zero = p.coset_slot[0] == 0;
+    sh.batch_fits_y = p.batch <= 65535;
+    sh.single_pass_max_log = ctx->ntt_single_pass_max_log;
+    NttRoute route;
+    const int32_t rc = ntt_route(sh, route);
+    if (rc != GL355_OK) return ctx->fail(rc, route.msg);
 
-    // n = 2^13, 2^14 in one pass need a 64 / 128-KB LDS tile and every VGPR of the CU: nothing else can share the CU with such
-    // a block.  GL355_OPT_NTT_SINGLE_PASS_MAX_LOG < 14 sends the commit-path shape (natural in, bit-reversed out, no
-    // post-multiplier, contiguous coset blocks) of those sizes through the two-pass path with 4096-point tiles instead.
-    const bool two_pass_ok = !p.in_bitrev && p.out_bitrev && !p.post_lo && (p.n_cosets == 1 || p.coset_out_stride == (1ull << p.log_n));
-    if (p.log_n <= 12 || (p.log_n <= 14 && !(two_pass_ok && p.log_n > ctx->ntt_single_pass_max_log))) {
-        // single pass over HBM
-        a.in = p.in; a.out = p.out;
-        a.in_col_stride = p.in_col_stride; a.out_col_stride = p.out_col_stride;
-        a.log_rows = 0;
-        a.pre_lo = p.pre_lo; a.pre_hi = p.log_n > 12 ? p.pre_hi : nullptr;
-        if (p.pre_lo && p.log_n > 12) {  // two-level lookups would cost an extra modmul per element
-            GL355_TRY(ctx->full_pow_table(p.pre_lo, p.pre_hi, p.n_cosets, p.log_n, &a.pre_full));
-            a.pre_full_stride = 1ull << p.log_n;
-        }
-        a.post_lo = p.post_lo; a.post_hi = p.log_n > 12 ? p.post_hi : nullptr;
-        a.scale = p.scale;
-        a.in_bitrev = p.in_bitrev; a.out_natural = p.out_bitrev ? 0 : 1;
-        a.canon = 1;
-        ProfScope ps(ctx, "ntt_rows_single_pass", ((uint64_t)p.batch << p.log_n) * 8 * (1 + p.n_cosets));
-        GL355_HIP(ctx, launch_rows(a, p.log_n, inv, ctx->stream));
-        return GL355_OK;
-    }
-
-    // two passes; 4-step twiddle omega_N^(+-e) tables
-    const uint64_t* step_lo; const uint64_t* step_hi;
-    int32_t rc = ctx->pow_tables(inv ? gl_inv(gl_root_of_unity(p.log_n)) : gl_root_of_unity(p.log_n), &step_lo, &step_hi);
-    if (rc) return rc;
-    uint32_t l1, l2;
-    // natural order in AND out, plain forward transform of 2^12 < n <= 2^20 points: two column-type passes with the transposition in LDS
-    // (ntt_cols_r8_nat_kernel) instead of two passes + the bit-reversal pass (A/B: profiles/r03_ntt_natural_two_pass.txt)
-    if (!inv && !p.in_bitrev && !p.out_bitrev && p.n_cosets == 1 && !p.pre_lo && !p.post_lo && p.scale == 1 &&
-        p.log_n <= 20 && p.coset_slot[0] == 0) {
-        l2 = p.log_n / 2; l1 = p.log_n - l2;               // l1 >= l2; both <= 10
-        Scratch mid(ctx);
-        GL355_TRY(mid.get(((uint64_t)p.batch << p.log_n) * 8));
-        const uint64_t n = 1ull << p.log_n;
-        a.in = p.in; a.in_col_stride = p.in_col_stride;
-        a.out = mid.as<uint64_t>(); a.out_col_stride = n;
-        a.log_rows = l2;                                   // pass A walks the [N1][N2] matrix: row stride N2
-        GL355_TRY(ctx->nat_step_table(step_lo, step_hi, l1, l2, &a.step_full));
-        { ProfScope ps(ctx, "ntt_cols_pass1", ((uint64_t)p.batch << p.log_n) * 8); GL355_HIP(ctx, launch_cols_r8_nat(a, l1, 0, ctx->stream)); }
-        PassArgs b = a;
-        b.in = mid.as<uint64_t>(); b.in_col_stride = n;
-        b.out = p.out; b.out_col_stride = p.out_col_stride;
-        b.log_rows = l1;                                   // pass B walks the [N2][N1] matrix: row stride N1
-        b.step_full = nullptr;
-        { ProfScope ps(ctx, "ntt_cols_pass2", ((uint64_t)p.batch << p.log_n) * 8); GL355_HIP(ctx, launch_cols_r8_nat(b, l2, 1, ctx->stream)); }
-        return GL355_OK;
-    }
-    if (!p.in_bitrev) {
-        // natural in -> (cols over N1, twiddle at store) -> (rows over N2) -> bit-reversed out
-        split_two_pass(p.log_n, true, &l1, &l2);
-        // From 2^22 points on, THREE passes over 4096-element tiles beat two with 16384-point rows (one block per CU, 4 waves per SIMD):
-        // after the column pass over N1 = N / 2^17 the rows are independent 2^17-point transforms, each the usual column + row pair.
-        // Forward, single coset, contiguous output columns, no pre-multiplier (plain forward NTT: cfg-2 (C)); 2^22 x 16: 1.44 -> see DESIGN 4.1
-        const bool three = !inv && p.log_n >= 22 && p.n_cosets == 1 && !p.pre_lo && !p.post_lo && p.scale == 1 &&
-                           p.out_col_stride == (1ull << p.log_n) && p.coset_slot[0] == 0;
-        // Round 5: from 2^21 points on the same shape runs in TWO passes with 4096-point limb rows: the column pass over 2^(log_n - 12) = 2^9 .. 2^11
-        // points on 8192- / 16384-element tiles (16 columns per tile at 2^21 / 2^22, 8 at 2^23: launch_cols_r8_big) -- 32 bytes of HBM traffic per
-        // element instead of the 48 of three passes.  2^23 (2^11-point columns, 16384-element tiles with the CU to themselves) measured slower than
-        // three passes and stays there (every split measured: profiles/r05_ntt_big_ab.txt).
-        const bool big_shape = !inv && p.log_n >= 21 && p.log_n <= 22 && p.n_cosets == 1 && !p.pre_lo && !p.post_lo && p.scale == 1 &&
-                               p.out_col_stride == (1ull << p.log_n) && p.coset_slot[0] == 0;
-        const uint32_t big_lt = big_shape ? 13 : 0;        // 8192-element column tiles: 16 columns per tile at 2^21, 8 at 2^22
-        const uint32_t big_row = 12;
-        const bool three_now = three && !big_lt;
-        if (big_lt) { l2 = big_row; l1 = p.log_n - big_row; }
-        else if (three) { l2 = 17; l1 = p.log_n - l2; }
-        a.in = p.in; a.out = p.out;
-        a.in_col_stride = p.in_col_stride; a.out_col_stride = p.out_col_stride;
-        a.log_rows = l2;  // log2(N2): row stride of the N1 x N2 matrix
-        a.pre_lo = p.pre_lo; a.pre_hi = p.pre_hi;
-        a.step_lo = step_lo; a.step_hi = step_hi;
-        if (p.log_n <= 20 || three_now || big_lt) {
-            // full-size tables (<= 8 MiB each; the three-pass form: up to 128 MiB of 288 GiB): 1 load + 1 modmul per element instead
-            // of 2 + 2 (beyond 2^20 measured a wash for the radix-16 kernels: 2^21 slower, 2^22 / 2^23 +2-3 %)
-            if (p.pre_lo && ((uint64_t)p.n_cosets << p.log_n) <= (1ull << 21)) {
-                GL355_TRY(ctx->full_pow_table(p.pre_lo, p.pre_hi, p.n_cosets, p.log_n, &a.pre_full));
-                a.pre_full_stride = 1ull << p.log_n;
-            }
-            GL355_TRY(ctx->full_step_table(step_lo, step_hi, l1, l2, inv, &a.step_full));
-            if (a.pre_full && p.n_cosets > 1 && p.coset_ratio) {
-                const uint64_t *rlo, *rhi;
-                GL355_TRY(ctx->pow_tables(p.coset_ratio, &rlo, &rhi));
-                GL355_TRY(ctx->full_pow_table(rlo, rhi, 1, p.log_n, &a.ratio_full));
-            }
-        }
-        a.in_bitrev = 0; a.out_natural = 0; a.canon = 0;
-        {
-            ProfScope ps(ctx, "ntt_cols_pass1", ((uint64_t)p.batch << p.log_n) * 8);
-            if (big_lt) GL355_HIP(ctx, launch_cols_r8_big(a, l1, big_lt, ctx->stream));
-            else GL355_HIP(ctx, launch_cols(a, l1, inv, ctx->stream));
-        }
-        if (three_now) {
-            NttPlan sub;
-            sub.in = p.out; sub.out = p.out;
-            sub.in_col_stride = sub.out_col_stride = 1ull << l2;
-            sub.log_n = l2; sub.batch = p.batch << l1;
-            sub.inverse = false; sub.in_bitrev = false; sub.out_bitrev = true;
-            GL355_TRY(ntt_run(ctx, sub));
-            if (!p.out_bitrev) GL355_TRY(bitrev_permute(ctx, p.out, p.out, p.log_n, 1, p.out_col_stride, p.out_col_stride, p.batch));
-            return GL355_OK;
-        }
-        PassArgs b = a;
-        b.in = p.out; b.in_col_stride = p.out_col_stride;
-        // each coset's intermediate lives in its own output block: rows pass runs per coset slot
-        b.pre_lo = b.pre_hi = nullptr; b.step_lo = b.step_hi = nullptr; b.pre_full = nullptr; b.step_full = nullptr; b.ratio_full = nullptr;
-        if (!inv && l2 == 12 && p.scale == 1) GL355_TRY(ctx->l24_mid_table(&b.mid));
-        b.log_rows = l1;  // rows per column = N1
-        b.scale = p.scale; b.canon = 1;
-        if (p.n_cosets == 1) {
-            b.in = p.out + (uint64_t)a.coset_slot[0] * a.coset_out_stride;
-            ProfScope ps(ctx, "ntt_rows_pass2", ((uint64_t)p.batch << p.log_n) * 8);
-            GL355_HIP(ctx, launch_rows(b, l2, inv, ctx->stream));
-        } else {
-            // the coset blocks are contiguous sub-ranges of every output column: treat (column,
-            // coset) pairs as 2^(l1) * n_cosets rows per column -- requires the blocks to tile the
-            // column, which is how the LDE lays them out (coset_out_stride == n).
-            if (p.coset_out_stride != (1ull << p.log_n))
-                return ctx->fail(GL355_E_INVALID_ARG, "ntt: multi-coset two-pass needs contiguous coset blocks");
-            uint32_t lc = 0;
-            while ((1u << lc) < p.n_cosets) lc++;
-            b.n_cosets = 1; b.coset_slot[0] = 0; b.coset_out_stride = 0;
-            b.log_rows = l1 + lc;
-            ProfScope ps(ctx, "ntt_rows_pass2", ((uint64_t)p.batch * p.n_cosets << p.log_n) * 8);
-            GL355_HIP(ctx, launch_rows(b, l2, inv, ctx->stream));
-        }
-        if (!p.out_bitrev) {
-            // natural order requested: one extra permutation pass (not used on the commit path)
-            if (p.n_cosets != 1) return ctx->fail(GL355_E_UNSUPPORTED, "ntt: natural-order multi-coset output is done by the caller");
+    Scratch mid(ctx);
+    const uint64_t *step_lo = nullptr, *step_hi = nullptr;
+    for (uint32_t i = 0; i < route.n_steps; i++) {
+        const NttStep& st = route.step[i];
+        if (st.form == NTT_BITREV) {
             GL355_TRY(bitrev_permute(ctx, p.out, p.out, p.log_n, 1, p.out_col_stride, p.out_col_stride, p.batch));
+            continue;
         }
-        if (p.post_lo) return ctx->fail(GL355_E_UNSUPPORTED, "ntt: post-multiplier needs natural-order output from the bitrev-input flow");
-        return GL355_OK;
+        PassArgs a;
+        memset(&a, 0, sizeof a);
+        a.batch = p.batch << st.batch_shift;
+        a.log_n = st.xform_log_n;
+        a.log_rows = st.log_rows;
+        a.tw = ctx->twr(4, p.inverse);
+        a.tw_r8 = ctx->twr(3, p.inverse);
+        a.in_bitrev = st.in_bitrev; a.out_natural = st.out_natural; a.canon = st.canon;
+        a.scale = st.scale ? p.scale : 1;
+        if (st.collapse_cosets) a.n_cosets = 1;               // slot 0 at offset 0: the coset blocks are rows of the column
+        else {
+            a.n_cosets = p.n_cosets;
+            a.coset_out_stride = p.coset_out_stride;
+            for (uint32_t c = 0; c < p.n_cosets; c++) a.coset_slot[c] = p.coset_slot[c];
+        }
+        // buffers: a pass that reads the output of a single-coset pass finds it in that coset's block
+        if (st.dst == NTT_BUF_MID) GL355_TRY(mid.get(((uint64_t)p.batch << p.log_n) * 8));
+        const uint64_t slot0 = a.n_cosets == 1 ? (uint64_t)a.coset_slot[0] * a.coset_out_stride : 0;
+        a.in = st.src == NTT_BUF_IN ? p.in : st.src == NTT_BUF_OUT ? p.out + slot0 : mid.as<uint64_t>();
+        a.out = st.dst == NTT_BUF_OUT ? p.out : mid.as<uint64_t>();
+        a.in_col_stride = st.batch_shift ? 1ull << st.xform_log_n : st.src == NTT_BUF_IN ? p.in_col_stride : st.src == NTT_BUF_OUT ? p.out_col_stride : n;
+        a.out_col_stride = st.batch_shift ? 1ull << st.xform_log_n : st.dst == NTT_BUF_OUT ? p.out_col_stride : n;
+        // tables, each built on first use and cached on the context, in this order
+        if (st.fetch_step_root) {
+            const uint64_t root = gl_root_of_unity(st.xform_log_n);
+            GL355_TRY(ctx->pow_tables(p.inverse ? gl_inv(root) : root, &step_lo, &step_hi));
+        }
+        switch (st.pre_tab) {
+            case NTT_TAB_TWO_LEVEL: a.pre_hi = p.pre_hi; [[fallthrough]];
+            case NTT_TAB_ONE_LEVEL: a.pre_lo = p.pre_lo; break;
+            case NTT_TAB_FULL:
+                GL355_TRY(ctx->full_pow_table(p.pre_lo, p.pre_hi, p.n_cosets, p.log_n, &a.pre_full));
+                a.pre_full_stride = n;
+                break;
+            case NTT_TAB_ONE_LEVEL_AS_FULL: a.pre_full = p.pre_lo; a.pre_full_stride = 4096; break;
+            default: break;
+        }
+        switch (st.step_tab) {
+            case NTT_TAB_TWO_LEVEL: a.step_lo = step_lo; a.step_hi = step_hi; break;
+            case NTT_TAB_FULL: GL355_TRY(ctx->full_step_table(step_lo, step_hi, st.log_t, st.log_rows, p.inverse, &a.step_full)); break;
+            case NTT_TAB_NAT: GL355_TRY(ctx->nat_step_table(step_lo, step_hi, st.log_t, st.log_rows, &a.step_full)); break;
+            default: break;
+        }
+        if (st.ratio_tab) {
+            const uint64_t *rlo, *rhi;
+            GL355_TRY(ctx->pow_tables(p.coset_ratio, &rlo, &rhi));
+            GL355_TRY(ctx->full_pow_table(rlo, rhi, 1, p.log_n, &a.ratio_full));
+        }
+        if (st.mid_tab) GL355_TRY(ctx->l24_mid_table(&a.mid));
+        if (st.post_tab != NTT_TAB_NONE) { a.post_lo = p.post_lo; a.post_hi = st.post_tab == NTT_TAB_TWO_LEVEL ? p.post_hi : nullptr; }
+        ProfScope ps(ctx, st.scope, ((uint64_t)p.batch << p.log_n) * st.bytes_per_point);
+        GL355_HIP(ctx, launch_step(st, a, ctx->stream));
     }
-    // bit-reversed in -> (rows over N1, natural within row) -> (cols over N2, twiddle at load) -> natural out
-    if (p.n_cosets != 1) return ctx->fail(GL355_E_UNSUPPORTED, "ntt: bitrev-input flow is single-coset");
-    if (p.out_bitrev) return ctx->fail(GL355_E_UNSUPPORTED, "ntt: bitrev -> bitrev not provided");
-    split_two_pass(p.log_n, false, &l1, &l2);
-    a.in = p.in; a.out = p.out;
-    a.in_col_stride = p.in_col_stride; a.out_col_stride = p.out_col_stride;
-    a.log_rows = l2;  // rows per column = N2 (row index = bitrev(i2))
-    a.in_bitrev = 1; a.out_natural = 1; a.canon = 0;
-    { ProfScope ps(ctx, "ntt_bitrev_in_rows_pass1", ((uint64_t)p.batch << p.log_n) * 8); GL355_HIP(ctx, launch_rows(a, l1, inv, ctx->stream)); }
-    PassArgs b = a;
-    b.in = p.out; b.in_col_stride = p.out_col_stride;
-    b.log_rows = l1;  // matrix is [N2 rows][N1 columns]
-    b.step_lo = step_lo; b.step_hi = step_hi;
-    b.post_lo = p.post_lo; b.post_hi = p.post_hi;
-    b.scale = p.scale; b.canon = 1;
-    b.in_bitrev = 1; b.out_natural = 1;
-    ProfScope ps(ctx, "ntt_bitrev_in_cols_pass2", ((uint64_t)p.batch << p.log_n) * 8);
-    GL355_HIP(ctx, launch_cols(b, l2, inv, ctx->stream));
     return GL355_OK;
 }
+
 
 int32_t bitrev_permute(Ctx* ctx, const uint64_t* in, uint64_t* out, uint32_t log_n, uint32_t width,
                        uint64_t in_col_stride, uint64_t out_col_stride, uint32_t batch) {
@@ -463,44 +307,22 @@ int32_t transpose_cols_to_rows(Ctx* ctx, const uint64_t* in, uint64_t* out, uint
 }
 
 int32_t Ctx::full_pow_table(const uint64_t* lo, const uint64_t* hi, uint32_t n_cosets, uint32_t log_n, const uint64_t** out) {
-    const std::vector<uint64_t> key{1, (uint64_t)(uintptr_t)lo, n_cosets, log_n};
-    auto it = full_cache.find(key);
-    if (it != full_cache.end()) { *out = it->second; return GL355_OK; }
     const uint64_t total = (uint64_t)n_cosets << log_n;
-    uint64_t* d = nullptr;
-    GL355_HIP(this, hipMalloc((void**)&d, total * 8));
-    hipLaunchKernelGGL(build_pow_table_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, lo, hi, n_cosets, 1ull << log_n, d);
-    GL355_HIP(this, hipGetLastError());
-    full_cache[key] = d;
-    *out = d;
-    return GL355_OK;
+    return cached_table({1, (uint64_t)(uintptr_t)lo, n_cosets, log_n}, total, out, [&](uint64_t* d) {
+        hipLaunchKernelGGL(build_pow_table_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, lo, hi, n_cosets, 1ull << log_n, d);
+    });
 }
 int32_t Ctx::full_step_table(const uint64_t* lo, const uint64_t* hi, uint32_t l1, uint32_t l2, bool inv, const uint64_t** out) {
-    const std::vector<uint64_t> key{2, l1, l2, inv ? 1ull : 0ull};
-    auto it = full_cache.find(key);
-    if (it != full_cache.end()) { *out = it->second; return GL355_OK; }
     const uint64_t total = 1ull << (l1 + l2);
-    uint64_t* d = nullptr;
-    GL355_HIP(this, hipMalloc((void**)&d, total * 8));
-    hipLaunchKernelGGL(build_step_table_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, lo, hi, l1, l2, d);
-    GL355_HIP(this, hipGetLastError());
-    full_cache[key] = d;
-    *out = d;
-    return GL355_OK;
+    return cached_table({2, l1, l2, inv ? 1ull : 0ull}, total, out, [&](uint64_t* d) {
+        hipLaunchKernelGGL(build_step_table_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, lo, hi, l1, l2, d);
+    });
 }
-
 int32_t Ctx::nat_step_table(const uint64_t* lo, const uint64_t* hi, uint32_t l1, uint32_t l2, const uint64_t** out) {
-    const std::vector<uint64_t> key{5, l1, l2};
-    auto it = full_cache.find(key);
-    if (it != full_cache.end()) { *out = it->second; return GL355_OK; }
     const uint64_t total = 1ull << (l1 + l2);
-    uint64_t* d = nullptr;
-    GL355_HIP(this, hipMalloc((void**)&d, total * 8));
-    hipLaunchKernelGGL(build_nat_step_table_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, lo, hi, l1, l2, d);
-    GL355_HIP(this, hipGetLastError());
-    full_cache[key] = d;
-    *out = d;
-    return GL355_OK;
+    return cached_table({5, l1, l2}, total, out, [&](uint64_t* d) {
+        hipLaunchKernelGGL(build_nat_step_table_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, lo, hi, l1, l2, d);
+    });
 }
 
 }  // namespace gl355

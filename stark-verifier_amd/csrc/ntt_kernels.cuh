@@ -3,6 +3,7 @@
 // experiments on exactly this code).  Conventions and the design notes are at the top of ntt.hip.
 #pragma once
 #include "gl355_internal.h"
+#include "ntt_route.h"
 
 namespace gl355 {
 
@@ -223,22 +224,24 @@ GL_DEV CosetSlots coset_slots_of(const PassArgs& a) {
 }
 GL_DEV uint32_t coset_slot_at(const CosetSlots& s, uint32_t c) { return (uint32_t)(((c < 8 ? s.lo : s.hi) >> (8 * (c & 7))) & 0xffu); }
 
-// radix-8 commit-path kernels, compiled in ntt_r8.hip
-hipError_t launch_rows_r8(const PassArgs& a, uint32_t log_t, bool inv, hipStream_t s);
-hipError_t launch_cols_r8(const PassArgs& a, uint32_t log_t, bool inv, hipStream_t s);
-hipError_t launch_cols_r8_big(const PassArgs& a, uint32_t log_t, uint32_t lt, hipStream_t s);
-hipError_t launch_cols_r8_cosets(const PassArgs& a, uint32_t log_t, hipStream_t s);
-// the 24-bit-limb passes of the LDE (ntt_l24.cuh), compiled in ntt_l24.hip
-hipError_t launch_rows_l24(const PassArgs& a, hipStream_t s);
-hipError_t launch_cols_l24_cosets(const PassArgs& a, hipStream_t s);
-hipError_t launch_cols_small_cosets(const PassArgs& a, uint32_t log_t, hipStream_t s);
+// One pass of a route (ntt_route.h): the kernel instance the step names, on the step's grid.  Each unit expands the instance lists of its own
+// forms, so a step that ntt_route let through always finds its kernel.  ntt.hip has the radix-16 forms;
+hipError_t launch_step_r8(const NttStep& st, const PassArgs& a, hipStream_t s);    // ntt_r8.hip: the radix-8 commit-path kernels
+hipError_t launch_step_l24(const NttStep& st, const PassArgs& a, hipStream_t s);   // ntt_l24.hip: the 24-bit-limb passes of the LDE (ntt_l24.cuh)
+template <class K>
+static hipError_t launch_pass(K k, const NttStep& st, uint32_t threads, size_t lds_bytes, const PassArgs& a, hipStream_t s) {
+    const NttGrid g = ntt_step_grid(st, a.batch, a.n_cosets);
+    if (lds_bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipLaunchKernelGGL(k, dim3((uint32_t)g.x, g.y), dim3(threads), lds_bytes, s, a);
+    return hipGetLastError();
+}
+// LDS bytes of a 2^lt-element tile with one pad word every 16 (lds_phys)
+constexpr size_t tile_lds_bytes(int lt) { return ((1u << lt) + (1u << (lt - 4))) * sizeof(uint64_t); }
 
-// Row pass: each row = 2^LOG_T contiguous elements; a tile packs 2^(LT-LOG_T) rows.
-// FAST = the commit-path shape with every optional multiplier compiled out: rows pass = no pre / post multiplier, no scaling,
-// natural tile order in and out, canonical store; cols pass = full pre and step tables, nothing else.  The general kernels test
-// those options per element at run time (~110 branches per phase); the LDE of a commitment never uses them.
-template <int LT, int LOG_T, bool INV, bool FAST = false, int WPE = (LT == 12 ? 3 : 1)>
-__global__ void __launch_bounds__(1 << (LT - 4)) __attribute__((amdgpu_waves_per_eu(WPE))) ntt_rows_kernel(PassArgs a) {
+// Row pass: each row = 2^LOG_T contiguous elements; a tile packs 2^(LT-LOG_T) rows.  The general kernels: every optional multiplier, the
+// tile orders and the canonical store are tested per element at run time (the commit-path shapes run the radix-8 kernels below).
+template <int LT, int LOG_T, bool INV>
+__global__ void __launch_bounds__(1 << (LT - 4)) __attribute__((amdgpu_waves_per_eu(LT == 12 ? 3 : 1))) ntt_rows_kernel(PassArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
     constexpr int NT = 1 << (LT - 4);
     constexpr int RPT = 1 << (LT - LOG_T);  // rows per tile
@@ -260,12 +263,10 @@ __global__ void __launch_bounds__(1 << (LT - 4)) __attribute__((amdgpu_waves_per
         if (row < total_rows) {
             const uint64_t col = row >> a.log_rows, rin = row & (rows_per_col - 1);
             v = a.in[col * a.in_col_stride + (rin << LOG_T) + e];
-            if constexpr (!FAST) {
-                if (a.pre_full) v = gl_mul(v, a.pre_full[(uint64_t)coset * a.pre_full_stride + (rin << LOG_T) + e]);
-                else if (pre_lo) v = gl_mul(v, pow2lvl(pre_lo, pre_hi, (rin << LOG_T) + e));
-            }
+            if (a.pre_full) v = gl_mul(v, a.pre_full[(uint64_t)coset * a.pre_full_stride + (rin << LOG_T) + e]);
+            else if (pre_lo) v = gl_mul(v, pow2lvl(pre_lo, pre_hi, (rin << LOG_T) + e));
         }
-        const uint32_t le = (!FAST && a.in_bitrev) ? brev(e, LOG_T) : e;
+        const uint32_t le = a.in_bitrev ? brev(e, LOG_T) : e;
         lds[lds_phys((lr << LOG_T) | le)] = v;
     }
     __syncthreads();
@@ -278,13 +279,11 @@ __global__ void __launch_bounds__(1 << (LT - 4)) __attribute__((amdgpu_waves_per
         const uint64_t row = row0 + lr;
         if (row < total_rows) {
             const uint64_t col = row >> a.log_rows, rin = row & (rows_per_col - 1);
-            const uint32_t le = (!FAST && a.out_natural) ? brev(e, LOG_T) : e;
+            const uint32_t le = a.out_natural ? brev(e, LOG_T) : e;
             uint64_t v = lds[lds_phys((lr << LOG_T) | le)];
-            if constexpr (!FAST) {
-                if (a.post_lo) v = gl_mul(v, pow2lvl(a.post_lo, a.post_hi, (rin << LOG_T) + e));
-                if (a.scale != 1) v = gl_mul(v, a.scale);
-                if (a.canon) v = gl_canon(v);
-            } else v = gl_canon(v);
+            if (a.post_lo) v = gl_mul(v, pow2lvl(a.post_lo, a.post_hi, (rin << LOG_T) + e));
+            if (a.scale != 1) v = gl_mul(v, a.scale);
+            if (a.canon) v = gl_canon(v);
             a.out[out_base + col * a.out_col_stride + (rin << LOG_T) + e] = v;
         }
     }
@@ -463,7 +462,7 @@ __global__ void __launch_bounds__(LT >= 13 ? 1024 : 512) __attribute__((amdgpu_w
 
 // Column pass: transform over the row index of an [2^LOG_T][N2] matrix (N2 = 2^log_rows... here
 // a.log_rows holds log2(N2)); a tile is all 2^LOG_T rows x TC = 2^(12-LOG_T) adjacent columns.
-template <int LOG_T, bool INV, bool FAST = false>
+template <int LOG_T, bool INV>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) ntt_cols_kernel(PassArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
     constexpr int LT = 12, NT = 256;
@@ -488,15 +487,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) n
         const uint32_t r = g >> LOG_TC, cc = g & (TC - 1);
         const uint64_t gi = ((uint64_t)r << log_n2) + c0 + cc;
         uint64_t v = in[gi];
-        uint32_t lr = r;  // logical transform index
-        if constexpr (FAST) {
-            v = gl_mul(v, a.pre_full[(uint64_t)coset * a.pre_full_stride + gi]);
-        } else {
-            lr = a.in_bitrev ? brev(r, LOG_T) : r;
-            if (a.pre_full) v = gl_mul(v, a.pre_full[(uint64_t)coset * a.pre_full_stride + gi]);
-            else if (pre_lo) v = gl_mul(v, pow2lvl(pre_lo, pre_hi, gi));
-            if (step_at_load && a.step_lo) v = gl_mul(v, pow2lvl(a.step_lo, a.step_hi, (uint64_t)lr * (c0 + cc)));
-        }
+        const uint32_t lr = a.in_bitrev ? brev(r, LOG_T) : r;  // logical transform index
+        if (a.pre_full) v = gl_mul(v, a.pre_full[(uint64_t)coset * a.pre_full_stride + gi]);
+        else if (pre_lo) v = gl_mul(v, pow2lvl(pre_lo, pre_hi, gi));
+        if (step_at_load && a.step_lo) v = gl_mul(v, pow2lvl(a.step_lo, a.step_hi, (uint64_t)lr * (c0 + cc)));
         lds[lds_phys((lr << LOG_TC) | cc)] = v;
     }
     __syncthreads();
@@ -505,21 +499,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) n
     for (int i = 0; i < 16; i++) {
         const uint32_t g = tid + i * NT;
         const uint32_t r = g >> LOG_TC, cc = g & (TC - 1);
-        const uint32_t lr = (!FAST && a.out_natural) ? brev(r, LOG_T) : r;  // LDS row holding output row r
+        const uint32_t lr = a.out_natural ? brev(r, LOG_T) : r;  // LDS row holding output row r
         uint64_t v = lds[lds_phys((lr << LOG_TC) | cc)];
         const uint64_t go = ((uint64_t)r << log_n2) + c0 + cc;
-        if constexpr (FAST) {
-            v = gl_mul(v, a.step_full[go]);
-        } else {
-            if (!step_at_load && a.step_full) v = gl_mul(v, a.step_full[go]);
-            else if (!step_at_load && a.step_lo) {
-                const uint32_t k1 = a.out_natural ? r : brev(r, LOG_T);  // transform output index
-                v = gl_mul(v, pow2lvl(a.step_lo, a.step_hi, (uint64_t)k1 * (c0 + cc)));
-            }
-            if (a.post_lo) v = gl_mul(v, pow2lvl(a.post_lo, a.post_hi, go));
-            if (a.scale != 1) v = gl_mul(v, a.scale);
-            if (a.canon) v = gl_canon(v);
+        if (!step_at_load && a.step_full) v = gl_mul(v, a.step_full[go]);
+        else if (!step_at_load && a.step_lo) {
+            const uint32_t k1 = a.out_natural ? r : brev(r, LOG_T);  // transform output index
+            v = gl_mul(v, pow2lvl(a.step_lo, a.step_hi, (uint64_t)k1 * (c0 + cc)));
         }
+        if (a.post_lo) v = gl_mul(v, pow2lvl(a.post_lo, a.post_hi, go));
+        if (a.scale != 1) v = gl_mul(v, a.scale);
+        if (a.canon) v = gl_canon(v);
         out[go] = v;
     }
 }
@@ -646,7 +636,6 @@ __global__ void __launch_bounds__(1 << (LT - 3)) __attribute__((amdgpu_waves_per
         dif_last_round_sink<LT, R8Last<LOG_T>::RHO, false, decltype(store), 1>(lds, LOG_TC, tid, NT, store);
     }
 }
-hipError_t launch_cols_r8_nat(const PassArgs& a, uint32_t log_t, int pass, hipStream_t s);
 
 // Column pass of an LDE whose coset bases form a geometric sequence (base[c] = shift * w^c: PolynomialCoeffs::lde): ONE block takes a
 // tile through ALL cosets.  The per-coset kernel above reads the coefficients once per coset (8 x 141 MB through the fabric at

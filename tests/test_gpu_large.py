@@ -121,6 +121,40 @@ def test_ntt_above_2p20_strided(ctx, orc, log_n):
         eq(ctx.coset_ifft(x[:1]), orc.ntt(x[:1], inverse=True, shift=7))
 
 
+def test_ntt_2p24_one_column(ctx, orc):
+    """the largest size: three passes with a 128-point first column pass forward, 1024-point general column passes in the coset forward
+    and in the inverse transform (the instances of csrc/ntt_route.h that only 2^24 reaches)"""
+    rng = np.random.default_rng(0x355 + 24)
+    x = rand_field(rng, (1, 1 << 24))
+    y = ctx.fft(x)
+    eq(y, orc.ntt(x))
+    eq(ctx.ifft(y), x)
+    eq(ctx.coset_fft(x), orc.ntt(x, shift=7))
+
+
+@pytest.mark.parametrize("log_n", [13, 14, 15])
+def test_lde_more_columns_than_a_grid_dimension(ctx, orc, log_n):
+    """65536 columns: the batch no longer fits a grid's second dimension, so the 2-, 4- and 8-point column passes leave the streaming kernel
+    for the all-cosets radix-8 kernel (its instances below 16 points have no other shape).  Coefficients generated on the device, rate 1,
+    bit-reversed output; the first, a middle and the last column against the oracle"""
+    import ctypes as C
+    import torch
+    B, n = 65536, 1 << log_n
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0x458 + log_n)
+    cd = torch.randint(0, (1 << 63) - 1, (B, n), dtype=torch.int64, device="cuda", generator=g)      # canonical (< p) by construction
+    out = torch.empty((B, 2 * n), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    ctx.check(ctx.lib.gl355_lde_bitrev(ctx.h, C.c_void_p(cd.data_ptr()), log_n, 1, 7, B, C.c_void_p(out.data_ptr())))
+    ctx.sync()
+    cols = [0, 40001, B - 1]
+    c = cd[cols].cpu().numpy().view(np.uint64)
+    got = out[cols].cpu().numpy().view(np.uint64)
+    del cd, out
+    torch.cuda.empty_cache()
+    eq(got, orc.reverse_index_bits(orc.lde(c, 1).T.copy()).T)
+
+
 @pytest.mark.parametrize("log_n", [18, 20])
 def test_lde_to_2p21_2p23(ctx, orc, log_n):
     rng = np.random.default_rng(0x455 + log_n)

@@ -3,8 +3,8 @@ values), batches that fill, overflow and nearly fill the 4096-element tile of th
 from n = 1, and small LDEs with many columns at every supported rate.  Integer arithmetic: every comparison is exact.
 
 The reference is the CPU oracle (orc.ntt / orc.lde / orc.reverse_index_bits); for n <= 64 a direct O(n^2) DFT in Python integers with
-omega_n = 7^((p-1)/n) (include/gl355.h) is a second witness.  Which dispatcher branch of ntt_run each size takes is recorded in
-docs/history/ntt_shapes.md."""
+omega_n = 7^((p-1)/n) (include/gl355.h) is a second witness.  Which route (csrc/ntt_route.h) each size takes is recorded in
+docs/history/ntt_shapes.md and, instance by instance, in docs/history/ntt_route.md."""
 import ctypes as C
 
 import numpy as np
@@ -186,6 +186,25 @@ def test_lde_small_sizes_many_columns(gl, ctx, orc, log_n, rate_bits):
                    "shift %d bit-reversed" % shift)
         finally:
             c2.close()
+
+
+# the kernel instances of the route table (csrc/ntt_route.h) that no other case reaches, each at the smallest shape that does
+# (docs/history/ntt_route.md has the instance of every case): radix-8 columns with a pre table over 4, 64, 128 and 256 points (one coset),
+# general radix-16 columns over 64 points (16 cosets: the full pre tables would pass 2^21 words), all-cosets radix-8 columns over 256 points
+@pytest.mark.parametrize("log_n,rate_bits", [(14, 0), (18, 0), (19, 0), (20, 0), (18, 4), (20, 1)])
+def test_lde_column_kernels_without_another_case(ctx, orc, log_n, rate_bits):
+    rng = np.random.default_rng(0x5760 + 8 * log_n + rate_bits)
+    c = rand_field(rng, (2, 1 << log_n))
+    want = orc.lde(c, rate_bits)
+    eq(ctx.lde(c, rate_bits), want, "natural")
+    eq(ctx.lde(c, rate_bits, bitrev=True), orc.reverse_index_bits(want.T.copy()).T, "bit-reversed")
+
+
+def test_inverse_2p19(ctx, orc):
+    """the only size whose inverse has a 128-point column pass (general radix-16 columns, step twiddle at the load)"""
+    rng = np.random.default_rng(0x5761)
+    x = rand_field(rng, (2, 1 << 19))
+    eq(ctx.ifft(x), orc.ntt(x, inverse=True), "inverse")
 
 
 def test_ntt_lde_refusals(ctx):

@@ -10,11 +10,6 @@
 #include <cstdlib>
 #include <vector>
 using namespace gl355;
-namespace gl355 {   // declared by ntt_kernels.cuh for the library build; not used here
-hipError_t launch_rows_r8(const PassArgs&, uint32_t, bool, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_cols_r8(const PassArgs&, uint32_t, bool, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_cols_r8_cosets(const PassArgs&, uint32_t, hipStream_t) { return hipErrorNotSupported; }
-}
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 __global__ void fill_kernel(uint64_t* p, uint64_t n) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
