@@ -979,18 +979,23 @@ int32_t gl355_bn254_g1_chain(gl355_ctx* ctx, int32_t form, const uint32_t* opera
  *                                  gl_mul_fill, _MUL2_FILL = gl_mul2_fill, _SQR = gl_sqr, _SBOX = psd_sbox, _SBOX4 = psd_sbox4 (x^7; these three read a only,
  *                                  b may be NULL), _RECOMBINE = psd_recombine and _RECOMBINE_MULTI4 = psd_recombine_multi<4> (a = al, b = ah, whose
  *                                  contract is (ah >> 32) + 1 < 2^32).  One lane takes N CONSECUTIVE records of an N-wide form (MULTI N; MUL2_FILL 2;
- *                                  SBOX4 and RECOMBINE_MULTI4 4): n must be a multiple of N.  The two FILL forms get fillers of the shape of the
+ *                                  SBOX4 and RECOMBINE_MULTI4 4; PARTIAL_ROUNDS 12): n must be a multiple of N.  The two FILL forms get fillers of the shape of the
  *                                  permutation's own (two multiply-adds each, into two accumulators, between a carry's writer and its reader) and
  *                                  write the accumulators out too, so `out` holds 3 n words for them: out[n + i] = al and out[2 n + i] = ah of the
  *                                  lane whose FIRST record is i (0 at a pair's second record), where with x_k = a[i] (k + 1) + b[i] mod 2^64 and the MDS
  *                                  row c = {17, 15, 41, 16, 2}: al = lo32(b[i]) + sum_k lo32(x_k) c_k, ah = hi32(b[i]) + sum_k hi32(x_k) c_k, k = 0 .. 4.
+ *                                  _PARTIAL_ROUNDS = psd_partial_rounds_b3, the permutation's rounds 4 .. 25 (seven blocks of three partial rounds, then
+ *                                  one dense): one lane takes TWELVE consecutive records, a = the state entering round 4 with that round's constants
+ *                                  added (any u64), out = the state entering round 26 with its constants added; b is not read and may be NULL.  (Its
+ *                                  number is 13: 12 stays unassigned, tests/test_gpu_gl_arith.py passes it as an unknown op.)
  *                                  GL355_E_INVALID_ARG for an unknown op, n not a multiple of N, or a null buffer with n > 0; n = 0 launches nothing.
  *   gl355_poseidon_permute_lanes   `count` states of 12 words permuted in place by the 16-lane permutation of the Merkle tops and FRI wide leaves
  *                                  (gates/poseidon.rs:504-589's rounds, one word per lane): form 0 (every round dense) or 3 (the partial rounds' row
  *                                  inside the S-box), any other form is GL355_E_INVALID_ARG.  Four states per 64-thread block; all 12 words come back
  *                                  canonical. */
 enum { GL355_GL_MUL = 0, GL355_GL_MUL_MULTI1 = 1, GL355_GL_MUL_MULTI2 = 2, GL355_GL_MUL_MULTI3 = 3, GL355_GL_MUL_MULTI4 = 4, GL355_GL_MUL_FILL = 5,
-       GL355_GL_MUL2_FILL = 6, GL355_GL_SQR = 7, GL355_GL_SBOX = 8, GL355_GL_SBOX4 = 9, GL355_GL_RECOMBINE = 10, GL355_GL_RECOMBINE_MULTI4 = 11 };
+       GL355_GL_MUL2_FILL = 6, GL355_GL_SQR = 7, GL355_GL_SBOX = 8, GL355_GL_SBOX4 = 9, GL355_GL_RECOMBINE = 10, GL355_GL_RECOMBINE_MULTI4 = 11,
+       GL355_GL_PARTIAL_ROUNDS = 13 };
 int32_t gl355_gl_arith_batch(gl355_ctx* ctx, int32_t op, const uint64_t* a /* n */, const uint64_t* b /* n or NULL */, uint64_t* out /* n, or 3 n */, uint64_t n);
 int32_t gl355_poseidon_permute_lanes(gl355_ctx* ctx, int32_t form, uint64_t* states /* count x 12 */, uint64_t count);
 

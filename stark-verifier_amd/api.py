@@ -189,7 +189,8 @@ class Context:
 
     def gl_arith_batch(self, op, a, b=None):
         """test hook (GL355_GL_*): op on raw u64 words, results as the device routine returns them (not reduced).  The two FILL forms
-        return (products, al, ah)."""
+        return (products, al, ah); GL355_GL_PARTIAL_ROUNDS (13) takes twelve consecutive words per lane, the state entering round 4, and
+        returns the twelve entering round 26."""
         a = _u64(a).reshape(-1)
         fill = op in (5, 6)          # GL355_GL_MUL_FILL, GL355_GL_MUL2_FILL
         out = np.empty(a.size * (3 if fill else 1), dtype=np.uint64)

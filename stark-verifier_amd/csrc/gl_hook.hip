@@ -1,5 +1,5 @@
-// Test hooks of the Goldilocks product forms and of the 16-lane Poseidon permutation (include/gl355.h "test hooks"; tests/test_gpu_gl_arith.py,
-// tests/test_gpu_poseidon_lanes.py): the shipped device functions of gl_field.cuh / poseidon.cuh / poseidon_lanes.cuh on raw u64 words.  No
+// Test hooks of the Goldilocks product forms, of the partial rounds and of the 16-lane Poseidon permutation (include/gl355.h "test hooks";
+// tests/test_gpu_gl_arith.py, tests/test_gpu_poseidon_b3.py, tests/test_gpu_poseidon_lanes.py): the shipped device functions of gl_field.cuh / poseidon.cuh / poseidon_lanes.cuh on raw u64 words.  No
 // product path calls them.
 #include "gl355_internal.h"
 #include "poseidon_lanes.cuh"
@@ -13,6 +13,7 @@ static int hk_gl_width(int32_t op) {
     case GL355_GL_MUL_MULTI2: case GL355_GL_MUL2_FILL: return 2;
     case GL355_GL_MUL_MULTI3: return 3;
     case GL355_GL_MUL_MULTI4: case GL355_GL_SBOX4: case GL355_GL_RECOMBINE_MULTI4: return 4;
+    case GL355_GL_PARTIAL_ROUNDS: return 12;
     default: return 0;
     }
 }
@@ -80,6 +81,15 @@ __global__ void __launch_bounds__(256) gl_arith_hook_kernel(int32_t op, int32_t 
         break;
     }
     case GL355_GL_RECOMBINE: po[0] = psd_recombine(pa[0], pb[0]); break;
+    case GL355_GL_PARTIAL_ROUNDS: {
+        uint64_t s[12];
+#pragma unroll
+        for (int j = 0; j < 12; j++) s[j] = pa[j];
+        psd_partial_rounds_b3(s);
+#pragma unroll
+        for (int j = 0; j < 12; j++) po[j] = s[j];
+        break;
+    }
     default: {      // GL355_GL_RECOMBINE_MULTI4
         const uint64_t al[4] = {pa[0], pa[1], pa[2], pa[3]}, ah[4] = {pb[0], pb[1], pb[2], pb[3]};
         uint64_t r[4];
@@ -117,7 +127,7 @@ int32_t gl355_gl_arith_batch(gl355_ctx* h, int32_t op, const uint64_t* a, const 
     if (!width) return ctx->fail(GL355_E_INVALID_ARG, "gl_arith_batch: bad op");
     if (n % (uint64_t)width) return ctx->fail(GL355_E_INVALID_ARG, "gl_arith_batch: n is not a multiple of the op's records per lane");
     if (n == 0) return GL355_OK;
-    const bool two = !(op == GL355_GL_SQR || op == GL355_GL_SBOX || op == GL355_GL_SBOX4);
+    const bool two = !(op == GL355_GL_SQR || op == GL355_GL_SBOX || op == GL355_GL_SBOX4 || op == GL355_GL_PARTIAL_ROUNDS);
     if (!a || !out || (two && !b)) return ctx->fail(GL355_E_INVALID_ARG, "gl_arith_batch: null argument");
     const uint64_t lanes = n / (uint64_t)width;
     if ((lanes + 255) / 256 > 0x7FFFFFFFull) return ctx->fail(GL355_E_UNSUPPORTED, "gl_arith_batch: too many records");

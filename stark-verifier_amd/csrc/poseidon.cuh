@@ -27,8 +27,8 @@ GL_DEV uint64_t psd_sbox(uint64_t x) {
 }
 
 // al + ah * 2^32  ->  u64 representative, for accumulators whose top word ah1 = ah >> 32 satisfies ah1 + 1 < 2^32: the two chains of an MDS row
-// (al, ah < 2^44) and the block form's dot products (66 products < 2^54 plus a 32-bit constant: al, ah < 2^61, ah1 < 2^29; the bound is asserted on
-// the generated tables by tools/gen_poseidon_tables.py and tests/test_tables.py).
+// (al, ah < 2^44) and the dot products of a block of three partial rounds (coefficients summing to < 2^24 times 32-bit halves plus a 32-bit constant:
+// al, ah < 2^56, ah1 < 2^24; the bound is asserted on the generated table by tools/gen_poseidon_tables.py and tests/test_poseidon_b3_tables.py).
 // = al0 + (al1 + ah0) 2^32 + ah1 2^64: one 32-bit add with carry into the top word, then top * EPS with the carry-out repaid.
 GL_DEV uint64_t psd_recombine(uint64_t al, uint64_t ah) {
     uint32_t t1 = (uint32_t)(al >> 32), top;     // t1 is updated in place: (al0, t1) stays the register pair of al
@@ -105,8 +105,8 @@ GL_DEV uint64_t psd_mds_chain(const uint32_t (&x)[12], uint64_t addend) {
 #undef PSD_X
     return acc;
 }
-template <int R>
-GL_DEV void psd_mds_rows(uint64_t (&s)[12], const uint32_t (&lo)[12], const uint32_t (&hi)[12], const uint64_t* rc) {
+template <int R, class RC>
+GL_DEV void psd_mds_rows(uint64_t (&s)[12], const uint32_t (&lo)[12], const uint32_t (&hi)[12], RC rc) {
     if constexpr (R < 12) {
         // four rows at a time: eight chains, then their recombinations in lock-step
         const uint64_t c0 = rc[R], c1 = rc[R + 1], c2 = rc[R + 2], c3 = rc[R + 3];
@@ -118,165 +118,148 @@ GL_DEV void psd_mds_rows(uint64_t (&s)[12], const uint32_t (&lo)[12], const uint
         __builtin_amdgcn_sched_barrier(0);
         psd_recombine_multi<4>(al, ah, o);
         s[R] = o[0]; s[R + 1] = o[1]; s[R + 2] = o[2]; s[R + 3] = o[3];
-        psd_mds_rows<R + 4>(s, lo, hi, rc);
+        psd_mds_rows<R + 4, RC>(s, lo, hi, rc);
     }
 }
-// rc: 12 constants at a wave-uniform address (scalar loads)
-GL_DEV void psd_mds(uint64_t (&s)[12], const uint64_t* rc) {
+// rc: 12 constants at a wave-uniform address (scalar loads); a pointer into PSD_ALL_RC, generic or in the constant address space
+template <class RC>
+GL_DEV void psd_mds(uint64_t (&s)[12], RC rc) {
     uint32_t lo[12], hi[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) { lo[i] = (uint32_t)s[i]; hi[i] = (uint32_t)(s[i] >> 32); }
-    psd_mds_rows<0>(s, lo, hi, rc);
+    psd_mds_rows<0, RC>(s, lo, hi, rc);
 }
 
 
-// ---- the 22 partial rounds in BLOCK form (round 5) ------------------------------------------------------------------------------
-// Only lane 0 meets the S-box in a partial round, so over a block of B = 11 rounds lanes 1..11 are a linear function of the state u that
-// entered the block and of the block's S-box outputs x_0..x_{B-1} (gates/poseidon.rs:504-589 factors the same linearity round by round;
-// here it is unrolled over a block, tools/gen_poseidon_tables.py has the algebra and a limb-exact model):
-//     y_j  = <alpha_j, u> + sum_{i<j} x_i kappa_{j-1-i} + gamma_j     (lane 0 entering round j of the block),   x_j = y_j^7
-//     s'_r = <(A^B)_r, u> + sum_{i<B} x_i beta_{B-1-i}[r] + Gamma_r   (the state leaving the block)
-// Every output is ONE dot product with 64-bit constants, reduced once: 429 multiply-accumulates + 22 reductions per block where the dense form
-// spends 11 x 144 small-constant multiply-accumulates + 11 x 12 reductions -- 6 864 instead of 8 976 vector instructions for the 22 rounds.
-// A multiply-accumulate x * c costs six v_mad_u64_u32 and nothing else: x is split ONCE into limbs of 22 / 22 / 20 bits (each x and u is used by
-// 11..22 outputs), the table holds (c, 2^22 c, 2^44 c) mod p, limb k times the low / high half of the k-th constant goes into the low / high
-// accumulator; 66 products < 2^54 and a 32-bit constant cannot overflow 64 bits, and psd_recombine folds al + ah 2^32 as for an MDS row.
+// ---- the partial rounds in blocks of THREE on integer matrix powers ----------------------------------------------------------------------
+// Only lane 0 meets the S-box in a partial round, so over a block of three rounds the state is a linear function of the state u that entered the
+// block and of the block's S-box outputs x_0, x_1, x_2 (gates/poseidon.rs:504-589 factors the same linearity round by round).  With M the MDS matrix
+// as INTEGERS, N = M with column 0 zeroed and m0 = column 0 of M (tools/gen_poseidon_tables.py has the algebra and a half-exact model):
+//     x_0 = u_0^7,   y_k = (N^k u)[0] + sum_{i<k} (N^(k-1-i) m0)[0] x_i + g_k[0],   x_k = y_k^7   (k = 1, 2: lane 0 entering the block's next rounds)
+//     s'  = N^3 u + sum_{i<3} (N^(2-i) m0) x_i + g_3                                              (the state leaving the block)
+// Three rounds of 6-bit entries give coefficients below 2^21 with row sums below 2^24 WITHOUT reduction mod p, so a term is the coefficient times
+// the two 32-bit halves the state already lives in: two v_mad_u64_u32 into two accumulators that start from the halves of the additive constant and
+// stay below 2^56 (psd_recombine's contract with 2^8 to spare; asserted on the generated table by tests/test_poseidon_b3_tables.py).  Nothing is split
+// and the constants are one 32-bit word each: 12 + 13 + 12 x 14 terms per block, the same for all seven blocks of rounds 4 .. 24; round 25 runs
+// dense.  (Blocks of eleven on matrix powers reduced mod p, the form before this one, paid six multiply-adds per term for their 64-bit constants:
+// docs/history/poseidon_b3.md.  Blocks of four no longer fit 64-bit accumulators.)
 // (the tables are NOT const-qualified on the device: with the values visible the compiler strength-reduces the small ones into 64-bit shifts and
-// adds, keeps every limb as a zero-extended register PAIR for them -- 174 VGPRs -- and materialises the rest as 32-bit literals with a wait state each)
+// adds on zero-extended register PAIRS and materialises the rest as 32-bit literals with a wait state each)
 #undef PSD_TABLE_QUAL
 #define PSD_TABLE_QUAL __device__ __constant__
-#include "poseidon_ktables.h"
+#include "poseidon_b3tables.h"
 
-GL_DEV void psd_split(uint64_t x, uint32_t (&l)[3]) {
-    const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
-    l[0] = lo & 0x3FFFFFu;
-    l[1] = __builtin_amdgcn_alignbit(hi, lo, 22) & 0x3FFFFFu;
-    l[2] = hi >> 12;
-}
-// c: the three table words of this multiply-accumulate, wave-uniform (SGPRs: the multiplier of every multiply-add)
-typedef const __attribute__((address_space(4))) uint64_t* psd_ktab;      // constant address space: wave-uniform reads become scalar loads
-GL_DEV void psd_mac(uint64_t& lo, uint64_t& hi, const uint32_t (&l)[3], const uint64_t (&c)[3]) {
-    const uint64_t c0 = c[0], c1 = c[1], c2 = c[2];
-    // written out: in C the compiler keeps one zero-extended 64-bit copy of every limb (a register PAIR each, 132 VGPRs of limbs) and truncates
-    // it at each use.  src0 = the constant (SGPR, the one constant-bus operand), src1 = the limb; the carry-out pair is never read.
+typedef const __attribute__((address_space(4))) uint32_t* psd_b3tab;      // constant address space: wave-uniform reads become scalar loads
+typedef const __attribute__((address_space(4))) uint64_t* psd_b3add;
+// one term: the coefficient c (an SGPR, the one constant-bus operand of both multiply-adds) times the halves of v, which are the registers of v
+// themselves; the carry-out pair is never read.  Written out: in C the compiler zero-extends each half into a register pair of its own.
+GL_DEV void psd_b3_term(uint64_t& lo, uint64_t& hi, uint32_t c, uint64_t v) {
     uint64_t unused;
-    asm("v_mad_u64_u32 %0, %2, %3, %9, %0\n\tv_mad_u64_u32 %1, %2, %4, %9, %1\n\t"
-        "v_mad_u64_u32 %0, %2, %5, %10, %0\n\tv_mad_u64_u32 %1, %2, %6, %10, %1\n\t"
-        "v_mad_u64_u32 %0, %2, %7, %11, %0\n\tv_mad_u64_u32 %1, %2, %8, %11, %1"
+    asm("v_mad_u64_u32 %0, %2, %3, %4, %0\n\tv_mad_u64_u32 %1, %2, %3, %5, %1"
+        : "+v"(lo), "+v"(hi), "=&s"(unused) : "s"(c), "v"((uint32_t)v), "v"((uint32_t)(v >> 32)));
+}
+// five terms in one statement (the compiler puts a wait state between two statements that write scalar pairs)
+GL_DEV void psd_b3_terms5(uint64_t& lo, uint64_t& hi, const uint32_t* c, const uint64_t* v) {
+    uint64_t unused;
+#define PSD_V(i) "v"((uint32_t)v[i]), "v"((uint32_t)(v[i] >> 32))
+    asm("v_mad_u64_u32 %0, %2, %3, %8, %0\n\tv_mad_u64_u32 %1, %2, %3, %9, %1\n\t"
+        "v_mad_u64_u32 %0, %2, %4, %10, %0\n\tv_mad_u64_u32 %1, %2, %4, %11, %1\n\t"
+        "v_mad_u64_u32 %0, %2, %5, %12, %0\n\tv_mad_u64_u32 %1, %2, %5, %13, %1\n\t"
+        "v_mad_u64_u32 %0, %2, %6, %14, %0\n\tv_mad_u64_u32 %1, %2, %6, %15, %1\n\t"
+        "v_mad_u64_u32 %0, %2, %7, %16, %0\n\tv_mad_u64_u32 %1, %2, %7, %17, %1"
         : "+v"(lo), "+v"(hi), "=&s"(unused)
-        : "s"((uint32_t)c0), "s"((uint32_t)(c0 >> 32)), "s"((uint32_t)c1), "s"((uint32_t)(c1 >> 32)), "s"((uint32_t)c2), "s"((uint32_t)(c2 >> 32)),
-          "v"(l[0]), "v"(l[1]), "v"(l[2]));
+        : "s"(c[0]), "s"(c[1]), "s"(c[2]), "s"(c[3]), "s"(c[4]), PSD_V(0), PSD_V(1), PSD_V(2), PSD_V(3), PSD_V(4));
+#undef PSD_V
 }
-// the first multiply-accumulate of an output: the accumulators start from the additive constant's halves.  Inside the statement, so that the
-// constant is read where the group's other constants are (a C initialisation is copied to VGPRs right behind its scalar load: a wait of its own).
-GL_DEV void psd_mac_first(uint64_t& lo, uint64_t& hi, const uint32_t (&l)[3], const uint64_t (&c)[3], const uint64_t (&add)[2]) {
-    const uint64_t c0 = c[0], c1 = c[1], c2 = c[2];
+// the first term of an output: the accumulators start from the additive constant's halves.  Inside the statement, so that the constant is read
+// where the row's coefficients are (a C initialisation is copied to VGPRs right behind its scalar load: a wait of its own).
+GL_DEV void psd_b3_term_first(uint64_t& lo, uint64_t& hi, uint32_t c, uint64_t v, const uint64_t (&add)[2]) {
     uint64_t unused;
-    asm("v_mov_b64 %0, %12\n\tv_mov_b64 %1, %13\n\t"
-        "v_mad_u64_u32 %0, %2, %3, %9, %0\n\tv_mad_u64_u32 %1, %2, %4, %9, %1\n\t"
-        "v_mad_u64_u32 %0, %2, %5, %10, %0\n\tv_mad_u64_u32 %1, %2, %6, %10, %1\n\t"
-        "v_mad_u64_u32 %0, %2, %7, %11, %0\n\tv_mad_u64_u32 %1, %2, %8, %11, %1"
-        : "=&v"(lo), "=&v"(hi), "=&s"(unused)
-        : "s"((uint32_t)c0), "s"((uint32_t)(c0 >> 32)), "s"((uint32_t)c1), "s"((uint32_t)(c1 >> 32)), "s"((uint32_t)c2), "s"((uint32_t)(c2 >> 32)),
-          "v"(l[0]), "v"(l[1]), "v"(l[2]), "s"(add[0]), "s"(add[1]));
+    asm("v_mov_b64 %0, %6\n\tv_mov_b64 %1, %7\n\t"
+        "v_mad_u64_u32 %0, %2, %3, %4, %0\n\tv_mad_u64_u32 %1, %2, %3, %5, %1"
+        : "=&v"(lo), "=&v"(hi), "=&s"(unused) : "s"(c), "v"((uint32_t)v), "v"((uint32_t)(v >> 32)), "s"(add[0]), "s"(add[1]));
 }
-constexpr int psd_k_group = 5;      // multiply-accumulates per group of scalar loads: 6 SGPRs of constants each, two groups in flight
-// The block's table is consumed front to back.  Scalar loads return out of order, so the only wait is "all of them": a group's constants are
-// therefore requested one group AHEAD -- the first multiply-accumulate of a group waits for the group's constants (requested while the previous
-// group was being consumed), then the next group's loads are issued, then the remaining multiply-accumulates run under their latency.  The
-// scheduling barriers pin that order; without them the scheduler either issues the loads of a whole dot product (132 SGPRs, spilled into VGPR
-// lanes) or waits for each group right after requesting it (a lonely wave then sits through the scalar-cache latency 90 times per block).
-struct PsdK {
-    uint64_t w[psd_k_group][3];     // (c, 2^22 c, 2^44 c) of the group's multiply-accumulates
-    uint64_t a[2];                  // when the group opens an output: the output's additive constant (low half, high half)
+// The table is consumed front to back, one row (= one output) per group of scalar loads.  Scalar loads return out of order, so the only wait is
+// "all of them": a row's constants are therefore requested one row AHEAD -- the first term of an output waits for its row (requested while the
+// previous output was being accumulated, or under an S-box), then the next row's loads are issued, then the remaining terms run under their
+// latency.  The scheduling barriers pin that order; without them the scheduler either issues the loads of a whole block (252 SGPRs, spilled into
+// VGPR lanes) or waits for each row right after requesting it (a lonely wave then sits through the scalar-cache latency 14 times per block).
+struct PsdB3Row {
+    uint32_t w[14];                 // the row's coefficients (12 or 13 of them for y_1, y_2: the rest is the row's zero padding and never loaded)
+    uint64_t a[2];                  // the output's additive constant (low half, high half)
 };
-template <int N, bool WITH_ADD>
-GL_DEV void psd_kload(PsdK& k, psd_ktab c, psd_ktab add) {
+template <int NT>
+GL_DEV void psd_b3_load(PsdB3Row& k, psd_b3tab c, psd_b3add add) {
 #pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) k.w[i][j] = c[3 * i + j];
-    if constexpr (WITH_ADD) { k.a[0] = add[0]; k.a[1] = add[1]; }
+    for (int i = 0; i < NT; i++) k.w[i] = c[i];
+    k.a[0] = add[0]; k.a[1] = add[1];
 }
-// -> (lo, hi): lo + hi 2^32 = add + sum_{t < 11} ul[t] c[t] + sum_{t < NX} xl[t] c[11 + t] (the caller folds it: psd_recombine).  k: this output's first group (requested
-// earlier); on return the NEXT output's first group (table position c + 3 (11 + NX), additive constant add_next), requested, if HAS_NEXT.
-template <int NX, bool HAS_NEXT, int XCAP>
-GL_DEV void psd_dot(const uint32_t (&ul)[11][3], const uint32_t (&xl)[XCAP][3], psd_ktab c, PsdK& k, psd_ktab add_next, uint64_t& lo, uint64_t& hi) {
-    constexpr int G = psd_k_group, NT = 11 + NX, NG = (NT + G - 1) / G;
-    PsdK cur = k;
+// -> (lo, hi): lo + hi 2^32 = add + sum_{t < 11} u[t + 1] w[t] + sum_{t < NX} x[t] w[11 + t] (the caller folds it).  k: this output's row (requested
+// earlier); on return the NEXT output's row (NT_NEXT terms at `next`, additive constant at `add_next`), requested, unless NT_NEXT is 0.
+template <int NX, int NT_NEXT>
+GL_DEV void psd_b3_dot(const uint64_t (&u)[12], const uint64_t (&x)[3], PsdB3Row& k, psd_b3tab next, psd_b3add add_next, uint64_t& lo, uint64_t& hi) {
+    const PsdB3Row cur = k;
+    psd_b3_term_first(lo, hi, cur.w[0], u[1], cur.a);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (NT_NEXT > 0) psd_b3_load<NT_NEXT>(k, next, add_next);
+    __builtin_amdgcn_sched_barrier(0);
+    psd_b3_terms5(lo, hi, &cur.w[1], &u[2]);
+    psd_b3_terms5(lo, hi, &cur.w[6], &u[7]);
 #pragma unroll
-    for (int g = 0; g < NG; g++) {
-        const int n = NT - g * G < G ? NT - g * G : G;
-        PsdK nxt;
-#pragma unroll
-        for (int i = 0; i < G; i++) {
-            const int t = g * G + i;
-            if (t == 0) psd_mac_first(lo, hi, ul[0], cur.w[0], cur.a);
-            else if (i < n) {
-                if (t < 11) psd_mac(lo, hi, ul[t], cur.w[i]);
-                else psd_mac(lo, hi, xl[t - 11], cur.w[i]);
-            }
-            if (i == 0) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (g + 1 < NG) {
-                    if (NT - (g + 1) * G >= G) psd_kload<G, false>(nxt, c + 3 * (g + 1) * G, add_next);
-                    else psd_kload<(NT % G ? NT % G : G), false>(nxt, c + 3 * (g + 1) * G, add_next);
-                } else if constexpr (HAS_NEXT) {
-                    psd_kload<G, true>(nxt, c + 3 * NT, add_next);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (g + 1 < NG || HAS_NEXT) cur = nxt;          // (the last group of the last output requested nothing: nxt is not initialised then)
-    }
-    if constexpr (HAS_NEXT) k = cur;
+    for (int t = 0; t < NX; t++) psd_b3_term(lo, hi, cur.w[11 + t], x[t]);
+    __builtin_amdgcn_sched_barrier(0);
 }
-template <int J>
-GL_DEV void psd_block_lane0(const uint32_t (&ul)[11][3], uint32_t (&xl)[PSD_K_BLOCK][3], psd_ktab mac, psd_ktab add, PsdK& k) {
-    if constexpr (J < PSD_K_BLOCK) {
-        uint64_t lo, hi;
-        psd_dot<J, true>(ul, xl, mac + 3 * (11 * (J - 1) + (J - 1) * J / 2), k, add + 2 * J, lo, hi);
-        psd_split(psd_sbox(psd_recombine(lo, hi)), xl[J]);
-        __builtin_amdgcn_sched_barrier(0);
-        psd_block_lane0<J + 1>(ul, xl, mac, add, k);
-    }
-}
+// outgoing lanes R .. R + 3: eight accumulators, then their recombinations in lock-step (no wait states of their own)
 template <int R>
-GL_DEV void psd_block_out(uint64_t (&s)[12], const uint32_t (&ul)[11][3], const uint32_t (&xl)[PSD_K_BLOCK][3], psd_ktab mac, psd_ktab add, PsdK& k) {
-    constexpr int B = PSD_K_BLOCK;
+GL_DEV void psd_b3_out(uint64_t (&o)[12], const uint64_t (&u)[12], const uint64_t (&x)[3], psd_b3tab mac, psd_b3add add, PsdB3Row& k) {
     if constexpr (R < 12) {
-        // (grouping four outgoing lanes for a lock-step recombination costs 12 live VGPRs: 102 instead of 96, a wave per SIMD less)
-        uint64_t lo, hi;
-        psd_dot<B, (R < 11)>(ul, xl, mac + 3 * (11 * (B - 1) + (B - 1) * B / 2 + (11 + B) * R), k, add + 2 * (B + R), lo, hi);
-        s[R] = psd_recombine(lo, hi);
+        constexpr int W = PSD_B3_ROW_WORDS;
+        uint64_t al[4], ah[4], r[4];
+        psd_b3_dot<3, 14>(u, x, k, mac + W * (R + 3), add + 2 * (R + 3), al[0], ah[0]);
+        psd_b3_dot<3, 14>(u, x, k, mac + W * (R + 4), add + 2 * (R + 4), al[1], ah[1]);
+        psd_b3_dot<3, 14>(u, x, k, mac + W * (R + 5), add + 2 * (R + 5), al[2], ah[2]);
+        psd_b3_dot<3, (R + 3 < 11 ? 14 : 0)>(u, x, k, mac + W * (R + 6), add + 2 * (R + 6), al[3], ah[3]);
+        psd_recombine_multi<4>(al, ah, r);
+        o[R] = r[0]; o[R + 1] = r[1]; o[R + 2] = r[2]; o[R + 3] = r[3];
         __builtin_amdgcn_sched_barrier(0);
-        psd_block_out<R + 1>(s, ul, xl, mac, add, k);
+        psd_b3_out<R + 4>(o, u, x, mac, add, k);
     }
 }
-GL_DEV void psd_partial_rounds_block(uint64_t (&s)[12]) {
-    constexpr int B = PSD_K_BLOCK;
+// rounds 4 .. 25 on the state entering round 4 (its constants added; ANY twelve u64) -> the state entering round 26 (constants added)
+GL_DEV void psd_partial_rounds_b3(uint64_t (&s)[12]) {
 #pragma unroll 1
-    for (int blk = 0; blk < 22 / B; blk++) {
-        psd_ktab add = (psd_ktab)PSD_K_ADD + blk * 2 * (B - 1 + 12);
-        psd_ktab mac = (psd_ktab)PSD_K_MAC;
-        asm volatile("" : "+s"(mac));         // re-read per block: hoisted out of this loop the table would sit in ~2 600 SGPRs
-        PsdK k;
-        psd_kload<psd_k_group, true>(k, mac, add);        // y_1's first group, under the first S-box
+    for (int blk = 0; blk < PSD_B3_BLOCKS; blk++) {
+        constexpr int W = PSD_B3_ROW_WORDS;
+        psd_b3add add = (psd_b3add)PSD_B3_ADD + blk * 2 * 14;
+        psd_b3tab mac = (psd_b3tab)PSD_B3_MAC;
+        asm volatile("" : "+s"(mac), "+s"(add));      // re-read per block (hoisted out of this loop the table would sit in ~200 SGPRs), at immediate offsets
+        PsdB3Row k;
+        psd_b3_load<12>(k, mac, add);         // y_1's row, under the first S-box
         __builtin_amdgcn_sched_barrier(0);
-        uint32_t ul[11][3], xl[B][3];
+        uint64_t x[3], o[12], lo, hi;
+        x[0] = psd_sbox(s[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        psd_b3_dot<1, 13>(s, x, k, mac + W, add + 2, lo, hi);
+        x[1] = psd_sbox(psd_recombine(lo, hi));
+        __builtin_amdgcn_sched_barrier(0);
+        psd_b3_dot<2, 14>(s, x, k, mac + 2 * W, add + 4, lo, hi);
+        x[2] = psd_sbox(psd_recombine(lo, hi));
+        __builtin_amdgcn_sched_barrier(0);
+        psd_b3_out<0>(o, s, x, mac, add, k);
 #pragma unroll
-        for (int i = 0; i < 11; i++) psd_split(s[i + 1], ul[i]);
-        psd_split(psd_sbox(s[0]), xl[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        psd_block_lane0<1>(ul, xl, mac, add, k);
-        psd_block_out<0>(s, ul, xl, mac, add, k);
+        for (int i = 0; i < 12; i++) s[i] = o[i];
     }
+    // round 25, dense.  Its constants are read here: at a visible address the compiler loads them once per kernel and, in the leaf hasher, keeps
+    // them in spilled SGPRs that every permutation reads back lane by lane
+    psd_b3add rc26 = (psd_b3add)PSD_ALL_RC + 12 * 26;
+    asm volatile("" : "+s"(rc26));
+    s[0] = psd_sbox(s[0]);
+    psd_mds(s, rc26);
 }
 
 // 30 rounds of (constants, S-box on every element [4 + 4 full rounds] or on element 0 [22 partial rounds], MDS); round r's MDS adds round
-// r+1's constants (PSD_ALL_RC row 30 is zero).  The full rounds are dense (S-boxes, whole MDS layer), the partial rounds run in the block form
-// above (against the dense form for all 30 rounds: profiles/r01_poseidon_dense_vs_sparse.txt, profiles/r05_poseidon_block_vs_dense.txt).
+// r+1's constants (PSD_ALL_RC row 30 is zero).  The full rounds are dense (S-boxes, whole MDS layer), the partial rounds run in blocks of three,
+// above (against the dense form for all 30 rounds: profiles/r01_poseidon_dense_vs_sparse.txt; against blocks of eleven: profiles/poseidon_b3.txt).
 // Two rounds per iteration (4 + 4: always whole pairs), so the state ping-pongs between two register sets instead of being copied back at the
 // loop edge.
 constexpr int psd_rounds_per_iter = 2;
@@ -295,7 +278,7 @@ GL_DEV void psd_permute(uint64_t (&s)[12]) {
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = gl_add_canonical(s[i], PSD_ALL_RC[i]);
     psd_dense_rounds(s, 0, 4);
-    psd_partial_rounds_block(s);
+    psd_partial_rounds_b3(s);
     psd_dense_rounds(s, 26, 30);
 }
 
