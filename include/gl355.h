@@ -988,6 +988,15 @@ int32_t gl355_bn254_g1_chain(gl355_ctx* ctx, int32_t form, const uint32_t* opera
  *                                  one dense): one lane takes TWELVE consecutive records, a = the state entering round 4 with that round's constants
  *                                  added (any u64), out = the state entering round 26 with its constants added; b is not read and may be NULL.  (Its
  *                                  number is 13: 12 stays unassigned, tests/test_gpu_gl_arith.py passes it as an unknown op.)
+ *                                  _ROW_DENSE (14) and _ROW_B3 (15) = the permutation's CHAINED rows (psd_mds; psd_b3_dot with psd_fold / psd_fold_multi<4>):
+ *                                  one lane takes TWELVE consecutive records of a, raw words.  Their constants are wave-uniform scalar operands on the
+ *                                  device, so they are read from the HEAD of b, the same for every lane of a launch (n >= 36 so that b holds them):
+ *                                  _ROW_DENSE  out[r] = b[2 + r] + sum_i CIRC[i] a[(i + r) % 12] (+ 8 a[0] for r = 0), r = 0 .. 11: one MDS layer, each row
+ *                                  at its own position of its four-wide group.  _ROW_B3  the rows of PSD_B3_MAC on u = a[0 .. 11] and x = a[0 .. 2] with
+ *                                  the additive constant of row r in b[2 + 2 r] (low half) and b[3 + 2 r] (high half), r = 0 .. 13 (PSD_B3_ADD's layout
+ *                                  for one block); b[0] = 0: out[0] = y_1 (row 0, 12 terms), 1: out[0] = y_2 (row 1, 13 terms), out[1 .. 11] = 0;
+ *                                  any other value: out[r] = row 2 + r (14 terms), r = 0 .. 11.  The caller keeps the rows' precondition:
+ *                                  high half + (low half + row sum (2^32 - 1)) / 2^32 < 2^32 for every constant passed.
  *                                  GL355_E_INVALID_ARG for an unknown op, n not a multiple of N, or a null buffer with n > 0; n = 0 launches nothing.
  *   gl355_poseidon_permute_lanes   `count` states of 12 words permuted in place by the 16-lane permutation of the Merkle tops and FRI wide leaves
  *                                  (gates/poseidon.rs:504-589's rounds, one word per lane): form 0 (every round dense) or 3 (the partial rounds' row
@@ -995,7 +1004,7 @@ int32_t gl355_bn254_g1_chain(gl355_ctx* ctx, int32_t form, const uint32_t* opera
  *                                  canonical. */
 enum { GL355_GL_MUL = 0, GL355_GL_MUL_MULTI1 = 1, GL355_GL_MUL_MULTI2 = 2, GL355_GL_MUL_MULTI3 = 3, GL355_GL_MUL_MULTI4 = 4, GL355_GL_MUL_FILL = 5,
        GL355_GL_MUL2_FILL = 6, GL355_GL_SQR = 7, GL355_GL_SBOX = 8, GL355_GL_SBOX4 = 9, GL355_GL_RECOMBINE = 10, GL355_GL_RECOMBINE_MULTI4 = 11,
-       GL355_GL_PARTIAL_ROUNDS = 13 };
+       GL355_GL_PARTIAL_ROUNDS = 13, GL355_GL_ROW_DENSE = 14, GL355_GL_ROW_B3 = 15 };
 int32_t gl355_gl_arith_batch(gl355_ctx* ctx, int32_t op, const uint64_t* a /* n */, const uint64_t* b /* n or NULL */, uint64_t* out /* n, or 3 n */, uint64_t n);
 int32_t gl355_poseidon_permute_lanes(gl355_ctx* ctx, int32_t form, uint64_t* states /* count x 12 */, uint64_t count);
 

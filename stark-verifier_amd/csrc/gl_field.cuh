@@ -63,9 +63,10 @@ GL_HD uint64_t gl_neg(uint64_t a) { return gl_sub(0, a); }
 // ---- device multiplication / 128-bit reduction ----
 // The compiler cannot be made to use the carry-out of v_mad_u64_u32 (it re-derives carries with 64-bit compares and
 // selects every correction with two v_cndmask: 26 VALU instructions per product).  Two device formulations:
-//   GL_MUL_VARIANT 1: the carry-out / borrow steps in inline asm: 15 VALU instructions, but gfx950 needs two wait states
+//   GL_MUL_VARIANT 1: the carry-out / borrow steps in inline asm: 14 VALU instructions (one signed correction for the borrow and the carry of the
+//     reduction together: gl_dev_reduce_tail), but gfx950 needs two wait states
 //     between a VALU write of an SGPR/VCC and a VALU read of it, the hazard recogniser does not look inside inline asm, and
-//     an asm block cannot be interleaved with its neighbours: 8 s_nop per product.  Best where many waves hide them (Poseidon).
+//     an asm block cannot be interleaved with its neighbours: three s_nop 1 per lone product (five before the single correction).  Best where many waves hide them (Poseidon).
 //   GL_MUL_VARIANT 2: carries re-derived in C the way the compiler digests best: 22 VALU instructions, no forced s_nop (latency-bound
 //     kernels with many independent products in flight: the NTT butterflies).
 // A translation unit picks with -DGL_MUL_VARIANT / #define before this header; the host always uses the 128-bit C product.
@@ -85,7 +86,24 @@ GL_HD uint64_t gl_neg(uint64_t a) { return gl_sub(0, a); }
 // the asm of a __device__ function).  The host-only .cpp units never see them.
 #if defined(__HIPCC__)
 #if GL_MUL_VARIANT == 1
-// x = lo - sub32: a borrow is repaid with -EPS (the wrapped x is >= p then, so no second borrow)
+// (lo0, lo1) - w_hi + w_lo * EPS with ONE correction for both wraps (docs/history/carry_tails.md): z = lo - w_hi with borrow b2, y = z + w_lo * EPS
+// with carry c1, result y + (c1 - b2) * EPS.  That last step cannot wrap: after a carry alone y <= 2^64 - 1 + (2^32 - 1)^2 - 2^64 = 2^64 - 2^33, so
+// y + EPS < 2^64; after a borrow alone lo < w_hi < 2^32, so y >= z >= 2^64 - 2^32 + 1 > EPS; both or neither: nothing to add.  d = c1 - b2 in
+// {-1, 0, 1} is applied as d * 2^32 - d: a signed multiply-add by -1 and a 32-bit add into the high word (tests/test_gl_tail_model.py steps
+// through exactly these instructions).  Subtracting first keeps (lo0, lo1) out of a register pair of their own (they are halves of two products).
+GL_DEV uint64_t gl_dev_reduce_tail(uint32_t lo0, uint32_t lo1, uint32_t w_hi, uint32_t w_lo) {
+    uint32_t x0, x1, d;
+    uint64_t b2, c1, r;
+    asm("v_sub_co_u32_e64 %0, %2, %3, %4\n\t" GL_HAZARD_NOP "v_subb_co_u32_e64 %1, %2, %5, 0, %2"
+        : "=&v"(x0), "=&v"(x1), "=&s"(b2) : "v"(lo0), "v"(w_hi), "v"(lo1));
+    // b2 is read four wait states after its write (multiply-add, s_nop 1, select)
+    asm("v_mad_u64_u32 %0, %1, %3, -1, %4\n\t" GL_HAZARD_NOP "v_cndmask_b32_e64 %2, 0, 1, %1\n\t"
+        "v_subb_co_u32_e64 %2, %1, %2, 0, %5\n\t"
+        "v_mad_i64_i32 %0, %1, %2, -1, %0"
+        : "=&v"(r), "=&s"(c1), "=&v"(d) : "v"(w_lo), "v"(((uint64_t)x1 << 32) | x0), "s"(b2));
+    return (((uint64_t)((uint32_t)(r >> 32) + d)) << 32) | (uint32_t)r;
+}
+// x = lo - sub32: a borrow is repaid with -EPS (the wrapped x is >= p then, so no second borrow).  On its own for the NTT's 2^48 twiddle.
 GL_DEV uint64_t gl_dev_sub32(uint32_t lo0, uint32_t lo1, uint32_t sub32) {
     uint32_t x0, x1, m;
     asm("v_sub_co_u32_e32 %0, vcc, %3, %5\n\t" GL_HAZARD_NOP ""
@@ -124,6 +142,10 @@ GL_DEV uint64_t gl_dev_add_mul_eps(uint64_t x, uint32_t k) {
     const uint64_t r = (uint64_t)k * 0xFFFFFFFFu + x;
     return r + (r < x ? 0xFFFFFFFFu : 0u);
 }
+// the compiler-scheduled form keeps its two corrections (the NTT's products are as they were)
+GL_DEV uint64_t gl_dev_reduce_tail(uint32_t lo0, uint32_t lo1, uint32_t w_hi, uint32_t w_lo) {
+    return gl_dev_add_mul_eps(gl_dev_sub32(lo0, lo1, w_hi), w_lo);
+}
 GL_DEV uint64_t gl_dev_mid(uint32_t a1, uint32_t b0, uint64_t u, uint32_t* v0) {
     const uint64_t v = (uint64_t)a1 * b0 + u;
     *v0 = (uint32_t)v;
@@ -135,7 +157,7 @@ GL_DEV uint64_t gl_dev_mid(uint32_t a1, uint32_t b0, uint64_t u, uint32_t* v0) {
 // (lo, hi) = hi*2^64 + lo  ->  lo - hi_hi + hi_lo*(2^32 - 1)      [2^64 = 2^32-1, 2^96 = -1 mod p]
 GL_HD uint64_t gl_reduce128(uint64_t lo, uint64_t hi) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    return gl_dev_add_mul_eps(gl_dev_sub32((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)(hi >> 32)), (uint32_t)hi);
+    return gl_dev_reduce_tail((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)(hi >> 32), (uint32_t)hi);
 #else
     uint32_t hi_hi = (uint32_t)(hi >> 32), hi_lo = (uint32_t)hi;
     uint64_t t0 = lo - hi_hi;
@@ -156,7 +178,7 @@ GL_HD uint64_t gl_mul(uint64_t a, uint64_t b) {
     uint32_t v0;
     const uint64_t mid = gl_dev_mid(a1, b0, u, &v0);
     const uint64_t w = (uint64_t)a1 * b1 + mid;
-    return gl_dev_add_mul_eps(gl_dev_sub32((uint32_t)t, v0, (uint32_t)(w >> 32)), (uint32_t)w);
+    return gl_dev_reduce_tail((uint32_t)t, v0, (uint32_t)(w >> 32), (uint32_t)w);
 #else
     unsigned __int128 pr = (unsigned __int128)a * b;
     return gl_reduce128((uint64_t)pr, (uint64_t)(pr >> 64));
@@ -165,7 +187,7 @@ GL_HD uint64_t gl_mul(uint64_t a, uint64_t b) {
 
 GL_HD uint64_t gl_sqr(uint64_t a) { return gl_mul(a, a); }
 
-// N independent products in lock-step, stage by stage (round 5).  The five carry steps of a product each need two wait states between the VALU
+// N independent products in lock-step, stage by stage (round 5).  The three carry readers of a product each need two wait states between the VALU
 // instruction that writes the carry (an SGPR pair) and the one that reads it; inside ONE product nothing else can go there (s_nop: 1.7 % of a
 // full-occupancy hash kernel, 18 % of one at one wave per SIMD, profiles/r05_poseidon_block_vs_dense.txt).  With N products issued round-robin the
 // partners' instructions ARE the wait states: every stage is its own asm statement (so the compiler still names the 32-bit halves of the 64-bit
@@ -185,7 +207,7 @@ GL_DEV void gl_mul_multi(const uint64_t (&a)[N], const uint64_t (&b)[N], uint64_
         else asm(INS : __VA_ARGS__);                                       \
     } while (0)
     uint32_t a0[N], a1[N], b0[N], b1[N], ch[N], x0[N], x1[N], m[N];
-    uint64_t t[N], u[N], v[N], w[N], c[N];
+    uint64_t t[N], u[N], v[N], w[N], c[N], bw[N];
 #pragma unroll
     for (int j = 0; j < N; j++) { a0[j] = (uint32_t)a[j]; a1[j] = (uint32_t)(a[j] >> 32); b0[j] = (uint32_t)b[j]; b1[j] = (uint32_t)(b[j] >> 32); }
 #pragma unroll
@@ -198,29 +220,29 @@ GL_DEV void gl_mul_multi(const uint64_t (&a)[N], const uint64_t (&b)[N], uint64_
 #pragma unroll
     for (int j = 0; j < N; j++) w[j] = (uint64_t)a1[j] * b1[j] + (((uint64_t)ch[j] << 32) | (v[j] >> 32));
     GL_MM_SB();
-    // x = (t_lo, v_lo) - w_hi, a borrow repaid with -EPS
+    // the tail of gl_dev_reduce_tail: z = (t_lo, v_lo) - w_hi, its borrow kept in a scalar pair of its own (bw) ...
 #pragma unroll
-    for (int j = 0; j < N; j++) { asm("v_sub_co_u32_e64 %0, %1, %2, %3" : "=v"(x0[j]), "=s"(c[j]) : "v"((uint32_t)t[j]), "v"((uint32_t)(w[j] >> 32))); GL_MM_SB(); }
+    for (int j = 0; j < N; j++) { asm("v_sub_co_u32_e64 %0, %1, %2, %3" : "=v"(x0[j]), "=s"(bw[j]) : "v"((uint32_t)t[j]), "v"((uint32_t)(w[j] >> 32))); GL_MM_SB(); }
 #pragma unroll
-    for (int j = 0; j < N; j++) { GL_MM_READ("v_subb_co_u32_e64 %0, %1, %2, 0, %1", "=v"(x1[j]), "+s"(c[j]) : "v"((uint32_t)v[j])); GL_MM_SB(); }
-#pragma unroll
-    for (int j = 0; j < N; j++) { GL_MM_READ("v_cndmask_b32_e64 %0, 0, -1, %1", "=v"(m[j]) : "s"(c[j])); GL_MM_SB(); }
-#pragma unroll
-    for (int j = 0; j < N; j++) { asm("v_sub_co_u32_e64 %0, %1, %0, %2" : "+v"(x0[j]), "=s"(c[j]) : "v"(m[j])); GL_MM_SB(); }
-#pragma unroll
-    for (int j = 0; j < N; j++) { GL_MM_READ("v_subb_co_u32_e64 %0, %1, %0, 0, %1", "+v"(x1[j]), "+s"(c[j])); GL_MM_SB(); }
-    // + w_lo * EPS, the carry-out repaid with +EPS.  The repayment is a second multiply-add (carry in {0, 1} times EPS): as a 64-bit add every product
-    // in flight needs a zero-extended register pair of its own for the addend, i.e. a register move each
+    for (int j = 0; j < N; j++) { GL_MM_READ("v_subb_co_u32_e64 %0, %1, %2, 0, %1", "=v"(x1[j]), "+s"(bw[j]) : "v"((uint32_t)v[j])); GL_MM_SB(); }
+    // ... y = z + w_lo * EPS with its carry ...
 #pragma unroll
     for (int j = 0; j < N; j++) {
         const uint64_t x = ((uint64_t)x1[j] << 32) | x0[j];
         asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(r[j]), "=s"(c[j]) : "v"((uint32_t)w[j]), "v"(x));
         GL_MM_SB();
     }
+    // ... and ONE correction y + d * EPS, d = carry - borrow in {-1, 0, 1}, as y - d (a signed multiply-add by -1) and d into the high word.  The borrow's
+    // reader is at least two instructions behind its writer for every N (the multiply-add and the select of the same product): no wait states of its own
 #pragma unroll
     for (int j = 0; j < N; j++) { GL_MM_READ("v_cndmask_b32_e64 %0, 0, 1, %1", "=v"(m[j]) : "s"(c[j])); GL_MM_SB(); }
+    // (the carry-outs of these two are never read; "+s" keeps each product's in its own pair: the compiler separates statements that write the SAME pair)
 #pragma unroll
-    for (int j = 0; j < N; j++) asm("v_mad_u64_u32 %0, %1, %2, -1, %0" : "+v"(r[j]), "=s"(c[j]) : "v"(m[j]));
+    for (int j = 0; j < N; j++) { asm("v_subb_co_u32_e64 %0, %1, %0, 0, %2" : "+v"(m[j]), "+s"(c[j]) : "s"(bw[j])); GL_MM_SB(); }
+#pragma unroll
+    for (int j = 0; j < N; j++) { asm("v_mad_i64_i32 %0, %1, %2, -1, %0" : "+v"(r[j]), "+s"(c[j]) : "v"(m[j])); GL_MM_SB(); }
+#pragma unroll
+    for (int j = 0; j < N; j++) r[j] = ((uint64_t)((uint32_t)(r[j] >> 32) + m[j]) << 32) | (uint32_t)r[j];
 #undef GL_MM_READ
 #undef GL_MM_SB
 }

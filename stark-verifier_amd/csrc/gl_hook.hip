@@ -6,6 +6,38 @@
 
 namespace gl355 {
 
+// N recombinations of psd_recombine's form in lock-step (the two carry steps of one fill the wait states of the others: see gl_mul_multi).  The
+// permutation's rows are chained now (poseidon.cuh psd_fold_multi) and no shipped kernel calls this; GL355_GL_RECOMBINE_MULTI4 keeps driving it.
+template <int N>
+GL_DEV void psd_recombine_multi(const uint64_t (&al)[N], const uint64_t (&ah)[N], uint64_t (&out)[N]) {
+    static_assert(N >= 3, "three or more: no wait states of their own");
+    uint32_t t1[N], top[N], m[N];
+    uint64_t c[N], r[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        asm("v_add_co_u32_e64 %0, %1, %2, %3" : "=v"(t1[j]), "=s"(c[j]) : "v"((uint32_t)(al[j] >> 32)), "v"((uint32_t)ah[j]));
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        asm("v_addc_co_u32_e64 %0, %1, 0, %2, %1" : "=v"(top[j]), "+s"(c[j]) : "v"((uint32_t)(ah[j] >> 32)));
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const uint64_t x = ((uint64_t)t1[j] << 32) | (uint32_t)al[j];
+        asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(r[j]), "=s"(c[j]) : "v"(top[j]), "v"(x));
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        asm("v_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(m[j]) : "s"(c[j]));
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) out[j] = r[j] + (uint64_t)m[j];
+}
+
 // records per lane of an op (one lane takes that many CONSECUTIVE records), 0 for an unknown op
 static int hk_gl_width(int32_t op) {
     switch (op) {
@@ -13,7 +45,7 @@ static int hk_gl_width(int32_t op) {
     case GL355_GL_MUL_MULTI2: case GL355_GL_MUL2_FILL: return 2;
     case GL355_GL_MUL_MULTI3: return 3;
     case GL355_GL_MUL_MULTI4: case GL355_GL_SBOX4: case GL355_GL_RECOMBINE_MULTI4: return 4;
-    case GL355_GL_PARTIAL_ROUNDS: return 12;
+    case GL355_GL_PARTIAL_ROUNDS: case GL355_GL_ROW_DENSE: case GL355_GL_ROW_B3: return 12;
     default: return 0;
     }
 }
@@ -90,6 +122,49 @@ __global__ void __launch_bounds__(256) gl_arith_hook_kernel(int32_t op, int32_t 
         for (int j = 0; j < 12; j++) po[j] = s[j];
         break;
     }
+    // the chained rows.  Their constants are wave-uniform scalar operands in the permutation, so here they come from the HEAD of b, the same for every
+    // lane of the launch: b[0] selects, the constants follow from b[2] in the layout the device tables have
+    case GL355_GL_ROW_DENSE: {      // one MDS layer on twelve raw words: row r = b[2 + r] + sum_i CIRC[i] a[(i + r) % 12] (+ 8 a[0] for r = 0)
+        uint64_t s[12];
+#pragma unroll
+        for (int j = 0; j < 12; j++) s[j] = pa[j];
+        psd_b3add rc = (psd_b3add)(b + 2);
+        asm volatile("" : "+s"(rc));
+        psd_mds(s, rc);
+#pragma unroll
+        for (int j = 0; j < 12; j++) po[j] = s[j];
+        break;
+    }
+    case GL355_GL_ROW_B3: {         // the rows of a block of three on u = a[0 .. 11], x = a[0 .. 2]; additive constants b[2 + 2 r], b[3 + 2 r] (low, high half) of row r
+        uint64_t u[12], x[3], o[12], lo, hi;
+#pragma unroll
+        for (int j = 0; j < 12; j++) { u[j] = pa[j]; o[j] = 0; }
+        x[0] = u[0]; x[1] = u[1]; x[2] = u[2];
+        constexpr int W = PSD_B3_ROW_WORDS;
+        psd_b3add add = (psd_b3add)(b + 2);
+        psd_b3tab mac = (psd_b3tab)PSD_B3_MAC;
+        const uint64_t row = b[0];
+        asm volatile("" : "+s"(mac), "+s"(add));
+        PsdB3Row k;
+        if (row == 0) {             // y_1: 12 terms, a lone fold
+            psd_b3_load<12>(k, mac, add);
+            __builtin_amdgcn_sched_barrier(0);
+            psd_b3_dot<1, 13>(u, x, k, mac + W, add + 2, lo, hi);
+            o[0] = psd_fold(lo, hi);
+        } else if (row == 1) {      // y_2: 13 terms
+            psd_b3_load<13>(k, mac + W, add + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            psd_b3_dot<2, 14>(u, x, k, mac + 2 * W, add + 4, lo, hi);
+            o[0] = psd_fold(lo, hi);
+        } else {                    // the twelve outgoing lanes, four folds in lock-step at a time
+            psd_b3_load<14>(k, mac + 2 * W, add + 4);
+            __builtin_amdgcn_sched_barrier(0);
+            psd_b3_out<0>(o, u, x, mac, add, k);
+        }
+#pragma unroll
+        for (int j = 0; j < 12; j++) po[j] = o[j];
+        break;
+    }
     default: {      // GL355_GL_RECOMBINE_MULTI4
         const uint64_t al[4] = {pa[0], pa[1], pa[2], pa[3]}, ah[4] = {pb[0], pb[1], pb[2], pb[3]};
         uint64_t r[4];
@@ -127,6 +202,8 @@ int32_t gl355_gl_arith_batch(gl355_ctx* h, int32_t op, const uint64_t* a, const 
     if (!width) return ctx->fail(GL355_E_INVALID_ARG, "gl_arith_batch: bad op");
     if (n % (uint64_t)width) return ctx->fail(GL355_E_INVALID_ARG, "gl_arith_batch: n is not a multiple of the op's records per lane");
     if (n == 0) return GL355_OK;
+    const bool rows = op == GL355_GL_ROW_DENSE || op == GL355_GL_ROW_B3;
+    if (rows && n < 36) return ctx->fail(GL355_E_INVALID_ARG, "gl_arith_batch: the row ops read 30 words of constants from the head of b: three lanes or more");
     const bool two = !(op == GL355_GL_SQR || op == GL355_GL_SBOX || op == GL355_GL_SBOX4 || op == GL355_GL_PARTIAL_ROUNDS);
     if (!a || !out || (two && !b)) return ctx->fail(GL355_E_INVALID_ARG, "gl_arith_batch: null argument");
     const uint64_t lanes = n / (uint64_t)width;

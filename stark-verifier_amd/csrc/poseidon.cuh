@@ -26,9 +26,9 @@ GL_DEV uint64_t psd_sbox(uint64_t x) {
     return gl_mul(r[0], r[1]);
 }
 
-// al + ah * 2^32  ->  u64 representative, for accumulators whose top word ah1 = ah >> 32 satisfies ah1 + 1 < 2^32: the two chains of an MDS row
-// (al, ah < 2^44) and the dot products of a block of three partial rounds (coefficients summing to < 2^24 times 32-bit halves plus a 32-bit constant:
-// al, ah < 2^56, ah1 < 2^24; the bound is asserted on the generated table by tools/gen_poseidon_tables.py and tests/test_poseidon_b3_tables.py).
+// al + ah * 2^32  ->  u64 representative, for two INDEPENDENT accumulators whose top word ah1 = ah >> 32 satisfies ah1 + 1 < 2^32: the rows of the
+// 16-lane permutation (poseidon_lanes.cuh) and of the witness tape, whose chains run side by side (al, ah < 2^44).  The one-state-per-lane
+// permutation below chains its rows instead (psd_chain_start / psd_fold) and does not come here.
 // = al0 + (al1 + ah0) 2^32 + ah1 2^64: one 32-bit add with carry into the top word, then top * EPS with the carry-out repaid.
 GL_DEV uint64_t psd_recombine(uint64_t al, uint64_t ah) {
     uint32_t t1 = (uint32_t)(al >> 32), top;     // t1 is updated in place: (al0, t1) stays the register pair of al
@@ -48,26 +48,28 @@ GL_DEV void psd_sbox4(uint64_t& x0, uint64_t& x1, uint64_t& x2, uint64_t& x3) {
     gl_mul_multi<4>(c3, c4, o);
     x0 = o[0]; x1 = o[1]; x2 = o[2]; x3 = o[3];
 }
-// N recombinations in lock-step (the two carry steps of one fill the wait states of the others: see gl_mul_multi)
+// The CHAINED row (docs/history/carry_tails.md): a row's low chain al = c_lo + sum coef lo_j runs first and its high chain starts from the ONE 32-bit
+// word (al >> 32) + c_hi, zero-extended, so ah' = start + sum coef hi_j already holds the low chain's overflow and the row's value is
+// al_0 + ah' 2^32 -- nothing with a carry joins the chains (psd_recombine spends v_add_co, v_addc on that; the start word costs a plain add and a
+// move, the pair (al_0, ah'_0) a move into al's dead high register).  Precondition: c_hi + (worst al >> 32) < 2^32.  Dense rows: al >> 32 <= 264
+// (the row sum) under a largest published c_hi of 0xfeed4db6; block rows: tightest at block 5, row 12, c_hi = 0xfd1e3e36 under a worst carry of
+// 13 098 586, room 35 251 056.  tools/gen_poseidon_tables.py asserts it for every row it emits, tests/test_poseidon_row_chain.py restates it.
+// Bounds: ah' < 2^44 + 2^32 in dense rows, < 2^57 in block rows, so top = ah' >> 32 < 2^25 and top * EPS wraps at most once.
+GL_DEV uint64_t psd_chain_start(uint64_t al, uint32_t c_hi) { return (uint64_t)((uint32_t)(al >> 32) + c_hi); }
+// al_0 + ah' 2^32 -> u64 representative: top * EPS onto (al_0, ah'_0), the carry-out repaid
+GL_DEV uint64_t psd_fold(uint64_t al, uint64_t ahp) {
+    return gl_dev_add_mul_eps(((uint64_t)(uint32_t)ahp << 32) | (uint32_t)al, (uint32_t)(ahp >> 32));
+}
+// N folds in lock-step (the others' instructions are the wait states between a multiply-add and the select on its carry: see gl_mul_multi)
 template <int N>
-GL_DEV void psd_recombine_multi(const uint64_t (&al)[N], const uint64_t (&ah)[N], uint64_t (&out)[N]) {
+GL_DEV void psd_fold_multi(const uint64_t (&al)[N], const uint64_t (&ahp)[N], uint64_t (&out)[N]) {
     static_assert(N >= 3, "three or more: no wait states of their own");
-    uint32_t t1[N], top[N], m[N];
+    uint32_t m[N];
     uint64_t c[N], r[N];
 #pragma unroll
     for (int j = 0; j < N; j++) {
-        asm("v_add_co_u32_e64 %0, %1, %2, %3" : "=v"(t1[j]), "=s"(c[j]) : "v"((uint32_t)(al[j] >> 32)), "v"((uint32_t)ah[j]));
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        asm("v_addc_co_u32_e64 %0, %1, 0, %2, %1" : "=v"(top[j]), "+s"(c[j]) : "v"((uint32_t)(ah[j] >> 32)));
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        const uint64_t x = ((uint64_t)t1[j] << 32) | (uint32_t)al[j];
-        asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(r[j]), "=s"(c[j]) : "v"(top[j]), "v"(x));
+        const uint64_t x = ((uint64_t)(uint32_t)ahp[j] << 32) | (uint32_t)al[j];
+        asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(r[j]), "=s"(c[j]) : "v"((uint32_t)(ahp[j] >> 32)), "v"(x));
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -81,8 +83,8 @@ GL_DEV void psd_recombine_multi(const uint64_t (&al)[N], const uint64_t (&ah)[N]
 
 // Full MDS layer, plus the NEXT round's constants.  Row r: sum_i s[(i+r)%12] * CIRC[i] + 8*s[0] (r == 0) + rc[r].  The entries
 // are < 64, so the 32-bit halves are accumulated separately in u64 (12 * 41 * 2^32 + 2^32 < 2^43: no overflow) with
-// v_mad_u64_u32 and recombined once per row; the two halves of the (canonical) round constant are the initial addends of
-// the two chains (scalar operands), so adding the constants costs no vector instruction.
+// v_mad_u64_u32 and folded once per row; the low half of the (canonical) round constant is the initial addend of the low
+// chain (a scalar operand), the high half goes into the high chain's start word (psd_chain_start: one 32-bit add per row).
 //
 // Each chain is written out as 12 multiply-adds: left to itself the compiler re-associates the sums (chains started at 0
 // and joined with extra 64-bit adds) and turns the entries 16 and 2 into shift-adds that need the 32-bit half zero-extended
@@ -92,31 +94,36 @@ GL_DEV void psd_recombine_multi(const uint64_t (&al)[N], const uint64_t (&ah)[N]
     "v_mad_u64_u32 %0, %1, %5, 16, %0\n\tv_mad_u64_u32 %0, %1, %6, 2, %0\n\tv_mad_u64_u32 %0, %1, %7, 28, %0\n\t"      \
     "v_mad_u64_u32 %0, %1, %8, 13, %0\n\tv_mad_u64_u32 %0, %1, %9, 13, %0\n\tv_mad_u64_u32 %0, %1, %10, 39, %0\n\t"    \
     "v_mad_u64_u32 %0, %1, %11, 18, %0\n\tv_mad_u64_u32 %0, %1, %12, 34, %0\n\tv_mad_u64_u32 %0, %1, %13, 20, %0"
-template <int R>
-GL_DEV uint64_t psd_mds_chain(const uint32_t (&x)[12], uint64_t addend) {
+// START: the chain's initial addend is a scalar pair (the low chain: the constant's low half) or a register pair (the high chain: psd_chain_start)
+template <int R, bool VSTART, class A>
+GL_DEV uint64_t psd_mds_chain(const uint32_t (&x)[12], A addend) {
     uint64_t acc, unused;
 #define PSD_X(i) "v"(x[((i) + R) % 12])
-    if constexpr (R == 0)
-        asm(PSD_MDS_CHAIN(25) : "=&v"(acc), "=&s"(unused) : PSD_X(0), PSD_X(1), PSD_X(2), PSD_X(3), PSD_X(4), PSD_X(5), PSD_X(6),
-            PSD_X(7), PSD_X(8), PSD_X(9), PSD_X(10), PSD_X(11), "s"(addend));
-    else
-        asm(PSD_MDS_CHAIN(17) : "=&v"(acc), "=&s"(unused) : PSD_X(0), PSD_X(1), PSD_X(2), PSD_X(3), PSD_X(4), PSD_X(5), PSD_X(6),
-            PSD_X(7), PSD_X(8), PSD_X(9), PSD_X(10), PSD_X(11), "s"(addend));
+#define PSD_MDS_ASM(C0, START)                                                                                                      \
+    asm(PSD_MDS_CHAIN(C0) : "=&v"(acc), "=&s"(unused) : PSD_X(0), PSD_X(1), PSD_X(2), PSD_X(3), PSD_X(4), PSD_X(5), PSD_X(6), PSD_X(7), \
+        PSD_X(8), PSD_X(9), PSD_X(10), PSD_X(11), START((uint64_t)addend))
+    if constexpr (R == 0 && VSTART) PSD_MDS_ASM(25, "v");
+    else if constexpr (R == 0) PSD_MDS_ASM(25, "s");
+    else if constexpr (VSTART) PSD_MDS_ASM(17, "v");
+    else PSD_MDS_ASM(17, "s");
+#undef PSD_MDS_ASM
 #undef PSD_X
     return acc;
 }
 template <int R, class RC>
 GL_DEV void psd_mds_rows(uint64_t (&s)[12], const uint32_t (&lo)[12], const uint32_t (&hi)[12], RC rc) {
     if constexpr (R < 12) {
-        // four rows at a time: eight chains, then their recombinations in lock-step
+        // four rows at a time: the four low chains, the four high chains from their start words, then the folds in lock-step
         const uint64_t c0 = rc[R], c1 = rc[R + 1], c2 = rc[R + 2], c3 = rc[R + 3];
-        const uint64_t al[4] = {psd_mds_chain<R>(lo, (uint32_t)c0), psd_mds_chain<R + 1>(lo, (uint32_t)c1), psd_mds_chain<R + 2>(lo, (uint32_t)c2),
-                                psd_mds_chain<R + 3>(lo, (uint32_t)c3)};
-        const uint64_t ah[4] = {psd_mds_chain<R>(hi, c0 >> 32), psd_mds_chain<R + 1>(hi, c1 >> 32), psd_mds_chain<R + 2>(hi, c2 >> 32),
-                                psd_mds_chain<R + 3>(hi, c3 >> 32)};
+        const uint64_t al[4] = {psd_mds_chain<R, false>(lo, (uint32_t)c0), psd_mds_chain<R + 1, false>(lo, (uint32_t)c1),
+                                psd_mds_chain<R + 2, false>(lo, (uint32_t)c2), psd_mds_chain<R + 3, false>(lo, (uint32_t)c3)};
+        const uint64_t ah[4] = {psd_mds_chain<R, true>(hi, psd_chain_start(al[0], (uint32_t)(c0 >> 32))),
+                                psd_mds_chain<R + 1, true>(hi, psd_chain_start(al[1], (uint32_t)(c1 >> 32))),
+                                psd_mds_chain<R + 2, true>(hi, psd_chain_start(al[2], (uint32_t)(c2 >> 32))),
+                                psd_mds_chain<R + 3, true>(hi, psd_chain_start(al[3], (uint32_t)(c3 >> 32)))};
         uint64_t o[4];
         __builtin_amdgcn_sched_barrier(0);
-        psd_recombine_multi<4>(al, ah, o);
+        psd_fold_multi<4>(al, ah, o);
         s[R] = o[0]; s[R + 1] = o[1]; s[R + 2] = o[2]; s[R + 3] = o[3];
         psd_mds_rows<R + 4, RC>(s, lo, hi, rc);
     }
@@ -138,8 +145,9 @@ GL_DEV void psd_mds(uint64_t (&s)[12], RC rc) {
 //     x_0 = u_0^7,   y_k = (N^k u)[0] + sum_{i<k} (N^(k-1-i) m0)[0] x_i + g_k[0],   x_k = y_k^7   (k = 1, 2: lane 0 entering the block's next rounds)
 //     s'  = N^3 u + sum_{i<3} (N^(2-i) m0) x_i + g_3                                              (the state leaving the block)
 // Three rounds of 6-bit entries give coefficients below 2^21 with row sums below 2^24 WITHOUT reduction mod p, so a term is the coefficient times
-// the two 32-bit halves the state already lives in: two v_mad_u64_u32 into two accumulators that start from the halves of the additive constant and
-// stay below 2^56 (psd_recombine's contract with 2^8 to spare; asserted on the generated table by tests/test_poseidon_b3_tables.py).  Nothing is split
+// the two 32-bit halves the state already lives in: two v_mad_u64_u32 into two accumulators, the low one from the low half of the additive constant
+// (below 2^56; asserted on the generated table by tests/test_poseidon_b3_tables.py), the high one chained behind it from the start word (below 2^57:
+// psd_chain_start above, tests/test_poseidon_row_chain.py).  Nothing is split
 // and the constants are one 32-bit word each: 12 + 13 + 12 x 14 terms per block, the same for all seven blocks of rounds 4 .. 24; round 25 runs
 // dense.  (Blocks of eleven on matrix powers reduced mod p, the form before this one, paid six multiply-adds per term for their 64-bit constants:
 // docs/history/poseidon_b3.md.  Blocks of four no longer fit 64-bit accumulators.)
@@ -151,33 +159,43 @@ GL_DEV void psd_mds(uint64_t (&s)[12], RC rc) {
 
 typedef const __attribute__((address_space(4))) uint32_t* psd_b3tab;      // constant address space: wave-uniform reads become scalar loads
 typedef const __attribute__((address_space(4))) uint64_t* psd_b3add;
-// one term: the coefficient c (an SGPR, the one constant-bus operand of both multiply-adds) times the halves of v, which are the registers of v
-// themselves; the carry-out pair is never read.  Written out: in C the compiler zero-extends each half into a register pair of its own.
-GL_DEV void psd_b3_term(uint64_t& lo, uint64_t& hi, uint32_t c, uint64_t v) {
+// K terms of ONE chain in one statement (the compiler puts a wait state between two statements that write scalar pairs): each coefficient c[i] (an
+// SGPR, the one constant-bus operand of its multiply-add) times the low or the high half of v[i], which is a register of v itself; the carry-out
+// pair is never read.  Written out: in C the compiler zero-extends each half into a register pair of its own.
+#define PSD_MA(C, V) "v_mad_u64_u32 %0, %1, %" #C ", %" #V ", %0"
+#define PSD_C(i) "s"(c[i])
+#define PSD_H(i) "v"(HI ? (uint32_t)(v[i] >> 32) : (uint32_t)v[i])
+template <int K, bool HI>
+GL_DEV void psd_b3_chain(uint64_t& acc, const uint32_t* c, const uint64_t* v) {
+    static_assert(K == 1 || K == 2 || K == 3 || K == 10 || K == 11, "the statement sizes the rows are cut into");
     uint64_t unused;
-    asm("v_mad_u64_u32 %0, %2, %3, %4, %0\n\tv_mad_u64_u32 %1, %2, %3, %5, %1"
-        : "+v"(lo), "+v"(hi), "=&s"(unused) : "s"(c), "v"((uint32_t)v), "v"((uint32_t)(v >> 32)));
+    if constexpr (K == 1)
+        asm(PSD_MA(2, 3) : "+v"(acc), "=&s"(unused) : PSD_C(0), PSD_H(0));
+    else if constexpr (K == 2)
+        asm(PSD_MA(2, 4) "\n\t" PSD_MA(3, 5) : "+v"(acc), "=&s"(unused) : PSD_C(0), PSD_C(1), PSD_H(0), PSD_H(1));
+    else if constexpr (K == 3)
+        asm(PSD_MA(2, 5) "\n\t" PSD_MA(3, 6) "\n\t" PSD_MA(4, 7) : "+v"(acc), "=&s"(unused) : PSD_C(0), PSD_C(1), PSD_C(2), PSD_H(0), PSD_H(1), PSD_H(2));
+    else if constexpr (K == 10)
+        asm(PSD_MA(2, 12) "\n\t" PSD_MA(3, 13) "\n\t" PSD_MA(4, 14) "\n\t" PSD_MA(5, 15) "\n\t" PSD_MA(6, 16) "\n\t"
+            PSD_MA(7, 17) "\n\t" PSD_MA(8, 18) "\n\t" PSD_MA(9, 19) "\n\t" PSD_MA(10, 20) "\n\t" PSD_MA(11, 21)
+            : "+v"(acc), "=&s"(unused)
+            : PSD_C(0), PSD_C(1), PSD_C(2), PSD_C(3), PSD_C(4), PSD_C(5), PSD_C(6), PSD_C(7), PSD_C(8), PSD_C(9),
+              PSD_H(0), PSD_H(1), PSD_H(2), PSD_H(3), PSD_H(4), PSD_H(5), PSD_H(6), PSD_H(7), PSD_H(8), PSD_H(9));
+    else
+        asm(PSD_MA(2, 13) "\n\t" PSD_MA(3, 14) "\n\t" PSD_MA(4, 15) "\n\t" PSD_MA(5, 16) "\n\t" PSD_MA(6, 17) "\n\t" PSD_MA(7, 18) "\n\t"
+            PSD_MA(8, 19) "\n\t" PSD_MA(9, 20) "\n\t" PSD_MA(10, 21) "\n\t" PSD_MA(11, 22) "\n\t" PSD_MA(12, 23)
+            : "+v"(acc), "=&s"(unused)
+            : PSD_C(0), PSD_C(1), PSD_C(2), PSD_C(3), PSD_C(4), PSD_C(5), PSD_C(6), PSD_C(7), PSD_C(8), PSD_C(9), PSD_C(10),
+              PSD_H(0), PSD_H(1), PSD_H(2), PSD_H(3), PSD_H(4), PSD_H(5), PSD_H(6), PSD_H(7), PSD_H(8), PSD_H(9), PSD_H(10));
 }
-// five terms in one statement (the compiler puts a wait state between two statements that write scalar pairs)
-GL_DEV void psd_b3_terms5(uint64_t& lo, uint64_t& hi, const uint32_t* c, const uint64_t* v) {
+#undef PSD_H
+#undef PSD_C
+#undef PSD_MA
+// the first term of an output's low chain: the accumulator starts from the additive constant's low half.  Inside the statement, so that the
+// constant is read where the row's coefficients are (a C initialisation is copied to VGPRs right behind its scalar load: a wait of its own).
+GL_DEV void psd_b3_first(uint64_t& lo, uint32_t c, uint64_t v, uint64_t add_lo) {
     uint64_t unused;
-#define PSD_V(i) "v"((uint32_t)v[i]), "v"((uint32_t)(v[i] >> 32))
-    asm("v_mad_u64_u32 %0, %2, %3, %8, %0\n\tv_mad_u64_u32 %1, %2, %3, %9, %1\n\t"
-        "v_mad_u64_u32 %0, %2, %4, %10, %0\n\tv_mad_u64_u32 %1, %2, %4, %11, %1\n\t"
-        "v_mad_u64_u32 %0, %2, %5, %12, %0\n\tv_mad_u64_u32 %1, %2, %5, %13, %1\n\t"
-        "v_mad_u64_u32 %0, %2, %6, %14, %0\n\tv_mad_u64_u32 %1, %2, %6, %15, %1\n\t"
-        "v_mad_u64_u32 %0, %2, %7, %16, %0\n\tv_mad_u64_u32 %1, %2, %7, %17, %1"
-        : "+v"(lo), "+v"(hi), "=&s"(unused)
-        : "s"(c[0]), "s"(c[1]), "s"(c[2]), "s"(c[3]), "s"(c[4]), PSD_V(0), PSD_V(1), PSD_V(2), PSD_V(3), PSD_V(4));
-#undef PSD_V
-}
-// the first term of an output: the accumulators start from the additive constant's halves.  Inside the statement, so that the constant is read
-// where the row's coefficients are (a C initialisation is copied to VGPRs right behind its scalar load: a wait of its own).
-GL_DEV void psd_b3_term_first(uint64_t& lo, uint64_t& hi, uint32_t c, uint64_t v, const uint64_t (&add)[2]) {
-    uint64_t unused;
-    asm("v_mov_b64 %0, %6\n\tv_mov_b64 %1, %7\n\t"
-        "v_mad_u64_u32 %0, %2, %3, %4, %0\n\tv_mad_u64_u32 %1, %2, %3, %5, %1"
-        : "=&v"(lo), "=&v"(hi), "=&s"(unused) : "s"(c), "v"((uint32_t)v), "v"((uint32_t)(v >> 32)), "s"(add[0]), "s"(add[1]));
+    asm("v_mov_b64 %0, %4\n\tv_mad_u64_u32 %0, %1, %2, %3, %0" : "=&v"(lo), "=&s"(unused) : "s"(c), "v"((uint32_t)v), "s"(add_lo));
 }
 // The table is consumed front to back, one row (= one output) per group of scalar loads.  Scalar loads return out of order, so the only wait is
 // "all of them": a row's constants are therefore requested one row AHEAD -- the first term of an output waits for its row (requested while the
@@ -194,22 +212,24 @@ GL_DEV void psd_b3_load(PsdB3Row& k, psd_b3tab c, psd_b3add add) {
     for (int i = 0; i < NT; i++) k.w[i] = c[i];
     k.a[0] = add[0]; k.a[1] = add[1];
 }
-// -> (lo, hi): lo + hi 2^32 = add + sum_{t < 11} u[t + 1] w[t] + sum_{t < NX} x[t] w[11 + t] (the caller folds it).  k: this output's row (requested
-// earlier); on return the NEXT output's row (NT_NEXT terms at `next`, additive constant at `add_next`), requested, unless NT_NEXT is 0.
+// -> (lo, hi) of a chained row: lo_0 + hi 2^32 = add + sum_{t < 11} u[t + 1] w[t] + sum_{t < NX} x[t] w[11 + t] (the caller folds it): the low
+// terms, the start word, then the high terms over the same scalar row.  k: this output's row (requested earlier); on return the NEXT output's row
+// (NT_NEXT terms at `next`, additive constant at `add_next`), requested, unless NT_NEXT is 0.
 template <int NX, int NT_NEXT>
 GL_DEV void psd_b3_dot(const uint64_t (&u)[12], const uint64_t (&x)[3], PsdB3Row& k, psd_b3tab next, psd_b3add add_next, uint64_t& lo, uint64_t& hi) {
     const PsdB3Row cur = k;
-    psd_b3_term_first(lo, hi, cur.w[0], u[1], cur.a);
+    psd_b3_first(lo, cur.w[0], u[1], cur.a[0]);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (NT_NEXT > 0) psd_b3_load<NT_NEXT>(k, next, add_next);
     __builtin_amdgcn_sched_barrier(0);
-    psd_b3_terms5(lo, hi, &cur.w[1], &u[2]);
-    psd_b3_terms5(lo, hi, &cur.w[6], &u[7]);
-#pragma unroll
-    for (int t = 0; t < NX; t++) psd_b3_term(lo, hi, cur.w[11 + t], x[t]);
+    psd_b3_chain<10, false>(lo, &cur.w[1], &u[2]);
+    psd_b3_chain<NX, false>(lo, &cur.w[11], &x[0]);
+    hi = psd_chain_start(lo, (uint32_t)cur.a[1]);
+    psd_b3_chain<11, true>(hi, &cur.w[0], &u[1]);
+    psd_b3_chain<NX, true>(hi, &cur.w[11], &x[0]);
     __builtin_amdgcn_sched_barrier(0);
 }
-// outgoing lanes R .. R + 3: eight accumulators, then their recombinations in lock-step (no wait states of their own)
+// outgoing lanes R .. R + 3: four chained rows, then their folds in lock-step (no wait states of their own)
 template <int R>
 GL_DEV void psd_b3_out(uint64_t (&o)[12], const uint64_t (&u)[12], const uint64_t (&x)[3], psd_b3tab mac, psd_b3add add, PsdB3Row& k) {
     if constexpr (R < 12) {
@@ -219,7 +239,7 @@ GL_DEV void psd_b3_out(uint64_t (&o)[12], const uint64_t (&u)[12], const uint64_
         psd_b3_dot<3, 14>(u, x, k, mac + W * (R + 4), add + 2 * (R + 4), al[1], ah[1]);
         psd_b3_dot<3, 14>(u, x, k, mac + W * (R + 5), add + 2 * (R + 5), al[2], ah[2]);
         psd_b3_dot<3, (R + 3 < 11 ? 14 : 0)>(u, x, k, mac + W * (R + 6), add + 2 * (R + 6), al[3], ah[3]);
-        psd_recombine_multi<4>(al, ah, r);
+        psd_fold_multi<4>(al, ah, r);
         o[R] = r[0]; o[R + 1] = r[1]; o[R + 2] = r[2]; o[R + 3] = r[3];
         __builtin_amdgcn_sched_barrier(0);
         psd_b3_out<R + 4>(o, u, x, mac, add, k);
@@ -240,10 +260,10 @@ GL_DEV void psd_partial_rounds_b3(uint64_t (&s)[12]) {
         x[0] = psd_sbox(s[0]);
         __builtin_amdgcn_sched_barrier(0);
         psd_b3_dot<1, 13>(s, x, k, mac + W, add + 2, lo, hi);
-        x[1] = psd_sbox(psd_recombine(lo, hi));
+        x[1] = psd_sbox(psd_fold(lo, hi));
         __builtin_amdgcn_sched_barrier(0);
         psd_b3_dot<2, 14>(s, x, k, mac + 2 * W, add + 4, lo, hi);
-        x[2] = psd_sbox(psd_recombine(lo, hi));
+        x[2] = psd_sbox(psd_fold(lo, hi));
         __builtin_amdgcn_sched_barrier(0);
         psd_b3_out<0>(o, s, x, mac, add, k);
 #pragma unroll
