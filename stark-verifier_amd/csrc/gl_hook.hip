@@ -2,6 +2,7 @@
 // tests/test_gpu_gl_arith.py, tests/test_gpu_poseidon_b3.py, tests/test_gpu_poseidon_lanes.py): the shipped device functions of gl_field.cuh / poseidon.cuh / poseidon_lanes.cuh on raw u64 words.  No
 // product path calls them.
 #include "gl355_internal.h"
+#include "poseidon.cuh"
 #include "poseidon_lanes.cuh"
 
 namespace gl355 {

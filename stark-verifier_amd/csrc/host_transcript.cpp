@@ -11,6 +11,7 @@
 
 #define PSD_TABLE_QUAL static const
 #include "poseidon_tables.h"
+#include "poseidon_fast_tables.h"
 
 namespace gl355 {
 
@@ -43,7 +44,7 @@ static void h_mds(uint64_t s[12]) {
 static void h_permute(uint64_t s[12], uint64_t* full_in /*[8][12]*/, uint64_t* part_in /*[22]*/) {
     for (int r = 0; r < 4; r++) {
         for (int i = 0; i < 12; i++) {
-            s[i] = gl_add(s[i], PSD_FULL_RC[12 * r + i]);
+            s[i] = gl_add(s[i], PSD_ALL_RC[12 * r + i]);
             if (full_in) full_in[12 * r + i] = gl_canon(s[i]);
             s[i] = h_sbox(s[i]);
         }
@@ -72,7 +73,7 @@ static void h_permute(uint64_t s[12], uint64_t* full_in /*[8][12]*/, uint64_t* p
     }
     for (int r = 4; r < 8; r++) {
         for (int i = 0; i < 12; i++) {
-            s[i] = gl_add(s[i], PSD_FULL_RC[12 * r + i]);
+            s[i] = gl_add(s[i], PSD_ALL_RC[12 * (r + 22) + i]);      // the closing full rounds are rounds 26 .. 29
             if (full_in) full_in[12 * r + i] = gl_canon(s[i]);
             s[i] = h_sbox(s[i]);
         }

@@ -1,7 +1,8 @@
 // The 16-lane Poseidon permutation (one state per 16 lanes of a wave) of the Merkle / FRI wide-leaf kernels (merkle.hip) and of its test hook
-// (gl_hook.hip: gl355_poseidon_permute_lanes).
+// (gl_hook.hip: gl355_poseidon_permute_lanes), and its round, psd_lane_round, which the witness tape's PoseidonGate row (witness_tape_dev.hip) runs too.
+// Built on poseidon_rounds.cuh alone: nothing here reads the block tables of poseidon.cuh.
 #pragma once
-#include "poseidon.cuh"
+#include "poseidon_rounds.cuh"
 #include "merkle_common.cuh"
 
 namespace gl355 {
@@ -20,6 +21,27 @@ namespace gl355 {
 // (const at namespace scope: internal linkage, so every unit that includes this header gets its own copy)
 __device__ __constant__ const uint32_t PSD_CIRC_DEV[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
 
+// ONE round of the one-element-per-lane form, the dense round of psd_permute_lanes below and of the witness tape's PoseidonGate row
+// (witness_tape_dev.hip): S-box (`sbox`: every lane in a full round, lane 0 alone in a partial one), the state through the ring, row `me` of the MDS
+// layer on the 32-bit halves from the NEXT round's constant, psd_recombine.  rc_next = PSD_ALL_RC[12 * (r + 1) + me] is the caller's load: the constant
+// index depends on the lane, so it is a vector load, issued before whatever the caller does ahead of the round (a load issued and awaited inside
+// the round costs an L2 round trip per round, ~40 % of the latency).
+GL_DEV uint64_t psd_lane_round(uint64_t s, uint64_t rc_next, bool sbox, bool active, int me, uint64_t* ring /* 24 u64 of this 16-lane group */) {
+    if (sbox) s = psd_sbox(s);
+    if (active) { ring[me] = s; ring[me + 12] = s; }
+    GL_WAVE_LDS_SYNC();
+    uint64_t al = (uint32_t)rc_next, ah = rc_next >> 32;
+#pragma unroll
+    for (int j = 0; j < 12; j++) {
+        const uint64_t x = ring[me + j];
+        const uint32_t c = PSD_CIRC_DEV[j] + ((me == 0 && j == 0) ? 8u : 0u);
+        al += (uint64_t)(uint32_t)x * c;
+        ah += (uint64_t)(uint32_t)(x >> 32) * c;
+    }
+    GL_WAVE_LDS_SYNC();
+    return psd_recombine(al, ah);
+}
+
 // FORM (round 6): the 22 PARTIAL rounds of the 16-lane permutation.
 //   0  as the full rounds: S-box (only lane 0's matters), the state through the ring, the whole MDS row: S-box + LDS round trip + 24 multiply-adds +
 //      recombination, one after the other on the critical path;
@@ -35,24 +57,10 @@ template <int FORM>
 GL_DEV uint64_t psd_permute_lanes(uint64_t s, int li, uint64_t* ring /* 24 u64 of this 16-lane group */) {
     const bool active = li < 12;
     const int me = active ? li : 0;
-    // the constant index depends on the lane, so this is a vector load: fetch round r+1's constant while round r
-    // computes (a load issued and awaited inside the round costs an L2 round trip per round, ~40 % of the latency)
     s = gl_add_canonical(s, PSD_ALL_RC[me]);
     auto dense_round = [&](int r, bool full) {
         const uint64_t rc_next = PSD_ALL_RC[12 * (r + 1) + me];     // row 30 is zero; consumed by this round's MDS accumulators
-        if (full || li == 0) s = psd_sbox(s);
-        if (active) { ring[me] = s; ring[me + 12] = s; }
-        GL_WAVE_LDS_SYNC();
-        uint64_t al = (uint32_t)rc_next, ah = rc_next >> 32;
-#pragma unroll
-        for (int j = 0; j < 12; j++) {
-            const uint64_t x = ring[me + j];
-            const uint32_t c = PSD_CIRC_DEV[j] + ((me == 0 && j == 0) ? 8u : 0u);
-            al += (uint64_t)(uint32_t)x * c;
-            ah += (uint64_t)(uint32_t)(x >> 32) * c;
-        }
-        GL_WAVE_LDS_SYNC();
-        s = psd_recombine(al, ah);
+        s = psd_lane_round(s, rc_next, full || li == 0, active, me, ring);
     };
     if constexpr (FORM == 0) {
 #pragma unroll 1

@@ -25,7 +25,6 @@
 // with the staged C entry points, which call them with B = 1), the quotient in quotient.hip, Merkle trees and the grinder in merkle.hip.
 #include "gl355_internal.h"
 #include "blinding.cuh"
-#include "poseidon.cuh"
 
 using namespace gl355;
 

@@ -18,7 +18,7 @@
 // is reduced with powers of each alpha on the fly, so no per-lane constraint array exists.
 // Roofline: integer VALU (a PoseidonGate row costs about one permutation), not HBM.
 #include "gl355_internal.h"
-#include "poseidon.cuh"
+#include "poseidon_rounds.cuh"
 
 namespace gl355 {
 
@@ -208,7 +208,7 @@ GL_DEV void gate_poseidon(const QuotArgs& a, const WireSrc& w, uint64_t t, GateA
         if (r < 3) wire_group<PF>(w, 29 + 12 * r, 64, sin);      // round r + 1's
         else wire_group<4>(w, 65, 86, pin);                      // the first four partial rounds'
 #pragma unroll
-        for (int i = 0; i < 12; i += 4) psd_sbox4(s[i], s[i + 1], s[i + 2], s[i + 3]);       // four S-boxes in lock-step (poseidon.cuh)
+        for (int i = 0; i < 12; i += 4) psd_sbox4(s[i], s[i + 1], s[i + 2], s[i + 3]);       // four S-boxes in lock-step (poseidon_rounds.cuh)
         psd_mds(s, &PSD_ALL_RC[12 * (r + 1)]);
     }
     // partial rounds in the dense form: the S-box input of round r is s[0] + RC[4+r][0] in either form, so the

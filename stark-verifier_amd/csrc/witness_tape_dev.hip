@@ -16,7 +16,7 @@
 // (ASSERT_EQ, range conditions = an invalid inner proof) are reported as the smallest failing entry per unit, exactly like the
 // host replay.
 #include "gl355_internal.h"
-#include "poseidon.cuh"
+#include "poseidon_lanes.cuh"
 #include "witness_tape.h"
 
 namespace gl355 {
@@ -26,11 +26,6 @@ namespace gl355 {
 // here also writes back and invalidates the XCD's L2, ~67 000 times per batch, and costs every other kernel on the chip its L2
 // hits (measured: -5 % job throughput).
 #define TAPE_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup")
-#define TAPE_WAVE_LDS_SYNC()                                    \
-    do {                                                        \
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  \
-        __builtin_amdgcn_wave_barrier();                        \
-    } while (0)
 
 struct TapeDevArgs {
     const uint64_t* tape;          // [n_ops][5]
@@ -41,7 +36,8 @@ struct TapeDevArgs {
     unsigned long long* status;                    // [units]: smallest failing entry, ~0 = none
 };
 
-// one PoseidonGate row: lanes 0..11 hold the state; wires as gl355_poseidon_gate_witness (host_transcript.cpp)
+// one PoseidonGate row: lanes 0..11 hold the state; wires as gl355_poseidon_gate_witness (host_transcript.cpp).  The rounds are psd_lane_round
+// (poseidon_lanes.cuh); the row's own part is the swap, the S-box-input wires stored ahead of each round, and the output wires.
 GL_DEV void tape_poseidon_row(uint64_t* row, int li, uint64_t* ring) {
     const bool active = li < 12;
     const int me = active ? li : 0;
@@ -70,19 +66,7 @@ GL_DEV void tape_poseidon_row(uint64_t* row, int li, uint64_t* ring) {
             else if (r >= 26) row[87 + 12 * (r - 26) + li] = gl_canon(s);
             else if (r >= 4 && r < 26 && li == 0) row[65 + (r - 4)] = gl_canon(s);
         }
-        if (full || li == 0) s = psd_sbox(s);
-        if (active) { ring[me] = s; ring[me + 12] = s; }
-        TAPE_WAVE_LDS_SYNC();
-        uint64_t al = (uint32_t)rc_next, ah = rc_next >> 32;
-#pragma unroll
-        for (int j = 0; j < 12; j++) {
-            const uint64_t x = ring[me + j];
-            const uint32_t c = GL_PSD_MDS_CIRC[j] + ((me == 0 && j == 0) ? GL_PSD_MDS_DIAG0 : 0u);
-            al += (uint64_t)(uint32_t)x * c;
-            ah += (uint64_t)(uint32_t)(x >> 32) * c;
-        }
-        TAPE_WAVE_LDS_SYNC();
-        s = psd_recombine(al, ah);
+        s = psd_lane_round(s, rc_next, full || li == 0, active, me, ring);
     }
     if (active) row[12 + li] = gl_canon(s);
 }

@@ -23,9 +23,9 @@ from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CON
                    GATE_POSEIDON_MDS, GATE_PUBLIC_INPUT, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT)
 from .plonk import (CircuitBuilder, CircuitConfig, P, coset_interpolation_param, coset_interpolation_shape, coset_interpolation_witness,
                     host_hash_no_pad, poseidon_gate_witness)
+from .poseidon_spec import MDS_MATRIX_CIRC as CIRC
 
 RA_PARAM = 4 | 4 << 8 | 2 << 16
-CIRC = [17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20]
 
 # witness-tape opcodes (include/gl355.h GL355_TAPE_*; what an entry touches and does, for the host replay and the device
 # interpreter alike: csrc/witness_tape.h).  Every builder

@@ -3,7 +3,7 @@ circuit restates, derived once per process from the round constants in data/ and
 
   fast_partial_tables()   plonky2's fast partial rounds, what PoseidonGate's constraints are written over (chip/plonk/gates/poseidon.rs:127-319
                           carries them as literals: FAST_PARTIAL_FIRST_ROUND_CONSTANT, _ROUND_CONSTANTS, _ROUND_VS, _ROUND_W_HATS,
-                          _ROUND_INITIAL_MATRIX); tests/golden/poseidon_fast_partial_tables.json and csrc/poseidon_tables.h hold the same numbers
+                          _ROUND_INITIAL_MATRIX); tests/golden/poseidon_fast_partial_tables.json and csrc/poseidon_fast_tables.h hold the same numbers
   optimized_spec()        Spec::new(8, 22) of chip/poseidon_spec/spec.rs:307-407, what PublicInputsHasherChip walks: the constants moved
                           behind the S-box (start, partial, end), the pre-sparse MDS and the 22 sparse matrices (row, col_hat)
 They are right exactly when the permutations below agree with the dense rounds (permute_dense), which is plonky2's permutation."""
@@ -80,7 +80,7 @@ def permute_dense(state):
 def derive_fast_partial(rc):
     """round constants [30][12] -> dict(first [12], post [22] (the last is 0), vs [22][11], w_hats [22][11], init [11][11]
     (result[c] += init[r - 1][c - 1] state[r]), m00 (the MDS matrix's corner, lane 0's own factor in a fast partial round)).  The one
-    derivation: tools/gen_poseidon_tables.py writes csrc/poseidon_tables.h from it"""
+    derivation: tools/gen_poseidon_tables.py writes csrc/poseidon_fast_tables.h from it"""
     m = mds_matrix()
     minv = mat_inv(m)
     part = rc[HALF_F:HALF_F + R_P]

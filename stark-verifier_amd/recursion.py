@@ -12,6 +12,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import poseidon_spec
 from ._lib import (GATE_ARITHMETIC, GATE_ARITHMETIC_EXT, GATE_BASE_SUM, GATE_CONSTANT, GATE_COSET_INTERPOLATION, GATE_NOOP, GATE_POSEIDON,
                    GATE_POSEIDON_MDS, GATE_PUBLIC_INPUT, GATE_RANDOM_ACCESS, GATE_REDUCING, GATE_REDUCING_EXT)
 from .gadgets import CIRC, GadgetBuilder, T
@@ -19,17 +20,10 @@ from .plonk import (CircuitConfig, P, _ptr, _u64, coset_interpolation_shape, cos
                     prove_sparse, require_arity_2)
 
 UNUSED_SELECTOR = 0xFFFFFFFF
-_RC = None
 
 
 def _round_constants():
-    global _RC
-    if _RC is None:
-        import os
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "poseidon_goldilocks_round_constants.txt")
-        vals = [int(l, 16) for l in open(path).read().split("\n") if l and not l.startswith("#")]
-        _RC = [vals[12 * r:12 * (r + 1)] for r in range(30)]
-    return _RC
+    return poseidon_spec.round_constants()
 
 
 class Challenger:

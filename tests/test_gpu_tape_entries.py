@@ -115,10 +115,15 @@ def hand_tape():
 
 
 @pytest.fixture(scope="module")
-def loaded(gl, ctx):
-    plonk = importlib.import_module("stark-verifier_amd.plonk")
+def data(gl, ctx):
+    """a small built circuit for the tapes to hang on"""
     aset, _, _ = make_access_set(gl, ctx, 4, 0x7A9E)
-    data, _ = aset.build(None)
+    return aset.build(None)[0]
+
+
+@pytest.fixture(scope="module")
+def loaded(gl, ctx, data):
+    plonk = importlib.import_module("stark-verifier_amd.plonk")
     t, ix, layout, pi_pos, n_rows = hand_tape()
     tape = np.array(t.entries, dtype=np.uint64)
     assert set(tape[:, 0].tolist()) == set(range(15))         # every opcode is there
@@ -143,6 +148,50 @@ def test_rows_of_every_opcode_agree(gl, ctx, loaded):
         assert np.any(d_rows[u, 2, 25:29] != 0)               # swap = 1: the delta wires are in use
         assert len({d_rows[u, r].tobytes() for r in range(13)}) == 13 and all(d_rows[u, r].any() for r in range(13))
     assert len({d_rows[u].tobytes() for u in range(3)}) == 3
+
+
+def poseidon_row_cases():
+    """(state, swap) of the PoseidonGate rows below: the edges of the field and of its 32-bit halves, both deltas of the swap wrapping
+    (lhs = lanes 0..3 against rhs = lanes 4..7), and four random states, each with swap 0 and swap 1"""
+    rng = np.random.default_rng(0x7AA0)
+    e = (1 << 32) - 1
+    states = [[0] * 12, [P - 1] * 12, [e] * 12, [P - e - 1] * 12, [0] * 4 + [P - 1] * 4 + [0] * 4, [P - 1] * 4 + [0] * 4 + [P - 1] * 4]
+    states += [rand_field(rng, 12).tolist() for _ in range(4)]
+    return [(np.array(s, dtype=np.uint64), swap) for swap in (0, 1) for s in states]
+
+
+@pytest.fixture(scope="module")
+def poseidon_rows(ctx, data):
+    """a tape of one POSEIDON entry per case behind its INPUT entries, all in the sequential part (one wave per unit); unit 1 takes the
+    cases in reverse order.  -> (circuit, inputs [2][20 * 13], the host's gate witness [2][20][135])"""
+    plonk = importlib.import_module("stark-verifier_amd.plonk")
+    cases = poseidon_row_cases()
+    assert len(cases) == 20
+    t = HandTape()
+    for k in range(len(cases)):
+        t.inputs(w(k, 0), 12)
+        t.input(w(k, 24))
+        t.add(gad.TAPE_POSEIDON, w(k, 0))
+    tape = np.array(t.entries, dtype=np.uint64)
+    nat = plonk.NativeCircuit(ctx, data.export_blob(np.arange(len(cases)), tape=tape, pi_pos=np.array([w(0, 12)], dtype=np.uint64), n_inputs=len(t.kinds)))
+    orders = (cases, cases[::-1])
+    inputs = np.stack([np.concatenate([np.append(s, np.uint64(swap)) for s, swap in order]) for order in orders])
+    want = np.stack([np.stack([plonk.poseidon_gate_witness(s, swap) for s, swap in order]) for order in orders])
+    return nat, inputs, want
+
+
+@pytest.mark.parametrize("units", (1, 2))
+def test_poseidon_rows_equal_the_host_gate_witness(ctx, poseidon_rows, units):
+    """tape_poseidon_row (the swap, psd_lane_round thirty times, the S-box-input and output wires) against gl355_poseidon_gate_witness: all 135
+    wires of every row"""
+    nat, inputs, want = poseidon_rows
+    rows, pis = nat.witness_rows(ctx, inputs[:units], on_device=True)
+    assert rows.shape == (units, 20, NW)
+    if not np.array_equal(rows, want[:units]):
+        bad = np.argwhere(rows != want[:units])
+        raise AssertionError("device rows differ from the host gate witness at %d positions, first (unit, row, wire) = %s" % (len(bad), bad[0]))
+    assert np.array_equal(pis[:, 0], want[:units, 0, 12])
+    assert np.any(want[0, 10:, 25:29] != 0) and not np.any(want[0, :10, 25:29])      # the delta wires are in use exactly under swap = 1
 
 
 def refused_at(gl, ctx, nat, inputs):

@@ -1,6 +1,7 @@
 """CPU: the tables of the partial rounds in blocks of three (tools/gen_poseidon_tables.py b3_tables; csrc/poseidon.cuh psd_partial_rounds_b3) and the
-half-exact model of the device algorithm: 32-bit halves, two 64-bit accumulators per dot product, every accumulator asserted to fit 64 bits with a top
-word that meets psd_recombine's contract."""
+half-exact model of the device algorithm: 32-bit halves, two 64-bit accumulators per dot product, the high one chained behind the low one
+(chained_row: the start word asserted to fit 32 bits, the high chain asserted below 2^57; tests/test_poseidon_row_chain.py restates the
+precondition row by row)."""
 import os
 import random
 import re
