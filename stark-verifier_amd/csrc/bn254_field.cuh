@@ -166,8 +166,12 @@ inline u256 to_u256(const uint64_t w[4]) {
 // prover (plonk_bn254.hip)
 int32_t bn254_fr_twiddles(Ctx* ctx, uint32_t log_n, bool inverse, uint64_t* tw /* n / 2 + 1 elements */);
 int32_t bn254_fr_power_table(Ctx* ctx, const uint64_t base[4], const uint64_t f[4], uint64_t count, uint64_t* tab);
-int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint64_t n_out, uint32_t log_n, const uint64_t* tw,
-                          const uint64_t* pre, const uint64_t* post, const uint64_t scale_plain[4], uint64_t* work);
+// the transforms on resident Montgomery data, n = 2^log_n values each (the index orders: bn254_fr_route.h)
+int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t scale_plain[4] /* or null */,
+                          uint64_t* work /* n elements */);
+int32_t bn254_fr_ntt_mont_coset_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t shift_plain[4],
+                                    uint64_t* btw /* n elements */, bool fill);
+int32_t bn254_fr_ntt_mont_from_bitrev(Ctx* ctx, const uint64_t* in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t* post /* or null */);
 // `bases` (gl355_bn254_g1_msm_prepare over the same points, or null): the table of the points' window multiples -- every window's digits then fall into ONE
 // set of buckets per scalar set (bn254_msm.hip, "shared buckets").
 // max_bits: every scalar of the call is below 2^max_bits (256: no promise; a scalar on a non-identity base that breaks the promise further than the
@@ -175,11 +179,6 @@ int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t*
 // sorted or reduced (range-check columns are 16-bit values, the arithmetic chip's operands 64-bit: 2 and 5 windows of 20 bits instead of 13)
 int32_t bn254_msm_bits(gl355_ctx* h, const uint64_t* points, const uint64_t* scalars, uint64_t n, uint32_t m, uint32_t max_bits, uint64_t* result,
                        const gl355_msm_bases* bases = nullptr, uint32_t* plan_out /* c, wps, one window, two-level sort */ = nullptr);
-int32_t bn254_fr_ntt_mont_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t* pre);
-int32_t bn254_fr_ntt_mont_coset_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t shift_plain[4],
-                                    uint64_t* btw /* n elements */, bool fill);
-int32_t bn254_fr_ntt_mont_from_bitrev(Ctx* ctx, const uint64_t* in, uint64_t* out, uint64_t n_out, uint32_t log_n, const uint64_t* tw, const uint64_t* post,
-                                      const uint64_t scale_plain[4]);
 // in: 2^log_in values, out: n_out values of the 2^log_n-point transform, device arrays of plain integers; shift == nullptr: the plain transform
 int32_t fr_ntt_run(Ctx* ctx, const uint64_t* in, uint32_t log_in, uint64_t* out, uint64_t n_out, uint32_t log_n, int32_t inverse, const uint64_t* shift);
 // Q[i] = sum_{j > i} A[j] z^(j - i - 1), E = sum_j A[j] z^j on device arrays (see the division kernels of bn254_kzg.hip)

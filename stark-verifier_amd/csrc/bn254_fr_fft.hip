@@ -7,27 +7,17 @@
 // (the other one, best_multiexp, is bn254_msm.hip).  halo2_proofs / halo2curves are un-vendored dependencies; the kernels follow their
 // published definitions and are checked against oracle/bn254_curve_oracle.c (itself pinned by halo2curves' ROOT_OF_UNITY).
 //
-// Arithmetic: 8 x 32-bit limbs, Montgomery form with R = 2^256 (bn254_field.cuh).  A transform is a few passes over HBM of up to ten stages
-// each in LDS (fr_fft_pass_kernel); the coset and resident forms the PLONK prover uses (plonk_bn254.hip) are parameters of the same pass.
+// Arithmetic: 8 x 32-bit limbs, Montgomery form with R = 2^256 (bn254_field.cuh).  A transform is a few passes over HBM with its stages in LDS
+// (fr_fft_pass_kernel): ten in the first pass, at most seven in each later one.  bn254_fr_route.h states that split and which buffer each pass reads
+// and writes; fr_launch below is the one place that fills and launches the passes.  The coset and resident forms the PLONK prover uses
+// (plonk_bn254.hip) are parameters of the same pass.
 #include "bn254_field.cuh"
+#include "bn254_fr_route.h"
 #include <vector>
 
 namespace gl355 {
 
 // ================================================================ Fr FFT ===========================================
-// values live in Montgomery form between the conversion kernels
-__global__ void fr_to_mont_kernel(uint64_t* data, uint64_t n) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    store256(data + 4 * i, m_from_int<F_R>(load256(data + 4 * i)));
-}
-// out of Montgomery form, optionally times `scale` (a plain integer, e.g. n^-1: x R * s * R^-1 = x s)
-__global__ void fr_from_mont_kernel(uint64_t* data, uint64_t n, u256 scale, int use_scale) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const u256 x = load256(data + 4 * i);
-    store256(data + 4 * i, use_scale ? m_canon<F_R>(m_mul<F_R>(x, scale)) : m_to_int<F_R>(x));
-}
 // tw[i] = w^i (Montgomery), i < count, in two steps: lo[j] = w^j (j < 1024) and hi[j] = w^(1024 j) by exponentiation (a few thousand
 // entries), then one product per entry.  (One exponentiation per entry -- ~30 products each -- cost more than the transform it served:
 // 1.5e7 against 1.0e7 field products at k = 20.)
@@ -53,38 +43,6 @@ __global__ void fr_power_mont_kernel(uint64_t* tab, uint64_t count, const uint64
     if (i >= count) return;
     store256(tab + 4 * i, m_mul<F_R>(m_mul<F_R>(load256(lo + 4 * (i & 1023)), load256(hi + 4 * (i >> 10))), f_mont));
 }
-// out[i] = in[i] (* post[i]) (* scale): the tail of a one-pass in-place resident transform
-__global__ void fr_scale_copy_kernel(const uint64_t* in, uint64_t* out, uint64_t n, const uint64_t* post, u256 scale, int use_scale) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    u256 x = load256(in + 4 * i);
-    if (post) x = m_mul<F_R>(x, load256(post + 4 * i));
-    else if (use_scale) x = m_mul<F_R>(x, scale);
-    store256(out + 4 * i, x);
-}
-__global__ void fr_bitrev_kernel(uint64_t* data, uint32_t log_n) {
-    const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (i >= (1ull << log_n)) return;
-    const uint64_t j = __brevll(i) >> (64 - log_n);
-    if (i < j) {
-        const u256 a = load256(data + 4 * i), b = load256(data + 4 * j);
-        store256(data + 4 * i, b);
-        store256(data + 4 * j, a);
-    }
-}
-// decimation-in-time stage s (span m = 2^s) after the bit reversal: one butterfly per lane
-__global__ void __launch_bounds__(256) fr_stage_kernel(uint64_t* data, const uint64_t* tw, uint32_t log_n, uint32_t s) {
-    const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (t >= (1ull << (log_n - 1))) return;
-    const uint64_t half = 1ull << (s - 1);
-    const uint64_t j = t & (half - 1), base = (t >> (s - 1)) << s;
-    uint64_t* pu = data + 4 * (base + j);
-    uint64_t* pv = pu + 4 * half;
-    const u256 w = load256(tw + 4 * (j << (log_n - s)));        // w_m^j = w_n^(j n / m)
-    const u256 u = load256(pu), v = m_mul<F_R>(load256(pv), w);
-    store256(pu, m_add<F_R>(u, v));
-    store256(pv, m_sub<F_R>(u, v));
-}
 
 // the block constants of the coset form (FrPass::btw): out[2^(t-1) + b] = gpow[t] * w_(2^t)^rev(b), 1 <= t <= log_n, b < 2^(t-1); gpow[t] = g^(n / 2^t)
 // (Montgomery, from the host), w_(2^t)^r = tw[r 2^(log_n - t)].  Entry 0 is unused.
@@ -100,7 +58,7 @@ __global__ void fr_coset_twiddle_kernel(const uint64_t* tw, const uint64_t* gpow
 // columns (1024 elements, 32 KB of LDS as 8 limb planes so that lanes hit consecutive banks) through stages s0+1 .. s0+ns.  The first
 // pass (s0 = 0: contiguous 1024-element blocks, ten stages) also does the bit reversal and the conversion to Montgomery form on its
 // loads, the last one the conversion back (and the 1/n of the inverse) on its stores: k = 20 is three passes (10 + 5 + 5 stages)
-// instead of 23 (conversion, bit reversal, 20 stages, conversion).
+// instead of 23 (conversion, bit reversal, 20 stages, conversion).  fr_launch fills one of these per step of the route.
 struct FrPass {
     const uint64_t* in;         // first pass: the caller's data (natural order, plain integers); later passes: == out
     uint64_t* out;
@@ -122,6 +80,7 @@ struct FrPass {
     // (u + v, (u - v) w), bit-reversed output.  The passes of a dif transform run from the highest s0 down; `first` then marks the pass that
     // reads the input (conversion, pre-multipliers, zero padding), `last` the s0 = 0 pass.
     uint32_t no_gather, dif;
+    // (every dif launch of the library passes `btw`: the per-position butterfly above is exercised by tools/ubench/ubench_fr_fft.hip alone)
     // COSET form (bn254_fr_ntt_mont_coset_dif): out[bitrev(k)] = sum_i in[i] g^i w^(ik) with NO multiplication by g^i up front and no per-position
     // twiddles.  Write a block of 2^s values as the coset transform of its own shift g': its halves u, v combine as (u + G v, u - G v) with the ONE
     // constant G = g'^(2^(s-1)) per block, and the halves are coset transforms again, with shifts g' and g' w_(2^s).  btw[2^(t-1) + b] holds the constant of
@@ -201,69 +160,105 @@ __global__ void __launch_bounds__(256) fr_fft_pass_kernel(FrPass a) {
     }
 }
 
+static dim3 fr_blocks(uint64_t count) { return dim3((uint32_t)((count + 255) / 256)); }
+
+// The seed of a table of `count` powers of w (Montgomery), in scratch of the context: what fr_twiddle_kernel and the fr_power_*_kernels multiply up
+struct FrSeed {
+    Scratch mem;
+    const uint64_t* lo = nullptr;      // w^j, j < 1024
+    const uint64_t* hi = nullptr;      // w^(1024 j), j < ceil(count / 1024)
+    explicit FrSeed(Ctx* ctx) : mem(ctx) {}
+    int32_t launch(const Fr& w, uint64_t count) {
+        const uint64_t n_hi = (count + 1023) / 1024;
+        GL355_TRY(mem.get((1024 + n_hi) * 32));
+        uint64_t* p = mem.as<uint64_t>();
+        lo = p;
+        hi = p + 4 * 1024;
+        hipLaunchKernelGGL(fr_twiddle_seed_kernel, fr_blocks(1024 + n_hi), dim3(256), 0, mem.ctx->stream, p, p + 4 * 1024, n_hi, to_u256(w.l));
+        return GL355_OK;
+    }
+};
 // w_n^i (Montgomery), i < n / 2, for the forward or the inverse transform of 2^log_n points: what every pass of fr_fft_pass_kernel reads.
-// `tw` holds n / 2 + 1 elements; scratch for the two seed tables comes from the context.
+// `tw` holds n / 2 + 1 elements.
 int32_t bn254_fr_twiddles(Ctx* ctx, uint32_t log_n, bool inverse, uint64_t* tw) {
-    const uint64_t n = 1ull << log_n;
+    const uint64_t count = std::max<uint64_t>(1, (1ull << log_n) / 2);
+    // omega_n = ROOT^(2^(28 - log_n)), or its inverse
     const Fr w = inverse ? Fr::root_of_unity(log_n).inv() : Fr::root_of_unity(log_n);
-    const uint64_t count = std::max<uint64_t>(1, n / 2), n_hi = (count + 1023) / 1024;
-    Scratch seed(ctx);
-    GL355_TRY(seed.get((1024 + n_hi) * 32));
-    uint64_t* lo = seed.as<uint64_t>();
-    uint64_t* hi = lo + 4 * 1024;
-    hipLaunchKernelGGL(fr_twiddle_seed_kernel, dim3((uint32_t)((1024 + n_hi + 255) / 256)), dim3(256), 0, ctx->stream, lo, hi, n_hi, to_u256(w.l));
-    hipLaunchKernelGGL(fr_twiddle_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, tw, count, lo, hi);
+    FrSeed seed(ctx);
+    GL355_TRY(seed.launch(w, count));
+    hipLaunchKernelGGL(fr_twiddle_kernel, fr_blocks(count), dim3(256), 0, ctx->stream, tw, count, seed.lo, seed.hi);
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }
 // tab[i] = f * base^i (Montgomery), i < count (base, f: plain integers; f = 1 for plain powers)
 int32_t bn254_fr_power_table(Ctx* ctx, const uint64_t base[4], const uint64_t f[4], uint64_t count, uint64_t* tab) {
-    const uint64_t n_hi = (count + 1023) / 1024;
-    Scratch seed(ctx);
-    GL355_TRY(seed.get((1024 + n_hi) * 32));
-    uint64_t* lo = seed.as<uint64_t>();
-    uint64_t* hi = lo + 4 * 1024;
-    hipLaunchKernelGGL(fr_twiddle_seed_kernel, dim3((uint32_t)((1024 + n_hi + 255) / 256)), dim3(256), 0, ctx->stream, lo, hi, n_hi, to_u256(Fr::from_words(base).l));
+    FrSeed seed(ctx);
+    GL355_TRY(seed.launch(Fr::from_words(base), count));
     // (lo hi) R * (f R) * R^-1 = lo hi f R: Montgomery again
-    hipLaunchKernelGGL(fr_power_mont_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, tab, count, lo, hi, to_u256(Fr::from_words(f).l));
+    hipLaunchKernelGGL(fr_power_mont_kernel, fr_blocks(count), dim3(256), 0, ctx->stream, tab, count, seed.lo, seed.hi, to_u256(Fr::from_words(f).l));
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }
-// The transform on resident data in Montgomery form: out[k] = post[k] * sum_i pre[i] in[i] w^(ik) (i < n_in, zero beyond; k < n_out), w from
-// `tw` (bn254_fr_twiddles: the caller picks the direction and owns the 1 / n, e.g. inside `post` or as `scale`).  `work`: n elements of
-// scratch; in may equal out.
-// Decimation in frequency on resident Montgomery data: natural-order input (n_in values, zero beyond, times pre[i] if given), BIT-REVERSED
-// output: out[bitrev(k)] = sum_i pre[i] in[i] w^(ik).  No pass gathers; the first one goes in -> out, the others run in place on `out`.
-int32_t bn254_fr_ntt_mont_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t* pre) {
-    const uint64_t n = 1ull << log_n;
-    if (log_n == 0) {
-        GL355_HIP(ctx, hipMemcpyAsync(out, in, 32, hipMemcpyDeviceToDevice, ctx->stream));
-        return GL355_OK;
-    }
-    std::vector<uint32_t> ns;
-    ns.push_back(std::min(10u, log_n));
-    const uint32_t rem = log_n - ns[0], more = (rem + 6) / 7;
-    for (uint32_t k = 0; k < more; k++) ns.push_back(rem / more + (k < rem % more ? 1 : 0));
-    std::vector<uint32_t> s0s(ns.size());
-    for (size_t k = 0, s0 = 0; k < ns.size(); k++) { s0s[k] = (uint32_t)s0; s0 += ns[k]; }
-    const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, n / 1024);
-    for (size_t k = ns.size(); k-- > 0;) {
+
+// One transform of 2^log_n points: out[k] = post[k] (or scale) * sum_i pre[i] in[i] w^(ik), i < n_in (zero beyond), k < n_out, with the index order of
+// input and output that `order` names (bn254_fr_route.h).  The entry points below fill one of these; fr_launch turns it into passes.
+struct FrJob {
+    FrOrder order = FR_GATHER;
+    const uint64_t* in = nullptr;
+    uint64_t* out = nullptr;           // may be `in`
+    uint64_t* work = nullptr;          // FR_GATHER: n elements of scratch
+    uint64_t n_in = 0, n_out = 0;
+    uint32_t log_n = 0;
+    const uint64_t* tw = nullptr;      // bn254_fr_twiddles of the direction
+    const uint64_t* btw = nullptr;     // FR_DIF: the block constants of the coset (FrPass::btw)
+    const uint64_t* pre = nullptr;     // Montgomery
+    const uint64_t* post = nullptr;    // in the form of the output: plain integers, or Montgomery with out_mont
+    bool use_scale = false;            // without post: every output times `scale`, in the form of the output too
+    u256 scale = {};
+    bool in_mont = false, out_mont = false;      // the data is resident in Montgomery form / stays in it
+};
+static int32_t fr_launch(Ctx* ctx, const FrJob& j) {
+    const FrRoute r = fr_route(j.order, j.log_n, j.in == j.out);
+    const uint64_t* const src[3] = {j.in, j.work, j.out};        // by FrBuf
+    uint64_t* const dst[3] = {nullptr, j.work, j.out};
+    const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, (1ull << j.log_n) / 1024);
+    for (uint32_t i = 0; i < r.n_steps; i++) {
+        const FrStep& st = r.step[i];
         FrPass pa;
         memset(&pa, 0, sizeof pa);
-        pa.first = k + 1 == ns.size(); pa.last = k == 0;
-        pa.in = pa.first ? in : out;
-        pa.out = out;
-        pa.tw = tw; pa.log_n = log_n; pa.s0 = s0s[k]; pa.ns = ns[k];
-        pa.in_mont = 1; pa.out_mont = 1; pa.no_gather = 1; pa.dif = 1;
-        pa.n_in = n_in; pa.n_out = n;
-        pa.pre = pre;
+        pa.in = src[st.src]; pa.out = dst[st.dst];
+        pa.tw = j.tw; pa.btw = j.btw;
+        pa.log_n = j.log_n; pa.s0 = st.s0; pa.ns = st.ns;
+        pa.first = st.first; pa.last = st.last;
+        pa.no_gather = r.no_gather; pa.dif = r.dif;
+        pa.in_mont = j.in_mont; pa.out_mont = j.out_mont;
+        // read by the first pass alone ...
+        pa.n_in = j.n_in; pa.pre = j.pre;
+        // ... and by the last one alone, wherever it writes
+        pa.n_out = j.n_out; pa.post = j.post; pa.use_scale = j.use_scale; pa.scale = j.scale;
         hipLaunchKernelGGL(fr_fft_pass_kernel, dim3(tiles), dim3(256), 0, ctx->stream, pa);
     }
+    if (r.tail_copy) GL355_HIP(ctx, hipMemcpyAsync(j.out, j.work, j.n_out * 32, hipMemcpyDeviceToDevice, ctx->stream));
     GL355_HIP(ctx, hipGetLastError());
     return GL355_OK;
 }
-// The coset transform in block form: out[bitrev(k)] = sum_i in[i] shift^i w^(ik) for i < n_in (zero beyond), the same values bn254_fr_ntt_mont_dif gives with
-// pre[i] = shift^i -- without the power table, its product per element and the scattered twiddle loads of the high stages (FrPass::btw).  `btw`: n elements,
+
+// The resident forms of the PLONK prover (plonk_bn254.hip): n values in Montgomery form in, n out, w from `tw` (bn254_fr_twiddles: the caller picks the direction).
+// Natural order in and out; every output times scale_plain if given (the 1 / n of an inverse transform).  `work`: n elements of scratch; in may equal out.
+int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t scale_plain[4] /* or null */, uint64_t* work) {
+    if (log_n == 0) {
+        GL355_HIP(ctx, hipMemcpyAsync(out, in, 32, hipMemcpyDeviceToDevice, ctx->stream));        // (the scale of a 1-point transform: not needed by any caller)
+        return GL355_OK;
+    }
+    FrJob j;
+    j.order = FR_GATHER; j.in = in; j.out = out; j.work = work;
+    j.n_in = j.n_out = 1ull << log_n; j.log_n = log_n; j.tw = tw;
+    j.in_mont = j.out_mont = true;
+    if (scale_plain) { j.use_scale = true; j.scale = to_u256(Fr::from_words(scale_plain).l); }
+    return fr_launch(ctx, j);
+}
+// The coset transform in block form, natural-order input, BIT-REVERSED output: out[bitrev(k)] = sum_i in[i] shift^i w^(ik) for i < n_in (zero beyond), with NO
+// table of shift^i, no product per element up front and none of the scattered twiddle loads of the high stages (FrPass::btw).  `btw`: n elements,
 // filled here for this shift (one product per entry: 0.1 ms at 2^23) -- callers transform many columns per shift and pass fill = false after the first.
 int32_t bn254_fr_ntt_mont_coset_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t shift_plain[4],
                                     uint64_t* btw, bool fill) {
@@ -284,109 +279,37 @@ int32_t bn254_fr_ntt_mont_coset_dif(Ctx* ctx, const uint64_t* in, uint64_t n_in,
         Scratch d(ctx);
         GL355_TRY(d.get(gp.size() * 32));
         GL355_HIP(ctx, hipMemcpyAsync(d.p, gp.data(), gp.size() * 32, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(fr_coset_twiddle_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, tw, d.as<uint64_t>(), log_n, btw);
+        hipLaunchKernelGGL(fr_coset_twiddle_kernel, fr_blocks(n), dim3(256), 0, ctx->stream, tw, d.as<uint64_t>(), log_n, btw);
         GL355_HIP(ctx, hipGetLastError());
         GL355_HIP(ctx, ctx->wait());                                     // gp is pageable host memory
     }
-    std::vector<uint32_t> ns;
-    ns.push_back(std::min(10u, log_n));
-    const uint32_t rem = log_n - ns[0], more = (rem + 6) / 7;
-    for (uint32_t k = 0; k < more; k++) ns.push_back(rem / more + (k < rem % more ? 1 : 0));
-    std::vector<uint32_t> s0s(ns.size());
-    for (size_t k = 0, s0 = 0; k < ns.size(); k++) { s0s[k] = (uint32_t)s0; s0 += ns[k]; }
-    const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, n / 1024);
-    for (size_t k = ns.size(); k-- > 0;) {
-        FrPass pa;
-        memset(&pa, 0, sizeof pa);
-        pa.first = k + 1 == ns.size(); pa.last = k == 0;
-        pa.in = pa.first ? in : out;
-        pa.out = out;
-        pa.tw = tw; pa.btw = btw; pa.log_n = log_n; pa.s0 = s0s[k]; pa.ns = ns[k];
-        pa.in_mont = 1; pa.out_mont = 1; pa.no_gather = 1; pa.dif = 1;
-        pa.n_in = n_in; pa.n_out = n;
-        hipLaunchKernelGGL(fr_fft_pass_kernel, dim3(tiles), dim3(256), 0, ctx->stream, pa);
-    }
-    GL355_HIP(ctx, hipGetLastError());
-    return GL355_OK;
+    FrJob j;
+    j.order = FR_DIF; j.in = in; j.out = out;
+    j.n_in = n_in; j.n_out = n; j.log_n = log_n; j.tw = tw; j.btw = btw;
+    j.in_mont = j.out_mont = true;
+    return fr_launch(ctx, j);
 }
-// Decimation in time from BIT-REVERSED input (what bn254_fr_ntt_mont_dif leaves) to natural-order output, no gather either:
-// out[k] = post[k] * sum_i in[bitrev(i)] w^(ik), k < n_out.  in may equal out.
-int32_t bn254_fr_ntt_mont_from_bitrev(Ctx* ctx, const uint64_t* in, uint64_t* out, uint64_t n_out, uint32_t log_n, const uint64_t* tw, const uint64_t* post,
-                                      const uint64_t scale_plain[4]) {
-    const uint64_t n = 1ull << log_n;
-    std::vector<uint32_t> ns;
-    ns.push_back(std::min(10u, log_n));
-    const uint32_t rem = log_n - ns[0], more = (rem + 6) / 7;
-    for (uint32_t k = 0; k < more; k++) ns.push_back(rem / more + (k < rem % more ? 1 : 0));
-    uint32_t s0 = 0;
-    const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, n / 1024);
-    // every pass reads and writes the same positions of its tile, so all of them but the last may run in place on the input ... which the
-    // caller may want to keep: the first pass goes in -> out when n_out == n, otherwise the intermediate passes need a full-size buffer
-    if (n_out != n && in != out) return ctx->fail(GL355_E_INVALID_ARG, "fr_ntt_from_bitrev: a truncated output needs the transform in place");
-    for (size_t k = 0; k < ns.size(); k++) {
-        FrPass pa;
-        memset(&pa, 0, sizeof pa);
-        pa.first = k == 0; pa.last = k + 1 == ns.size();
-        pa.in = pa.first ? in : out;
-        pa.out = out;
-        pa.tw = tw; pa.log_n = log_n; pa.s0 = s0; pa.ns = ns[k];
-        pa.in_mont = 1; pa.out_mont = 1; pa.no_gather = 1;
-        if (scale_plain) { pa.use_scale = 1; pa.scale = to_u256(Fr::from_words(scale_plain).l); }
-        pa.n_in = n; pa.n_out = pa.last ? n_out : n;
-        pa.post = pa.last ? post : nullptr;
-        hipLaunchKernelGGL(fr_fft_pass_kernel, dim3(tiles), dim3(256), 0, ctx->stream, pa);
-        s0 += ns[k];
-    }
-    GL355_HIP(ctx, hipGetLastError());
-    return GL355_OK;
-}
-int32_t bn254_fr_ntt_mont(Ctx* ctx, const uint64_t* in, uint64_t n_in, uint64_t* out, uint64_t n_out, uint32_t log_n, const uint64_t* tw,
-                          const uint64_t* pre, const uint64_t* post, const uint64_t scale_plain[4] /* or null */, uint64_t* work) {
-    const uint64_t n = 1ull << log_n;
-    if (log_n == 0) {
-        GL355_HIP(ctx, hipMemcpyAsync(out, in, 32, hipMemcpyDeviceToDevice, ctx->stream));        // (pre / post of a 1-point transform: not needed by any caller)
-        return GL355_OK;
-    }
-    std::vector<uint32_t> ns;
-    ns.push_back(std::min(10u, log_n));
-    const uint32_t rem = log_n - ns[0], more = (rem + 6) / 7;
-    for (uint32_t k = 0; k < more; k++) ns.push_back(rem / more + (k < rem % more ? 1 : 0));
-    uint32_t s0 = 0;
-    const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, n / 1024);
-    for (size_t k = 0; k < ns.size(); k++) {
-        FrPass pa;
-        memset(&pa, 0, sizeof pa);
-        pa.first = k == 0; pa.last = k + 1 == ns.size();
-        pa.in = pa.first ? in : work;
-        pa.out = (pa.last && !(pa.first && in == out)) ? out : work;
-        pa.tw = tw; pa.log_n = log_n; pa.s0 = s0; pa.ns = ns[k];
-        pa.in_mont = 1; pa.out_mont = 1;
-        if (scale_plain) { pa.use_scale = 1; pa.scale = to_u256(Fr::from_words(scale_plain).l); }
-        pa.n_in = n_in; pa.n_out = pa.out == out ? n_out : n;
-        pa.pre = pre;
-        pa.post = pa.out == out ? post : nullptr;
-        if (pa.out != out) pa.use_scale = 0;
-        hipLaunchKernelGGL(fr_fft_pass_kernel, dim3(tiles), dim3(256), 0, ctx->stream, pa);
-        s0 += ns[k];
-    }
-    if (ns.size() == 1 && in == out) {
-        // single pass in place: the pass wrote `work` without post / scale (bit-reversed reads cannot run in place): apply them in the copy
-        hipLaunchKernelGGL(fr_scale_copy_kernel, dim3((uint32_t)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t*)work, out, n_out, post,
-                           to_u256((scale_plain ? Fr::from_words(scale_plain) : Fr::zero()).l), scale_plain ? 1 : 0);
-    }
-    GL355_HIP(ctx, hipGetLastError());
-    return GL355_OK;
+// Bit-reversed input (what bn254_fr_ntt_mont_coset_dif leaves) to natural-order output, no gather either: out[k] = post[k] * sum_i in[bitrev(i)] w^(ik).
+// Every pass reads and writes the same positions of its tile, so in may equal out.
+int32_t bn254_fr_ntt_mont_from_bitrev(Ctx* ctx, const uint64_t* in, uint64_t* out, uint32_t log_n, const uint64_t* tw, const uint64_t* post) {
+    FrJob j;
+    j.order = FR_FROM_BITREV; j.in = in; j.out = out;
+    j.n_in = j.n_out = 1ull << log_n; j.log_n = log_n; j.tw = tw; j.post = post;
+    j.in_mont = j.out_mont = true;
+    return fr_launch(ctx, j);
 }
 
-// in: n_in = 2^log_in values, out: n_out values of the 2^log_n-point transform; shift == nullptr: the plain transform
+// The public forms on plain integers.  in: 2^log_in values, out: n_out values of the 2^log_n-point transform (log_n >= 1), natural order; shift == nullptr: the
+// plain transform.  in may equal out.
 int32_t fr_ntt_run(Ctx* ctx, const uint64_t* in, uint32_t log_in, uint64_t* out, uint64_t n_out, uint32_t log_n, int32_t inverse, const uint64_t* shift) {
     const uint64_t n = 1ull << log_n, n_in = 1ull << log_in;
-    // omega_n = ROOT^(2^(28 - log_n)) (or its inverse), Montgomery
-    const Fr w = inverse ? Fr::root_of_unity(log_n).inv() : Fr::root_of_unity(log_n);
-    const u256 w_mont = to_u256(w.l);
+    FrJob j;
+    j.order = FR_GATHER; j.in = in; j.out = out;
+    j.n_in = n_in; j.n_out = n_out; j.log_n = log_n;
     uint64_t scale_w[4] = {1, 0, 0, 0};
     if (inverse) Fr::from_u64(n).inv().to_words(scale_w);                    // n^-1 mod r, plain
-    const u256 scale = to_u256(scale_w);
+    j.use_scale = inverse != 0;
+    j.scale = to_u256(scale_w);
     // coset: powers of the shift multiply the inputs of the forward form, powers of its inverse (and 1/n) the outputs of the inverse form
     Fr sh = Fr::zero();
     if (shift) {
@@ -394,59 +317,26 @@ int32_t fr_ntt_run(Ctx* ctx, const uint64_t* in, uint32_t log_in, uint64_t* out,
         if (sh.is_zero()) return ctx->fail(GL355_E_INVALID_ARG, "bn254_fr_coset_ntt: the shift must not be zero");
         if (inverse) sh = sh.inv();
     }
-    const u256 pow_base = to_u256(sh.l);
     const uint64_t n_pow = shift ? (inverse ? n_out : n_in) : 0;
-    Scratch tw(ctx);
-    const uint64_t n_hi = (std::max(n / 2, n_pow) + 1023) / 1024;
-    GL355_TRY(tw.get((n / 2) * 32 + 32 + n * 32 + 2 * (1024 + n_hi) * 32 + n_pow * 32));
-    uint64_t* twp = tw.as<uint64_t>();
-    uint64_t* work = twp + 4 * (n / 2) + 4;                 // the first pass reads the data bit-reversed: it cannot run in place
-    uint64_t* tw_lo = work + 4 * n;
-    uint64_t* tw_hi = tw_lo + 4 * 1024;
-    uint64_t* pw_lo = tw_hi + 4 * n_hi;
-    uint64_t* pw_hi = pw_lo + 4 * 1024;
-    uint64_t* pw = pw_hi + 4 * n_hi;
-    const uint32_t hblk = (uint32_t)((n / 2 + 255) / 256);
-    {
-        ProfScope ps(ctx, "bn254_fr_ntt", (n_in + n_out) * 32);
-        hipLaunchKernelGGL(fr_twiddle_seed_kernel, dim3((uint32_t)((1024 + n_hi + 255) / 256)), dim3(256), 0, ctx->stream, tw_lo, tw_hi, n_hi, w_mont);
-        hipLaunchKernelGGL(fr_twiddle_kernel, dim3(hblk ? hblk : 1), dim3(256), 0, ctx->stream, twp, n / 2, tw_lo, tw_hi);
-        if (n_pow) {
-            hipLaunchKernelGGL(fr_twiddle_seed_kernel, dim3((uint32_t)((1024 + n_hi + 255) / 256)), dim3(256), 0, ctx->stream, pw_lo, pw_hi, n_hi, pow_base);
-            if (inverse) hipLaunchKernelGGL(fr_power_plain_kernel, dim3((uint32_t)((n_pow + 255) / 256)), dim3(256), 0, ctx->stream, pw, n_pow, pw_lo, pw_hi, scale);
-            else hipLaunchKernelGGL(fr_twiddle_kernel, dim3((uint32_t)((n_pow + 255) / 256)), dim3(256), 0, ctx->stream, pw, n_pow, pw_lo, pw_hi);
+    Scratch tw(ctx), work(ctx), pw(ctx);
+    GL355_TRY(tw.get((n / 2 + 1) * 32));
+    GL355_TRY(work.get(n * 32));                             // the first pass reads the data bit-reversed: it cannot run in place
+    if (n_pow) GL355_TRY(pw.get(n_pow * 32));
+    j.tw = tw.as<uint64_t>(); j.work = work.as<uint64_t>();
+    ProfScope ps(ctx, "bn254_fr_ntt", (n_in + n_out) * 32);
+    GL355_TRY(bn254_fr_twiddles(ctx, log_n, inverse != 0, tw.as<uint64_t>()));
+    if (n_pow) {
+        FrSeed seed(ctx);
+        GL355_TRY(seed.launch(sh, n_pow));
+        if (inverse) {
+            hipLaunchKernelGGL(fr_power_plain_kernel, fr_blocks(n_pow), dim3(256), 0, ctx->stream, pw.as<uint64_t>(), n_pow, seed.lo, seed.hi, j.scale);
+            j.post = pw.as<uint64_t>();
+        } else {
+            hipLaunchKernelGGL(fr_twiddle_kernel, fr_blocks(n_pow), dim3(256), 0, ctx->stream, pw.as<uint64_t>(), n_pow, seed.lo, seed.hi);
+            j.pre = pw.as<uint64_t>();
         }
-        {
-            // stages per pass: ten in the first (contiguous blocks), the rest in passes of at most six
-            std::vector<uint32_t> ns;
-            ns.push_back(std::min(10u, log_n));
-            const uint32_t rem = log_n - ns[0], more = (rem + 6) / 7;
-            for (uint32_t k = 0; k < more; k++) ns.push_back(rem / more + (k < rem % more ? 1 : 0));
-            uint32_t s0 = 0;
-            const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, n / 1024);
-            for (size_t k = 0; k < ns.size(); k++) {
-                FrPass pa;
-                memset(&pa, 0, sizeof pa);
-                pa.first = k == 0; pa.last = k + 1 == ns.size();
-                pa.in = pa.first ? in : work;
-                // the last pass may write straight to `out` unless it is also the first one and out aliases in (bit-reversed reads)
-                pa.out = (pa.last && !(pa.first && in == out)) ? out : work;
-                pa.tw = twp; pa.log_n = log_n; pa.s0 = s0; pa.ns = ns[k];
-                pa.use_scale = inverse ? 1 : 0; pa.scale = scale;
-                pa.n_in = n_in; pa.n_out = pa.out == out ? n_out : n;
-                pa.pre = (shift && !inverse) ? pw : nullptr;
-                pa.post = (shift && inverse && pa.out == out) ? pw : nullptr;
-                hipLaunchKernelGGL(fr_fft_pass_kernel, dim3(tiles), dim3(256), 0, ctx->stream, pa);
-                s0 += ns[k];
-            }
-            if (ns.size() == 1 && in == out) {
-                if (shift && inverse) return ctx->fail(GL355_E_UNSUPPORTED, "bn254_fr_coset_ntt: in-place inverse coset transform of <= 1024 points");
-                GL355_HIP(ctx, hipMemcpyAsync(out, work, n_out * 32, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-        }
-        GL355_HIP(ctx, hipGetLastError());
     }
-    return GL355_OK;
+    return fr_launch(ctx, j);
 }
 }  // namespace gl355
 

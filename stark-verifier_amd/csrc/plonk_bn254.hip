@@ -123,7 +123,7 @@ int32_t to_coeffs(gl355_plonk_pk* pk, const uint64_t* vals, uint64_t* coeffs, ui
     uint64_t ninv[4];
     Fr::from_u64(n).inv().to_words(ninv);
     for (uint32_t c = 0; c < count; c++)
-        GL355_TRY(bn254_fr_ntt_mont(pk->ctx, vals + 4ull * c * n, n, coeffs + (dst_stride ? dst_stride : 4 * n) * c, n, pk->k, pk->tw_inv, nullptr, nullptr, ninv, work));
+        GL355_TRY(bn254_fr_ntt_mont(pk->ctx, vals + 4ull * c * n, coeffs + (dst_stride ? dst_stride : 4 * n) * c, pk->k, pk->tw_inv, ninv, work));
     return GL355_OK;
 }
 
@@ -730,7 +730,7 @@ struct Proving {
                 pk->coset_base[c].inv().to_words(bw);
                 n_inv.to_words(fw);
                 GL355_TRY(bn254_fr_power_table(ctx, bw, fw, n, pre));
-                GL355_TRY(bn254_fr_ntt_mont_from_bitrev(ctx, h_ext + 4ull * c * n, h_ext + 4ull * c * n, n, pk->k, pk->tw_inv, pre, nullptr));
+                GL355_TRY(bn254_fr_ntt_mont_from_bitrev(ctx, h_ext + 4ull * c * n, h_ext + 4ull * c * n, pk->k, pk->tw_inv, pre));
                 const Fr tc = pk->coset_base[c].pow_u64(n);
                 Fr pw = Fr::one();
                 for (uint32_t q = 0; q < P; q++) { V[c][q] = pw; pw = pw * tc; }

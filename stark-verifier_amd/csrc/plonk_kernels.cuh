@@ -76,7 +76,7 @@ struct PlkEvalArgs {
     const int32_t* q_col[3];         // per kind: query -> column
     const int32_t* q_rot[3];         // per kind: query -> rotation
     uint64_t n;
-    uint32_t log_n, bitrev;          // bitrev: the columns hold point bitrev(i) at position i (cosets as bn254_fr_ntt_mont_dif leaves them)
+    uint32_t log_n, bitrev;          // bitrev: the columns hold point bitrev(i) at position i (cosets as bn254_fr_ntt_mont_coset_dif leaves them)
     u256 fold;
     const uint64_t* acc_in;          // running sums to continue from, or null (zero)
     uint64_t* acc_out;

@@ -31,7 +31,8 @@ def gpu_msm(ctx, pts, sc):
     return out
 
 
-@pytest.mark.parametrize("log_n", [1, 2, 5, 9, 12, 16])
+# 10: the largest single pass, in place, so through the scratch copy; 11: the smallest two-pass shape, a last pass of one stage
+@pytest.mark.parametrize("log_n", [1, 2, 5, 9, 10, 11, 12, 16])
 def test_fr_ntt_vs_oracle(ctx, orc, log_n):
     cv = Bn254Curve(orc)
     rng = np.random.default_rng(0x4E0 + log_n)
@@ -40,6 +41,11 @@ def test_fr_ntt_vs_oracle(ctx, orc, log_n):
     a[-1] = cv.scalars([pm.R - 1])[0]
     assert np.array_equal(gpu_ntt(ctx, a), cv.ntt_array(a))
     assert np.array_equal(gpu_ntt(ctx, a, inverse=True), cv.ntt_array(a, inverse=True))
+    # one point: status 0 and the element as it was
+    one = a[-1:].copy()
+    for inverse in (0, 1):
+        assert ctx.lib.gl355_bn254_fr_ntt(ctx.h, one.ctypes.data, 0, inverse) == 0
+        assert np.array_equal(one, a[-1:])
 
 
 def test_fr_ntt_k20_properties(ctx, orc):
@@ -308,11 +314,12 @@ def test_g1_msm_prepared_errors(ctx, orc):
     assert ctx.lib.gl355_bn254_g1_msm_bases_free(ctx.h, None) == 0
 
 
-@pytest.mark.parametrize("log_small,log_n", [(2, 3), (3, 3), (6, 9), (9, 11), (10, 13), (12, 14)])
+@pytest.mark.parametrize("log_small,log_n", [(2, 3), (3, 3), (6, 9), (10, 10), (1, 11), (9, 11), (10, 13), (12, 14)])
 def test_fr_coset_ntt_vs_oracle(ctx, orc, log_small, log_n):
     """coeff_to_extended / extended_to_coeff of halo2's EvaluationDomain: c_i shift^i zero-padded, transformed -- against the oracle's FFT of
     the shifted coefficients (Python integers for the powers); the inverse form gives the coefficients back.  The case (2, 3) hands the shift
-    over unreduced, as shift + r (still below 2^256): the library reduces it, so everything below holds unchanged"""
+    over unreduced, as shift + r (still below 2^256): the library reduces it, so everything below holds unchanged.  (10, 10) is one pass straight
+    into `out`, nothing padded or cut; (1, 11) pads two inputs and cuts the inverse to two outputs"""
     cv = Bn254Curve(orc)
     rng = np.random.default_rng(0x4E8 + log_n)
     ns, n = 1 << log_small, 1 << log_n
